@@ -1,6 +1,6 @@
 """Headline benchmark: event-frames/sec through the whole hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one batch of the BASELINE.json config "N-Caltech101 zero-shot, ViT-L/14,
@@ -20,7 +20,10 @@ of the logits took on rank 0's stream.
 
 Rank 0 prints one JSON line; `roofline` comes from HIP events the library records
 around its own launches during the timed steps, `cpu_baseline` is the CPU oracle
-(test infrastructure) timed on a bounded sample on the host.
+(test infrastructure) timed on a bounded sample on the host.  `--dump-outputs DIR`
+writes what the last timed step returned (rank 0's out_dict) as DIR/<name>.npy: the
+inputs are seeded, so two builds run with the same arguments can be compared output
+for output.
 """
 import argparse
 import json
@@ -62,7 +65,7 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--config', type=int, default=1, choices=sorted(CONFIGS),
                     help='BASELINE.json configs[i]; 1 (default) is the headline line')
-    ap.add_argument('--steps', type=int, default=5)
+    ap.add_argument('--steps', type=int, default=5, help='timed steps (>= 1)')
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--batch', type=int, default=None,
                     help='samples per step: per GPU for configs 1 / 2, over all GPUs for 3 / 4 (default: the config\'s)')
@@ -100,13 +103,48 @@ def parse():
                     help='skip the extra steps (after the timed region) that price the 1e-3 mode: tolerance_mode')
     ap.add_argument('--other-configs-batch', type=int, default=None,
                     help='samples per step of each of other_configs (tests; default: the per-GPU shard of BASELINE\'s batch)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the last one returned (rank 0) as DIR/<name>.npy, '
+                         'float32 (float64 where computed so), at most 64 MB in all (a fixed, seeded sample of rows beyond)')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error(f'--steps must be >= 1 and --warmup >= 0 (got {a.steps}, {a.warmup})')
     a.arch_given, a.classes_given = a.arch, a.classes        # overrides (tests) also apply to other_configs
     c = CONFIGS[a.config]
     a.batch = a.batch or c['batch']
     a.arch = a.arch or c['arch']
     a.classes = a.classes or c['K']
     return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: bytes in all, .npy headers included
+NPY_HEADER_BYTES = 4096          # an upper bound of one .npy header
+
+
+def dump_outputs(out, path, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of the step's out_dict as path/<name>.npy -- float64 stays float64, everything else
+    (logits, probs, the boolean valid_masks as 0 / 1) is written as float32.  When the arrays exceed `limit` bytes in all,
+    each keeps the same fraction of its rows (first axis), drawn by a fixed seed from the shapes alone, so that runs of
+    two builds with the same arguments write the same rows.  Returns {name: (shape as computed, rows written)}."""
+    arrays = {}
+    for name, v in sorted(out.items()):
+        if torch.is_tensor(v):
+            t = v.detach().cpu()
+            arrays[name] = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+    rowed = sum(x.nbytes for x in arrays.values() if x.ndim)
+    budget = limit - NPY_HEADER_BYTES * len(arrays) - sum(x.nbytes for x in arrays.values() if not x.ndim)
+    frac = budget / rowed if rowed > budget else 1.0
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, x in arrays.items():
+        shape = list(x.shape)
+        if frac < 1.0 and x.ndim:
+            assert int(x.shape[0] * frac) >= 1, f'{name} {shape}: a single row exceeds the --dump-outputs limit'
+            rows = np.random.default_rng(0).choice(x.shape[0], int(x.shape[0] * frac), replace=False)
+            x = x[np.sort(rows)]
+        np.save(os.path.join(path, name + '.npy'), x)
+        written[name] = (shape, x.shape[0] if x.ndim else None)
+    return written
 
 
 def _cpu_event2img(args):
@@ -674,6 +712,10 @@ def main():
         dist.all_gather_object(rank_ms, dt_own / a.steps * 1e3)
         gather_ms = sum(e0.elapsed_time(e1) for e0, e1 in gather_events) / a.steps
     total_frames = sum(shard_sizes) * views     # all ranks, one step
+    if a.dump_outputs and rank == 0:
+        # what the last timed step returned (the logits all-gathered over the ranks; the rest is rank 0's shard)
+        for name, (shape, rows) in dump_outputs(out, a.dump_outputs).items():
+            sys.stderr.write(f'[bench] --dump-outputs: {name} {shape}, {rows} rows written\n')
 
     # ---- the same steps with every batch starting in host memory (never part of `value`) ----
     host_line = None

@@ -18,7 +18,10 @@ fp16; its ``LayerNorm`` subclass computes in fp32 and casts back; every activati
 included, is an fp16 tensor; GEMMs and softmax accumulate in fp32 and round their result once).  It is the
 YARDSTICK of the logit-parity tests: the HIP path's distance from the fp32 oracle must not exceed the
 reference's own.  Emulated on the CPU in fp32 with an explicit round-to-fp16 after every op, so sums
-associate differently from cuBLAS -- a property of any two GPU libraries too.
+associate differently from cuBLAS -- a property of any two GPU libraries too.  Those sums also follow the
+host's BLAS path and thread count, which the fp16 roundings amplify (up to 2.6e-3 of the largest logit between two
+CPUs); ``emulate='fp16_reference_exact'`` runs the same emulation on float64 carriers instead -- every op exact
+before its fp16 rounding -- and gives the same values on every host.
 """
 import torch
 import torch.nn.functional as F
@@ -28,9 +31,12 @@ def quick_gelu(x):
     return x * torch.sigmoid(1.702 * x)
 
 
+EMULATIONS = {'fp16_reference': torch.float32, 'fp16_reference_exact': torch.float64}   # -> carrier dtype
+
+
 def _h(x):
-    """round to fp16 and back: the value an fp16 tensor would hold"""
-    return x.half().float()
+    """round to fp16 and back: the value an fp16 tensor would hold (carried in x's own dtype)"""
+    return x.half().to(x.dtype)
 
 
 def _quick_gelu_h(x):
@@ -73,12 +79,12 @@ def _blocks_h(x, sd, prefix, layers, heads, mask=None):
     return x
 
 
-def fp16_reference_weights(sd):
+def fp16_reference_weights(sd, dtype=torch.float32):
     """openai/CLIP convert_weights: what becomes fp16 (values kept as fp32 tensors holding fp16 values).  LayerNorm
     terms, class / positional / token embeddings and logit_scale stay fp32 parameters (the embeddings are cast
-    with .to(x.dtype) where they are added)."""
+    with .to(x.dtype) where they are added).  dtype: the carrier (EMULATIONS)."""
     keep32 = ('ln_', 'class_embedding', 'positional_embedding', 'token_embedding', 'logit_scale')
-    return {k: (v.float() if any(t in k for t in keep32) else _h(v.float())) for k, v in sd.items()}
+    return {k: (v.to(dtype) if any(t in k for t in keep32) else _h(v.to(dtype))) for k, v in sd.items()}
 
 
 def _mha(x, w_in, b_in, w_out, b_out, heads, mask=None):
@@ -129,13 +135,12 @@ def encode_image_autograd(sd, cfg, image):
 @torch.no_grad()
 def encode_image(sd, cfg, image, emulate=None):
     """image float32 [N, 3, R, R] -> [N, embed_dim].  emulate='fp16_reference': the reference's GPU arithmetic
-    (module docstring); returns fp32 tensors holding the fp16 values."""
+    (module docstring); returns fp32 tensors holding the fp16 values ('fp16_reference_exact': fp64 tensors)."""
     if emulate is None:
         return encode_image_autograd({k: v.float() for k, v in sd.items()}, cfg, image.float())
-    assert emulate == 'fp16_reference', emulate
-    sd = fp16_reference_weights(sd)
+    sd = fp16_reference_weights(sd, EMULATIONS[emulate])
     W, P = cfg['width'], cfg['patch']
-    x = _h(F.conv2d(_h(image.float()), sd['visual.conv1.weight'], stride=P))   # image.type(self.dtype)
+    x = _h(F.conv2d(_h(image.to(EMULATIONS[emulate])), sd['visual.conv1.weight'], stride=P))   # image.type(self.dtype)
     x = x.reshape(x.shape[0], W, -1).permute(0, 2, 1)
     cls = _h(sd['visual.class_embedding']).expand(x.shape[0], 1, W)
     x = _h(torch.cat([cls, x], dim=1) + _h(sd['visual.positional_embedding']))
@@ -150,8 +155,7 @@ def encode_text(sd, cfg, tokens, emulate=None):
     """tokens int [K, ctx] -> [K, embed_dim] (not normalised)."""
     TW, ctx = cfg['text_width'], cfg['context_length']
     if emulate is not None:
-        assert emulate == 'fp16_reference', emulate
-        sd = fp16_reference_weights(sd)
+        sd = fp16_reference_weights(sd, EMULATIONS[emulate])
         tokens = tokens.long()
         x = _h(sd['token_embedding.weight'][tokens])                         # .type(self.dtype)
         x = _h(x + _h(sd['positional_embedding']))

@@ -168,7 +168,7 @@ def oracle_forward(evs, geo, qa, cfg, sd, tokens, T, agg, adapter=None, emulate=
         frames.append(f)
     imgs = torch.from_numpy(op.preprocess(np.concatenate(frames), cfg['image_size']))
     feats = clip_ref.encode_image(sd, cfg, imgs, emulate=emulate)
-    h = (lambda x: x.half().float()) if emulate else (lambda x: x)
+    h = clip_ref._h if emulate else (lambda x: x)
     if adapter is None:
         text = clip_ref.encode_text(sd, cfg, tokens, emulate=emulate)
         text = h(text / h(text.norm(dim=-1, keepdim=True)))                 # F.normalize on the fp16 tensor

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -145,30 +146,37 @@ def test_other_baseline_configs_two_ranks_over_gloo(hip, config, batch, expect):
     assert (cfg['adapter'] is None) == (config == 3)
 
 
+# ranks of one bench.py run that share the single GPU: with this test process (which holds the GPU too) at most five
+# processes have it open, inside the shared box's limit of six.  Eight ranks, one node of the scaling run, are
+# exercised without a GPU by tests/test_harness_cpu.py::test_sharded_forward_and_all_gather_gloo_world8.
+SHARED_GPU_RANKS = 4
+
+
 @pytest.mark.parametrize('config,batch,expect', [
-    (3, 20, dict(scaling='strong', samples=[3, 3, 3, 3, 2, 2, 2, 2], views=2)),    # uneven shards over 8 ranks
-    (1, 1, dict(scaling='weak', samples=[1] * 8, views=10)),
+    (3, 10, dict(scaling='strong', samples=[3, 3, 2, 2], views=2)),    # uneven shards over 4 ranks
+    (1, 1, dict(scaling='weak', samples=[1] * 4, views=10)),
 ])
-def test_eight_ranks_over_gloo(hip, config, batch, expect):
-    """The rank count the scaling run uses (/root/reference/scripts/sbatch_run.sh:46-51 launches
-    `--nproc_per_node=$GPUS`), exercised before the driver does: eight gloo ranks sharing the one GPU.  Uneven
-    shards (the all-gather's padding path), eight entries in rank_devices / ms_per_step_per_rank, the whole-job
-    value.  A functional check of the N = 8 code path, not a measurement."""
+def test_four_ranks_over_gloo(hip, config, batch, expect):
+    """More ranks than the two-rank tests, launched the way the scaling run launches them
+    (`--nproc_per_node=$GPUS`): four gloo ranks sharing the one GPU.  Uneven shards (the all-gather's padding
+    path), four entries in rank_devices / ms_per_step_per_rank, the whole-job value.  A functional check of the
+    N > 2 code path, not a measurement."""
+    n = SHARED_GPU_RANKS
     env = dict(os.environ, EVENTCLIP_DIST_BACKEND='gloo')
     env.pop('WORLD_SIZE', None)
-    cmd = [sys.executable, 'bench.py', '--gpus', '8', '--config', str(config), '--batch', str(batch), '--steps', '2',
+    cmd = [sys.executable, 'bench.py', '--gpus', str(n), '--config', str(config), '--batch', str(batch), '--steps', '2',
            '--warmup', '1', '--arch', 'ViT-B/32', '--classes', '11', '--no-cpu-baseline']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json(r.stdout)
-    assert REQUIRED <= set(d) and d['n_gpus'] == 8 and d['scaling'] == expect['scaling']
+    assert REQUIRED <= set(d) and d['n_gpus'] == n and d['scaling'] == expect['scaling']
     cfg = d['config']
-    assert cfg['collective_ranks'] == 8 and len(cfg['rank_devices']) == 8
+    assert cfg['collective_ranks'] == n and len(cfg['rank_devices']) == n
     assert cfg['samples_per_rank'] == expect['samples']
     frames = sum(expect['samples']) * expect['views']
     assert cfg['frames_per_step_total'] == frames
     assert abs(d['value'] - frames * 1e3 / d['ms_per_step']) < 1e-6 * d['value']
-    assert len(d['ms_per_step_per_rank']) == 8 and all(0 < t <= d['ms_per_step'] * 1.001 for t in d['ms_per_step_per_rank'])
+    assert len(d['ms_per_step_per_rank']) == n and all(0 < t <= d['ms_per_step'] * 1.001 for t in d['ms_per_step_per_rank'])
     assert d['all_gather_ms_per_step'] is not None and d['all_gather_ms_per_step'] >= 0
 
 
@@ -195,3 +203,30 @@ def test_split_precision_lines_are_labelled(hip, flags, tag):
     assert d['metric'].startswith('event-frames/sec (whole node) ViT-L/14 zero-shot @224 -- ') and tag in d['metric']
     assert ('rounded to 16 bit first' in d['config']['weights']) == ('--f16-weights' in flags)
     assert d['value'] > 0
+
+
+def test_dump_outputs_and_steps(hip, tmp_path):
+    """--dump-outputs DIR: the arrays the last timed step returned, as float32 .npy files -- the same for the same
+    arguments at any --steps (seeded inputs).  --steps sets the number of timed steps: every kernel's launches per
+    step come out the same at 2 and at 3 steps."""
+    quick = ['--gpus', '1', '--warmup', '1', '--batch', '4', '--arch', 'ViT-B/32', '--classes', '11', '--no-cpu-baseline',
+             '--no-dvfs', '--no-other-configs', '--no-from-host', '--no-strict-line', '--no-tolerance-mode']
+    lines, dumps = [], []
+    for steps in (2, 3):
+        d = tmp_path / f'steps{steps}'
+        r = subprocess.run([sys.executable, 'bench.py', '--steps', str(steps), '--dump-outputs', str(d)] + quick, cwd=ROOT,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        ln = last_json(r.stdout)
+        assert ln['steps'] == steps
+        lines.append(ln)
+        dumps.append({p.name: np.load(p) for p in d.iterdir()})
+    assert lines[0]['kernel_launches_per_step'] == lines[1]['kernel_launches_per_step']
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ['full_logits.npy', 'logits.npy', 'probs.npy', 'valid_masks.npy']
+    assert all(x.dtype == np.float32 for x in a.values())
+    assert a['full_logits.npy'].shape == (4, 10, 11) and a['logits.npy'].shape == a['probs.npy'].shape == (4, 11)
+    assert (a['valid_masks.npy'] == 1).all() and a['valid_masks.npy'].shape == (4, 10)          # 10 views per sample
+    for name in a:
+        scale = float(np.abs(a[name]).max())
+        np.testing.assert_allclose(b[name], a[name], rtol=0, atol=1e-5 * scale, err_msg=name)
