@@ -163,6 +163,21 @@ class EcVitLora(ctypes.Structure):
     _fields_ = [('rank', c_int), ('blocks', ctypes.POINTER(EcBlockLora))]
 
 
+class EcResnetConvW(ctypes.Structure):
+    _fields_ = [('w', c_void_p), ('scale', c_void_p), ('bias', c_void_p), ('ks', c_int), ('cin', c_int), ('cout', c_int)]
+
+
+class EcResnetBlock(ctypes.Structure):
+    _fields_ = [('stride', c_int), ('c1', EcResnetConvW), ('c2', EcResnetConvW), ('c3', EcResnetConvW),
+                ('ds', EcResnetConvW)]
+
+
+class EcResnetWeights(ctypes.Structure):
+    _fields_ = [('struct_bytes', ctypes.c_size_t), ('dtype', c_int), ('image_size', c_int), ('n_blocks', c_int),
+                ('embed_dim', c_int), ('stem', EcResnetConvW * 3), ('blocks', ctypes.POINTER(EcResnetBlock)),
+                ('pos', c_void_p), ('q', EcResnetConvW), ('kv', EcResnetConvW), ('c', EcResnetConvW)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check that every
 # symbol of the header is exported.
 SIGNATURES = {
@@ -272,6 +287,16 @@ SIGNATURES = {
     'ec_lora_grad_batched': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'ec_adam_step_multi': (c_int, [c_void_p, c_int, ctypes.c_int64, c_float, c_float, c_float, c_float, c_float,
                                    c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    'ec_resnet_conv': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    'ec_resnet_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(EcResnetWeights), c_int]),
+    'ec_resnet_encode': (c_int, [ctypes.POINTER(EcResnetWeights), c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                 ctypes.c_size_t, c_int, c_void_p]),
+    'ec_resnet_stem_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'ec_resnet_avgpool': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'ec_resnet_attnpool_tokens': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                          c_void_p]),
+    'ec_resnet_attnpool_attend': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
 
 }
 

@@ -12,9 +12,10 @@ this much of it:
 
 ``CLIP`` below provides the same, with OpenAI's state-dict key names so released
 checkpoints load unchanged.  The parameters are fp32 masters; 16-bit copies for
-the MFMA GEMMs are packed once per device/dtype.  Only ViT backbones are
-supported (the ResNet variants are outside the north-star path).  Everything
-numeric runs in libeventclip_hip.so; there is no CPU fallback.
+the MFMA GEMMs are packed once per device/dtype.  The ResNet backbones (RN50 ..
+RN50x64) are ``resnet.ResNetCLIP``; ``build_random``, ``build_from_state_dict``
+and ``load`` return one for a ResNet name or checkpoint.  Everything numeric runs
+in libeventclip_hip.so; there is no CPU fallback.
 """
 import ctypes
 import gzip
@@ -27,7 +28,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import resnet as _resnet
 from .preprocess import Preprocess
+from .resnet import RESNET_ARCHS, resnet_config
+
+_RESNETS = tuple(RESNET_ARCHS)
 
 # (image_size, patch, vision width, vision layers, embed dim, text width, text heads, text layers)
 ARCHS = {
@@ -42,17 +47,17 @@ ARCHS = {
 }
 CONTEXT_LENGTH = 77
 VOCAB_SIZE = 49408
-_RESNETS = ('RN50', 'RN101', 'RN50x4', 'RN50x16', 'RN50x64')
 
 
 def available_models():
-    return list(ARCHS)
+    return list(_RESNETS) + list(ARCHS)
 
 
 def arch_config(arch, **override):
+    """Config of a ViT architecture; ResNet names raise (their configs come from resnet_config)."""
     if arch in _RESNETS:
-        raise NotImplementedError(f'{arch}: ResNet CLIP backbones are not built for MI355X; '
-                                  f'use one of {available_models()}')
+        raise NotImplementedError(f'{arch}: arch_config holds the ViT architectures; '
+                                  f'use resnet_config({arch!r}) for the ResNet backbones')
     if arch not in ARCHS:
         raise RuntimeError(f'Model {arch} not found; available models = {available_models()}')
     cfg = dict(ARCHS[arch], context_length=CONTEXT_LENGTH, vocab_size=VOCAB_SIZE)
@@ -82,6 +87,10 @@ def random_state_dict(cfg, seed=0, qk_gain=1.0, branch_gain=1.0):
     content-dependent attention) and ``branch_gain`` its out_proj / c_proj (the branches against the residual
     stream): (6, 4) makes a third of the ViT-L/14 feature norm input-dependent -- the weights the logit-parity
     tests use, so that their error is measured against a signal and not against a constant."""
+    if _resnet.is_resnet_config(cfg):
+        if qk_gain != 1.0:
+            raise ValueError('qk_gain applies to the ViT tower only')
+        return _resnet.random_state_dict(cfg, seed=seed, **({} if branch_gain == 1.0 else dict(branch_gain=branch_gain)))
     g = torch.Generator().manual_seed(seed)
 
     def rn(*shape, std=1.0):
@@ -138,9 +147,11 @@ def random_state_dict(cfg, seed=0, qk_gain=1.0, branch_gain=1.0):
 
 
 def config_from_state_dict(sd):
-    """Recover the architecture from an OpenAI-format state dict (ViT only)."""
+    """Recover the architecture from an OpenAI-format state dict (ViT or ResNet)."""
+    if 'visual.attnpool.positional_embedding' in sd:
+        return _resnet.config_from_state_dict(sd)
     if 'visual.proj' not in sd:
-        raise NotImplementedError('only ViT CLIP checkpoints are supported')
+        raise NotImplementedError('not an OpenAI CLIP checkpoint (neither visual.proj nor visual.attnpool)')
     W = sd['visual.conv1.weight'].shape[0]
     P = sd['visual.conv1.weight'].shape[-1]
     g = round((sd['visual.positional_embedding'].shape[0] - 1) ** 0.5)
@@ -516,8 +527,12 @@ class CLIP(nn.Module):
 
 def build_random(arch, seed=0, dtype='float16', device='cuda', chunk=2560, **override):
     """Random-weight CLIP of a named architecture (benchmarks / tests: no checkpoints ship)."""
-    cfg = arch_config(arch, **override)
-    model = CLIP(cfg, random_state_dict(cfg, seed), dtype=dtype, chunk=chunk)
+    if arch in RESNET_ARCHS:
+        cfg = resnet_config(arch, **override)
+        model = _resnet.ResNetCLIP(cfg, random_state_dict(cfg, seed), dtype=dtype)
+    else:
+        cfg = arch_config(arch, **override)
+        model = CLIP(cfg, random_state_dict(cfg, seed), dtype=dtype, chunk=chunk)
     if device is not None:
         model = model.to(device)
     return model.eval()
@@ -527,7 +542,10 @@ def build_from_state_dict(sd, dtype='float16', device='cuda', chunk=2560):
     sd = {k: v for k, v in sd.items() if k not in ('input_resolution', 'context_length',
                                                    'vocab_size')}
     cfg = config_from_state_dict(sd)
-    model = CLIP(cfg, sd, dtype=dtype, chunk=chunk)
+    if _resnet.is_resnet_config(cfg):
+        model = _resnet.ResNetCLIP(cfg, sd, dtype=dtype)
+    else:
+        model = CLIP(cfg, sd, dtype=dtype, chunk=chunk)
     if device is not None:
         model = model.to(device)
     return model.eval()
@@ -541,7 +559,7 @@ def load(name, device='cuda', jit=False, download_root=None, dtype='float16'):
     archive or plain state dict in OpenAI's key layout).  Nothing is downloaded."""
     path = name
     if not os.path.isfile(path):
-        cfg = arch_config(name)   # raises for unknown / ResNet names
+        cfg = resnet_config(name) if name in RESNET_ARCHS else arch_config(name)   # raises for unknown names
         root = download_root or os.path.expanduser('~/.cache/clip')
         path = os.path.join(root, name.replace('/', '-') + '.pt')
         if not os.path.isfile(path):

@@ -115,6 +115,9 @@ class ZSCLIPClassifier(nn.Module):
         if 'patches' in data_dict:
             feats = self.model.encode_patches(data_dict['patches'])
             row_idx = data_dict['row_idx']
+        elif 'frames_u8' in data_dict:
+            feats = self.model.encode_frames(data_dict['frames_u8'])
+            row_idx = data_dict['row_idx']
         else:
             imgs = data_dict['img']                                      # [B, T, C, H, W]
             valid_imgs = imgs[valid_masks]                               # clip_cls.py:139

@@ -28,10 +28,12 @@ class Event2ImagePipeline:
         ``background_mask``).
     n_px: CLIP input resolution.  patch/kpad/dtype: when given, ``__call__`` emits the
         16-bit im2col rows for ``CLIP.encode_patches`` instead of fp32 images.
+    frames_u8: emit the resized + cropped uint8 frames (``frames_u8`` [Fv, R, R, 3]) instead, the input of
+        ``ResNetCLIP.encode_frames`` (ToTensor and Normalize run in its stem kernel).
     """
 
     def __init__(self, resolution, max_n, quantize_args, n_px=224, patch=None, kpad=None,
-                 dtype=torch.float16, generator=None, augment=False):
+                 dtype=torch.float16, generator=None, augment=False, frames_u8=False):
         qa = copy.deepcopy(quantize_args)
         self.resolution = tuple(resolution)
         self.split_method = qa['split_method']
@@ -50,6 +52,8 @@ class Event2ImagePipeline:
         # not a key of the reference's configs: which numpy the frames should agree with (vis.py:27)
         self.float_stage = qa.get('float_stage', vis.DEFAULT_FLOAT_STAGE)
         self.n_px, self.patch, self.kpad, self.dtype = int(n_px), patch, kpad, dtype
+        self.frames_u8 = bool(frames_u8)
+        assert not (self.frames_u8 and self.patch), 'frames_u8 and patch rows are two different outputs'
         self.generator = generator
         self.strict = True   # raise on events outside the sensor, as the reference does
         # training-time RandAugment on the frames (event2img.py:34-42, :120-121): two ops per sample,
@@ -132,7 +136,7 @@ class Event2ImagePipeline:
         N-ImageNet readers do (caltech.py:176).
 
         Returns a dict with ``valid_mask`` [B, T] (CUDA bool), ``row_idx`` [B, T] (CUDA
-        int32) and either ``patches`` [Fv, G, kpad] (fused path) or ``img``
+        int32) and either ``patches`` [Fv, G, kpad] (fused path), ``frames_u8`` [Fv, R, R, 3] or ``img``
         [B, T, 3, R, R] float32 (the reference's batch layout, padded views all-zero)."""
         dev = _lib.require_gpu()
         if isinstance(events, (list, tuple)):
@@ -151,7 +155,9 @@ class Event2ImagePipeline:
         out = dict(valid_mask=vm.to(dev), row_idx=ri.to(dev))
         if self.augment:
             frames = self._augment_frames(frames, ri)
-        if self.patch:
+        if self.frames_u8:
+            out['frames_u8'] = preprocess_frames(frames, self.n_px, mode='u8')
+        elif self.patch:
             out['patches'] = preprocess_frames(frames, self.n_px, mode='patches', patch=self.patch,
                                                kpad=self.kpad, dtype=self.dtype)
         else:
@@ -192,7 +198,10 @@ def build_event2img_pipeline(params, resolution, max_n, clip_model=None):
     if clip_model is not None:
         c = clip_model.cfg
         n_px = c['image_size']
-        kw = dict(patch=c['patch'], kpad=clip_model.kpad, dtype=clip_model.compute_dtype)
+        if 'patch' in c:
+            kw = dict(patch=c['patch'], kpad=clip_model.kpad, dtype=clip_model.compute_dtype)
+        else:                       # ResNet tower: uint8 frames for its stem kernel
+            kw = dict(frames_u8=True)
     return Event2ImagePipeline(resolution, max_n, params.quantize_args, n_px=n_px, **kw)
 
 

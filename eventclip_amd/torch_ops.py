@@ -12,6 +12,7 @@ mirrors of the reference's interface (vis / preprocess / clip / adapter / clip_c
     torch.ops.eventclip_hip.text_encode        ec_text_encode                  models/clip_cls.py:84
     torch.ops.eventclip_hip.adapter_fwd        ec_adapter_forward              models/adapter.py:82-105
     torch.ops.eventclip_hip.classify           ec_classify_v2                   models/clip_cls.py:139-154, :319-343
+    torch.ops.eventclip_hip.resnet_encode      ec_resnet_encode                models/clip_cls.py:101 (ResNet backbones)
 
 Weights live in packed C structs owned by the Python modules; an op receives them as an integer
 handle into a registry of live modules (tensors-only signatures keep the ops traceable, and the
@@ -253,4 +254,29 @@ def _(feats, row_idx, text_t, logit_scale, agg, normalize):
     return feats.new_empty((B, T, K)), feats.new_empty((B, K)), feats.new_empty((B, K))
 
 
-OPS = ('events_to_frames', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify')
+@custom_op(f'{NAMESPACE}::resnet_encode', mutates_args=(), device_types='cuda')
+def resnet_encode(inp: torch.Tensor, input_mode: int, clip_handle: int) -> torch.Tensor:
+    """ResNet image tower: fp32 [N, 3, R, R] (EC_PRE_CHW_F32) or uint8 [N, R, R, 3] (EC_PRE_HWC_U8) -> fp32 [N, D]."""
+    m = _resolve(clip_handle, 'resnet_encode')
+    pk = m._pack()
+    n = int(inp.shape[0])
+    feats = torch.empty((n, m.cfg['embed_dim']), dtype=torch.float32, device=inp.device)
+    if n == 0:
+        return feats
+    chunk = max(1, min(int(m.chunk), n))
+    need = _lib.lib().ec_resnet_workspace_bytes(ctypes.byref(pk['resnet']), chunk)
+    if need == 0:
+        _lib.check(_lib.EC_ERR_INVALID, 'ec_resnet_workspace_bytes')
+    ws = m._workspace(need, pk['dev'])
+    rc = _lib.lib().ec_resnet_encode(ctypes.byref(pk['resnet']), _lib.ptr(inp), int(input_mode), n, _lib.ptr(feats),
+                                     _lib.ptr(ws), ws.numel(), chunk, _lib.stream_ptr())
+    _lib.check(rc, 'ec_resnet_encode')
+    return feats
+
+
+@resnet_encode.register_fake
+def _(inp, input_mode, clip_handle):
+    return inp.new_empty((inp.shape[0], _resolve(clip_handle, 'resnet_encode').cfg['embed_dim']), dtype=torch.float32)
+
+
+OPS = ('events_to_frames', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode')

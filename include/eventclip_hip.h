@@ -890,6 +890,66 @@ EC_API int ec_grad_unscale_check(float *grad, int64_t n, float inv_scale, int32_
                                  const float *step_scalars /* NULL, or [EC_STEP_INV_SCALE] replaces inv_scale */,
                                  ec_stream_t stream);
 
+
+/* ---- ResNet CLIP image tower (OpenAI ModifiedResNet), csrc/resnet.hip ----
+ * Activations are NHWC 16-bit (dtype EC_F16 / EC_BF16), channel counts padded to multiples of 64 at pack time
+ * (zero weights, zero scale and bias: a padded channel stays 0 through ReLU, pooling and the residual add).  The
+ * convolution weights are the checkpoint's, rounded once to 16 bit; BatchNorm runs in the fp32 epilogue as a
+ * per-channel scale and bias (gamma / sqrt(var + eps), beta - mean * scale).
+ *
+ * out[m, n] = epi(scale[n] * sum_k x_rows[m, k] w[n, k] + bias[n]) (scale NULL: 1): a stride-1 ks x ks convolution (ks 1 or 3, zero padding
+ * (ks - 1) / 2) as an implicit GEMM on MFMA.  x: [n_img, H, W, Cin]; w: [Cout, ks, ks, Cin] (tap-major K);
+ * bias fp32 [Cout]; resid: NULL or 16-bit [n_img, H, W, Cout], added before the ReLU; relu: 0 / 1;
+ * out: 16-bit [n_img, H, W, Cout], or fp32 with out32 (no resid).  Cin and Cout multiples of 64.  With ks = 1
+ * it is a plain GEMM over n_img * H * W rows. */
+EC_API int ec_resnet_conv(const void *x, int n_img, int H, int W, int Cin, int Cout, int ks, const void *w,
+                          const float *scale, const float *bias, const void *resid, int relu, void *out, int out32,
+                          int dtype, ec_stream_t stream);
+/* The stem's stride-2 3x3 rows: input EC_PRE_CHW_F32 (fp32 [n_img, 3, R, R], normalised) or EC_PRE_HWC_U8
+ * (uint8 [n_img, R, R, 3] as ec_preprocess writes it; ToTensor + Normalize applied here) -> rows 16-bit
+ * [n_img, R/2, R/2, 64]: k = (ky * 3 + kx) * 3 + c for the 27 taps rounded to 16 bit, k + 27 the rounding's
+ * remainder (16 bit), zeros beyond (R even).  The stem weights repeat their 27 columns at 27 .. 53. */
+EC_API int ec_resnet_stem_rows(const void *input, int input_mode, int n_img, int R, void *rows, int dtype,
+                               ec_stream_t stream);
+/* AvgPool2d(2): x [n_img, H, W, C] -> y [n_img, H/2, W/2, C], fp32 sum, one rounding (C a multiple of 8). */
+EC_API int ec_resnet_avgpool(const void *x, int n_img, int H, int W, int C, void *y, int dtype, ec_stream_t stream);
+/* Attention-pool tokens: x [n_img, HW, C] -> tokens [n_img, HW + 1, C] = [mean over HW; x] + pos (fp32 [HW + 1, C]),
+ * and token 0 again in q_in [n_img, C]. */
+EC_API int ec_resnet_attnpool_tokens(const void *x, int n_img, int HW, int C, const float *pos, void *tokens,
+                                     void *q_in, int dtype, ec_stream_t stream);
+/* One query per head: q [n_img, C] (q_proj of token 0), kv [n_img, L, 2C] (k_proj | v_proj of every token)
+ * -> out [n_img, C], softmax(q k^T / 8) v per head of 64 (L <= 256). */
+EC_API int ec_resnet_attnpool_attend(const void *q, const void *kv, int n_img, int L, int C, void *out, int dtype,
+                                     ec_stream_t stream);
+
+
+/* The whole image tower. */
+typedef struct {
+    const void *w;        /* 16-bit [cout, ks, ks, cin] */
+    const float *scale;   /* fp32 [cout] or NULL (1) */
+    const float *bias;    /* fp32 [cout] */
+    int ks, cin, cout;    /* cin, cout: padded channel counts (multiples of 64) */
+} ec_resnet_conv_w;
+typedef struct {
+    int stride;                          /* 1 or 2 (AvgPool2d(2) after c2 and in front of ds) */
+    ec_resnet_conv_w c1, c2, c3, ds;     /* ds.w NULL: identity shortcut */
+} ec_resnet_block;
+typedef struct {
+    size_t struct_bytes;                 /* sizeof(ec_resnet_weights): checked by the library */
+    int dtype, image_size, n_blocks, embed_dim;
+    ec_resnet_conv_w stem[3];            /* stem[0]: 1x1 over the 64-wide stem rows; stem[1], stem[2]: 3x3 */
+    const ec_resnet_block *blocks;       /* n_blocks Bottlenecks, layer1.0 first */
+    const float *pos;                    /* attention pool: fp32 [HW + 1, C] */
+    ec_resnet_conv_w q, kv, c;           /* 1x1: q_proj [C, C], k_proj | v_proj [2C, C], c_proj [embed_dim, C] */
+} ec_resnet_weights;
+/* Workspace of ec_resnet_encode for `chunk` images at a time (0 on invalid weights). */
+EC_API size_t ec_resnet_workspace_bytes(const ec_resnet_weights *w, int chunk);
+/* input: EC_PRE_CHW_F32 fp32 [n_img, 3, R, R] (normalised) or EC_PRE_HWC_U8 uint8 [n_img, R, R, 3] (ec_preprocess
+ * output) -> feats fp32 [n_img, embed_dim].  Runs `chunk` images at a time through the workspace; a frame's features
+ * do not depend on the batch or chunk it is in. */
+EC_API int ec_resnet_encode(const ec_resnet_weights *w, const void *input, int input_mode, int n_img, float *feats,
+                            void *ws, size_t ws_bytes, int chunk, ec_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
