@@ -5,8 +5,8 @@
 Every ``csrc/*.hip`` is compiled to an object next to it (cached by mtime) and
 linked into ``eventclip_amd/libeventclip_hip.so``.  The .so is git-ignored but
 travels with the tree to the GPU box.  ``--diag`` builds ``libeventclip_hip_diag.so`` with
--DEC_GEMM_DIAG -DEC_ATTN_DIAG -DEC_EVENTS_DIAG instead: the same library plus ec_gemm's timing / stamp /
-timeline variants (csrc/gemm_diag.inc) and the attention / events phase stamps, for
+-DEC_GEMM_DIAG -DEC_ATTN_DIAG -DEC_EVENTS_DIAG instead: the same library plus ec_gemm's timeline / clock-stamp
+variants (18, 19) and MFMA rate probe, and the attention / events phase stamps, for
 tools/ only (the product never loads it).
 """
 import argparse

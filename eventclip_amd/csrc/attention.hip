@@ -20,7 +20,6 @@
 //    row order is permuted so each lane ends with 16 contiguous head-dim outputs
 //    (two 16-B stores).
 //  * fp32 scores / softmax / accumulation; the 1/sqrt(64) scale is a power of two.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -65,89 +64,7 @@ struct AttnArgs {
                       // scaled-score domain (m * scale_log2e + log2 l), kept for ec_attention_backward
 };
 
-// One 64-key (or, for the last odd step, 32-key) block of the online softmax:
-// scores -> running max / sum -> P^T as the B operand -> O^T += V^T . P^T.
-template <int DT, int KSTEPS, bool MASK>  // KSTEPS = 32-key steps in this block (2 or 1)
-__device__ __forceinline__ void attn_block(const unsigned char *ldsK, const unsigned char *ldsV,
-                                           int key0, int klimit, const typename T16<DT>::v8 (&qf)[2],
-                                           float scale_log2e, float &m_run, float &l_run,
-                                           f32x4 (&o)[4], int g, int c16)
-{
-    typedef typename T16<DT>::elem elem;
-    typedef typename T16<DT>::v8 v8;
-    typedef typename T16<DT>::v4 v4;
-    constexpr int NT = 2 * KSTEPS;
-    // ---- scores: acc[kt][r] = <k[key0 + 16 kt + 4 g + r], q[c16]> ----
-    f32x4 acc[NT];
-#pragma unroll
-    for (int kt = 0; kt < NT; kt++) {
-        acc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int row = key0 + kt * 16 + c16;
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-            const v8 kf = *reinterpret_cast<const v8 *>(ldsK + row * 128 +
-                                                        (((ks * 4 + g) ^ (row & 7)) << 4));
-            acc[kt] = mfma16(kf, qf[ks], acc[kt]);
-        }
-    }
-    // ---- (mask,) block max, rescale factor ----
-    float mx = m_run;
-#pragma unroll
-    for (int kt = 0; kt < NT; kt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            if (MASK) {   // only blocks that reach past klimit (padding, causal diagonal)
-                const int key = key0 + kt * 16 + 4 * g + r;
-                acc[kt][r] = key < klimit ? acc[kt][r] : -INFINITY;
-            }
-            mx = fmaxf(mx, acc[kt][r]);
-        }
-    mx = xor_max(mx);   // the four lane groups hold different keys of the same query
-    const float alpha = __builtin_amdgcn_exp2f((m_run - mx) * scale_log2e);
-    m_run = mx;
-    const float mc = -mx * scale_log2e;
-    float psum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NT; kt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[kt][r], scale_log2e, mc));
-            acc[kt][r] = p;
-            psum += p;
-        }
-    l_run = l_run * alpha + psum;   // per-lane partial; summed over the lane groups at the end
-#pragma unroll
-    for (int dt = 0; dt < 4; dt++) o[dt] *= alpha;
-    // ---- O^T += V^T . P^T ----
-#pragma unroll
-    for (int s = 0; s < KSTEPS; s++) {
-        // B operand element j <-> key key0 + 32 s + 16 (j >> 2) + 4 g + (j & 3)
-        v8 pf;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            pf[r] = to16(acc[2 * s][r], elem());
-            pf[4 + r] = to16(acc[2 * s + 1][r], elem());
-        }
-#pragma unroll
-        for (int dt = 0; dt < 4; dt++) {
-            // A operand row i <-> head dim (i >> 2) * 16 + 4 dt + (i & 3), same key order
-            v8 vf;
-#pragma unroll
-            for (int hh = 0; hh < 2; hh++) {
-                const int row = key0 + 32 * s + 16 * hh + 4 * g + (c16 >> 2);
-                const int u = ((c16 & 3) * 4 + dt) ^ ((row >> 1) & 3);
-                const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) s16x4 *)(ldsV + row * 128 + u * 8));
-                const v4 tv = __builtin_bit_cast(v4, t);
-                vf[4 * hh] = tv[0], vf[4 * hh + 1] = tv[1], vf[4 * hh + 2] = tv[2],
-                        vf[4 * hh + 3] = tv[3];
-            }
-            o[dt] = mfma16(vf, pf, o[dt]);
-        }
-    }
-}
-
-// Version 2 of the block (the product path; `attn_block` above is kept for A/B in the diagnostic build).
+// One block of the online softmax: scores -> running max / sum -> P^T as the B operand -> O^T += V^T . P^T.
 // The vector ALU is the saturated pipe of this kernel (profiles/r2_attention.md), so the block is
 // arranged to leave it only what no other unit can do -- one exp2, half a max3 and half a convert per score:
 //  * the query fragment arrives pre-multiplied by log2(e) / sqrt(64), so the MFMA result is already the
@@ -233,16 +150,13 @@ __device__ __forceinline__ void attn_move(float d, float d_log2, bool down, f32x
     }
 }
 
-// Position of a key row's 16-byte K chunk c / 8-byte V slot u inside its 128-byte LDS row: IMG 0 = the image of the
-// 16-query-tile kernel (conflict-free for ITS fragment reads), IMG 1 = the image of attention32_kernel, whose 32-row
-// A-operand reads and transposed reads would be two-way conflicted on image 0 (MI355X_MICROARCH.md, LDS lane groups:
-// rows r and r + 24 / r + 8 of a ds_read_b128 group share row & 7; the two key pairs of a transposed read share a
-// 64-byte half).  The 16-row block functions take IMG so that attention32_kernel's last-row path can read its image.
-template <int IMG> __device__ __forceinline__ int kkey(int row) { return IMG ? (row >> 1) & 7 : row & 7; }
-template <int IMG> __device__ __forceinline__ int vkey(int row) { return IMG ? ((row >> 1) & 1) << 3 : (row >> 1) & 3; }
+// Position of a key row's 16-byte K chunk c / 8-byte V slot u inside its 128-byte LDS row: c ^ kkey(row), u ^ vkey(row)
+// (conflict-free for the fragment reads of a 16-query tile)
+__device__ __forceinline__ int kkey(int row) { return row & 7; }
+__device__ __forceinline__ int vkey(int row) { return (row >> 1) & 3; }
 
 // One block of KSTEPS 32-key steps.  `down`: the tile has added nothing yet (m may move down too).
-template <int DT, int KSTEPS, bool MASK, int QM, int IMG = 0>
+template <int DT, int KSTEPS, bool MASK, int QM>
 __device__ __forceinline__ void attn_block2(const unsigned char *ldsK, const unsigned char *ldsV,
                                             int key0, int klimit, const typename T16<DT>::v8 (&qf)[2],
                                             const typename T16<DT>::v8 &ones, bool down, float c, f32x4 &mneg,
@@ -259,8 +173,8 @@ __device__ __forceinline__ void attn_block2(const unsigned char *ldsK, const uns
 #pragma unroll
     for (int kt = 0; kt < NT; kt++) {
         const int row = key0 + kt * 16 + c16;
-        const v8 k0 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((0 + g) ^ kkey<IMG>(row)) << 4));
-        const v8 k1 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((4 + g) ^ kkey<IMG>(row)) << 4));
+        const v8 k0 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((0 + g) ^ kkey(row)) << 4));
+        const v8 k1 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((4 + g) ^ kkey(row)) << 4));
         acc[kt] = mfma16(k0, qf[0], mneg);
         acc[kt] = mfma16(k1, qf[1], acc[kt]);
     }
@@ -298,7 +212,7 @@ __device__ __forceinline__ void attn_block2(const unsigned char *ldsK, const uns
 #pragma unroll
             for (int hh = 0; hh < 2; hh++) {
                 const int row = key0 + 32 * s + 16 * hh + 4 * g + (c16 >> 2);
-                const int u = ((c16 & 3) * 4 + dt) ^ vkey<IMG>(row);
+                const int u = ((c16 & 3) * 4 + dt) ^ vkey(row);
                 const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                     (__attribute__((address_space(3))) s16x4 *)(ldsV + row * 128 + u * 8));
                 const v4 tv = __builtin_bit_cast(v4, t);
@@ -328,7 +242,7 @@ __device__ __forceinline__ void attn_block2(const unsigned char *ldsK, const uns
 // key -- one exp2, and 16 multiply-adds of the key's V row (head dims 16 g .. 16 g + 15 for this lane, as the
 // epilogue stores them) instead of 8 masked scores, 5 MFMAs and 16 LDS reads.  P is rounded to 16 bit like
 // every other P.  Must follow the tile's last block (its last MFMA waited for O to settle).
-template <int DT, int QM, int IMG = 0>
+template <int DT, int QM>
 __device__ __forceinline__ void attn_odd_key(const unsigned char *ldsK, const unsigned char *ldsV, int key,
                                              const typename T16<DT>::v8 (&qf)[2], bool down, float c, f32x4 &mneg,
                                              f32x4 (&o)[5], int g, int c16)
@@ -339,12 +253,12 @@ __device__ __forceinline__ void attn_odd_key(const unsigned char *ldsK, const un
     constexpr bool PRE = QM != QM_RAW;
     const float thr = PRE ? ATTN_THR : ATTN_THR / c, lo = PRE ? ATTN_LO : ATTN_LO / c;
     const int row = key + c16;
-    const v8 k0 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((0 + g) ^ kkey<IMG>(row)) << 4));
-    const v8 k1 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((4 + g) ^ kkey<IMG>(row)) << 4));
+    const v8 k0 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((0 + g) ^ kkey(row)) << 4));
+    const v8 k1 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((4 + g) ^ kkey(row)) << 4));
     v4 vv[4];
 #pragma unroll
     for (int dt = 0; dt < 4; dt++)   // logical 8-byte slot 4 g + dt of V's row, stored at slot ^ vkey(row)
-        vv[dt] = *reinterpret_cast<const v4 *>(ldsV + key * 128 + ((4 * g + dt) ^ vkey<IMG>(key)) * 8);
+        vv[dt] = *reinterpret_cast<const v4 *>(ldsV + key * 128 + ((4 * g + dt) ^ vkey(key)) * 8);
     f32x4 acc = mfma16(k0, qf[0], mneg);
     acc = mfma16(k1, qf[1], acc);
     float sc = acc[0];
@@ -363,7 +277,7 @@ __device__ __forceinline__ void attn_odd_key(const unsigned char *ldsK, const un
 
 // Keys of one tile, not causal: the full 32-key steps [step0, step1) in blocks of two, then (`tail`) whatever
 // lies behind the last full step of the sequence: nothing, one key (rank-one update) or a masked step.
-template <int DT, int QM, int IMG = 0>
+template <int DT, int QM>
 __device__ __forceinline__ void attn_keys(const unsigned char *ldsK, const unsigned char *ldsV, int S, int step0,
                                           int step1, bool tail, const typename T16<DT>::v8 (&qf)[2],
                                           const typename T16<DT>::v8 &ones, float c, f32x4 &mneg, f32x4 (&o)[5],
@@ -372,19 +286,19 @@ __device__ __forceinline__ void attn_keys(const unsigned char *ldsK, const unsig
     bool down = true;
     int s = step0;
     for (; s + 2 <= step1; s += 2) {
-        attn_block2<DT, 2, false, QM, IMG>(ldsK, ldsV, 32 * s, S, qf, ones, down, c, mneg, o, g, c16);
+        attn_block2<DT, 2, false, QM>(ldsK, ldsV, 32 * s, S, qf, ones, down, c, mneg, o, g, c16);
         down = false;
     }
     if (s < step1) {
-        attn_block2<DT, 1, false, QM, IMG>(ldsK, ldsV, 32 * s, S, qf, ones, down, c, mneg, o, g, c16);
+        attn_block2<DT, 1, false, QM>(ldsK, ldsV, 32 * s, S, qf, ones, down, c, mneg, o, g, c16);
         down = false;
     }
     if (tail) {
         const int full = S >> 5, nt = S - 32 * full;
         if (nt == 1)
-            attn_odd_key<DT, QM, IMG>(ldsK, ldsV, S - 1, qf, down, c, mneg, o, g, c16);
+            attn_odd_key<DT, QM>(ldsK, ldsV, S - 1, qf, down, c, mneg, o, g, c16);
         else if (nt > 1)
-            attn_block2<DT, 1, true, QM, IMG>(ldsK, ldsV, 32 * full, S, qf, ones, down, c, mneg, o, g, c16);
+            attn_block2<DT, 1, true, QM>(ldsK, ldsV, 32 * full, S, qf, ones, down, c, mneg, o, g, c16);
     }
 }
 
@@ -398,7 +312,7 @@ __host__ __device__ constexpr bool attn_lone_tile(int S, int causal, int waves)
     return !causal && (S & 15) == 1 && (S + 15) / 16 > waves && ((S + 15) / 16) % waves == 1;
 }
 
-template <int DT, int AT_WAVES, bool LSE = false, bool V2 = true, int QM = (DT == 0 ? QM_KERNEL : QM_RAW)>
+template <int DT, int AT_WAVES, bool LSE = false, int QM = (DT == 0 ? QM_KERNEL : QM_RAW)>
 __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnArgs a)
 {
     typedef typename T16<DT>::elem elem;
@@ -421,10 +335,10 @@ __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnA
     attn_stamp(0);
 
     // ---- stage K and V of this head: AT_THREADS / 8 rows x 8 chunks of 16 B per pass, at most five passes
-    // (S <= 320 on 8 waves, <= 640 on 16).  V2: every load of the head is requested before the first LDS
+    // (S <= 320 on 8 waves, <= 640 on 16).  Every load of the head is requested before the first LDS
     // write, so the staging costs one memory round trip instead of one per pass (a third of a workgroup's
     // life at S = 257 otherwise) ----
-    if constexpr (V2) {
+    {
         const int r_in = threadIdx.x >> 3, ch = threadIdx.x & 7;
         u32x4 kv[5], vv[5];
 #pragma unroll
@@ -448,26 +362,14 @@ __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnA
                 *reinterpret_cast<u32x4 *>(ldsV + row * 128 + ((ch ^ ((row >> 2) & 1)) << 4)) = t;
             }
         }
-    } else {
-        const int r_in = threadIdx.x >> 3, ch = threadIdx.x & 7;
-        for (int row = r_in; row < SP; row += AT_THREADS / 8) {
-            const int srow = row < S ? row : S - 1;  // padded keys: finite data, masked below
-            const elem *src = base + (long)srow * ld + ch * 8;
-            const u32x4 kv = *reinterpret_cast<const u32x4 *>(src + W);
-            u32x4 vv = *reinterpret_cast<const u32x4 *>(src + 2 * W);
-            *reinterpret_cast<u32x4 *>(ldsK + row * 128 + ((ch ^ (row & 7)) << 4)) = kv;
-            // V: 8-byte slot u -> u ^ ((row>>1)&3): chunk moves by bit 1, halves swap by bit 0
-            if ((row >> 1) & 1) vv = u32x4{vv[2], vv[3], vv[0], vv[1]};
-            *reinterpret_cast<u32x4 *>(ldsV + row * 128 + ((ch ^ ((row >> 2) & 1)) << 4)) = vv;
-        }
     }
     // Query tiles.  A sequence of 16 n + 1 tokens whose tile count leaves ONE tile over after whole rounds of
     // the waves (S = 257 on 8 waves: 17 tiles) would keep seven waves idle for a third round that holds a
     // single query row: that tile's KEYS are split over all waves instead and the partial (m, l, O) merged
-    // through LDS (V2 kernels, not causal).  Whether a tile is split depends on S alone, never on q_rows, so
+    // through LDS (not causal).  Whether a tile is split depends on S alone, never on q_rows, so
     // ec_attention_rows stays a bit-exact prefix of ec_attention.
     const int n_qt_all = (S + 15) / 16;
-    const bool lone = V2 && attn_lone_tile(S, a.causal, AT_WAVES);
+    const bool lone = attn_lone_tile(S, a.causal, AT_WAVES);
     const int n_qt_req = (a.q_rows + 15) / 16;                           // tiles the caller asked for
     const int n_qt = lone ? min(n_qt_req, n_qt_all - 1) : n_qt_req;      // ... that are walked tile by tile
     const bool do_lone = lone && n_qt_req == n_qt_all;
@@ -512,57 +414,32 @@ __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnA
         // tile path cost a memory round trip each)
         int g = g_lane, c16 = c_lane;
         asm volatile("" : "+v"(g), "+v"(c16));
-        float lsum, m_log2;   // softmax denominator and maximum (log2 domain, scaled scores)
         f32x4 o[5];
 #pragma unroll
         for (int dt = 0; dt < 5; dt++) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (V2) {
-            f32x4 mneg = f32x4{0.f, 0.f, 0.f, 0.f};
-            scale_q(qf);
-            if (!a.causal) {
-                attn_keys<DT, QM>(ldsK, ldsV, S, 0, S >> 5, true, qf, ones, a.scale_log2e, mneg, o, g, c16);
-            } else {
-                const int klimit = qrow < S ? qrow + 1 : S;   // keys < klimit are visible
-                // rows of this tile see no key beyond 16 qt + 15: skip the blocks past it; blocks entirely
-                // below every lane's klimit (16 qt + 1 ..) need no masking
-                const int kend = min(SP, ((qt * 16 + 16 + 31) / 32) * 32);
-                const int kfree = min(qt * 16 + 1, kend);
-                bool down = true;
-                int key0 = 0;
-                for (; key0 + 64 <= kfree; key0 += 64, down = false)
-                    attn_block2<DT, 2, false, QM>(ldsK, ldsV, key0, klimit, qf, ones, down, a.scale_log2e, mneg, o, g, c16);
-                for (; key0 + 64 <= kend; key0 += 64, down = false)
-                    attn_block2<DT, 2, true, QM>(ldsK, ldsV, key0, klimit, qf, ones, down, a.scale_log2e, mneg, o, g, c16);
-                if (key0 < kend)
-                    attn_block2<DT, 1, true, QM>(ldsK, ldsV, key0, klimit, qf, ones, down, a.scale_log2e, mneg, o, g, c16);
-            }
-            lsum = o[4][0];      // every row of the ones tile carries the query's row sum
-            m_log2 = QM != QM_RAW ? -mneg[0] : -mneg[0] * a.scale_log2e;
+        f32x4 mneg = f32x4{0.f, 0.f, 0.f, 0.f};
+        scale_q(qf);
+        if (!a.causal) {
+            attn_keys<DT, QM>(ldsK, ldsV, S, 0, S >> 5, true, qf, ones, a.scale_log2e, mneg, o, g, c16);
         } else {
-            const int klimit = a.causal ? (qrow < S ? qrow + 1 : S) : S;
-            const int kend = a.causal ? min(SP, ((qt * 16 + 16 + 31) / 32) * 32) : SP;
-            const int kfree = a.causal ? qt * 16 + 1 : S;
-            float m_run = -1e30f, l_run = 0.f;
-            f32x4 o4[4];
-#pragma unroll
-            for (int dt = 0; dt < 4; dt++) o4[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const int klimit = qrow < S ? qrow + 1 : S;   // keys < klimit are visible
+            // rows of this tile see no key beyond 16 qt + 15: skip the blocks past it; blocks entirely
+            // below every lane's klimit (16 qt + 1 ..) need no masking
+            const int kend = min(SP, ((qt * 16 + 16 + 31) / 32) * 32);
+            const int kfree = min(qt * 16 + 1, kend);
+            bool down = true;
             int key0 = 0;
-            for (; key0 + 64 <= kend; key0 += 64) {
-                if (key0 + 64 <= kfree)
-                    attn_block<DT, 2, false>(ldsK, ldsV, key0, klimit, qf, a.scale_log2e, m_run, l_run, o4,
-                                             g, c16);
-                else
-                    attn_block<DT, 2, true>(ldsK, ldsV, key0, klimit, qf, a.scale_log2e, m_run, l_run, o4,
-                                            g, c16);
-            }
+            for (; key0 + 64 <= kfree; key0 += 64, down = false)
+                attn_block2<DT, 2, false, QM>(ldsK, ldsV, key0, klimit, qf, ones, down, a.scale_log2e, mneg, o, g, c16);
+            for (; key0 + 64 <= kend; key0 += 64, down = false)
+                attn_block2<DT, 2, true, QM>(ldsK, ldsV, key0, klimit, qf, ones, down, a.scale_log2e, mneg, o, g, c16);
             if (key0 < kend)
-                attn_block<DT, 1, true>(ldsK, ldsV, key0, klimit, qf, a.scale_log2e, m_run, l_run, o4, g,
-                                        c16);
-            lsum = xor_sum(l_run);
-            m_log2 = m_run * a.scale_log2e;
-#pragma unroll
-            for (int dt = 0; dt < 4; dt++) o[dt] = o4[dt];
+                attn_block2<DT, 1, true, QM>(ldsK, ldsV, key0, klimit, qf, ones, down, a.scale_log2e, mneg, o, g, c16);
         }
+        // softmax denominator (every row of the ones tile carries the query's row sum) and maximum (log2 domain,
+        // scaled scores)
+        const float lsum = o[4][0];
+        const float m_log2 = QM != QM_RAW ? -mneg[0] : -mneg[0] * a.scale_log2e;
 
         // ---- normalise and store: lane owns query c16, head dims 16 g .. 16 g + 15 ----
         const float inv = 1.f / lsum;
@@ -579,50 +456,48 @@ __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnA
             *reinterpret_cast<u32x4 *>(dst + 8) = *reinterpret_cast<const u32x4 *>(&ov[8]);
         }
     }
-    if constexpr (V2) {
-        if (do_lone) {
-            // ---- the tile left over: this wave's share of its keys, then the merge ----
-            float *part = reinterpret_cast<float *>(smem + 2 * SP * 128);
-            const int steps = S >> 5;
-            const int s0 = wave * steps / AT_WAVES, s1 = (wave + 1) * steps / AT_WAVES;
-            const bool tail = wave == AT_WAVES - 1;
-            int g = g_lane, c16 = c_lane;
-            asm volatile("" : "+v"(g), "+v"(c16));
-            qf[0] = qn[0], qf[1] = qn[1];
-            scale_q(qf);
-            f32x4 o[5];
+    if (do_lone) {
+        // ---- the tile left over: this wave's share of its keys, then the merge ----
+        float *part = reinterpret_cast<float *>(smem + 2 * SP * 128);
+        const int steps = S >> 5;
+        const int s0 = wave * steps / AT_WAVES, s1 = (wave + 1) * steps / AT_WAVES;
+        const bool tail = wave == AT_WAVES - 1;
+        int g = g_lane, c16 = c_lane;
+        asm volatile("" : "+v"(g), "+v"(c16));
+        qf[0] = qn[0], qf[1] = qn[1];
+        scale_q(qf);
+        f32x4 o[5];
 #pragma unroll
-            for (int dt = 0; dt < 5; dt++) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            f32x4 mneg = f32x4{0.f, 0.f, 0.f, 0.f};
-            attn_keys<DT, QM>(ldsK, ldsV, S, s0, s1, tail, qf, ones, a.scale_log2e, mneg, o, g, c16);
-            if (c16 == 0) {   // the tile's one valid query (row S - 1) lives in lanes 0, 16, 32, 48
-                float *dst = part + wave * ATTN_PART;
+        for (int dt = 0; dt < 5; dt++) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 mneg = f32x4{0.f, 0.f, 0.f, 0.f};
+        attn_keys<DT, QM>(ldsK, ldsV, S, s0, s1, tail, qf, ones, a.scale_log2e, mneg, o, g, c16);
+        if (c16 == 0) {   // the tile's one valid query (row S - 1) lives in lanes 0, 16, 32, 48
+            float *dst = part + wave * ATTN_PART;
 #pragma unroll
-                for (int dt = 0; dt < 4; dt++)
-                    *reinterpret_cast<f32x4 *>(dst + 16 * g + 4 * dt) = o[dt];
-                if (g == 0) {
-                    const float mw = QM != QM_RAW ? -mneg[0] : -mneg[0] * a.scale_log2e;   // log2 units
-                    dst[64] = (s1 > s0 || tail) ? mw : -1e30f;   // a wave without keys: weight 0
-                    dst[65] = o[4][0];
-                }
+            for (int dt = 0; dt < 4; dt++)
+                *reinterpret_cast<f32x4 *>(dst + 16 * g + 4 * dt) = o[dt];
+            if (g == 0) {
+                const float mw = QM != QM_RAW ? -mneg[0] : -mneg[0] * a.scale_log2e;   // log2 units
+                dst[64] = (s1 > s0 || tail) ? mw : -1e30f;   // a wave without keys: weight 0
+                dst[65] = o[4][0];
             }
-            __syncthreads();
-            if (wave == 0) {   // lane = head dim
-                float m = -1e30f;
+        }
+        __syncthreads();
+        if (wave == 0) {   // lane = head dim
+            float m = -1e30f;
 #pragma unroll
-                for (int w = 0; w < AT_WAVES; w++) m = fmaxf(m, part[w * ATTN_PART + 64]);
-                float num = 0.f, den = 0.f;
+            for (int w = 0; w < AT_WAVES; w++) m = fmaxf(m, part[w * ATTN_PART + 64]);
+            float num = 0.f, den = 0.f;
 #pragma unroll
-                for (int w = 0; w < AT_WAVES; w++) {
-                    const float f = __builtin_amdgcn_exp2f(part[w * ATTN_PART + 64] - m);
-                    num = __builtin_fmaf(f, part[w * ATTN_PART + lane], num);
-                    den = __builtin_fmaf(f, part[w * ATTN_PART + 65], den);
-                }
-                const int qrow = S - 1;
-                ((elem *)a.out)[((long)seq * a.q_rows + qrow) * W + head * 64 + lane] = to16(num / den, elem());
-                if (LSE && lane == 0)
-                    a.lse[((long)seq * a.heads + head) * S + qrow] = m + __builtin_amdgcn_logf(den);
+            for (int w = 0; w < AT_WAVES; w++) {
+                const float f = __builtin_amdgcn_exp2f(part[w * ATTN_PART + 64] - m);
+                num = __builtin_fmaf(f, part[w * ATTN_PART + lane], num);
+                den = __builtin_fmaf(f, part[w * ATTN_PART + 65], den);
             }
+            const int qrow = S - 1;
+            ((elem *)a.out)[((long)seq * a.q_rows + qrow) * W + head * 64 + lane] = to16(num / den, elem());
+            if (LSE && lane == 0)
+                a.lse[((long)seq * a.heads + head) * S + qrow] = m + __builtin_amdgcn_logf(den);
         }
     }
     attn_stamp(2);
@@ -1053,171 +928,6 @@ __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl2_kernel(const A
     }
 }
 
-#ifdef EC_ATTN_DIAG
-// ---------------------------------------------------------------------------------------
-// DIAGNOSTIC BUILD ONLY (measured, not kept: profiles/r5_attention.md).
-// Key-half workgroup pair (round 5) for sequences whose K and V leave room for one 16-wave workgroup per CU only
-// (S = 577: 148 KiB).  Each (sequence, head) is handled by TWO 8-wave workgroups that stage HALF of the keys and
-// values each (keys [0, split) / [split, S), split a multiple of 32), so two workgroups are resident per CU and one's
-// staging runs under the other's compute (the one-workgroup kernel spends 26 % of its time in un-overlapped staging,
-// profiles/r4_attention.md) and the 37 query tiles make 4.6 rounds of 8 waves instead of 2.3 of 16 (92 % against 77 %
-// occupancy).  Every workgroup walks ALL query tiles against its keys; a tile's partial (m, l, O) goes to a fp32
-// workspace, a ticket per (unit, tile) says who is second, and the second one merges -- always as (half 0, half 1), so
-// the result does not depend on who finished first -- and writes the output.  The pair is mapped onto ONE XCD
-// (workgroup ids b and b + 8 share an XCD): the exchange stays in that XCD's L2.
-// ---------------------------------------------------------------------------------------
-constexpr int PAIR_REC = 68;     // floats per query in a partial record: O[64], m (log2 units), l, 2 pad
-template <int DT, int QM>
-__global__ __launch_bounds__(512, 2) void attention_pair_kernel(const AttnArgs a, float *part, int *ticket, int split, int SPL,
-                                                                int n_units)
-{
-    typedef typename T16<DT>::elem elem;
-    typedef typename T16<DT>::v8 v8;
-    constexpr int WAVES = 8, THREADS = 512;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int S = a.S, W = a.W;
-    const int w = blockIdx.x, half = (w >> 3) & 1, unit = (w >> 4) * 8 + (w & 7);
-    if (unit >= n_units) return;
-    const int key0 = half ? split : 0, Sl = half ? S - split : split;      // this workgroup's keys
-    unsigned char *ldsK = smem;
-    unsigned char *ldsV = smem + SPL * 128;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g_lane = lane >> 4, c_lane = lane & 15;
-    const int head = unit % a.heads, seq = unit / a.heads;
-    const long ld = 3L * W;
-    const elem *base = (const elem *)a.qkv + (long)seq * S * ld + head * 64;
-    {   // stage this half's K and V: every load in flight before the first LDS write (rows behind the last key: copies of it)
-        const int r_in = threadIdx.x >> 3, ch = threadIdx.x & 7;
-        u32x4 kv[5], vv[5];
-#pragma unroll
-        for (int p = 0; p < 5; p++) {
-            const int row = r_in + p * (THREADS / 8);
-            if (row < SPL) {
-                const int srow = key0 + (row < Sl ? row : Sl - 1);
-                const elem *src = base + (long)srow * ld + ch * 8;
-                kv[p] = *reinterpret_cast<const u32x4 *>(src + W);
-                vv[p] = *reinterpret_cast<const u32x4 *>(src + 2 * W);
-            }
-        }
-#pragma unroll
-        for (int p = 0; p < 5; p++) {
-            const int row = r_in + p * (THREADS / 8);
-            if (row < SPL) {
-                *reinterpret_cast<u32x4 *>(ldsK + row * 128 + ((ch ^ (row & 7)) << 4)) = kv[p];
-                u32x4 t = vv[p];
-                if ((row >> 1) & 1) t = u32x4{t[2], t[3], t[0], t[1]};
-                *reinterpret_cast<u32x4 *>(ldsV + row * 128 + ((ch ^ ((row >> 2) & 1)) << 4)) = t;
-            }
-        }
-    }
-    const int n_qt_all = (S + 15) / 16, n_qt = (a.q_rows + 15) / 16;
-    v8 qf[2], qn[2];
-    auto load_q = [&](int qt, v8(&dst)[2]) {
-        int qsrc = qt * 16 + c_lane;
-        qsrc = qsrc < S ? qsrc : S - 1;
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++)
-            dst[ks] = *reinterpret_cast<const v8 *>(base + (long)qsrc * ld + ks * 32 + g_lane * 8);
-    };
-    if (wave < n_qt) load_q(wave, qn);
-    __syncthreads();
-    v8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; j++) ones[j] = to16(1.f, elem());
-    asm volatile("" : "+v"(ones));
-    for (int qt = wave; qt < n_qt; qt += WAVES) {
-        qf[0] = qn[0], qf[1] = qn[1];
-        if (qt + WAVES < n_qt) load_q(qt + WAVES, qn);
-        int g = g_lane, c16 = c_lane;
-        asm volatile("" : "+v"(g), "+v"(c16));
-        f32x4 o[5];
-#pragma unroll
-        for (int dt = 0; dt < 5; dt++) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        f32x4 mneg = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (QM == QM_KERNEL) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-                for (int j = 0; j < 8; j++) qf[ks][j] = to16((float)qf[ks][j] * a.scale_log2e, elem());
-        }
-        attn_keys<DT, QM>(ldsK, ldsV, Sl, 0, Sl >> 5, true, qf, ones, a.scale_log2e, mneg, o, g, c16);
-        const float l_me = o[4][0];
-        const float m_me = QM != QM_RAW ? -mneg[0] : -mneg[0] * a.scale_log2e;     // log2 units
-        // ---- this half's partial -> workspace (no wait here: the exchange of all of the wave's tiles comes behind the loop) ----
-        // The exchange is made of agent-scope ACCESSES, not fences: stores and loads with the sc1 bit are coherent at the
-        // device's coherence point line by line.  (The first version took an acq_rel ticket per tile: hipcc brackets that
-        // with buffer_wbl2 / buffer_inv -- a write-back and an invalidate of the whole L2 -- 26 x slower than the kernel it
-        // was meant to beat; the second waited per tile for store acknowledgement, ticket and loads in a row: 3.3 x slower.)
-        float *mine = part + ((((long)unit * n_qt_all + qt) * 2 + half) * 16 + c16) * PAIR_REC;
-        if (a.causal == 2) continue;      // (timing experiment: no exchange at all -- nothing is written)
-        if (a.causal != 1) {              // write-back stores: the pair shares an XCD, hence an L2 (the form that is correct and least slow)
-#pragma unroll
-            for (int dt = 0; dt < 4; dt++) *reinterpret_cast<f32x4 *>(mine + 16 * g + 4 * dt) = o[dt];
-            if (g == 0) *reinterpret_cast<float2 *>(mine + 64) = make_float2(m_me, l_me);
-            continue;
-        }
-        // (a.causal == 1: agent-scope write-through stores -- slower still, and the merger's sc1 loads of its OWN partial
-        // came back stale in this form)
-#pragma unroll
-        for (int dt = 0; dt < 4; dt++)
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(mine + 16 * g + 4 * dt), "v"(o[dt]) : "memory");
-        if (g == 0) {
-            const float2 mlv = make_float2(m_me, l_me);
-            asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(mine + 64), "v"(mlv) : "memory");
-        }
-    }
-    if (a.causal == 2) return;
-    // ---- exchange: every partial of this wave is acknowledged, then one ticket per tile (lane i takes tile wave + 8 i),
-    // then the tiles this workgroup came second on are merged -- as (half 0, half 1) whoever merges -- and written ----
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int my_tiles = n_qt > wave ? (n_qt - wave + WAVES - 1) / WAVES : 0;
-    int old = 0;
-    if (lane < my_tiles)
-        old = __hip_atomic_fetch_add(ticket + (long)unit * n_qt_all + wave + WAVES * lane, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long second = __builtin_amdgcn_ballot_w64(old != 0);
-    for (int i = 0; i < my_tiles; i++) {
-        if (!((second >> i) & 1)) continue;       // first on this tile: the other half's workgroup finishes it
-        const int qt = wave + WAVES * i, qrow = qt * 16 + c_lane, g = g_lane, c16 = c_lane;
-        const long rec = ((long)unit * n_qt_all + qt) * 2;
-        const float *p0 = part + ((rec + 0) * 16 + c16) * PAIR_REC, *p1 = part + ((rec + 1) * 16 + c16) * PAIR_REC;
-        f32x4 o0[4], o1[4];
-        float2 ml0, ml1;
-#pragma unroll
-        for (int dt = 0; dt < 4; dt++) {
-            asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(o0[dt]) : "v"(p0 + 16 * g + 4 * dt) : "memory");
-            asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(o1[dt]) : "v"(p1 + 16 * g + 4 * dt) : "memory");
-        }
-        asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(ml0) : "v"(p0 + 64) : "memory");
-        asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(ml1) : "v"(p1 + 64) : "memory");
-        asm volatile("" : "+v"(o0[0]), "+v"(o0[1]), "+v"(o0[2]), "+v"(o0[3]), "+v"(o1[0]), "+v"(o1[1]), "+v"(o1[2]), "+v"(o1[3]), "+v"(ml0));
-        const float m = fmaxf(ml0.x, ml1.x);
-        const float f0 = __builtin_amdgcn_exp2f(ml0.x - m), f1 = __builtin_amdgcn_exp2f(ml1.x - m);
-        const float inv = 1.f / (ml0.y * f0 + ml1.y * f1);
-        if (lane == 0) ticket[(long)unit * n_qt_all + qt] = 0;     // ready for the next launch on this workspace
-        if (qrow < a.q_rows) {
-            elem ov[16];
-#pragma unroll
-            for (int dt = 0; dt < 4; dt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) ov[4 * dt + r] = to16((o0[dt][r] * f0 + o1[dt][r] * f1) * inv, elem());
-            elem *dst = (elem *)a.out + ((long)seq * a.q_rows + qrow) * W + head * 64 + g * 16;
-            *reinterpret_cast<u32x4 *>(dst) = *reinterpret_cast<const u32x4 *>(&ov[0]);
-            *reinterpret_cast<u32x4 *>(dst + 8) = *reinterpret_cast<const u32x4 *>(&ov[8]);
-        }
-    }
-}
-
-#endif
-
-#ifdef EC_ATTN_DIAG
-#include "attention_diag.inc"     // attention32_kernel, the round-1 fp32 kernel: A / B forms of the diagnostic build
-#endif
-
-#ifdef EC_ATTN_DIAG
-int g_attn_variant = 0;
-#endif
-
 template <int DT> int dispatch(const AttnArgs &a, int n_seq, int heads, hipStream_t s)
 {
     const int n32 = (a.S + 31) / 32;
@@ -1239,17 +949,10 @@ template <int DT> int dispatch(const AttnArgs &a, int n_seq, int heads, hipStrea
     void (*kern)(const AttnArgs) = a.lse ? (wide ? attention_kernel<DT, 16, true> : attention_kernel<DT, 8, true>)
                                          : (wide ? attention_kernel<DT, 16> : attention_kernel<DT, 8>);
     if (a.q_scaled == 1)   // the inference towers (never with a log-sum-exp)
-        kern = wide ? attention_kernel<DT, 16, false, true, QM_INPUT> : attention_kernel<DT, 8, false, true, QM_INPUT>;
+        kern = wide ? attention_kernel<DT, 16, false, QM_INPUT> : attention_kernel<DT, 8, false, QM_INPUT>;
     if (a.q_scaled == 2)   // a plain q, every score scaled in fp32: q is rounded ONCE (the split-operand blocks behind the
                            // fp32-attention ones; QM_KERNEL's second rounding of q cost configs[2] 30 % there)
-        kern = wide ? attention_kernel<DT, 16, false, true, QM_RAW> : attention_kernel<DT, 8, false, true, QM_RAW>;
-#ifdef EC_ATTN_DIAG
-    if (g_attn_variant == 5 && a.q_scaled && DT == EC_F16 && !a.causal && !a.lse)   // round 4: 32-query tiles (A / B)
-        kern = wide ? attention32_kernel<16> : attention32_kernel<8>;
-    if (g_attn_variant == 1 && !a.q_scaled)   // round 1 / 2 block (per-block maximum, vector-ALU row sum), for A/B
-        kern = a.lse ? (wide ? attention_kernel<DT, 16, true, false> : attention_kernel<DT, 8, true, false>)
-                     : (wide ? attention_kernel<DT, 16, false, false> : attention_kernel<DT, 8, false, false>);
-#endif
+        kern = wide ? attention_kernel<DT, 16, false, QM_RAW> : attention_kernel<DT, 8, false, QM_RAW>;
     const int nw = wide ? 16 : 8;
     // always the full carve (one attribute call per kernel and device, thread-safe)
     if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024)) return rc;
@@ -1449,7 +1152,6 @@ extern "C" __attribute__((visibility("default"))) int ec_attn_stamps_read(unsign
 {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(ec_attn_stamps), (size_t)n * 8) == hipSuccess ? 0 : 1;
 }
-extern "C" __attribute__((visibility("default"))) void ec_attn_set_variant(int v) { g_attn_variant = v; }
 #endif
 
 static int attention_rows(const void *qkv, void *out, int n_seq, int S, int width, int heads, int causal, int q_rows,
@@ -1536,21 +1238,6 @@ extern "C" EC_API int ec_attention_f32(const float *qkv, void *out_hi, void *out
     EC_REQUIRE(qkv && out_hi && out_lo, "ec_attention_f32: null buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_ATTENTION, s, 4.0 * S * S * 64.0 * heads * n_seq, 0);
-#ifdef EC_ATTN_DIAG
-    if (g_attn_variant == 6) {      // the round-1 kernel (vector ALU, K / V rows straight from L2), for the A / B
-        const int lds = (16 * 64 + 16 * S) * 4;
-        EC_REQUIRE(lds <= 64 * 1024, "ec_attention_f32: sequence length %d too long", S);
-        const unsigned grid = (unsigned)n_seq * heads * ((S + 15) / 16);
-        if (dtype == EC_F16)
-            hipLaunchKernelGGL(attention_f32_kernel<EC_F16>, dim3(grid), dim3(256), lds, s, qkv, out_hi, out_lo, S, width,
-                               heads, causal);
-        else
-            hipLaunchKernelGGL(attention_f32_kernel<EC_BF16>, dim3(grid), dim3(256), lds, s, qkv, out_hi, out_lo, S, width,
-                               heads, causal);
-        EC_CHECK_HIP(hipGetLastError());
-        return EC_OK;
-    }
-#endif
     const long blocks = (long)n_seq * heads * ((S + 63) / 64);
     EC_REQUIRE(blocks < (1L << 31), "ec_attention_f32: %ld workgroups", blocks);
     if (dtype == EC_F16)
@@ -1564,15 +1251,6 @@ extern "C" EC_API int ec_attention_f32(const float *qkv, void *out_hi, void *out
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }
-
-// EC_ATTN_SPLIT_F32 (tools/bench_attn_split.py, debug_attn_hl.py: force the fp32-MFMA kernel) is read by the diagnostic
-// build only: the product library's kernel choice -- numerics and speed of the tolerance mode -- never depends on the
-// process environment
-#ifdef EC_ATTN_DIAG
-static bool split_force_f32() { return getenv("EC_ATTN_SPLIT_F32") != nullptr; }
-#else
-static constexpr bool split_force_f32() { return false; }
-#endif
 
 extern "C" EC_API int ec_attention_split(const void *qkv_hi, const void *qkv_lo, void *out_hi, void *out_lo, int n_seq, int S,
                                          int width, int heads, int q_prescaled, int dtype, ec_stream_t stream)
@@ -1589,7 +1267,7 @@ extern "C" EC_API int ec_attention_split(const void *qkv_hi, const void *qkv_lo,
     // instruction (attention_hl_kernel); anything else: fp32 on v_mfma_f32_16x16x4_f32
     const int sp = 32 * ((S + 31) / 32);
     const int hl_lds = 4 * sp * 128 + (attn_lone_tile(S, 0, HL_WAVES) ? HL_WAVES * ATTN_PART * 4 : 0);
-    if (dtype == EC_F16 && !q_prescaled && hl_lds <= 160 * 1024 && !split_force_f32()) {
+    if (dtype == EC_F16 && !q_prescaled && hl_lds <= 160 * 1024) {
         AttnHlArgs h;
         h.qkv_hi = static_cast<const _Float16 *>(qkv_hi), h.qkv_lo = static_cast<const _Float16 *>(qkv_lo);
         h.out_hi = static_cast<_Float16 *>(out_hi), h.out_lo = static_cast<_Float16 *>(out_lo);
@@ -1603,8 +1281,7 @@ extern "C" EC_API int ec_attention_split(const void *qkv_hi, const void *qkv_lo,
     {
         const int split = (S / 2) & ~31, sl = S - split;
         const int spl = (sl & 31) == 1 ? ((sl + 15 + 15) / 16) * 16 : ((sl + 31) / 32) * 32;     // the odd key's 16 copies, else whole steps
-        if (dtype == EC_F16 && !q_prescaled && split >= 32 && 4 * spl * 128 <= 160 * 1024 && (S + 15) / 16 <= HL_WAVES * HL2_TILES &&
-            !split_force_f32()) {
+        if (dtype == EC_F16 && !q_prescaled && split >= 32 && 4 * spl * 128 <= 160 * 1024 && (S + 15) / 16 <= HL_WAVES * HL2_TILES) {
             AttnHlArgs h;
             h.qkv_hi = static_cast<const _Float16 *>(qkv_hi), h.qkv_lo = static_cast<const _Float16 *>(qkv_lo);
             h.out_hi = static_cast<_Float16 *>(out_hi), h.out_lo = static_cast<_Float16 *>(out_lo);
@@ -1627,52 +1304,3 @@ extern "C" EC_API int ec_attention_split(const void *qkv_hi, const void *qkv_lo,
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }
-
-#ifdef EC_ATTN_DIAG
-// (diagnostic build only; not part of the public header)
-// ---- key-half workgroup pair (see attention_pair_kernel) ----
-static inline int pair_split(int S) { return (S / 2) & ~31; }
-static inline int pair_rows(int S)
-{
-    const int split = pair_split(S), sl = S - split;          // the second half is the longer one
-    return (sl & 31) == 1 ? ((sl + 15 + 15) / 16) * 16 : ((sl + 31) / 32) * 32;   // its odd key's 16 copies, else whole steps
-}
-extern "C" __attribute__((visibility("default"))) size_t ec_attention_pair_workspace_bytes(int n_seq, int S, int heads)
-{
-    if (n_seq <= 0 || S <= 0 || heads <= 0) return 0;
-    const size_t tiles = (size_t)n_seq * heads * ((S + 15) / 16);
-    return tiles * 2 * 16 * PAIR_REC * 4 + ((tiles * 4 + 255) & ~(size_t)255);
-}
-extern "C" __attribute__((visibility("default"))) int ec_attention_pair(const void *qkv, void *out, int n_seq, int S, int width, int heads, int q_rows,
-                                        int q_scaled, int dtype, void *workspace, size_t workspace_bytes, ec_stream_t stream)
-{
-    EC_REQUIRE(n_seq >= 0 && S >= 64 && heads > 0 && width == heads * 64, "ec_attention_pair: bad shape (S >= 64, head dim 64)");
-    EC_REQUIRE(q_rows >= 1 && q_rows <= S, "ec_attention_pair: q_rows=%d outside 1..%d", q_rows, S);
-    if (n_seq == 0) return EC_OK;
-    EC_REQUIRE(qkv && out && workspace && ((uintptr_t)workspace & 255) == 0, "ec_attention_pair: null or misaligned buffer");
-    const size_t need = ec_attention_pair_workspace_bytes(n_seq, S, heads);
-    if (workspace_bytes < need)
-        return ec::fail(EC_ERR_WORKSPACE, "ec_attention_pair: workspace %zu < %zu bytes", workspace_bytes, need);
-    const int SPL = pair_rows(S), lds = SPL * 128 * 2;
-    EC_REQUIRE(SPL <= 5 * 64 && lds <= 80 * 1024, "ec_attention_pair: sequence length %d needs %d bytes of LDS per workgroup (<= 81920)", S, lds);
-    AttnArgs a;
-    a.qkv = qkv, a.out = out, a.S = S, a.W = width, a.heads = heads, a.causal = 0, a.q_rows = q_rows, a.lse = nullptr;
-    a.scale_log2e = 0.125f * 1.4426950408889634f, a.q_scaled = q_scaled;
-    if (const char *dbg = getenv("EC_PAIR_DEBUG")) a.causal = atoi(dbg);      // 1: sc1 stores, 2: no exchange (timing experiments)
-    const size_t tiles = (size_t)n_seq * heads * ((S + 15) / 16);
-    float *part = static_cast<float *>(workspace);
-    int *ticket = reinterpret_cast<int *>(static_cast<unsigned char *>(workspace) + tiles * 2 * 16 * PAIR_REC * 4);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    EC_CHECK_HIP(hipMemsetAsync(ticket, 0, tiles * 4, s));
-    void (*kern)(const AttnArgs, float *, int *, int, int, int) = nullptr;
-    if (dtype == EC_F16) kern = q_scaled ? attention_pair_kernel<EC_F16, QM_INPUT> : attention_pair_kernel<EC_F16, QM_KERNEL>;
-    else if (dtype == EC_BF16) kern = q_scaled ? attention_pair_kernel<EC_BF16, QM_INPUT> : attention_pair_kernel<EC_BF16, QM_RAW>;
-    else return ec::fail(EC_ERR_INVALID, "ec_attention_pair: unknown dtype %d", dtype);
-    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 80 * 1024)) return rc;
-    const int n_units = n_seq * heads;
-    ec::ProfScope prof(ec::PROF_ATTENTION, s, 4.0 * q_rows * S * 64.0 * heads * n_seq, (double)n_seq * width * 2.0 * (2.0 * S + 2.0 * q_rows));
-    hipLaunchKernelGGL(kern, dim3((unsigned)((n_units + 7) / 8 * 16)), dim3(512), lds, s, a, part, ticket, pair_split(S), SPL, n_units);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
-}
-#endif

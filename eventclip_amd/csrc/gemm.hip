@@ -74,7 +74,7 @@ struct GemmArgs {
     int nf8;
     long f8_oa[2], f8_ow[2];    // bytes from A / W to the e4m3 operands of fp8 segment s
     int f8_scale[2];            // e8m0 byte (x 0x01010101) on the W side of segment s: 2^(byte - 127) undoes both operands' scales
-    float aux8_scale;           // STORE16 / GELU16 with the lo output as e4m3 (HLM bit 3): lo . aux8_scale, one byte per element
+    float aux8_scale;           // STORE16 / GELU16 with the lo output as e4m3 (LO_E4M3): lo . aux8_scale, one byte per element
 };
 
 // sixteen zero bytes for the LDS-DMA lanes whose reduction row does not exist (transposed operands)
@@ -84,8 +84,6 @@ __device__ __attribute__((aligned(16))) unsigned int tn_zero16[4];
 // spreads the 8 rows a 32-lane half of ds_read_b64_tr_b16 takes ({0..3, 8..11} + 4 hh + 16 n) over the 64 banks
 __device__ __forceinline__ int tn_key(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
 
-
-__device__ __forceinline__ int swz_key(int row) { return (row & 7) ^ ((row >> 3) & 6); }
 
 template <int CTRL> __device__ __forceinline__ float dpp_f32(float v)
 {
@@ -139,11 +137,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk)
     return start + (bid >> 3);
 }
 
-// (The direct epilogue, the general fp32 LDS-transposed epilogue and the general hi-lo epilogue are only used by the
-// diagnostic kernels now: csrc/gemm_diag.inc.  The persistent kernel runs the buffer-addressed forms below; the
-// general 16-bit form stays here for the training epilogues with a second output / input.)
-
-// 16-bit counterpart: a 16 x 64 row group is 16 rows of 128 B (pitch 144 B); after the transpose
+// General 16-bit epilogue (the training epilogues with a second output / input; everything else runs the
+// buffer-addressed forms below): a 16 x 64 row group is 16 rows of 128 B (pitch 144 B); after the transpose
 // 8 consecutive lanes cover one full 128-B row and a store instruction writes 8 whole lines.
 // scratch: 2 x 16 x 144 bytes per wave.
 template <int DT, int EPI, int TM>
@@ -270,9 +265,9 @@ __device__ __forceinline__ void epilogue16_lds(const GemmArgs &g, f32x4 (&acc)[T
 //    the counted hand-over wait of the tile loop needs.  (What is range-checked on gfx950 is the SUM of the vector
 //    and the scalar offset -- measured in round 5, when a segment's part addressed through the scalar offset read
 //    zeros: the row / column offsets here are vector offsets and the scalar one stays 0.)
-//  * The general forms above spend 64 - 80 quarter-rate v_mul_lo_u32 / v_mad_u64_u32 and ~100 64-bit vector adds
+//  * The general form above spends 64 - 80 quarter-rate v_mul_lo_u32 / v_mad_u64_u32 and ~100 64-bit vector adds
 //    per wave tile on `(long)m * ldc + col` -- more vector-ALU time than the arithmetic of the epilogue itself
-//    (tile timelines: profiles/r4_gemm.md).  They stay for the diagnostic kernels and the training epilogues.
+//    (tile timelines: profiles/r4_gemm.md).  It stays for the training epilogues.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const void *origin, long bytes)
 {
@@ -354,17 +349,11 @@ __device__ __forceinline__ void load_bias(const GemmArgs &g, int nb, f32x4 (&bia
 // `between` runs once the epilogue's first loads (bias, the first residual row groups) are issued: the kernel puts the
 // DMA requests of the next tile's first K tile there, so that they are YOUNGER than those loads -- the epilogue's first
 // wait then is for its own data only (in-order vmcnt: waiting for a load also waits for everything issued before it).
-// MODE (A / B switch, diagnostic build variants 30 .. 33): bit 0 = two scratch buffers, row group i + 1 written while
-// the transposed reads of group i are in flight; bit 1 = the residual prefetch grows from DEPTH to the whole tile.
-constexpr int HL_MODE_DEFAULT = 1;
-template <int DT, int TM, int MODE, typename F>
+// scratch: 2 x 16 x 68 floats per wave.
+template <int DT, int TM, typename F>
 __device__ __forceinline__ void epilogue_hl_buf(const GemmArgs &g, f32x4 (&acc)[TM][4], int m_base, int n_base,
                                                 int lane, float *scratch, F &&between)
 {
-    constexpr bool PIPE = (MODE & 1) != 0, GROW = (MODE & 2) != 0;
-    // cost-splitting forms of the diagnostic build (variants 34 .. 37, tools/bench_resid_split.py; WRONG results on purpose):
-    // bit 5 no residual loads (the planes read as zero), bit 6 no store of the lo plane, bit 7 no store at all
-    constexpr bool NOLOAD = (MODE & 32) != 0, NOLO = (MODE & 64) != 0, NOST = (MODE & 128) != 0;
     typedef typename T16<DT>::elem elem;
     typedef typename T16<DT>::v8 v8;
     constexpr int PITCH = 68;
@@ -384,20 +373,15 @@ __device__ __forceinline__ void epilogue_hl_buf(const GemmArgs &g, f32x4 (&acc)[
     const int svoff = r8 * g.stat_groups * 2;                              // floats
     const int sstep8 = g.stat_groups * 16;
     const int rows_left = g.M - m_base - r8;                               // row 16 i + 8 p + r8 exists iff 16 i + 8 p < rows_left
-    // Residual loads run DEPTH row groups ahead; the registers a finished row group frees (its 16 accumulators and
-    // its 16 loaded values) take the loads of TWO later groups, so the whole tile's planes are in flight from the
-    // second row group on (the epilogue is bound by the latency of these HBM reads, not by their bandwidth).
+    // Residual loads run DEPTH row groups ahead of the arithmetic (the epilogue is bound by the latency of these HBM
+    // reads, not by their bandwidth).
     constexpr int DEPTH = TM < 3 ? TM : 3;
     u32x4 xh[TM][2], xl[TM][2];
     auto fetch = [&](int i) {
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-            if constexpr (NOLOAD) {
-                xh[i][p] = xl[i][p] = u32x4{0u, 0u, 0u, 0u};
-            } else {
-                xh[i][p] = bload16(rh, voff + (2 * i + p) * step8);
-                xl[i][p] = bload16(rl, voff + (2 * i + p) * step8);
-            }
+            xh[i][p] = bload16(rh, voff + (2 * i + p) * step8);
+            xl[i][p] = bload16(rl, voff + (2 * i + p) * step8);
         }
     };
 #pragma unroll
@@ -405,23 +389,22 @@ __device__ __forceinline__ void epilogue_hl_buf(const GemmArgs &g, f32x4 (&acc)[
     between();
     // two scratch buffers per wave: row group i + 1 is written while the transposed reads of group i are in flight
     auto produce = [&](int i) {
-        float *buf = scratch + (PIPE ? (i & 1) * 16 * PITCH : 0);
+        float *buf = scratch + (i & 1) * 16 * PITCH;
 #pragma unroll
         for (int j = 0; j < 4; j++)
             *reinterpret_cast<f32x4 *>(buf + lr * PITCH + q * 16 + j * 4) = acc[i][j] + bias[j];
     };
-    if (PIPE) produce(0);
+    produce(0);
 #pragma unroll
     for (int i = 0; i < TM; i++) {
-        const float *buf = scratch + (PIPE ? (i & 1) * 16 * PITCH : 0);
-        if (!PIPE) produce(i);
+        const float *buf = scratch + (i & 1) * 16 * PITCH;
         f32x4 ta[2], tb[2];
 #pragma unroll
         for (int p = 0; p < 2; p++) {
             ta[p] = *reinterpret_cast<const f32x4 *>(buf + (r8 + 8 * p) * PITCH + c8 * 8);
             tb[p] = *reinterpret_cast<const f32x4 *>(buf + (r8 + 8 * p) * PITCH + c8 * 8 + 4);
         }
-        if (PIPE && i + 1 < TM) produce(i + 1);
+        if (i + 1 < TM) produce(i + 1);
         u32x4 oh[2], ol[2];
         float ps[2], pq[2];
 #pragma unroll
@@ -457,19 +440,12 @@ __device__ __forceinline__ void epilogue_hl_buf(const GemmArgs &g, f32x4 (&acc)[
                 oh[p] = __builtin_bit_cast(u32x4, wh), ol[p] = __builtin_bit_cast(u32x4, wl);
             }
         }
-        // before the stores (see above); two groups per finished group until everything is requested
-        if constexpr (GROW) {
-            if (DEPTH + 2 * i < TM) fetch(DEPTH + 2 * i);
-            if (DEPTH + 2 * i + 1 < TM) fetch(DEPTH + 2 * i + 1);
-        } else {
-            if (i + DEPTH < TM) fetch(i + DEPTH);
-        }
+        // before the stores (see above)
+        if (i + DEPTH < TM) fetch(i + DEPTH);
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-            if constexpr (!NOST) bstore16(oh[p], rh, voff + (2 * i + p) * step8);
-            if constexpr (!NOST && !NOLO) bstore16(ol[p], rl, voff + (2 * i + p) * step8);
-            if constexpr (NOST) asm volatile("" ::"v"(oh[p]), "v"(ol[p]));      // keep the arithmetic
-            else if constexpr (NOLO) asm volatile("" ::"v"(ol[p]));
+            bstore16(oh[p], rh, voff + (2 * i + p) * step8);
+            bstore16(ol[p], rl, voff + (2 * i + p) * step8);
         }
         if (stats) {
 #pragma unroll
@@ -488,7 +464,7 @@ __device__ __forceinline__ void epilogue_hl_buf(const GemmArgs &g, f32x4 (&acc)[
 // 16-bit outputs (STORE16 / GELU16 and their folded-LayerNorm forms).  lds_rowstat: the wave row's 128 statistics
 // pairs in LDS (has_lds; always a pointer INTO the shared array, so that the reads compile to ds_read and not to
 // flat loads, whose s_waitcnt vmcnt(0) lgkmcnt(0) also waited for the next tile's first K tile), else g.rowstat
-template <int DT, int EPI, int TM, bool HAS_LDS, bool EARLY = false, bool LOUT = false, bool LOUT8 = false, typename F>
+template <int DT, int EPI, int TM, bool HAS_LDS, bool LOUT = false, bool LOUT8 = false, typename F>
 __device__ __forceinline__ void epilogue16_buf(const GemmArgs &g, f32x4 (&acc)[TM][4], int m_base, int n_base,
                                                int lane, unsigned char *scratch, const float *lds_rowstat, F &&between)
 {
@@ -529,7 +505,6 @@ __device__ __forceinline__ void epilogue16_buf(const GemmArgs &g, f32x4 (&acc)[T
             }
         }
     }
-    if constexpr (EARLY) between();     // (A / B: the requests in front of the first use of bias, rounds 1 - 3 and early round 4)
     const __amdgpu_buffer_rsrc_t rc = tile_rsrc(reinterpret_cast<char *>(g.C) + ((long)m_base * g.ldc + n_base) * 2,
                                                 tile_span(g.M, m_base, TM * 16, g.ldc * 2));
     const bool col_ok = n_base + (lane & 7) * 8 < g.N;
@@ -633,11 +608,9 @@ __device__ __forceinline__ void epilogue16_buf(const GemmArgs &g, f32x4 (&acc)[T
     // wait-count pass does not count the LDS-DMA requests when it waits for those loads (it asks for vmcnt(1) and
     // vmcnt(0) where 9 and 8 would do), so with the requests in front of that use every tile's epilogue opened with a
     // wait for the whole first K tile of the next one
-    if constexpr (!EARLY) {
-        __builtin_amdgcn_sched_barrier(0);     // (all of produce(0), hence every such wait, stays in front of the requests)
-        between();
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    __builtin_amdgcn_sched_barrier(0);     // (all of produce(0), hence every such wait, stays in front of the requests)
+    between();
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < TM; i++) {
         const unsigned char *buf = scratch + (i & 1) * 16 * PITCH;
@@ -740,21 +713,25 @@ __device__ __forceinline__ void raster(int id, int tiles_m, int tiles_n, int &tm
 // is on its way into staging buffer 0 while the epilogue drains the accumulators through a
 // scratch area in buffer 1, so neither the workgroup turnaround (~1.5 k cycles) nor the
 // prologue's HBM latency (~2.9 k cycles of a 48 k-cycle tile at K = 1024) is exposed.
-// TL (diagnostic build): 1 = per-tile timeline records as in gemm2p_kernel<DBG = 9>; 2 = nothing but (s_memtime,
-// s_memrealtime) of wave 0 at the workgroup's start and end -> args.diag[4 b .. 4 b + 3]: the in-kernel clock
-// (shader cycles per 100 MHz tick) with no stamp inside the tile loop.
+// TL (diagnostic build): 1 = per-tile timeline records -> args.diag[8 id .. 8 id + 7] of tile id: [0] HW_ID of the
+// workgroup, [1 .. 5] s_memtime at the tile's start, main loop start, main loop end, epilogue end and hand-over,
+// [6] XCC_ID; 2 = nothing but (s_memtime, s_memrealtime) of wave 0 at the workgroup's start and end ->
+// args.diag[4 b .. 4 b + 3]: the in-kernel clock (shader cycles per 100 MHz tick) with no stamp inside the tile loop.
 // ---------------------------------------------------------------------------------------
 // SEG: the reduction runs over g.nseg segments (split-precision operands, see GemmArgs): K tile t belongs to segment
 // t / (K / 64).  A segment's parts are reached by rebuilding the tile's descriptors on the other part at the segment
 // change (2 - 3 times per tile, scalar work; the instruction's scalar offset is no way there: it IS part of the range
 // check on gfx950 -- offset + soffset >= num_records reads zeros -- so a range that covers it no longer ends at the
 // tile's last row).  Region 1 is requested one K tile apart from regions 0, 2, 3 and has a descriptor of its own.
-template <int DT, int EPI, int TL = 0, bool TN = false, int HLM = HL_MODE_DEFAULT, int SEG = 0>
+// LO: STORE16 / GELU16 also write the lo part of their output to args.aux (the split-precision launches only)
+enum { LO_NONE = 0, LO_16 = 1, LO_E4M3 = 2 };
+template <int DT, int EPI, int TL = 0, bool TN = false, int LO = LO_NONE, int SEG = 0>
 __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
 {
     typedef typename T16<DT>::v8 v8;
     typedef typename T16<DT>::v4 v4;
     static_assert(!TN || EPI == EC_EPI_STORE32, "transposed operands: fp32 store only");
+    static_assert(LO == LO_NONE || EPI == EC_EPI_STORE16 || EPI == EC_EPI_GELU16, "a lo output goes with STORE16 / GELU16");
     constexpr int BM = 256, BN = 256;
     constexpr int REGION = 128 * 128;
     constexpr int KT = 4 * REGION;
@@ -1017,13 +994,7 @@ __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
     // long as both operands hold the same ones, and both are read through the same layout.  scale_w: e8m0 x 4 (uniform).
     auto mma2_g = [&](int mq, int nqa, i32x8(&ga)[2], int nqb, i32x8(&gb)[2], int scale_w) {
         if constexpr (SEG == 2) {
-            // operand format code of the scaled product: 0 = e4m3.  -DEC_LO_FMT=2 (e2m3, FP6) / 4 (e2m1, FP4) in a diagnostic
-            // build reads the SAME bytes as that format -- a rate experiment with meaningless results (tools/build_lo_fmt_probe.sh)
-#if defined(EC_GEMM_DIAG) && defined(EC_LO_FMT)
-            constexpr int FMT = EC_LO_FMT;
-#else
-            constexpr int FMT = 0;
-#endif
+            constexpr int FMT = 0;     // operand format code of the scaled product: e4m3
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int mt = 0; mt < 4; mt++) {
@@ -1157,25 +1128,6 @@ __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
                 // (satisfied already; tells hipcc's wait-count pass that no staging DMA is pending behind the main
                 // loop, so that it does not put a vmcnt(0) of its own in front of the epilogue's first LDS read)
                 __builtin_amdgcn_s_waitcnt(0x0F70);
-                if constexpr (EPI == EC_EPI_RESID_HL && (HLM & 256) != 0) {
-                    // A / B (diagnostic variant 38, round 6): touch the wave tile's residual planes one K tile ahead of the
-                    // epilogue that reads them -- one dword of each 128-byte line by LDS-DMA into a dump area (no register
-                    // destination; issued as inline asm: requests OLDER than anything the epilogue issues only make its
-                    // counted waits conservative), so that the epilogue's loads find the lines in L2 / on their way
-                    int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                    const int tm0 = m0 + wm * 128, tn0 = n0 + wn * 64;
-                    const long torg = ((long)tm0 * g.ldc + tn0) * 2, tspan = tile_span(g.M, tm0, 128, g.ldc * 2);
-                    const __amdgpu_buffer_rsrc_t th = tile_rsrc(reinterpret_cast<const char *>(g.C) + torg, tspan);
-                    const __amdgpu_buffer_rsrc_t tlo = tile_rsrc(reinterpret_cast<const char *>(g.aux) + torg, tspan);
-                    const int dump = 2 * KT + 4608 + wave * 256;
-                    const int v0 = tn0 < g.N ? ln * (int)g.ldc * 2 : BUF_OOB, v1 = tn0 < g.N ? (ln + 64) * (int)g.ldc * 2 : BUF_OOB;
-                    asm volatile("s_mov_b32 m0, %4\n\t"
-                                 "buffer_load_dword %0, %2, 0 offen lds\n\t"
-                                 "buffer_load_dword %1, %2, 0 offen lds\n\t"
-                                 "buffer_load_dword %0, %3, 0 offen lds\n\t"
-                                 "buffer_load_dword %1, %3, 0 offen lds"
-                                 :: "v"(v0), "v"(v1), "s"(th), "s"(tlo), "s"(dump) : "memory");
-                }
             }
             bar_l();
             if constexpr (F8) mma2_g(0, 0, gn0, 1, gn1, sc8);
@@ -1236,22 +1188,20 @@ __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
         // wait-count pass what has completed.
         constexpr bool BUF_EPI = EPI == EC_EPI_RESID_HL || EPI == EC_EPI_STORE16 || EPI == EC_EPI_GELU16 || epi_is_ln(EPI) ||
                                  EPI == EC_EPI_STORE32 || EPI == EC_EPI_RESID32;
-        constexpr bool LOUT = (EPI == EC_EPI_STORE16 || EPI == EC_EPI_GELU16) && (HLM & 16) != 0;   // 16-bit output as hi + lo parts (args.aux)
-        constexpr bool LOUT8 = LOUT && (HLM & 8) != 0;                                              // ... the lo part as e4m3 bytes
-        constexpr int TAIL_HL = ((HLM & 32) && (HLM & 128)) ? 0 : (HLM & (32 | 64 | 128)) ? 16 : 48;     // (diagnostic forms issue fewer operations)
-        constexpr int TAIL = !BUF_EPI ? 0 : EPI == EC_EPI_RESID_HL ? TAIL_HL : EPI == EC_EPI_STORE32 ? 32 : EPI == EC_EPI_RESID32 ? 48 : LOUT ? 32 : 16;
+        constexpr bool LOUT = LO != LO_NONE;       // 16-bit output as hi + lo parts (args.aux)
+        constexpr bool LOUT8 = LO == LO_E4M3;      // ... the lo part as e4m3 bytes
+        constexpr int TAIL = !BUF_EPI ? 0 : EPI == EC_EPI_RESID_HL ? 48 : EPI == EC_EPI_STORE32 ? 32 : EPI == EC_EPI_RESID32 ? 48 : LOUT ? 32 : 16;
         constexpr int enc_tail = (TAIL & 15) | (7 << 4) | (15 << 8) | ((TAIL >> 4) << 14);
         if constexpr (EPI == EC_EPI_RESID_HL)
-            epilogue_hl_buf<DT, 8, HLM>(ge, acc, wm0, wn0, elane,
-                                        reinterpret_cast<float *>(smem + KT) + wave * ((HLM & 1) ? 2 * 16 * 68 : 16 * 68), next_tile);
+            epilogue_hl_buf<DT, 8>(ge, acc, wm0, wn0, elane, reinterpret_cast<float *>(smem + KT) + wave * (2 * 16 * 68), next_tile);
         else if constexpr (!epi_is16(EPI))
             epilogue32_buf<EPI, 8, TN>(ge, acc, wm0, wn0, elane, reinterpret_cast<float *>(smem + KT) + wave * (16 * 68), next_tile);
         else if constexpr (BUF_EPI) {
             if (lds_stats)
-                epilogue16_buf<DT, EPI, 8, true, (HLM & 4) != 0, LOUT, LOUT8>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144),
+                epilogue16_buf<DT, EPI, 8, true, LOUT, LOUT8>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144),
                                                  side + slot * 512 + wm * 256, next_tile);
             else
-                epilogue16_buf<DT, EPI, 8, false, (HLM & 4) != 0, LOUT, LOUT8>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144), nullptr, next_tile);
+                epilogue16_buf<DT, EPI, 8, false, LOUT, LOUT8>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144), nullptr, next_tile);
         }
         else {    // the training epilogues (second output / second input): the general form
             next_tile();
@@ -1283,7 +1233,7 @@ __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
     if constexpr (TL == 2) clock_stamp(g.diag, 2);
 }
 
-template <int DT, int EPI, int TL = 0, bool TN = false, int HLM = HL_MODE_DEFAULT, int SEG = 0>
+template <int DT, int EPI, int TL = 0, bool TN = false, int LO = LO_NONE, int SEG = 0>
 int launch2pp(const GemmArgs &g0, hipStream_t stream)
 {
     GemmArgs g = g0;
@@ -1291,16 +1241,15 @@ int launch2pp(const GemmArgs &g0, hipStream_t stream)
     g.tiles_n = ec::ceil_div(g.N, 256);
     // two staging buffers + the row-statistics side area (LN epilogues) / the tail of the hi-lo epilogue's double
     // scratch (8 waves x 2 x 16 rows x 68 floats = 68 KiB from the second staging buffer on)
-    constexpr int lds = 2 * 4 * 128 * 128 + (epi_is_ln(EPI) ? 2 * 2048 : 0) + (EPI == EC_EPI_RESID_HL ? 4608 : 0) +
-                        (EPI == EC_EPI_RESID_HL && (HLM & 256) ? 2048 : 0);      // (+ the dump area of the prefetch A / B)
-    auto kern = gemm2pp_kernel<DT, EPI, TL, TN, HLM, SEG>;
+    constexpr int lds = 2 * 4 * 128 * 128 + (epi_is_ln(EPI) ? 2 * 2048 : 0) + (EPI == EC_EPI_RESID_HL ? 4608 : 0);
+    auto kern = gemm2pp_kernel<DT, EPI, TL, TN, LO, SEG>;
     if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds)) return rc;
     const int cus = ec::cu_count();
     EC_REQUIRE(cus > 0, "ec_gemm: cannot read the device's compute-unit count");
     constexpr int cls = (EPI == EC_EPI_STORE16 || EPI == EC_EPI_GELU_BWD16 || EPI == EC_EPI_STORE16_LN) ? ec::PROF_GEMM_STORE16
                         : (EPI == EC_EPI_GELU16 || EPI == EC_EPI_GELU16_SAVE || EPI == EC_EPI_GELU16_LN) ? ec::PROF_GEMM_GELU16
                         : (EPI == EC_EPI_RESID32 || EPI == EC_EPI_RESID_HL) ? ec::PROF_GEMM_RESID32 : ec::PROF_GEMM_STORE32;
-    constexpr double out_b = (EPI == EC_EPI_STORE16 || EPI == EC_EPI_GELU16 || epi_is_ln(EPI)) ? (!epi_is_ln(EPI) && (HLM & 16) ? 4.0 : 2.0)
+    constexpr double out_b = (EPI == EC_EPI_STORE16 || EPI == EC_EPI_GELU16 || epi_is_ln(EPI)) ? (LO != LO_NONE ? 4.0 : 2.0)
                              : (EPI == EC_EPI_GELU16_SAVE || EPI == EC_EPI_GELU_BWD16) ? 4.0
                              : ((EPI == EC_EPI_RESID32 || EPI == EC_EPI_RESID_HL) ? 8.0 : 4.0);
     // segments: every product's flops; the bytes of the parts that exist (a part shared by two segments counts once)
@@ -1318,47 +1267,92 @@ int launch2pp(const GemmArgs &g0, hipStream_t stream)
 }
 
 #ifdef EC_GEMM_DIAG
-#include "gemm_diag.inc"
+// ---------------------------------------------------------------------------------------
+// Probe (diagnostic build): what one wave per SIMD can issue.  256 threads per CU; a block = 64 independent
+// v_mfma_f32_16x16x32_f16 on AGPR accumulators (the four-wave layout's quarter tile), optionally with what the GEMM
+// loop puts between blocks: bit 0 = 16 ds_read_b128 of fresh fragments, bit 1 = a workgroup barrier, bit 2 = 8 LDS-DMA
+// requests (waited for two blocks later).  tools/mfma_probe.py turns the launch time into cycles per block.
+// ---------------------------------------------------------------------------------------
+template <int MODE>
+__global__ __launch_bounds__(256, 1) void mfma_probe_kernel(const unsigned char *src, float *out, int iters)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int i = threadIdx.x; i < 32768; i += 256) reinterpret_cast<unsigned *>(smem)[i] = 0x3c003c00u;   // f16 1.0
+    __syncthreads();
+    f32x4 acc[8][8];
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+#pragma unroll
+        for (int j = 0; j < 8; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f16x8 fa[8], fb[8];
+    int off[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) off[i] = (wave * 128 + i * 16 + (lane & 15)) * 64 + (((lane >> 4) ^ ((lane >> 2) & 3)) << 4);
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        fa[i] = *reinterpret_cast<const f16x8 *>(smem + off[i]);
+        fb[i] = *reinterpret_cast<const f16x8 *>(smem + 65536 + off[i]);
+    }
+    const unsigned char *gsrc = src + ((size_t)blockIdx.x * 4 + wave) * 8192 + lane * 16;
+    for (int it = 0; it < iters; it++) {
+        if (MODE & 4) {
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+#pragma unroll
+            for (int p = 0; p < 8; p++) glds16(gsrc + p * 1024, smem + 98304 + (it & 1) * 16384 + wave * 8192 + p * 1024 - (wave * 8192 / 2));
+        }
+        if (MODE & 2) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        f16x8 na[8], nb[8];
+        if ((MODE & 1) && !(MODE & 8)) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                na[i] = *reinterpret_cast<const f16x8 *>(smem + ((it & 1) << 15) + off[i]);
+                nb[i] = *reinterpret_cast<const f16x8 *>(smem + 65536 + ((it & 1) << 14) + off[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            if ((MODE & 1) && (MODE & 8)) {        // bit 3: the reads spread through the block, one pair per eight MFMAs
+                const unsigned a0 = (unsigned)(((it & 1) << 15) + off[i]), a1 = (unsigned)(65536 + ((it & 1) << 14) + off[i]);
+                asm volatile("ds_read_b128 %0, %1" : "=v"(na[i]) : "v"(a0));
+                asm volatile("ds_read_b128 %0, %1" : "=v"(nb[i]) : "v"(a1));
+            }
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fa[j]), "v"(fb[i]));
+        }
+        if (MODE & 1) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int i = 0; i < 8; i++) fa[i] = na[i], fb[i] = nb[i];
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 7" ::: "memory");
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+#pragma unroll
+        for (int j = 0; j < 8; j++) s += acc[i][j][0] + acc[i][j][3];
+    if (s == 12345.f) out[threadIdx.x] = s;            // (keeps the accumulators alive)
+}
 #endif
 
 
-// Variants that ship: the default and three independent tilings (kept as cross-checks of each
-// other in the GPU tests).  Everything else -- timing experiments that compute wrong results on
-// purpose, stamp / timeline builds that write s_memtime records through args.diag, retired A/B
-// schedules -- only exists in a -DEC_GEMM_DIAG build (python -m eventclip_amd.build --diag), which
-// tools/ load explicitly; the product library rejects those variant numbers.
+// Variant 0, the default kernel, is the only one that ships.  The diagnostic build (-DEC_GEMM_DIAG: python -m
+// eventclip_amd.build --diag, which tools/ load explicitly) adds the same kernel with s_memtime records through
+// args.diag: 18 = per-tile timeline records, 19 = clock stamps at the workgroup's start and end.  The product
+// library rejects those variant numbers.
 template <int DT, int EPI> int dispatch_variant(const GemmArgs &g, int variant, hipStream_t s)
 {
     switch (variant) {
     case 0: return launch2pp<DT, EPI>(g, s);                     // default: persistent staggered 2-phase
 #ifdef EC_GEMM_DIAG
-    // the kernels the default one grew out of, kept for comparisons in the diagnostic build only: nothing in the
-    // product calls them, and the plain 128 x 128 one once returned five wrong elements in ~10^9 on one box
-    case 1: return launch<DT, 256, 256, 2, 4, EPI>(g, s);        // plain two-barrier loop, 256 x 256
-    case 2: return launch<DT, 128, 128, 2, 2, EPI>(g, s);
-    case 3: return launch<DT, 128, 256, 1, 4, EPI>(g, s);
-    case 5: return launch2p<DT, EPI>(g, s);                      // staggered 2-phase, one tile per workgroup
-    case 4: return launch4p<DT, EPI>(g, s);
-    case 6: return launch2p<DT, EPI, 1>(g, s);   // timing experiment: no DMA in the loop (wrong results)
-    case 7: return launch2p<DT, EPI, 2>(g, s);   // timing experiment: every WG streams tile (0,0)
-    case 8: return launch2p<DT, EPI, 3>(g, s);   // no s_setprio
-    case 9: return launch2p<DT, EPI, 4>(g, s);   // priority on the load segments
-    case 10: return launch2p<DT, EPI, 5>(g, s);  // s_memtime stamps of one workgroup -> args.diag
-    case 11: return launch2p<DT, EPI, 6>(g, s);
-    case 12: return launch_b2<DT, EPI>(g, s);     // two 4-wave workgroups per CU, 128x256x32
-    case 13: return launch_b2p<DT, EPI>(g, s);    // same with register-prefetched fragments
-    case 14: return launch2p<DT, EPI, 7>(g, s);   // first-round start times spread over a tile period
-    case 15: return launch2p<DT, EPI, 8>(g, s);   // ... over half a period
-    case 16: return launch2p<DT, EPI, 9>(g, s);   // per-workgroup timeline -> args.diag
-    case 18: return launch2pp<DT, EPI, true>(g, s);  // persistent, with timeline records -> args.diag
-    case 19: return launch2pp<DT, EPI, 2>(g, s);     // persistent, clock stamps at the workgroup's start and end -> args.diag
-    case 43: return launch2pp<DT, EPI, false, false, 5>(g, s);   // 16-bit epilogues: next tile's DMA requested in FRONT of the first use of bias (A / B)
-    case 20:                                         // probe: four waves x 128 x 128, 16-bit store only
-        if constexpr (EPI == EC_EPI_STORE16) return launch4w<DT>(g, s);
-        return ec::fail(EC_ERR_INVALID, "ec_gemm variant 20: store16 only");
-    case 21:                                         // ... ring of four quarter tiles, reads and DMA spread through the MFMAs
-        if constexpr (EPI == EC_EPI_STORE16) return launch4i<DT>(g, s);
-        return ec::fail(EC_ERR_INVALID, "ec_gemm variant 21: store16 only");
+    case 18: return launch2pp<DT, EPI, 1>(g, s);     // timeline records -> args.diag
+    case 19: return launch2pp<DT, EPI, 2>(g, s);     // clock stamps at the workgroup's start and end -> args.diag
 #endif
     default:
         return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown variant %d (diagnostic variants need an "
@@ -1368,7 +1362,6 @@ template <int DT, int EPI> int dispatch_variant(const GemmArgs &g, int variant, 
 
 template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipStream_t s)
 {
-    constexpr int HLO = HL_MODE_DEFAULT | 16;    // 16-bit epilogues that also write the lo part (args.aux)
     if (g.nseg > 1) {
         // split-precision operands: the segmented main loop (default variant only)
         EC_REQUIRE(variant == 0, "ec_gemm: A_lo / W_lo need variant 0");
@@ -1377,16 +1370,16 @@ template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipS
             if constexpr (DT == EC_F16) {
                 switch (epi) {
                 case EC_EPI_STORE16:
-                    return g.aux ? launch2pp<DT, EC_EPI_STORE16, false, false, HLO, 2>(g, s)
-                                 : launch2pp<DT, EC_EPI_STORE16, false, false, HL_MODE_DEFAULT, 2>(g, s);
+                    return g.aux ? launch2pp<DT, EC_EPI_STORE16, 0, false, LO_16, 2>(g, s)
+                                 : launch2pp<DT, EC_EPI_STORE16, 0, false, LO_NONE, 2>(g, s);
                 case EC_EPI_GELU16:
-                    if (g.aux && g.aux8_scale != 0.f) return launch2pp<DT, EC_EPI_GELU16, false, false, HLO | 8, 2>(g, s);
-                    return g.aux ? launch2pp<DT, EC_EPI_GELU16, false, false, HLO, 2>(g, s)
-                                 : launch2pp<DT, EC_EPI_GELU16, false, false, HL_MODE_DEFAULT, 2>(g, s);
-                case EC_EPI_STORE32: return launch2pp<DT, EC_EPI_STORE32, false, false, HL_MODE_DEFAULT, 2>(g, s);
+                    if (g.aux && g.aux8_scale != 0.f) return launch2pp<DT, EC_EPI_GELU16, 0, false, LO_E4M3, 2>(g, s);
+                    return g.aux ? launch2pp<DT, EC_EPI_GELU16, 0, false, LO_16, 2>(g, s)
+                                 : launch2pp<DT, EC_EPI_GELU16, 0, false, LO_NONE, 2>(g, s);
+                case EC_EPI_STORE32: return launch2pp<DT, EC_EPI_STORE32, 0, false, LO_NONE, 2>(g, s);
                 case EC_EPI_RESID_HL:
                     EC_REQUIRE(g.aux, "ec_gemm: EC_EPI_RESID_HL needs args.aux (the lo plane)");
-                    return launch2pp<DT, EC_EPI_RESID_HL, false, false, HL_MODE_DEFAULT, 2>(g, s);
+                    return launch2pp<DT, EC_EPI_RESID_HL, 0, false, LO_NONE, 2>(g, s);
                 default: return ec::fail(EC_ERR_INVALID, "ec_gemm: e4m3 lo products go with the STORE16, GELU16, STORE32 and RESID_HL epilogues (got %d)", epi);
                 }
             } else {
@@ -1395,16 +1388,16 @@ template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipS
         }
         switch (epi) {
         case EC_EPI_STORE16:
-            return g.aux ? launch2pp<DT, EC_EPI_STORE16, false, false, HLO, 1>(g, s)
-                         : launch2pp<DT, EC_EPI_STORE16, false, false, HL_MODE_DEFAULT, 1>(g, s);
+            return g.aux ? launch2pp<DT, EC_EPI_STORE16, 0, false, LO_16, 1>(g, s)
+                         : launch2pp<DT, EC_EPI_STORE16, 0, false, LO_NONE, 1>(g, s);
         case EC_EPI_GELU16:
-            return g.aux ? launch2pp<DT, EC_EPI_GELU16, false, false, HLO, 1>(g, s)
-                         : launch2pp<DT, EC_EPI_GELU16, false, false, HL_MODE_DEFAULT, 1>(g, s);
-        case EC_EPI_STORE32: return launch2pp<DT, EC_EPI_STORE32, false, false, HL_MODE_DEFAULT, 1>(g, s);
-        case EC_EPI_RESID32: return launch2pp<DT, EC_EPI_RESID32, false, false, HL_MODE_DEFAULT, 1>(g, s);
+            return g.aux ? launch2pp<DT, EC_EPI_GELU16, 0, false, LO_16, 1>(g, s)
+                         : launch2pp<DT, EC_EPI_GELU16, 0, false, LO_NONE, 1>(g, s);
+        case EC_EPI_STORE32: return launch2pp<DT, EC_EPI_STORE32, 0, false, LO_NONE, 1>(g, s);
+        case EC_EPI_RESID32: return launch2pp<DT, EC_EPI_RESID32, 0, false, LO_NONE, 1>(g, s);
         case EC_EPI_RESID_HL:
             EC_REQUIRE(g.aux, "ec_gemm: EC_EPI_RESID_HL needs args.aux (the lo plane)");
-            return launch2pp<DT, EC_EPI_RESID_HL, false, false, HL_MODE_DEFAULT, 1>(g, s);
+            return launch2pp<DT, EC_EPI_RESID_HL, 0, false, LO_NONE, 1>(g, s);
         default: return ec::fail(EC_ERR_INVALID, "ec_gemm: A_lo / W_lo go with the STORE16, GELU16, STORE32, RESID32 and RESID_HL epilogues (got %d)", epi);
         }
     }
@@ -1425,37 +1418,19 @@ template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipS
     // LayerNorm folded into the GEMMs (default kernel only)
     case EC_EPI_RESID_HL:
 #ifdef EC_GEMM_DIAG
-        if (variant == 18 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, true>(g, s);   // timeline records -> args.diag
-        if (variant == 19 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, 2>(g, s);      // clock stamps
-        // A / B forms of the hi-lo epilogue (epilogue_hl_buf MODE 0 .. 3)
-        if (variant == 30 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, false, false, 0>(g, s);
-        if (variant == 31 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, false, false, 1>(g, s);
-        if (variant == 32 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, false, false, 2>(g, s);
-        if (variant == 33 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, false, false, 3>(g, s);
-        // cost-splitting forms (wrong results on purpose; tools/bench_resid_split.py): no residual loads / no lo store /
-        // no store at all / neither loads nor stores
-        if (variant == 34 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, false, false, HL_MODE_DEFAULT | 32>(g, s);
-        if (variant == 35 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, false, false, HL_MODE_DEFAULT | 64>(g, s);
-        if (variant == 36 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, false, false, HL_MODE_DEFAULT | 128>(g, s);
-        if (variant == 37 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, false, false, HL_MODE_DEFAULT | 32 | 128>(g, s);
-        if (variant == 38 && g.aux) return launch2pp<DT, EC_EPI_RESID_HL, false, false, HL_MODE_DEFAULT | 256>(g, s);   // residual planes touched a K tile ahead
-        if (variant == 13 && g.aux) return launch_b2p<DT, EC_EPI_RESID_HL>(g, s);   // two 4-wave workgroups per CU
+        if ((variant == 18 || variant == 19) && g.aux) return dispatch_variant<DT, EC_EPI_RESID_HL>(g, variant, s);
 #endif
         EC_REQUIRE(variant == 0 && g.aux, "ec_gemm: EC_EPI_RESID_HL needs variant 0 and args.aux (the lo plane)");
         return launch2pp<DT, EC_EPI_RESID_HL>(g, s);
     case EC_EPI_STORE16_LN:
 #ifdef EC_GEMM_DIAG
-        if (variant == 18 && g.rowstat && g.colsum) return launch2pp<DT, EC_EPI_STORE16_LN, true>(g, s);
-        if (variant == 19 && g.rowstat && g.colsum) return launch2pp<DT, EC_EPI_STORE16_LN, 2>(g, s);
-        if (variant == 43 && g.rowstat && g.colsum) return launch2pp<DT, EC_EPI_STORE16_LN, false, false, 5>(g, s);
+        if ((variant == 18 || variant == 19) && g.rowstat && g.colsum) return dispatch_variant<DT, EC_EPI_STORE16_LN>(g, variant, s);
 #endif
         EC_REQUIRE(variant == 0 && g.rowstat && g.colsum, "ec_gemm: EC_EPI_STORE16_LN needs variant 0, row_stats and col_sums");
         return launch2pp<DT, EC_EPI_STORE16_LN>(g, s);
     case EC_EPI_GELU16_LN:
 #ifdef EC_GEMM_DIAG
-        if (variant == 18 && g.rowstat && g.colsum) return launch2pp<DT, EC_EPI_GELU16_LN, true>(g, s);
-        if (variant == 19 && g.rowstat && g.colsum) return launch2pp<DT, EC_EPI_GELU16_LN, 2>(g, s);
-        if (variant == 43 && g.rowstat && g.colsum) return launch2pp<DT, EC_EPI_GELU16_LN, false, false, 5>(g, s);
+        if ((variant == 18 || variant == 19) && g.rowstat && g.colsum) return dispatch_variant<DT, EC_EPI_GELU16_LN>(g, variant, s);
 #endif
         EC_REQUIRE(variant == 0 && g.rowstat && g.colsum, "ec_gemm: EC_EPI_GELU16_LN needs variant 0, row_stats and col_sums");
         return launch2pp<DT, EC_EPI_GELU16_LN>(g, s);
@@ -1639,7 +1614,7 @@ extern "C" EC_API int ec_gemm(const ec_gemm_args *a, ec_stream_t stream)
 #ifdef EC_GEMM_DIAG
     {
         const int v = a->variant;
-        EC_REQUIRE(!(v == 10 || v == 16 || v == 18 || v == 19) || a->diag, "ec_gemm: variant %d needs args.diag", v);
+        EC_REQUIRE(!(v == 18 || v == 19) || a->diag, "ec_gemm: variant %d needs args.diag", v);
     }
 #endif
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -277,8 +277,8 @@ typedef struct {
     int M, N, K;       /* K % 64 == 0, N % 16 == 0 */
     int dtype;         /* EC_F16 / EC_BF16: A, W and 16-bit outputs */
     int epilogue;      /* EC_EPI_* */
-    int variant;       /* 0 = the kernel; anything else is EC_ERR_INVALID.  (The tilings it grew out of and the
-                          stamp / timeline variants exist in the -DEC_GEMM_DIAG build for tools/ only.) */
+    int variant;       /* 0 = the kernel; anything else is EC_ERR_INVALID.  (Its timeline / clock-stamp forms,
+                          variants 18 / 19, exist in the -DEC_GEMM_DIAG build for tools/ only.) */
     const void *A;     /* [M, K] 16-bit, row stride lda elements (0 = K).  Row strides (lda, ldw, ldc) are multiples of
                           8 elements below 2^21: a tile's rows are addressed with 32-bit byte offsets from the tile's
                           origin (buffer descriptors), EC_ERR_INVALID otherwise */
@@ -288,7 +288,7 @@ typedef struct {
     void *C;           /* [M, N] 16-bit or fp32 by epilogue, row stride ldc (0 = N) */
     long ldc;
     void *diag;        /* NULL.  (Only a -DEC_GEMM_DIAG build of the library reads it: device buffer
-                          for the s_memtime records of its stamp / timeline variants.) */
+                          for the s_memtime records of variants 18 / 19.) */
     /* The rest serves the training path (variant 0 only); all zero = the plain GEMM above. */
     long ldw;          /* row stride of W in elements (0 = K) */
     const float *resid;/* EC_EPI_RESID32: C = resid + acc + bias with resid [M, N] at stride ldc (NULL = C, in place) */

@@ -93,3 +93,24 @@ def test_gemm_kernels_keep_their_schedule_and_have_no_scratch():
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import check_gemm_isa
     assert check_gemm_isa.main() == 0
+
+
+def test_diagnostic_build_of_gemm_and_attention_compiles():
+    """The diagnostic build (python -m eventclip_amd.build --diag) keeps its instrumentation of the shipped kernels -- the
+    GEMM's timeline / clock-stamp variants and MFMA rate probe, the attention's phase stamps -- and nothing else builds it:
+    compile both files device-only with its flags, so that the instrumentation cannot rot unseen."""
+    import shutil
+    import subprocess
+    import tempfile
+    import pytest
+    from eventclip_amd import build
+    if not (os.path.exists(build.HIPCC) or shutil.which(build.HIPCC)):
+        pytest.skip('no hipcc')
+    with tempfile.TemporaryDirectory() as tmp:
+        procs = [(f, subprocess.Popen([build.HIPCC] + build.FLAGS + build.DIAG_FLAGS +
+                                      ['--cuda-device-only', '-c', os.path.join(build.CSRC, f), '-o', os.path.join(tmp, f + '.o')],
+                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+                 for f in ('gemm.hip', 'attention.hip')]
+        for f, p in procs:
+            out, _ = p.communicate()
+            assert p.returncode == 0, f'{f} (diagnostic build):\n{out}'

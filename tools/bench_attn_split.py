@@ -1,8 +1,7 @@
 """ec_attention_split at the bench shape (2560 sequences x 16 heads, S = 257; round 5): the hi + lo fp16 kernel on the 16-bit
-matrix instruction against the fp32 kernel on v_mfma_f32_16x16x4_f32 (EC_ATTN_SPLIT_F32=1 selects the latter), and the
-default 16-bit attention kernel beside them.
+matrix instruction, and the default 16-bit attention kernel beside it.
 
-    python tools/bench_attn_split.py [--n-seq 2560] [--S 257];   EC_ATTN_SPLIT_F32=1 python tools/bench_attn_split.py
+    python tools/bench_attn_split.py [--n-seq 2560] [--S 257]
 """
 import argparse
 import os
@@ -12,8 +11,6 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# EC_ATTN_SPLIT_F32 is read by the DIAGNOSTIC build only since round 6 (the product library's kernel choice never depends on the environment)
-os.environ.setdefault('EVENTCLIP_HIP_LIB', os.path.join(ROOT, 'eventclip_amd', 'libeventclip_hip_diag.so'))
 from eventclip_amd import _lib  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -50,7 +47,7 @@ for name, fn in (('ec_attention_split', split), ('ec_attention (16-bit)', plain)
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 10
-    print(f'S={S} n_seq={n} {name:24s} {"(fp32 kernel)" if os.environ.get("EC_ATTN_SPLIT_F32") and "split" in name else "":14s}: {ms:.3f} ms = '
+    print(f'S={S} n_seq={n} {name:24s}: {ms:.3f} ms = '
           f'{4.0 * S * S * 64 * heads * n / ms / 1e9:5.0f} TFLOP/s', flush=True)
 split()
 n_ref = 4

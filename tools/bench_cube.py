@@ -10,7 +10,7 @@ for n in (4096, 8192):
             A = (torch.rand(n, n, device='cuda') * 2 - 1 if dist == 'uniform' else torch.randn(n, n, device='cuda')).to(dt)
             W = (torch.rand(n, n, device='cuda') * 2 - 1 if dist == 'uniform' else torch.randn(n, n, device='cuda')).to(dt)
             out = torch.empty(n, n, device='cuda', dtype=dt)
-            for v in (0, 4, 5):
+            for v in (0,):
                 for _ in range(5): ops.gemm(A, W, None, 'store16', out=out, variant=v)
                 torch.cuda.synchronize()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

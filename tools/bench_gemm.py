@@ -16,7 +16,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=256)
     ap.add_argument('--iters', type=int, default=10)
-    ap.add_argument('--variants', type=int, nargs='+', default=[1, 4, 5])
+    ap.add_argument('--variants', type=int, nargs='+', default=[0])
     ap.add_argument('--dtypes', nargs='+', default=['float16', 'bfloat16'])
     a = ap.parse_args()
     M = a.frames * 257

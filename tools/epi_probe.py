@@ -10,7 +10,7 @@ from eventclip_amd import ops  # noqa: E402
 M = 2560 * 257
 
 
-def run(N, K, epi, v, iters=5):
+def run(N, K, epi, v=0, iters=5):
     A = torch.randn(M, K, device='cuda').half()
     W = (torch.randn(N, K, device='cuda') / K ** 0.5).half()
     bias = torch.randn(N, device='cuda')
@@ -32,15 +32,11 @@ if __name__ == '__main__':
     which = sys.argv[1] if len(sys.argv) > 1 else 'all'
     if which in ('all', 'k'):
         for K in (64, 128, 256, 512, 1024, 2048):
-            run(1024, K, 'resid32', 5)
+            run(1024, K, 'resid32')
     if which in ('all', 's'):
         for K in (64, 1024):
-            run(1024, K, 'store32', 5)
-            run(1024, K, 'store16', 5)
-    if which in ('all', 'd'):
-        for v in (6, 7):
-            run(1024, 1024, 'resid32', v)
-            run(1024, 1024, 'store16', v)
+            run(1024, K, 'store32')
+            run(1024, K, 'store16')
     if which in ('all', 'rmw'):
         x = torch.zeros(M, 1024, device='cuda')
         for _ in range(3):

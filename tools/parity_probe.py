@@ -24,12 +24,7 @@ def main():
     ap.add_argument('--branch', type=float, nargs='+', default=[1.0, 4.0])
     ap.add_argument('--dtype', default='float16')
     ap.add_argument('--blob', type=float, default=0.7, help='share of the events in a Gaussian blob (structured frames)')
-    ap.add_argument('--attn-variant', type=int, default=None, help='diagnostic build: 1 = the round-1/2 attention block')
     a = ap.parse_args()
-    if a.attn_variant is not None:
-        os.environ.setdefault('EVENTCLIP_HIP_LIB', os.path.join(ROOT, 'eventclip_amd', 'libeventclip_hip_diag.so'))
-        import ctypes
-        ctypes.CDLL(os.environ['EVENTCLIP_HIP_LIB']).ec_attn_set_variant(a.attn_variant)
     from eventclip_amd import clip as eclip
     from eventclip_amd.clip_cls import ZSCLIPClassifier
     from eventclip_amd.event2img import Event2ImagePipeline

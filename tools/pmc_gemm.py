@@ -9,7 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from eventclip_amd import ops  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--variant', type=int, default=4)
+ap.add_argument('--variant', type=int, default=0)
 ap.add_argument('--n', type=int, default=3072)
 ap.add_argument('--k', type=int, default=1024)
 ap.add_argument('--frames', type=int, default=256)

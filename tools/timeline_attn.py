@@ -19,11 +19,9 @@ S = int(sys.argv[1]) if len(sys.argv) > 1 else 257
 n_seq = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 heads = 16
 W = heads * 64
-if len(sys.argv) > 3:   # block variant of the diagnostic build (1 = round-1/2 block)
-    ctypes.CDLL(os.environ['EVENTCLIP_HIP_LIB']).ec_attn_set_variant(int(sys.argv[3]))
 qkv = torch.randn(n_seq * S, 3 * W, device='cuda').half()
 out = torch.empty(n_seq * S, W, dtype=torch.float16, device='cuda')
-scaled = os.environ.get('ATTN_SCALED', '0') != '0'     # the tower's entry point (variant 5 = 32-query tiles needs it)
+scaled = os.environ.get('ATTN_SCALED', '0') != '0'     # the tower's entry point
 for _ in range(3):
     if scaled:
         _lib.check(_lib.lib().ec_attention_scaled_q(_lib.ptr(qkv), _lib.ptr(out), n_seq, S, W, heads, 0, S, _lib.EC_F16,

@@ -1,5 +1,5 @@
-"""Diagnostic: per-CU timeline of the default GEMM (variant 16): how long a CU spends between one
-workgroup's last store and the next one's first MFMA.  Run on the GPU box.
+"""Diagnostic: per-CU timeline of the default GEMM (variant 18 of the diagnostic build: per-tile records): how long a CU
+spends between one tile's last store and the next one's first MFMA.  Run on the GPU box.
 
     python tools/timeline_gemm.py [N] [K] [epilogue]
 """
@@ -25,7 +25,7 @@ out = torch.zeros(M, N, device='cuda', dtype=torch.float32 if epi.endswith('32')
 tiles = ((M + 255) // 256) * ((N + 255) // 256)
 dbg = torch.zeros(tiles * 8 * 2, device='cuda', dtype=torch.float32)
 for _ in range(2):
-    ops.gemm(A, W, None, epi, out=out, variant=int(os.environ.get('TL_VARIANT', '16')), diag=dbg)
+    ops.gemm(A, W, None, epi, out=out, variant=int(os.environ.get('TL_VARIANT', '18')), diag=dbg)
 torch.cuda.synchronize()
 r = dbg.cpu().numpy().view(np.uint64).reshape(tiles, 8).astype(np.int64)
 hw, xcc = r[:, 0], r[:, 6]

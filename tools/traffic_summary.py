@@ -15,10 +15,7 @@ EPI = {0: 'STORE16', 1: 'GELU16', 2: 'RESID32', 3: 'STORE32', 4: 'GELU16', 5: 'S
 
 
 def classify(name):
-    m = re.search(r'(gemm2pp_kernel|gemm2p_kernel|gemm4p_kernel|gemm_b2p?_kernel)<(\d+), (\d+)', name)
-    if m:
-        return f'gemm_kernel<{EPI[int(m.group(3))]}>'
-    m = re.search(r'gemm_kernel<(\d+), \d+, \d+, \d+, \d+, (\d+)', name)
+    m = re.search(r'gemm2pp_kernel<(\d+), (\d+)', name)
     if m:
         return f'gemm_kernel<{EPI[int(m.group(2))]}>'
     if 'events_pack10_kernel' in name or 'events_band10_kernel' in name:      # same launch site as the 32-bit kernel behind them (one class in bench.py)
