@@ -2,7 +2,8 @@
 nn.Conv2d / nn.BatchNorm2d (eval) / nn.AvgPool2d and F.multi_head_attention_forward, loading the state dict in
 OpenAI's key layout.  ``emulate16=True`` rounds as the reference's fp16 GPU model does: conv inputs, weights and
 outputs in fp16, BatchNorm in fp32 with an fp16 output, the attention pool's tokens, projections and output in fp16.
-Test infrastructure only."""
+``emulate16=torch.bfloat16`` rounds at the same places to bf16.  ``conv_classes`` walks the module tree for the shapes
+the packed tower launches.  Test infrastructure only."""
 from collections import OrderedDict
 
 import torch
@@ -11,7 +12,10 @@ import torch.nn.functional as F
 
 
 def _r16(t, on):
-    return t.half().float() if on else t
+    """t rounded to 16 bit when on: torch.bfloat16 rounds to bf16, any other true value to fp16."""
+    if not on:
+        return t
+    return t.to(torch.bfloat16 if on is torch.bfloat16 else torch.float16).float()
 
 
 class Bottleneck(nn.Module):
@@ -164,3 +168,51 @@ def flops_by_walk(model, image_size):
     L, C = feat.shape[2] * feat.shape[3] + 1, feat.shape[1]
     total[0] += 2 * (C * ap.q_proj.out_features + 2 * L * C * C + C * ap.c_proj.out_features)
     return total[0]
+
+
+def _pad64(c):
+    return (c + 63) // 64 * 64
+
+
+def conv_classes(cfg):
+    """The convolutions of the tower of ``cfg`` (full ModifiedResNet module tree, built on the meta device) as the
+    packed tower launches them, from forward hooks on a meta-device forward (nothing is computed): {(ks, cin, cout, H_in): set of roles} with the channels padded to multiples of 64, and the
+    attention pool's projections [(role, cin, cout, L)].  Every convolution runs at stride 1 on its input's H: the
+    stem's stride-2 conv1 is the 1x1 product over the 64-wide stem rows at R / 2, and a downsample or a stride-2
+    conv3 reads the AvgPool2d's output.  Roles: 'relu' (BatchNorm + ReLU), 'resid' (BatchNorm + residual + ReLU),
+    'ds' (BatchNorm, no ReLU); projections 'q' (M = n images), 'kv' (M = n * L), 'c' (M = n, fp32 store)."""
+    with torch.device('meta'):
+        w = cfg['vision_width']
+        meta = ModifiedResNet(cfg['vision_layers'], cfg['embed_dim'], w * 32 // 64, cfg['image_size'], w)
+    image_size = cfg['image_size']
+    roles = {}
+    for name, m in meta.named_modules():
+        if isinstance(m, nn.Conv2d):
+            leaf = name.rsplit('.', 1)[-1]
+            roles[m] = 'resid' if leaf == 'conv3' and name.startswith('layer') else \
+                'ds' if name.endswith('downsample.0') else 'relu'
+    out, pool_in = {}, []
+
+    def conv_hook(m, i, o):
+        h = i[0].shape[2]
+        if m.stride[0] == 2:          # the stem's conv1 on the stem rows
+            key = (1, 64, _pad64(m.out_channels), h // 2)
+        else:
+            key = (m.kernel_size[0], _pad64(m.in_channels), _pad64(m.out_channels), h)
+        out.setdefault(key, set()).add(roles[m])
+
+    hooks = [m.register_forward_hook(conv_hook) for m in roles]
+    hooks.append(meta.attnpool.register_forward_pre_hook(lambda m, i: pool_in.append(i[0].shape)))
+    try:
+        with torch.no_grad():
+            meta(torch.zeros(1, 3, image_size, image_size, device='meta'))
+    finally:
+        for h in hooks:
+            h.remove()
+    _, C, h, w = pool_in[0]
+    ap = meta.attnpool
+    L = h * w + 1
+    assert ap.q_proj.in_features == ap.k_proj.in_features == ap.v_proj.in_features == C
+    proj = [('q', C, ap.q_proj.out_features, L), ('kv', C, ap.k_proj.out_features + ap.v_proj.out_features, L),
+            ('c', C, ap.c_proj.out_features, L)]
+    return out, proj

@@ -144,3 +144,114 @@ def test_random_state_dict_gains():
     assert torch.equal(b['visual.layer2.0.bn2.weight'], a['visual.layer2.0.bn2.weight'])
     with pytest.raises(ValueError):
         eclip.random_state_dict(cfg, 0, qk_gain=2.0)
+
+
+def _packer_classes(cfg):
+    """{(ks, cin, cout, H_in): roles} and the projections as the packer (blocks_of + pad64) and ec_resnet_encode lay
+    the tower out."""
+    p = resnet.pad64
+    w, R = cfg['vision_width'], cfg['image_size']
+    h = R // 2
+    out = {}
+
+    def add(key, role):
+        out.setdefault(key, set()).add(role)
+    add((1, 64, p(w // 2), h), 'relu')
+    add((3, p(w // 2), p(w // 2), h), 'relu')
+    add((3, p(w // 2), p(w), h), 'relu')
+    h //= 2
+    for _, inp, planes, stride, ds in resnet.blocks_of(cfg):
+        ho = h // stride
+        add((1, p(inp), p(planes), h), 'relu')
+        add((3, p(planes), p(planes), h), 'relu')
+        add((1, p(planes), p(4 * planes), ho), 'resid')
+        if ds:
+            add((1, p(inp), p(4 * planes), ho), 'ds')
+        h = ho
+    C, L = 32 * w, h * h + 1
+    return out, [('q', C, C, L), ('kv', C, 2 * C, L), ('c', C, cfg['embed_dim'], L)]
+
+
+def test_launch_shapes_match_module_walk():
+    """The packer's block spec against OpenAI's module tree: the convolutions that forward hooks see in a full-depth
+    meta-device forward of the restatement (resnet_ref.conv_classes) are, for every arch, the classes that
+    blocks_of + pad64 give ec_resnet_encode, with the same epilogue roles; 99 conv classes over the five towers."""
+    every, projs = {}, set()
+    for arch in OPENAI:
+        cfg = eclip.resnet_config(arch)
+        walk, walk_proj = resnet_ref.conv_classes(cfg)
+        packed, packed_proj = _packer_classes(cfg)
+        assert walk == packed, arch
+        assert walk_proj == packed_proj, arch
+        for k, v in walk.items():
+            every.setdefault(k, set()).update(v)
+        projs.update(walk_proj)
+    assert len(every) == 99, len(every)
+    assert len(projs) == 13, sorted(projs)        # RN50 and RN101 share q and kv
+    assert sum(k[0] == 1 for k in every) > sum(k[0] == 3 for k in every)
+    assert (1, 4096, 8192, 197) in {(1, ci, co, L) for r, ci, co, L in projs if r == 'kv'}
+
+
+def _refused(rc, fn):
+    from eventclip_amd import _lib
+    assert rc == _lib.EC_ERR_INVALID, (fn, rc)
+    msg = _lib.lib().ec_last_error()
+    assert msg and fn.encode() in msg, (fn, msg)
+
+
+def test_resnet_kernel_arguments_checked():
+    """Every EC_REQUIRE of the five ResNet kernel entry points refuses before any launch (EC_ERR_INVALID, and
+    ec_last_error names the function); n_img = 0 is a no-op that returns EC_OK even with null buffers."""
+    import ctypes
+    from eventclip_amd import _lib
+    lib = _lib.lib()
+    F16, BF16 = _lib.EC_F16, _lib.EC_BF16
+    buf = ctypes.c_void_p(256)            # never dereferenced: every call below returns before a launch
+    fn = 'ec_resnet_conv'
+
+    def conv(n=1, H=4, W=4, cin=64, cout=64, ks=1, resid=None, out32=0, dt=F16):
+        return lib.ec_resnet_conv(buf, n, H, W, cin, cout, ks, buf, None, buf, resid, 1, buf, out32, dt, None)
+    for ks in (0, 2, 5, -1):
+        _refused(conv(ks=ks), fn)
+    for cin, cout in ((32, 64), (96, 64), (0, 64), (64, 32), (64, 200), (64, 0), (-64, 64)):
+        _refused(conv(cin=cin, cout=cout), fn)
+    _refused(conv(resid=buf, out32=1), fn)
+    for dt in (-1, 2, 7):
+        _refused(conv(dt=dt), fn)
+    for n, H, W in ((-1, 4, 4), (1, 0, 4), (1, 4, 0)):
+        _refused(conv(n=n, H=H, W=W), fn)
+    _refused(lib.ec_resnet_conv(None, 1, 4, 4, 64, 64, 1, None, None, None, None, 1, None, 0, F16, None), fn)
+
+    fn = 'ec_resnet_stem_rows'
+    for R in (3, 225, 0, -2):
+        _refused(lib.ec_resnet_stem_rows(buf, _lib.EC_PRE_HWC_U8, 1, R, buf, F16, None), fn)
+    _refused(lib.ec_resnet_stem_rows(buf, _lib.EC_PRE_PATCHES16, 1, 224, buf, F16, None), fn)
+    _refused(lib.ec_resnet_stem_rows(buf, _lib.EC_PRE_CHW_F32, 1, 224, buf, 2, None), fn)
+    _refused(lib.ec_resnet_stem_rows(None, _lib.EC_PRE_CHW_F32, 1, 224, None, F16, None), fn)
+
+    fn = 'ec_resnet_avgpool'
+    for H, W, C in ((1, 4, 8), (4, 1, 8), (4, 4, 12), (4, 4, 0)):
+        _refused(lib.ec_resnet_avgpool(buf, 1, H, W, C, buf, F16, None), fn)
+    _refused(lib.ec_resnet_avgpool(buf, 1, 4, 4, 8, buf, 3, None), fn)
+    _refused(lib.ec_resnet_avgpool(None, 1, 4, 4, 8, None, BF16, None), fn)
+
+    fn = 'ec_resnet_attnpool_tokens'
+    _refused(lib.ec_resnet_attnpool_tokens(buf, 1, 49, 64, buf, buf, buf, 2, None), fn)
+    _refused(lib.ec_resnet_attnpool_tokens(buf, 65536, 49, 64, buf, buf, buf, F16, None), fn)
+    _refused(lib.ec_resnet_attnpool_tokens(buf, 1, 0, 64, buf, buf, buf, F16, None), fn)
+    _refused(lib.ec_resnet_attnpool_tokens(None, 1, 49, 64, None, None, None, F16, None), fn)
+
+    fn = 'ec_resnet_attnpool_attend'
+    for L, C in ((257, 64), (0, 64), (50, 96), (50, 32), (50, 0)):
+        _refused(lib.ec_resnet_attnpool_attend(buf, buf, 1, L, C, buf, F16, None), fn)
+    _refused(lib.ec_resnet_attnpool_attend(buf, buf, 1, 50, 64, buf, -1, None), fn)
+    _refused(lib.ec_resnet_attnpool_attend(buf, buf, 65536, 50, 64, buf, F16, None), fn)
+    _refused(lib.ec_resnet_attnpool_attend(None, None, 1, 50, 64, None, BF16, None), fn)
+
+    # n_img = 0: nothing to do, and no buffer is needed
+    for dt in (F16, BF16):
+        assert lib.ec_resnet_conv(None, 0, 7, 7, 64, 128, 3, None, None, None, None, 1, None, 0, dt, None) == _lib.EC_OK
+        assert lib.ec_resnet_stem_rows(None, _lib.EC_PRE_HWC_U8, 0, 224, None, dt, None) == _lib.EC_OK
+        assert lib.ec_resnet_avgpool(None, 0, 14, 14, 64, None, dt, None) == _lib.EC_OK
+        assert lib.ec_resnet_attnpool_tokens(None, 0, 49, 2048, None, None, None, dt, None) == _lib.EC_OK
+        assert lib.ec_resnet_attnpool_attend(None, None, 0, 50, 2048, None, dt, None) == _lib.EC_OK

@@ -209,12 +209,112 @@ def test_chunked_encode_rn50x64():
 
 
 def test_bf16_tower():
-    """bf16 operands at reduced depth (full-depth random towers amplify 16-bit rounding to 8 - 30 % even in fp16)."""
+    """bf16 operands at reduced depth (full-depth random towers amplify 16-bit rounding to 8 - 30 % even in fp16), and
+    no further from the fp32 restatement than a bf16 emulation of the reference's arithmetic (the slack rule of
+    test_tower_parity_against_restatement)."""
     cfg, sd, m = _model('RN50', (1, 1, 1, 1), 0, dtype='bfloat16')
     x = torch.randn(2, 3, 224, 224, generator=torch.Generator().manual_seed(1))
+    ref_m = resnet_ref.from_state_dict(sd, cfg)
     with torch.no_grad():
-        ref = resnet_ref.from_state_dict(sd, cfg)(x)
-    assert _maxnorm_err(m.encode_image(x.cuda()).cpu(), ref) < 5e-2
+        ref = ref_m(x)
+        emu = ref_m(x, emulate16=torch.bfloat16)
+    e_hip = _maxnorm_err(m.encode_image(x.cuda()).cpu(), ref)
+    assert e_hip < 5e-2
+    e_emu = _maxnorm_err(emu, ref)
+    print(f'RN50 layers=(1, 1, 1, 1) bf16: hip {e_hip:.2e}  bf16 emulation {e_emu:.2e}')
+    assert e_hip <= 1.05 * e_emu, (e_hip, e_emu)
+
+
+@pytest.mark.parametrize('arch,layers', [('RN50x4', (1, 1, 1, 1))])
+def test_bf16_tower_against_emulation(arch, layers):
+    """The bf16 tower's max-normalised error against the fp32 restatement is at most that of a bf16 emulation of the
+    reference's own arithmetic (resnet_ref, emulate16=torch.bfloat16), for two weight seeds and 16 images; the slack
+    rule of test_tower_parity_against_restatement.
+
+    Reduced depth only.  At full RN50 depth the bf16 comparison does not decide anything: there the max-normalised
+    error moves by about 10 % when only the fp32 summation order changes (the HIP arithmetic emulated on the CPU
+    with two conv algorithms: 1.9e-2 and 2.1e-2), while the bf16 emulation's own error (2.2e-2) sits within that
+    spread of the tower's (2.3e-2, seed 0).  RN50x4 measures 1.01 and 0.99 x the emulation's error (seeds 0, 1)."""
+    for seed in _SEEDS:
+        cfg, sd, m = _model(arch, layers, seed, dtype='bfloat16')
+        R = cfg['image_size']
+        x = torch.randn(16, 3, R, R, generator=torch.Generator().manual_seed(200 + seed))
+        ref_m = resnet_ref.from_state_dict(sd, cfg)
+        with torch.no_grad():
+            ref = ref_m(x)
+            emu = ref_m(x, emulate16=torch.bfloat16)
+        e_hip, e_emu = _maxnorm_err(m.encode_image(x.cuda()).cpu(), ref), _maxnorm_err(emu, ref)
+        print(f'{arch} layers={layers} seed={seed} bf16: hip {e_hip:.2e}  bf16 emulation {e_emu:.2e}')
+        slack = 1.0 if layers is None else 1.05
+        assert e_hip <= slack * e_emu, (arch, seed, e_hip, e_emu)
+
+
+# ---- ec_resnet_encode's buffers and input modes ----
+_MEAN = torch.tensor([0.48145466, 0.4578275, 0.40821073])
+_STD = torch.tensor([0.26862954, 0.26130258, 0.27577711])
+_GUARD, _GUARD_BYTES = 0x5A, 1 << 20
+
+
+def _frames(n, R, seed):
+    """uint8 HWC frames and the fp32 CHW images CLIP's ToTensor + Normalize make of them (on the CPU)."""
+    u8 = torch.randint(0, 256, (n, R, R, 3), generator=torch.Generator().manual_seed(seed), dtype=torch.uint8)
+    return u8, ((u8.float() / 255 - _MEAN) / _STD).permute(0, 3, 1, 2).contiguous()
+
+
+def _encode_guarded(lib, rw, inp, mode, n, chunk, E, short=0):
+    """ec_resnet_encode with a workspace of exactly ec_resnet_workspace_bytes(min(chunk, n)) (less ``short``) bytes
+    followed by a guard, and feats followed by guard rows -> (rc, feats [n, E]); asserts both guards intact."""
+    import ctypes
+    from eventclip_amd import _lib
+    need = lib.ec_resnet_workspace_bytes(ctypes.byref(rw), min(chunk, n))
+    assert need > 0
+    ws = torch.full((need + _GUARD_BYTES,), _GUARD, dtype=torch.uint8, device='cuda')
+    feats = torch.empty((n + 4) * E, dtype=torch.float32, device='cuda')
+    feats.view(torch.uint8).fill_(_GUARD)
+    rc = lib.ec_resnet_encode(ctypes.byref(rw), _lib.ptr(inp), mode, n, _lib.ptr(feats), _lib.ptr(ws), need - short,
+                              chunk, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert int((ws[need - short:] != _GUARD).sum()) == 0, ('workspace guard', chunk, mode)
+    assert int((feats[n * E:].view(torch.uint8) != _GUARD).sum()) == 0, ('feats guard', chunk, mode)
+    return rc, feats[:n * E].view(n, E)
+
+
+@pytest.mark.parametrize('arch,layers', [(a, (1, 1, 1, 1)) for a, _ in _TOWERS] + [('RN50', None)])
+def test_encode_stays_in_its_buffers(arch, layers):
+    """ec_resnet_encode, called through the C ABI with ResNetCLIP._pack()'s weights, writes nothing past the
+    workspace ec_resnet_workspace_bytes(min(chunk, n)) asks for nor past feats, for 5 images in chunks of 1, 2, 5 and
+    8 and both input modes; the features are bit-identical across chunk sizes and input modes, and a workspace one
+    byte short is refused."""
+    from eventclip_amd import _lib
+    lib = _lib.lib()
+    cfg, sd, m = _model(arch, layers, 0)
+    rw = m._pack()['resnet']
+    n, R, E = 5, cfg['image_size'], cfg['embed_dim']
+    u8, img = _frames(n, R, 7)
+    first = None
+    for mode, inp in ((_lib.EC_PRE_HWC_U8, u8.cuda()), (_lib.EC_PRE_CHW_F32, img.cuda())):
+        for chunk in (1, 2, 5, 8):
+            rc, f = _encode_guarded(lib, rw, inp, mode, n, chunk, E)
+            _lib.check(rc, 'ec_resnet_encode')
+            assert torch.isfinite(f).all()
+            if first is None:
+                first = f.clone()
+            assert torch.equal(f, first), (mode, chunk)
+        rc, _ = _encode_guarded(lib, rw, inp, mode, n, 2, E, short=1)
+        assert rc == _lib.EC_ERR_INVALID and b'workspace' in lib.ec_last_error()
+
+
+@pytest.mark.parametrize('dtype', ['float16', 'bfloat16'])
+@pytest.mark.parametrize('arch,layers', [('RN50', None), ('RN50x4', (1, 1, 1, 1))])
+def test_input_modes_bit_identical(arch, layers, dtype):
+    """encode_frames on uint8 frames and encode_image on ((u8 / 255 - mean) / std) computed on the CPU feed the same
+    stem rows, so their features agree bit for bit."""
+    cfg, sd, m = _model(arch, layers, 1, dtype=dtype)
+    u8, img = _frames(3, cfg['image_size'], 11)
+    a = m.encode_frames(u8.cuda())
+    b = m.encode_image(img.cuda())
+    assert torch.isfinite(a).all()
+    assert torch.equal(a, b)
 
 
 def test_zero_shot_classifier_events_match_images():
