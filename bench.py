@@ -1,6 +1,6 @@
 """Headline benchmark: event-frames/sec through the whole hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one batch of the BASELINE.json config "N-Caltech101 zero-shot, ViT-L/14,
@@ -19,11 +19,15 @@ them: "DP-sharded across 8").  The line also carries every rank's own ms per ste
 of the logits took on rank 0's stream.
 
 Rank 0 prints one JSON line; `roofline` comes from HIP events the library records
-around its own launches during the timed steps, `cpu_baseline` is the CPU oracle
-(test infrastructure) timed on a bounded sample on the host.  `--dump-outputs DIR`
-writes what the last timed step returned (rank 0's out_dict) as DIR/<name>.npy: the
-inputs are seeded, so two builds run with the same arguments can be compared output
-for output.
+around its own launches during the timed steps.  `--dump-outputs DIR` writes what the
+last timed step returned (rank 0's out_dict) as DIR/<name>.npy: the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+
+A plain run sets up, warms up, times the steps, dumps and prints: nothing else.  `--full`
+adds, on one GPU and after the timed region (never part of `value`), what `extras` lists:
+the host-fed steps, clock / power sampling, the tolerance mode's price, the strict
+pipeline's price, `cpu_baseline` (the CPU oracle, test infrastructure, timed on a bounded
+sample on the host) and BASELINE configs[2..4] as `other_configs`.
 """
 import argparse
 import json
@@ -79,15 +83,19 @@ def parse():
     ap.add_argument('--cpu-baseline-frames', type=int, default=10, help='views per baseline sample')
     ap.add_argument('--packed-events', action='store_true',
                     help='feed the 8-byte packed event form (SURVEY 8(f)) instead of float32 [n, 4]')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure, after the timed region, what the headline does not need (single GPU): '
+                         'value_from_host, dvfs, tolerance_mode, ms_per_step_strict, cpu_baseline, other_configs; '
+                         'each --no-* option below drops one of them')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without cpu_baseline')
     ap.add_argument('--from-host', action='store_true',
                     help='also time the step with every batch starting in HOST memory (pinned staging ring + copy '
                          'stream, the upload of batch i + 1 under the tower of batch i): value_from_host')
-    ap.add_argument('--no-from-host', action='store_true', help='skip the host-fed steps of the default single-GPU line')
+    ap.add_argument('--no-from-host', action='store_true', help='--full without the host-fed steps')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='skip BASELINE configs[2..4] at their per-GPU shards after the timed region: other_configs')
-    ap.add_argument('--no-strict-line', action='store_true', help='skip the 3 steps with pipe.strict = True: ms_per_step_strict')
-    ap.add_argument('--no-dvfs', action='store_true', help='skip the clock / power sampling steps')
+                    help='--full without BASELINE configs[2..4] at their per-GPU shards: other_configs')
+    ap.add_argument('--no-strict-line', action='store_true', help='--full without the 3 steps with pipe.strict = True: ms_per_step_strict')
+    ap.add_argument('--no-dvfs', action='store_true', help='--full without the clock / power sampling steps')
     ap.add_argument('--precise', action='store_true',
                     help='image tower with hi + lo operands in every GEMM (ec_vit_weights.precise, 3 x the MFMA work): '
                          'the mode that meets 1e-3 on input-dependent weights; a line of its own, never the headline')
@@ -100,7 +108,7 @@ def parse():
     ap.add_argument('--tolerance-mode', action='store_true',
                     help='time the headline config IN the tolerance mode (eventclip_amd.clip.TOLERANCE_MODE): a line of its own, never the headline')
     ap.add_argument('--no-tolerance-mode', action='store_true',
-                    help='skip the extra steps (after the timed region) that price the 1e-3 mode: tolerance_mode')
+                    help='--full without the extra steps that price the 1e-3 mode: tolerance_mode')
     ap.add_argument('--other-configs-batch', type=int, default=None,
                     help='samples per step of each of other_configs (tests; default: the per-GPU shard of BASELINE\'s batch)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -115,6 +123,24 @@ def parse():
     a.arch = a.arch or c['arch']
     a.classes = a.classes or c['K']
     return a
+
+
+def extras(a, world):
+    """The keys of what this run measures besides its headline, all of it after the timed region.  A plain run adds
+    only what --from-host asks for; --full adds the rest on one GPU, less what the --no-* options drop and what does not
+    apply to a line of its own (--precise, --precise-blocks, --tolerance-mode, --f16-weights)."""
+    run = {'value_from_host'} if a.from_host else set()
+    if not a.full or world > 1:
+        return run
+    headline = a.config == 1
+    split = a.precise or a.precise_blocks or a.tolerance_mode
+    wanted = {'value_from_host': headline and not a.no_from_host,
+              'dvfs': not a.no_dvfs,
+              'tolerance_mode': headline and not (a.no_tolerance_mode or split),
+              'ms_per_step_strict': not a.no_strict_line,
+              'cpu_baseline': not a.no_cpu_baseline,
+              'other_configs': headline and not (a.no_other_configs or split or a.f16_weights)}
+    return run | {k for k, on in wanted.items() if on}
 
 
 DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: bytes in all, .npy headers included
@@ -719,8 +745,9 @@ def main():
 
     # ---- the same steps with every batch starting in host memory (never part of `value`) ----
     host_line = None
-    # (on by default for the headline line on one GPU -- VERDICT r5 item 3: the host-fed number in the driver's record)
-    if a.from_host or (world == 1 and a.config == 1 and not a.no_from_host):
+    run = extras(a, world)
+    # (in every --full line of the headline on one GPU -- VERDICT r5 item 3: the host-fed number in the driver's record)
+    if 'value_from_host' in run:
         # (measured after the timed region: a failure here must not cost the line its `value`; an explicit --from-host run raises)
         try:
             host_samples = [evs[i % uniq_n] for i in range(local_batch)]      # numpy float32 [n_ev, 4] each
@@ -848,7 +875,7 @@ def main():
             res['all_gather_ms_per_step'] = gather_ms
         if host_line is not None:
             res.update(host_line)
-        if world == 1 and not a.no_dvfs:
+        if 'dvfs' in run:
             dv = sample_dvfs(step, fence, device=local)
             if dv:
                 res['dvfs'] = dv
@@ -859,10 +886,10 @@ def main():
             except Exception as e:   # noqa: BLE001
                 res[key + '_error'] = repr(e)
                 sys.stderr.write(f'[bench] {key} failed: {e!r}\n')
-        if world == 1 and a.config == 1 and not (a.no_tolerance_mode or a.precise or a.precise_blocks or a.tolerance_mode):
+        if 'tolerance_mode' in run:
             extra('tolerance_mode', lambda: tolerance_mode(a, cfg, sd, clip_dict, step, fence, pipe, events, n_events,
                                                            frames_per_step, res['ms_per_step']))
-        if world == 1 and not a.no_strict_line:
+        if 'ms_per_step_strict' in run:
             # Event2ImagePipeline's DEFAULT (strict = True) reads the events kernel's out-of-sensor count back to the
             # host every batch (event2img.py:106-110; the reference syncs per batch too, test.py:66); the timed region
             # runs strict = False: this is what the default costs on the same batch
@@ -881,12 +908,12 @@ def main():
             extra('ms_per_step_strict', strict_ms)
             res['strict_note'] = ('pipe.strict = True (the pipeline default: one 4-byte read-back of the dropped-event count per '
                                   'batch), 3 steps after the timed region; `value` is timed with strict = False')
-        if world == 1 and not a.no_cpu_baseline:
+        if 'cpu_baseline' in run:
             extra('cpu_baseline', lambda: cpu_baseline(cfg, sd, tokens, evs, quantize_args,
                                                        a.cpu_baseline_samples if a.config == 1 else 1,
                                                        min(a.cpu_baseline_frames, T) if a.config != 3 else 2,
                                                        shape=geo['resolution'], pool=(a.config == 1)))
-        if world == 1 and a.config == 1 and not (a.no_other_configs or a.precise or a.precise_blocks or a.f16_weights or a.tolerance_mode):
+        if 'other_configs' in run:
             # release the headline's model / workspace / events first: the other configs build their own
             del w, model, clip_model, clip_dict, pipe, events, out, step
             torch.cuda.empty_cache()

@@ -55,6 +55,31 @@ def test_dump_samples_the_same_rows_within_the_limit(tmp_path):
     np.testing.assert_array_equal(np.load(a / 'logits.npy'), out['logits'].numpy()[idx])
 
 
+def _extras(monkeypatch, argv, world=1):
+    monkeypatch.setattr(sys, 'argv', ['bench.py'] + argv)
+    return bench.extras(bench.parse(), world)
+
+
+def test_a_plain_run_measures_nothing_behind_the_timed_steps(monkeypatch):
+    """Only --full adds measurements after the timed region; an explicit --from-host stays on in any run."""
+    every = {'value_from_host', 'dvfs', 'tolerance_mode', 'ms_per_step_strict', 'cpu_baseline', 'other_configs'}
+    assert _extras(monkeypatch, []) == set()
+    assert _extras(monkeypatch, ['--config', '3', '--no-dvfs']) == set()
+    assert _extras(monkeypatch, ['--from-host']) == {'value_from_host'}
+    assert _extras(monkeypatch, ['--full']) == every
+    assert _extras(monkeypatch, ['--full', '--gpus', '2'], world=2) == set()
+    assert _extras(monkeypatch, ['--full', '--from-host', '--gpus', '2'], world=2) == {'value_from_host'}
+    for flag, key in (('--no-from-host', 'value_from_host'), ('--no-dvfs', 'dvfs'), ('--no-tolerance-mode', 'tolerance_mode'),
+                      ('--no-strict-line', 'ms_per_step_strict'), ('--no-cpu-baseline', 'cpu_baseline'),
+                      ('--no-other-configs', 'other_configs')):
+        assert _extras(monkeypatch, ['--full', flag]) == every - {key}, flag
+    # the other configs and the lines of their own carry no headline-only measurement
+    assert _extras(monkeypatch, ['--full', '--config', '3']) == {'dvfs', 'ms_per_step_strict', 'cpu_baseline'}
+    for own in (['--precise'], ['--precise-blocks', '2'], ['--tolerance-mode']):
+        assert _extras(monkeypatch, ['--full'] + own) == every - {'tolerance_mode', 'other_configs'}, own
+    assert _extras(monkeypatch, ['--full', '--f16-weights']) == every - {'other_configs'}
+
+
 def test_steps_below_one_is_refused():
     for bad in (['--steps', '0'], ['--warmup', '-1']):
         r = subprocess.run([sys.executable, 'bench.py'] + bad, cwd=ROOT, capture_output=True, text=True, timeout=120)

@@ -23,7 +23,7 @@ def last_json(text):
 
 
 def test_single_rank_line(hip):
-    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--other-configs-batch', '2'] + SMALL, cwd=ROOT,
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--full', '--other-configs-batch', '2'] + SMALL, cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
@@ -64,6 +64,27 @@ def test_single_rank_line(hip):
         assert abs(ln['value'] - ln['frames_per_step'] * 1e3 / ln['ms_per_step']) < 1e-6 * ln['value']
         assert ln['dominant_kernel'] in ln['kernel_ms_per_step'] and 0 <= ln['frac'] < 1      # (two samples: a latency-bound kernel may dominate)
         assert ln['cpu_baseline']['value'] > 0 and ln['cpu_baseline']['kind'] == 'port'
+
+
+FULL_ONLY = {'value_from_host', 'ms_per_step_from_host', 'from_host', 'dvfs', 'tolerance_mode', 'ms_per_step_strict',
+             'strict_note', 'cpu_baseline', 'other_configs'}
+
+
+def test_plain_line_measures_only_the_headline(hip):
+    """Without --full the run sets up, warms up, times its steps and prints: the headline fields and the roofline of the
+    timed steps, none of what --full measures behind them, and no more than 30 s of wall time outside the steps."""
+    import time
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1'] + SMALL, cwd=ROOT, capture_output=True, text=True,
+                       timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = last_json(r.stdout)
+    assert REQUIRED <= set(d) and d['n_gpus'] == 1 and d['steps'] == 2 and d['warmup'] == 1
+    assert abs(d['value'] - 4 * 10 * 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+    assert d['roofline']['kernel'] in d['kernel_ms_per_step']
+    assert not FULL_ONLY & set(d) and not [k for k in d if k.endswith('_error')], sorted(d)
+    assert wall - (2 + 1) * d['ms_per_step'] * 1e-3 < 30, wall
 
 
 def test_two_ranks_share_the_gpu_over_gloo(hip):
