@@ -79,6 +79,11 @@ EC_STEP_LR0, EC_STEP_LR1, EC_STEP_BC1, EC_STEP_BC2_SQRT, EC_STEP_GRAD_SCALE, EC_
 EC_PRE_CHW_F32, EC_PRE_PATCHES16, EC_PRE_HWC_U8 = 0, 1, 2
 EC_AGG_SUM, EC_AGG_MEAN, EC_AGG_MAX = 0, 1, 2
 EC_OK, EC_ERR_INVALID, EC_ERR_HIP, EC_ERR_UNSUPPORTED, EC_ERR_WORKSPACE = 0, -1, -2, -3, -4
+# ec_vit_train_layout: the training workspace's slots (tower-wide, then EC_VT_PER_BLOCK per block)
+(EC_VT_PRE, EC_VT_X_LAST, EC_VT_DX, EC_VT_DX16, EC_VT_DH32, EC_VT_DA16, EC_VT_G16, EC_VT_DELTA, EC_VT_CLSLN, EC_VT_DCLSLN,
+ EC_VT_BLOCK0) = range(11)
+(EC_VT_B_X, EC_VT_B_XM, EC_VT_B_QKV, EC_VT_B_ATT, EC_VT_B_U, EC_VT_B_GACT, EC_VT_B_H1, EC_VT_B_H2, EC_VT_B_LSE,
+ EC_VT_PER_BLOCK) = range(10)
 
 
 class EcBlockWeights(ctypes.Structure):
@@ -274,6 +279,7 @@ SIGNATURES = {
     'ec_vit_train_backward_stages': (c_int, [ctypes.POINTER(EcVitWeights), ctypes.POINTER(EcVitTrainWeights), c_void_p,
                                              c_int, c_void_p, ctypes.POINTER(EcVitGrads), ctypes.POINTER(EcVitLora), c_int,
                                              c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    'ec_vit_train_layout': (c_int, [ctypes.POINTER(EcVitWeights), c_int, c_void_p, c_int]),
     'ec_pack_weight16_batched': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'ec_layernorm_backward_partials': (ctypes.c_size_t, [c_int, c_int]),
     'ec_layernorm_backward': (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_float,
@@ -303,7 +309,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 600      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
+ABI_VERSION = 601      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
 
 
 class HipLibraryError(RuntimeError):

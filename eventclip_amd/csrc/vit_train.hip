@@ -1345,6 +1345,34 @@ EC_API size_t ec_vit_train_workspace_bytes(const ec_vit_weights *w, int n_img)
     return carve_train(sc, w, n_img, b);
 }
 
+// The offsets come from carve_train itself, run on a Scratch whose base is a sentinel address (a null base would
+// hand out null pointers): the two cannot drift apart.
+EC_API int ec_vit_train_layout(const ec_vit_weights *w, int n_img, int64_t *offsets, int n_offsets)
+{
+    EC_REQUIRE(w && n_img > 0 && w->patch > 0 && w->layers >= 1 && w->layers <= 64,
+               "ec_vit_train_layout: bad geometry (n_img %d)", n_img);
+    const int L = w->layers, need = EC_VT_BLOCK0 + EC_VT_PER_BLOCK * L;
+    if (!offsets) return need;
+    EC_REQUIRE(n_offsets >= need, "ec_vit_train_layout: %d slots for %d", n_offsets, need);
+    unsigned char *const sentinel = reinterpret_cast<unsigned char *>(uintptr_t(1) << 40);
+    Scratch sc{sentinel, 0, ~(size_t)0};
+    TrainBufs b;
+    carve_train(sc, w, n_img, b);
+    auto off = [&](const void *p) { return (int64_t)(static_cast<const unsigned char *>(p) - sentinel); };
+    offsets[EC_VT_PRE] = off(b.pre);
+    offsets[EC_VT_X_LAST] = off(b.x[L]);
+    offsets[EC_VT_DX] = off(b.dx), offsets[EC_VT_DX16] = off(b.dx16), offsets[EC_VT_DH32] = off(b.dh32);
+    offsets[EC_VT_DA16] = off(b.da16), offsets[EC_VT_G16] = off(b.g16), offsets[EC_VT_DELTA] = off(b.delta);
+    offsets[EC_VT_CLSLN] = off(b.clsln), offsets[EC_VT_DCLSLN] = off(b.dclsln);
+    for (int l = 0; l < L; l++) {
+        int64_t *o = offsets + EC_VT_BLOCK0 + EC_VT_PER_BLOCK * l;
+        o[EC_VT_B_X] = off(b.x[l]), o[EC_VT_B_XM] = off(b.xm[l]), o[EC_VT_B_QKV] = off(b.qkv[l]);
+        o[EC_VT_B_ATT] = off(b.att[l]), o[EC_VT_B_U] = off(b.u[l]), o[EC_VT_B_GACT] = off(b.gact[l]);
+        o[EC_VT_B_H1] = off(b.h1[l]), o[EC_VT_B_H2] = off(b.h2[l]), o[EC_VT_B_LSE] = off(b.lse[l]);
+    }
+    return need;
+}
+
 EC_API int ec_vit_train_forward(const ec_vit_weights *w, const void *patches, int n_img, float *feats, void *workspace,
                                 size_t workspace_bytes, ec_stream_t stream)
 {

@@ -241,6 +241,40 @@ class VisualTower:
         _lib.check(rc, 'ec_vit_encode')
         return feats
 
+    def workspace_views(self, n):
+        """Typed views of the training workspace of the last ``forward`` over n images (``ec_vit_train_layout``): the
+        tape and the backward pass's state between stages, for tests.  -> (tower-wide {name: view}, [block {name: view}])"""
+        assert self._ws is not None, 'workspace_views before a forward'
+        L, W, M, H, cd = self.L, self.W, n * self.S, self.W // 64, self.cd
+        cnt = _lib.EC_VT_BLOCK0 + _lib.EC_VT_PER_BLOCK * L
+        offs = (ctypes.c_int64 * cnt)()
+        rc = _lib.lib().ec_vit_train_layout(ctypes.byref(self._vit), n, offs, cnt)
+        _lib.check(rc if rc < 0 else 0, 'ec_vit_train_layout')
+
+        def view(slot, dtype, *shape):
+            numel = 1
+            for s in shape:
+                numel *= s
+            nbytes = numel * torch.empty((), dtype=dtype).element_size()
+            o = offs[slot]
+            assert 0 <= o and o + nbytes <= self._ws.numel()
+            return self._ws[o:o + nbytes].view(dtype).view(shape)
+        f32 = torch.float32
+        top = dict(pre=view(_lib.EC_VT_PRE, f32, M, W), x_last=view(_lib.EC_VT_X_LAST, f32, M, W),
+                   dx=view(_lib.EC_VT_DX, f32, M, W), dx16=view(_lib.EC_VT_DX16, cd, M, W),
+                   dh32=view(_lib.EC_VT_DH32, f32, M, W), da16=view(_lib.EC_VT_DA16, cd, M, W),
+                   g16=view(_lib.EC_VT_G16, cd, M, 4 * W), delta=view(_lib.EC_VT_DELTA, f32, n, H, self.S),
+                   clsln=view(_lib.EC_VT_CLSLN, f32, n, W), dclsln=view(_lib.EC_VT_DCLSLN, f32, n, W))
+        blocks = []
+        for l in range(L):
+            b = _lib.EC_VT_BLOCK0 + _lib.EC_VT_PER_BLOCK * l
+            blocks.append(dict(x=view(b + _lib.EC_VT_B_X, f32, M, W), xm=view(b + _lib.EC_VT_B_XM, f32, M, W),
+                               qkv=view(b + _lib.EC_VT_B_QKV, cd, M, 3 * W), att=view(b + _lib.EC_VT_B_ATT, cd, M, W),
+                               u=view(b + _lib.EC_VT_B_U, cd, M, 4 * W), gact=view(b + _lib.EC_VT_B_GACT, cd, M, 4 * W),
+                               h1=view(b + _lib.EC_VT_B_H1, cd, M, W), h2=view(b + _lib.EC_VT_B_H2, cd, M, W),
+                               lse=view(b + _lib.EC_VT_B_LSE, f32, n, H, self.S)))
+        return top, blocks
+
     def grad_buffer(self, want):
         """One flat fp32 buffer with a slot per wanted gradient (a single all-reduce / unscale covers it)."""
         key = tuple(want)

@@ -48,12 +48,13 @@ EC_API const char *ec_last_error(void);
  *   100  rounds 1 - 5 (the number was never bumped; ec_classify changed its argument list twice and ec_gemm_args /
  *        ec_vit_weights grew in that time -- a caller built against any of those headers must be rebuilt)
  *   600  round 6: ec_classify -> ec_classify_prep_text + ec_classify_v2; ec_abi_check
+ *   601  + ec_vit_train_layout (additive: no struct or argument list changed)
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does, with its ctypes mirrors.) */
-#define EC_ABI_VERSION 600
+#define EC_ABI_VERSION 601
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);
@@ -819,6 +820,25 @@ EC_API int ec_vit_train_backward_stages(const ec_vit_weights *w, const ec_vit_tr
                                         int n_img, const float *d_feats, const ec_vit_grads *grads,
                                         const ec_vit_lora *lora, int stage_begin, int stage_end, void *workspace,
                                         size_t workspace_bytes, ec_stream_t stream);
+
+/* Where the training workspace of n_img images keeps its tape and the backward pass's state between stages: byte
+ * offsets from the workspace's start, for tests that check one stage against a restatement of it.  offsets[EC_VT_*]
+ * are the tower-wide slots; block l's slot k (EC_VT_B_*) is offsets[EC_VT_BLOCK0 + EC_VT_PER_BLOCK * l + k].
+ * Returns the slot count (EC_VT_BLOCK0 + EC_VT_PER_BLOCK * layers; offsets NULL: just that) or an EC_ERR_* code.
+ *   pre    fp32 [M, W] the embedding before ln_pre       x_last fp32 [M, W] x[layers], ln_post's input
+ *   dx     fp32 [M, W] d loss / d x at the stage boundary dx16  16-bit [M, W] its copy (the dX GEMMs' operand)
+ *   dh32   fp32 [M, W] d loss / d (a LayerNorm output)   da16  16-bit [M, W] d loss / d (attention output)
+ *   g16    16-bit [M, 4W] du (MLP) / [M, 3W] dq | dk | dv delta fp32 [n, heads, S] attention backward's D
+ *   clsln, dclsln  fp32 [n, W] ln_post of the class rows and its gradient
+ *   block: x, xm fp32 [M, W]; qkv 16-bit [M, 3W]; att, h1, h2 16-bit [M, W]; u, gact 16-bit [M, 4W];
+ *          lse fp32 [n, heads, S] (log2 units) */
+enum {
+    EC_VT_PRE = 0, EC_VT_X_LAST, EC_VT_DX, EC_VT_DX16, EC_VT_DH32, EC_VT_DA16, EC_VT_G16, EC_VT_DELTA, EC_VT_CLSLN,
+    EC_VT_DCLSLN, EC_VT_BLOCK0
+};
+enum { EC_VT_B_X = 0, EC_VT_B_XM, EC_VT_B_QKV, EC_VT_B_ATT, EC_VT_B_U, EC_VT_B_GACT, EC_VT_B_H1, EC_VT_B_H2, EC_VT_B_LSE,
+       EC_VT_PER_BLOCK };
+EC_API int ec_vit_train_layout(const ec_vit_weights *w, int n_img, int64_t *offsets, int n_offsets);
 
 /* fp32 [rows, cols] -> any of: hi = round16(w) [rows, cols]; lo = round16(w - hi); hi_t = hi transposed
  * [cols, rows] (NULL outputs are skipped), for a list of same-shape matrices in one launch (`items`: DEVICE array):
