@@ -169,7 +169,8 @@ class EcVitLora(ctypes.Structure):
 
 
 class EcResnetConvW(ctypes.Structure):
-    _fields_ = [('w', c_void_p), ('scale', c_void_p), ('bias', c_void_p), ('ks', c_int), ('cin', c_int), ('cout', c_int)]
+    _fields_ = [('w', c_void_p), ('scale', c_void_p), ('bias', c_void_p), ('ks', c_int), ('cin', c_int), ('cout', c_int),
+                ('w_lo', c_void_p)]
 
 
 class EcResnetBlock(ctypes.Structure):
@@ -180,7 +181,8 @@ class EcResnetBlock(ctypes.Structure):
 class EcResnetWeights(ctypes.Structure):
     _fields_ = [('struct_bytes', ctypes.c_size_t), ('dtype', c_int), ('image_size', c_int), ('n_blocks', c_int),
                 ('embed_dim', c_int), ('stem', EcResnetConvW * 3), ('blocks', ctypes.POINTER(EcResnetBlock)),
-                ('pos', c_void_p), ('q', EcResnetConvW), ('kv', EcResnetConvW), ('c', EcResnetConvW)]
+                ('pos', c_void_p), ('q', EcResnetConvW), ('kv', EcResnetConvW), ('c', EcResnetConvW),
+                ('precise_blocks', c_int)]
 
 
 # name -> (restype, argtypes); kept in one table so tests can check that every
@@ -303,13 +305,23 @@ SIGNATURES = {
     'ec_resnet_attnpool_tokens': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                           c_void_p]),
     'ec_resnet_attnpool_attend': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'ec_resnet_conv_hl': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                  c_void_p]),
+    'ec_resnet_stem_rows_hl': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    'ec_resnet_avgpool_hl': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                     c_void_p]),
+    'ec_resnet_attnpool_tokens_hl': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_int, c_void_p]),
+    'ec_resnet_attnpool_attend_hl': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                             c_void_p, c_int, c_void_p]),
 
 }
 
 _lib = None
 
 
-ABI_VERSION = 601      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
+ABI_VERSION = 602      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
 
 
 class HipLibraryError(RuntimeError):

@@ -206,7 +206,16 @@ DEFAULT_LO_FP8 = True
 
 
 def tolerance_mode_kwargs(arch_or_cfg):
-    """CLIP(...) keyword arguments of the tolerance mode for an architecture name or config dict."""
+    """CLIP(...) / ResNetCLIP(...) keyword arguments of the tolerance mode for an architecture name or config dict.
+
+    ResNet towers: every Bottleneck (and the stem and the attention pool) on split-precision operands.  No smaller count
+    has been chosen yet: that needs a sweep over tuning and held-out weight draws (tools/bench_resnet.py
+    --precise-blocks prices and measures the counts), and a count picked on the tuning draws alone is what failed for the
+    ViT mode above."""
+    if isinstance(arch_or_cfg, str) and arch_or_cfg in RESNET_ARCHS:
+        arch_or_cfg = resnet_config(arch_or_cfg)
+    if not isinstance(arch_or_cfg, str) and _resnet.is_resnet_config(arch_or_cfg):
+        return dict(precise_blocks=sum(arch_or_cfg['vision_layers']))
     cfg = arch_config(arch_or_cfg) if isinstance(arch_or_cfg, str) else arch_or_cfg
     tokens = (cfg['image_size'] // cfg['patch']) ** 2 + 1
     pb, pa = TOLERANCE_MODE[0 if tokens <= 288 else 1]
@@ -528,8 +537,9 @@ class CLIP(nn.Module):
 def build_random(arch, seed=0, dtype='float16', device='cuda', chunk=2560, **override):
     """Random-weight CLIP of a named architecture (benchmarks / tests: no checkpoints ship)."""
     if arch in RESNET_ARCHS:
+        mode = {k: override.pop(k) for k in ('precise_blocks', 'precise') if k in override}   # tolerance_mode_kwargs(arch)
         cfg = resnet_config(arch, **override)
-        model = _resnet.ResNetCLIP(cfg, random_state_dict(cfg, seed), dtype=dtype)
+        model = _resnet.ResNetCLIP(cfg, random_state_dict(cfg, seed), dtype=dtype, **mode)
     else:
         cfg = arch_config(arch, **override)
         model = CLIP(cfg, random_state_dict(cfg, seed), dtype=dtype, chunk=chunk)
@@ -538,13 +548,17 @@ def build_random(arch, seed=0, dtype='float16', device='cuda', chunk=2560, **ove
     return model.eval()
 
 
-def build_from_state_dict(sd, dtype='float16', device='cuda', chunk=2560):
+def build_from_state_dict(sd, dtype='float16', device='cuda', chunk=2560, precise_blocks=0):
+    """precise_blocks: the split-precision form of a ResNet tower (tolerance_mode_kwargs); ViT checkpoints refuse it."""
     sd = {k: v for k, v in sd.items() if k not in ('input_resolution', 'context_length',
                                                    'vocab_size')}
     cfg = config_from_state_dict(sd)
     if _resnet.is_resnet_config(cfg):
-        model = _resnet.ResNetCLIP(cfg, sd, dtype=dtype)
+        model = _resnet.ResNetCLIP(cfg, sd, dtype=dtype, precise_blocks=precise_blocks)
     else:
+        if precise_blocks:
+            raise ValueError('precise_blocks is the ResNet towers\' keyword; a ViT takes CLIP(cfg, sd, '
+                             '**tolerance_mode_kwargs(cfg))')
         model = CLIP(cfg, sd, dtype=dtype, chunk=chunk)
     if device is not None:
         model = model.to(device)

@@ -421,6 +421,18 @@ int check_weights(const ec_resnet_weights *w, const char *fn)
                w->c.cout == w->embed_dim && w->pos, "%s: attention pool shapes (C=%d, embed_dim=%d)", fn, C, w->embed_dim);
     const int g = w->image_size / 32;
     EC_REQUIRE(g * g + 1 <= 256, "%s: %d attention-pool tokens (at most 256)", fn, g * g + 1);
+    const int pb = w->precise_blocks;
+    EC_REQUIRE(pb >= 0 && pb <= w->n_blocks, "%s: precise_blocks=%d (0 .. n_blocks=%d)", fn, pb, w->n_blocks);
+    if (pb > 0) {
+        EC_REQUIRE(w->dtype == EC_F16, "%s: precise_blocks=%d needs dtype EC_F16 (the split form is f16 only)", fn, pb);
+        bool lo = w->stem[0].w_lo && w->stem[1].w_lo && w->stem[2].w_lo;
+        for (int b = 0; b < pb; b++) {
+            const ec_resnet_block &k = w->blocks[b];
+            lo = lo && k.c1.w_lo && k.c2.w_lo && k.c3.w_lo && (!k.ds.w || k.ds.w_lo);
+        }
+        if (pb == w->n_blocks) lo = lo && w->q.w_lo && w->kv.w_lo && w->c.w_lo;
+        EC_REQUIRE(lo, "%s: precise_blocks=%d needs w_lo of every convolution that runs split", fn, pb);
+    }
     return EC_OK;
 }
 
@@ -452,9 +464,12 @@ TowerPlan plan_of(const ec_resnet_weights *w, int n)
     return p;
 }
 
-size_t ws_bytes_of(const TowerPlan &p)
+// 16-bit elements of one plane of the workspace; the split form keeps a second plane (lo) right behind the first
+size_t plane_elems_of(const TowerPlan &p) { return 4 * p.act_elems + p.tok_elems + 2 * p.c_elems + p.kv_elems; }
+
+size_t ws_bytes_of(const TowerPlan &p, int precise_blocks = 0)
 {
-    return 2 * (4 * p.act_elems + p.tok_elems + 2 * p.c_elems + p.kv_elems);
+    return 2 * plane_elems_of(p) * (precise_blocks > 0 ? 2 : 1);
 }
 
 int conv_w(const void *x, int n, int H, const ec_resnet_conv_w &c, const void *resid, int relu, void *out, int out32,
@@ -468,7 +483,7 @@ int conv_w(const void *x, int n, int H, const ec_resnet_conv_w &c, const void *r
 EC_API size_t ec_resnet_workspace_bytes(const ec_resnet_weights *w, int chunk)
 {
     if (check_weights(w, "ec_resnet_workspace_bytes") != EC_OK || chunk <= 0) return 0;
-    return ws_bytes_of(plan_of(w, chunk));
+    return ws_bytes_of(plan_of(w, chunk), w->precise_blocks);
 }
 
 #define EC_TRY(expr)                                                                                               \
@@ -487,8 +502,9 @@ EC_API int ec_resnet_encode(const ec_resnet_weights *w, const void *input, int i
     EC_REQUIRE(input && feats && ws, "ec_resnet_encode: null buffer");
     const int cn = chunk < n_img ? chunk : n_img;
     const TowerPlan p = plan_of(w, cn);
-    EC_REQUIRE(ws_bytes >= ws_bytes_of(p), "ec_resnet_encode: workspace %zu bytes, %zu needed for chunk %d", ws_bytes,
-               ws_bytes_of(p), cn);
+    const int pb = w->precise_blocks;
+    EC_REQUIRE(ws_bytes >= ws_bytes_of(p, pb), "ec_resnet_encode: workspace %zu bytes, %zu needed for chunk %d", ws_bytes,
+               ws_bytes_of(p, pb), cn);
     const int dt = w->dtype, R = w->image_size;
     const size_t in_img = (size_t)3 * R * R * (input_mode == EC_PRE_HWC_U8 ? 1 : 4);
     uint16_t *base = (uint16_t *)ws;
@@ -504,28 +520,46 @@ EC_API int ec_resnet_encode(const ec_resnet_weights *w, const void *input, int i
         }
         return nullptr;
     };
+    // the split form (precise_blocks > 0): every buffer's lo plane lies plane_elems behind its hi plane
+    const size_t plane = plane_elems_of(p);
+    auto lo = [&](const void *hi) -> void * { return hi ? (uint16_t *)hi + plane : nullptr; };
+    // one convolution / pooling step, split (pr) or 16-bit; the 16-bit calls are those of the default path
+    auto conv = [&](bool pr, const void *x, int n, int H, const ec_resnet_conv_w &c, const void *resid, int relu, void *out,
+                    int out32) -> int {
+        if (pr)
+            return ec_resnet_conv_hl(x, lo(x), n, H, H, c.cin, c.cout, c.ks, c.w, c.w_lo, c.scale, c.bias, resid, lo(resid),
+                                     relu, out, out32 ? nullptr : lo(out), out32, dt, stream);
+        return conv_w(x, n, H, c, resid, relu, out, out32, dt, stream);
+    };
+    auto pool = [&](bool pr, const void *x, int n, int H, int C, void *y) -> int {
+        if (pr) return ec_resnet_avgpool_hl(x, lo(x), n, H, H, C, y, lo(y), dt, stream);
+        return ec_resnet_avgpool(x, n, H, H, C, y, dt, stream);
+    };
     for (int i0 = 0; i0 < n_img; i0 += cn) {
         const int n = n_img - i0 < cn ? n_img - i0 : cn;
         const void *in = (const char *)input + (size_t)i0 * in_img;
         int h = R / 2;
-        EC_TRY(ec_resnet_stem_rows(in, input_mode, n, R, buf[0], dt, stream));
-        EC_TRY(conv_w(buf[0], n, h, w->stem[0], nullptr, 1, buf[1], 0, dt, stream));
-        EC_TRY(conv_w(buf[1], n, h, w->stem[1], nullptr, 1, buf[0], 0, dt, stream));
-        EC_TRY(conv_w(buf[0], n, h, w->stem[2], nullptr, 1, buf[1], 0, dt, stream));
-        EC_TRY(ec_resnet_avgpool(buf[1], n, h, h, w->stem[2].cout, buf[0], dt, stream));
+        bool pr = pb > 0;
+        if (pr) EC_TRY(ec_resnet_stem_rows_hl(in, input_mode, n, R, buf[0], lo(buf[0]), dt, stream));
+        else EC_TRY(ec_resnet_stem_rows(in, input_mode, n, R, buf[0], dt, stream));
+        EC_TRY(conv(pr, buf[0], n, h, w->stem[0], nullptr, 1, buf[1], 0));
+        EC_TRY(conv(pr, buf[1], n, h, w->stem[1], nullptr, 1, buf[0], 0));
+        EC_TRY(conv(pr, buf[0], n, h, w->stem[2], nullptr, 1, buf[1], 0));
+        EC_TRY(pool(pr, buf[1], n, h, w->stem[2].cout, buf[0]));
         h /= 2;
         void *x = buf[0];
         for (int b = 0; b < w->n_blocks; b++) {
             const ec_resnet_block &k = w->blocks[b];
             EC_REQUIRE(k.stride == 1 || k.stride == 2, "ec_resnet_encode: block %d stride %d", b, k.stride);
             EC_REQUIRE(k.stride == 1 || k.ds.w, "ec_resnet_encode: block %d strides without a downsample", b);
+            pr = b < pb;   // past the last split block the 16-bit path goes on from the hi plane
             void *o1 = other({x});
-            EC_TRY(conv_w(x, n, h, k.c1, nullptr, 1, o1, 0, dt, stream));
+            EC_TRY(conv(pr, x, n, h, k.c1, nullptr, 1, o1, 0));
             void *o2 = other({x, o1});
-            EC_TRY(conv_w(o1, n, h, k.c2, nullptr, 1, o2, 0, dt, stream));
+            EC_TRY(conv(pr, o1, n, h, k.c2, nullptr, 1, o2, 0));
             void *o = o2;
             if (k.stride > 1) {
-                EC_TRY(ec_resnet_avgpool(o2, n, h, h, k.c2.cout, o1, dt, stream));
+                EC_TRY(pool(pr, o2, n, h, k.c2.cout, o1));
                 o = o1;
             }
             const int ho = h / k.stride;
@@ -535,24 +569,35 @@ EC_API int ec_resnet_encode(const ec_resnet_weights *w, const void *input, int i
                 const void *src = x;
                 if (k.stride > 1) {
                     void *t2 = other({x, o, t});
-                    EC_TRY(ec_resnet_avgpool(x, n, h, h, k.ds.cin, t2, dt, stream));
+                    EC_TRY(pool(pr, x, n, h, k.ds.cin, t2));
                     src = t2;
                 }
-                EC_TRY(conv_w(src, n, ho, k.ds, nullptr, 0, t, 0, dt, stream));
+                EC_TRY(conv(pr, src, n, ho, k.ds, nullptr, 0, t, 0));
                 idt = t;
             }
             void *y = other({o, idt});
-            EC_TRY(conv_w(o, n, ho, k.c3, idt, 1, y, 0, dt, stream));
+            EC_TRY(conv(pr, o, n, ho, k.c3, idt, 1, y, 0));
             x = y;
             h = ho;
+        }
+        float *f = feats + (size_t)i0 * w->embed_dim;
+        if (pb == w->n_blocks) {
+            EC_TRY(ec_resnet_attnpool_tokens_hl(x, lo(x), n, p.hw_last, p.C, w->pos, tok, lo(tok), q_in, lo(q_in), dt, stream));
+            EC_TRY(ec_resnet_conv_hl(q_in, lo(q_in), n, 1, 1, p.C, p.C, 1, w->q.w, w->q.w_lo, w->q.scale, w->q.bias, nullptr,
+                                     nullptr, 0, att, lo(att), 0, dt, stream));
+            EC_TRY(ec_resnet_conv_hl(tok, lo(tok), n * p.L, 1, 1, p.C, 2 * p.C, 1, w->kv.w, w->kv.w_lo, w->kv.scale, w->kv.bias,
+                                     nullptr, nullptr, 0, kv, lo(kv), 0, dt, stream));
+            EC_TRY(ec_resnet_attnpool_attend_hl(att, lo(att), kv, lo(kv), n, p.L, p.C, q_in, lo(q_in), dt, stream));
+            EC_TRY(ec_resnet_conv_hl(q_in, lo(q_in), n, 1, 1, p.C, w->embed_dim, 1, w->c.w, w->c.w_lo, w->c.scale, w->c.bias,
+                                     nullptr, nullptr, 0, f, nullptr, 1, dt, stream));
+            continue;
         }
         EC_TRY(ec_resnet_attnpool_tokens(x, n, p.hw_last, p.C, w->pos, tok, q_in, dt, stream));
         EC_TRY(ec_resnet_conv(q_in, n, 1, 1, p.C, p.C, 1, w->q.w, w->q.scale, w->q.bias, nullptr, 0, att, 0, dt, stream));
         EC_TRY(ec_resnet_conv(tok, n * p.L, 1, 1, p.C, 2 * p.C, 1, w->kv.w, w->kv.scale, w->kv.bias, nullptr, 0, kv, 0,
                               dt, stream));
         EC_TRY(ec_resnet_attnpool_attend(att, kv, n, p.L, p.C, q_in, dt, stream));
-        EC_TRY(ec_resnet_conv(q_in, n, 1, 1, p.C, w->embed_dim, 1, w->c.w, w->c.scale, w->c.bias, nullptr, 0,
-                              feats + (size_t)i0 * w->embed_dim, 1, dt, stream));
+        EC_TRY(ec_resnet_conv(q_in, n, 1, 1, p.C, w->embed_dim, 1, w->c.w, w->c.scale, w->c.bias, nullptr, 0, f, 1, dt, stream));
     }
     return EC_OK;
 }

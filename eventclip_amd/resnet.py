@@ -6,6 +6,9 @@ epilogues, 2x2 average pooling, and the attention pool (token building, q / k+v 
 GEMMs, one query per head), all driven by ec_resnet_encode (torch.ops.eventclip_hip.resnet_encode).  Channel
 counts that are not multiples of 64 are padded with zero channels at pack time.  The text tower is ``ec_text_encode``, as for the ViT models.
 
+``precise_blocks`` selects the tower's split-precision form (csrc/resnet_hl.hip): activations and weights as f16 hi + lo
+planes, three MFMA products per convolution, fp32 in between -- the ResNet side of ``clip.tolerance_mode_kwargs``.
+
 Architecture facts follow OpenAI's ``clip/model.py`` (``ModifiedResNet``, ``Bottleneck``, ``AttentionPool2d``,
 ``build_model``)."""
 import ctypes
@@ -30,6 +33,17 @@ RESNET_ARCHS = {
                     text_width=1024, text_heads=16, text_layers=12),
 }
 BN_EPS = 1e-5
+LO_SCALE = 2048.0       # the lo plane of a split value holds (v - hi) * 2^11 (csrc/resnet_hl.hip)
+
+
+def split_hl(t):
+    """fp32 tensor -> (hi, lo) f16 planes of the split-precision kernels: hi = f16(t), lo = f16((t - hi) * 2^11).
+    t - hi is exact in fp32, the scaling is exact, so hi + lo / 2^11 restores t to 2^-22 |t| + 2^-36 (one f16 rounding
+    of lo, which is at most 2^-11 |t| before the scaling and normal wherever hi is; 2^-25 / 2^11 below that)."""
+    t = t.float()
+    hi = t.to(torch.float16)
+    lo = ((t - hi.float()) * LO_SCALE).to(torch.float16)
+    return hi, lo
 
 
 def is_resnet_config(cfg):
@@ -212,7 +226,9 @@ class ResNetCLIP(nn.Module):
     encode_text, visual.output_dim / input_resolution, logit_scale, state_dict in OpenAI's keys), plus
     ``encode_frames`` for the uint8 frames of ``ec_preprocess`` (EC_PRE_HWC_U8)."""
 
-    def __init__(self, cfg, state_dict, dtype='float16', chunk=64):
+    def __init__(self, cfg, state_dict, dtype='float16', chunk=64, precise_blocks=0, precise=False):
+        """precise_blocks: 0, the 16-bit tower; n_blocks (or precise=True), the stem, every Bottleneck and the attention
+        pool on split-precision (hi + lo) operands; 0 < n < n_blocks, the stem and the first n Bottlenecks."""
         super().__init__()
         from .clip import _assign
         self.cfg = dict(cfg)
@@ -224,6 +240,13 @@ class ResNetCLIP(nn.Module):
         self.compute_dtype = {'float16': torch.float16, 'fp16': torch.float16,
                               'bfloat16': torch.bfloat16, 'bf16': torch.bfloat16}[str(dtype)]
         self.chunk = int(chunk)        # images per pass through the tower (bounds the activation workspace)
+        n_blocks = sum(cfg['vision_layers'])
+        self.precise_blocks = n_blocks if precise else int(precise_blocks)
+        if not 0 <= self.precise_blocks <= n_blocks:
+            raise ValueError(f'precise_blocks={precise_blocks} outside 0 .. {n_blocks} (the Bottlenecks of this tower)')
+        if self.precise_blocks and self.compute_dtype != torch.float16:
+            raise ValueError(f'precise_blocks={self.precise_blocks} needs dtype float16 (the split-precision kernels '
+                             'carry f16 hi + lo planes; bfloat16 is not supported)')
         self._packed = None
         self._ws = None
 
@@ -270,15 +293,21 @@ class ResNetCLIP(nn.Module):
             keep.append(t)
             return t
 
-        def cw(wp, scale, bias, ks, cin, cout):
+        pb = self.precise_blocks
+
+        def cw(wp, scale, bias, ks, cin, cout, split=False):
             r = _lib.EcResnetConvW()
-            r.w = up(wp, cd).data_ptr()
+            if split:       # hi is the 16-bit path's weight bit for bit; lo what that rounding lost
+                hi, lo = split_hl(wp)
+                r.w, r.w_lo = up(hi, cd).data_ptr(), up(lo, cd).data_ptr()
+            else:
+                r.w = up(wp, cd).data_ptr()
             r.scale = None if scale is None else up(scale, torch.float32).data_ptr()
             r.bias = up(bias, torch.float32).data_ptr()
             r.ks, r.cin, r.cout = ks, cin, cout
             return r
 
-        def conv(wkey, bn_prefix, cin_p, cout_p, rows27=False):
+        def conv(wkey, bn_prefix, cin_p, cout_p, rows27=False, split=False):
             # the weights as the checkpoint holds them (one rounding to 16 bit); BatchNorm as an fp32 per-channel
             # scale and bias in the epilogue -- folding the scale into the weights would add a rounding of w * scale
             wt = sd[wkey]
@@ -291,33 +320,37 @@ class ResNetCLIP(nn.Module):
             if rows27:      # the stem's rows (ec_resnet_stem_rows): a 1x1 product over k = (ky*3 + kx)*3 + c
                 wp = torch.zeros(cout_p, 64)
                 wp[:cout, :27] = wf.reshape(cout, 27)
-                wp[:cout, 27:54] = wf.reshape(cout, 27)                 # times the rows' rounding remainders
-                return cw(wp, scale, bias, 1, 64, cout_p)
+                if not split:   # (split: ec_resnet_stem_rows_hl carries the remainders in the rows' lo plane)
+                    wp[:cout, 27:54] = wf.reshape(cout, 27)             # times the rows' rounding remainders
+                return cw(wp, scale, bias, 1, 64, cout_p, split)
             wp = torch.zeros(cout_p, k, k, cin_p)
             wp[:cout, :, :, :cin] = wf
-            return cw(wp, scale, bias, k, cin_p, cout_p)
+            return cw(wp, scale, bias, k, cin_p, cout_p, split)
 
         def linear(wt, b):
-            return cw(wt, None, b, 1, wt.shape[1], wt.shape[0])
+            return cw(wt, None, b, 1, wt.shape[1], wt.shape[0], pb == len(spec))
 
         c = self.cfg
         w = c['vision_width']
         rw = _lib.EcResnetWeights()
         rw.struct_bytes = ctypes.sizeof(_lib.EcResnetWeights)
         rw.dtype, rw.image_size, rw.embed_dim = self.dtype_code, c['image_size'], c['embed_dim']
-        rw.stem[0] = conv('visual.conv1.weight', 'visual.bn1', 64, pad64(w // 2), rows27=True)
-        rw.stem[1] = conv('visual.conv2.weight', 'visual.bn2', pad64(w // 2), pad64(w // 2))
-        rw.stem[2] = conv('visual.conv3.weight', 'visual.bn3', pad64(w // 2), pad64(w))
         spec = blocks_of(c)
+        sp = pb > 0
+        rw.stem[0] = conv('visual.conv1.weight', 'visual.bn1', 64, pad64(w // 2), rows27=True, split=sp)
+        rw.stem[1] = conv('visual.conv2.weight', 'visual.bn2', pad64(w // 2), pad64(w // 2), split=sp)
+        rw.stem[2] = conv('visual.conv3.weight', 'visual.bn3', pad64(w // 2), pad64(w), split=sp)
         blocks = (_lib.EcResnetBlock * len(spec))()
-        for bk, (pre, inp, planes, stride, ds) in zip(blocks, spec):
+        for i, (bk, (pre, inp, planes, stride, ds)) in enumerate(zip(blocks, spec)):
+            sp = i < pb
             bk.stride = stride
-            bk.c1 = conv(f'{pre}.conv1.weight', f'{pre}.bn1', pad64(inp), pad64(planes))
-            bk.c2 = conv(f'{pre}.conv2.weight', f'{pre}.bn2', pad64(planes), pad64(planes))
-            bk.c3 = conv(f'{pre}.conv3.weight', f'{pre}.bn3', pad64(planes), pad64(4 * planes))
+            bk.c1 = conv(f'{pre}.conv1.weight', f'{pre}.bn1', pad64(inp), pad64(planes), split=sp)
+            bk.c2 = conv(f'{pre}.conv2.weight', f'{pre}.bn2', pad64(planes), pad64(planes), split=sp)
+            bk.c3 = conv(f'{pre}.conv3.weight', f'{pre}.bn3', pad64(planes), pad64(4 * planes), split=sp)
             if ds:
-                bk.ds = conv(f'{pre}.downsample.0.weight', f'{pre}.downsample.1', pad64(inp), pad64(4 * planes))
+                bk.ds = conv(f'{pre}.downsample.0.weight', f'{pre}.downsample.1', pad64(inp), pad64(4 * planes), split=sp)
         rw.n_blocks = len(spec)
+        rw.precise_blocks = pb
         rw.blocks = ctypes.cast(blocks, ctypes.POINTER(_lib.EcResnetBlock))
         a = 'visual.attnpool.'
         rw.pos = up(sd[a + 'positional_embedding'], torch.float32).data_ptr()

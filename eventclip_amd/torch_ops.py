@@ -256,7 +256,9 @@ def _(feats, row_idx, text_t, logit_scale, agg, normalize):
 
 @custom_op(f'{NAMESPACE}::resnet_encode', mutates_args=(), device_types='cuda')
 def resnet_encode(inp: torch.Tensor, input_mode: int, clip_handle: int) -> torch.Tensor:
-    """ResNet image tower: fp32 [N, 3, R, R] (EC_PRE_CHW_F32) or uint8 [N, R, R, 3] (EC_PRE_HWC_U8) -> fp32 [N, D]."""
+    """ResNet image tower: fp32 [N, 3, R, R] (EC_PRE_CHW_F32) or uint8 [N, R, R, 3] (EC_PRE_HWC_U8) -> fp32 [N, D].
+    The model's mode travels in its packed weights (ec_resnet_weights.precise_blocks: the split-precision form, whose
+    workspace ec_resnet_workspace_bytes sizes with the second plane)."""
     m = _resolve(clip_handle, 'resnet_encode')
     pk = m._pack()
     n = int(inp.shape[0])

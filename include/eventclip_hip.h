@@ -49,12 +49,14 @@ EC_API const char *ec_last_error(void);
  *        ec_vit_weights grew in that time -- a caller built against any of those headers must be rebuilt)
  *   600  round 6: ec_classify -> ec_classify_prep_text + ec_classify_v2; ec_abi_check
  *   601  + ec_vit_train_layout (additive: no struct or argument list changed)
+ *   602  ec_resnet_conv_w + w_lo, ec_resnet_weights + precise_blocks (the ResNet towers' split-precision form); + the
+ *        ec_resnet_*_hl entry points
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does, with its ctypes mirrors.) */
-#define EC_ABI_VERSION 601
+#define EC_ABI_VERSION 602
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);
@@ -942,6 +944,35 @@ EC_API int ec_resnet_attnpool_tokens(const void *x, int n_img, int HW, int C, co
 EC_API int ec_resnet_attnpool_attend(const void *q, const void *kv, int n_img, int L, int C, void *out, int dtype,
                                      ec_stream_t stream);
 
+/* ---- the split-precision ("precise") form of the same kernels, csrc/resnet_hl.hip (EC_F16 only) ----
+ * A value v travels as two f16 planes of the same geometry: hi = f16(v) and lo = f16((v - hi) * 2^11), so that
+ * v ~ hi + lo * 2^-11 to 2^-22 |v| + 2^-36 (the factor 2^11 keeps lo a normal f16 number wherever hi is one).  Weights
+ * are split the same way at pack time.  Everything between the convolutions is fp32.
+ *
+ * ec_resnet_conv on split operands: the sum over k runs over x_hi w_hi + (x_lo w_hi + x_hi w_lo) 2^-11 in the MFMA's fp32
+ * accumulators (lo . lo, 2^-22 of the result, is dropped); scale, bias, the residual resid_hi + resid_lo 2^-11 (both
+ * planes or neither) and the ReLU in fp32; then out: fp32 [.., Cout] with out32 (out_lo unused, no residual), or the
+ * split store out = hi plane, out_lo = lo plane.  Shapes and limits as ec_resnet_conv. */
+EC_API int ec_resnet_conv_hl(const void *x_hi, const void *x_lo, int n_img, int H, int W, int Cin, int Cout, int ks,
+                             const void *w_hi, const void *w_lo, const float *scale, const float *bias,
+                             const void *resid_hi, const void *resid_lo, int relu, void *out, void *out_lo, int out32,
+                             int dtype, ec_stream_t stream);
+/* The stem's rows as two planes [n_img, R/2, R/2, 64]: the 27 taps as hi and as lo, zeros beyond; the first
+ * convolution is ec_resnet_conv_hl (ks 1) over them with the stem weights' 27 columns (not repeated) as hi and lo. */
+EC_API int ec_resnet_stem_rows_hl(const void *input, int input_mode, int n_img, int R, void *rows_hi, void *rows_lo,
+                                  int dtype, ec_stream_t stream);
+/* AvgPool2d(2) of split activations: fp32 sum of the four joined values, split store. */
+EC_API int ec_resnet_avgpool_hl(const void *x_hi, const void *x_lo, int n_img, int H, int W, int C, void *y_hi,
+                                void *y_lo, int dtype, ec_stream_t stream);
+/* ec_resnet_attnpool_tokens on split activations; tokens and q_in leave as hi and lo planes. */
+EC_API int ec_resnet_attnpool_tokens_hl(const void *x_hi, const void *x_lo, int n_img, int HW, int C, const float *pos,
+                                        void *tokens_hi, void *tokens_lo, void *q_in_hi, void *q_in_lo, int dtype,
+                                        ec_stream_t stream);
+/* ec_resnet_attnpool_attend on split q and kv; out leaves as hi and lo planes [n_img, C]. */
+EC_API int ec_resnet_attnpool_attend_hl(const void *q_hi, const void *q_lo, const void *kv_hi, const void *kv_lo,
+                                        int n_img, int L, int C, void *out_hi, void *out_lo, int dtype,
+                                        ec_stream_t stream);
+
 
 /* The whole image tower. */
 typedef struct {
@@ -949,6 +980,7 @@ typedef struct {
     const float *scale;   /* fp32 [cout] or NULL (1) */
     const float *bias;    /* fp32 [cout] */
     int ks, cin, cout;    /* cin, cout: padded channel counts (multiples of 64) */
+    const void *w_lo;     /* f16 lo plane of w, f16((w32 - w) * 2^11), or NULL: the 16-bit path only */
 } ec_resnet_conv_w;
 typedef struct {
     int stride;                          /* 1 or 2 (AvgPool2d(2) after c2 and in front of ds) */
@@ -961,6 +993,11 @@ typedef struct {
     const ec_resnet_block *blocks;       /* n_blocks Bottlenecks, layer1.0 first */
     const float *pos;                    /* attention pool: fp32 [HW + 1, C] */
     ec_resnet_conv_w q, kv, c;           /* 1x1: q_proj [C, C], k_proj | v_proj [2C, C], c_proj [embed_dim, C] */
+    /* 0: the 16-bit path.  n_blocks: the stem, every Bottleneck and the attention pool run the split-precision kernels.
+     * 0 < n < n_blocks: the stem and the first n Bottlenecks do, the rest and the pool run the 16-bit path on the hi
+     * plane.  Needs dtype EC_F16 and w_lo of every convolution that runs split; with any n > 0 stem[0] is packed for
+     * ec_resnet_stem_rows_hl (27 columns, not repeated).  The workspace doubles. */
+    int precise_blocks;
 } ec_resnet_weights;
 /* Workspace of ec_resnet_encode for `chunk` images at a time (0 on invalid weights). */
 EC_API size_t ec_resnet_workspace_bytes(const ec_resnet_weights *w, int chunk);

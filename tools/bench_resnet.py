@@ -6,7 +6,14 @@ Per arch: frames/s and ms per step of ResNetCLIP.encode_image over --frames norm
 them), a per-kernel-class table from ec_profile_* (TFLOP/s and the fraction of the 2.5 PFLOP/s dense 16-bit MFMA peak;
 HBM fraction of 8 TB/s for the stem rows and pooling), and the same module in torch fp16 channels_last (the restatement
 of tests/resnet_ref.py) on the same GPU with its time and its max-normalised error against fp32, next to the HIP
-tower's.  Weights are calibrated random weights (eventclip_amd.clip.random_state_dict)."""
+tower's.  Weights are calibrated random weights (eventclip_amd.clip.random_state_dict).
+
+    python tools/bench_resnet.py --precise-blocks all[,N...] [--layers 1,1,1,1] [--precise-out profiles/resnet_precise.txt]
+
+prices the split-precision form instead: per arch, ms per --frames images of the default path and of each count in the
+same process (every model warmed up, --reps timed passes each, median and min .. max), the ratio to the default, and the
+max-normalised error of each against the float64 restatement on the inputs of tests/test_resnet_precise_gpu.py (16
+images, weight seeds 0 and 1; --err-seeds adds held-out ones)."""
 import argparse
 import json
 import os
@@ -78,14 +85,77 @@ def bench(arch, frames, chunk):
                 padded_flop_overhead=round(resnet.padded_flop_overhead(cfg), 4), kernels=table)
 
 
+def bench_precise(arch, frames, chunk, counts, reps, layers, err_seeds, say):
+    import statistics
+    import resnet_ref
+    from eventclip_amd import resnet
+    from eventclip_amd import clip as eclip
+    cfg = eclip.resnet_config(arch, **({'vision_layers': layers} if layers else {}))
+    nb = sum(cfg['vision_layers'])
+    counts = [0] + sorted({nb if c == 'all' else min(int(c), nb) for c in counts} - {0})
+    R = cfg['image_size']
+    x = torch.randn(frames, 3, R, R, generator=torch.Generator().manual_seed(0)).cuda()
+    sd0 = eclip.random_state_dict(cfg, seed=0)
+    ms = {}
+    for c in counts:
+        m = resnet.ResNetCLIP(cfg, sd0, chunk=chunk, precise_blocks=c).cuda().eval()
+        for _ in range(2):
+            m.encode_image(x)
+        ts = [timed(lambda: m.encode_image(x), 1) * 1e3 for _ in range(reps)]
+        ms[c] = (statistics.median(ts), min(ts), max(ts))
+        del m
+    errs = {c: [] for c in counts}
+    floors = []
+    for seed in err_seeds:
+        sd = sd0 if seed == 0 else eclip.random_state_dict(cfg, seed=seed)
+        xs = torch.randn(16, 3, R, R, generator=torch.Generator().manual_seed(100 + seed))
+        ref_m = resnet_ref.from_state_dict(sd, cfg)
+        with torch.no_grad():
+            ref32 = ref_m(xs).double()
+            ref = ref_m.double()(xs.double())
+        floors.append(float((ref32 - ref).abs().max() / ref.abs().max()))
+        for c in counts:
+            m = resnet.ResNetCLIP(cfg, sd, precise_blocks=c).cuda().eval()
+            got = m.encode_image(xs.cuda()).cpu().double()
+            errs[c].append(float((got - ref).abs().max() / ref.abs().max()))
+            del m
+    say(f'{arch} layers={cfg["vision_layers"]} ({nb} blocks), {frames} images, chunk {chunk}, {reps} timed passes; '
+        f'error against float64 on seeds {list(err_seeds)}; fp32 restatement: ' + ' '.join(f'{e:.2e}' for e in floors))
+    for c in counts:
+        med, lo, hi = ms[c]
+        say(f'  precise_blocks={c:3d}  {med:9.2f} ms (min {lo:.2f} .. max {hi:.2f})  x{med / ms[0][0]:.2f} of default   err '
+            + ' '.join(f'{e:.2e}' for e in errs[c]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--archs', default='RN50,RN101,RN50x4,RN50x16,RN50x64')
     ap.add_argument('--frames', type=int, default=2560)
     ap.add_argument('--chunk', type=int, default=128)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--precise-blocks', default=None, help="counts to price, e.g. 'all' or '4,8,all'")
+    ap.add_argument('--layers', default=None, help='vision_layers override for --precise-blocks, e.g. 1,1,1,1')
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--err-seeds', default='0,1')
+    ap.add_argument('--precise-out', default=None)
     a = ap.parse_args()
     torch.cuda.set_device(0)
+    if a.precise_blocks:
+        lines = []
+
+        def say(t):
+            print(t, flush=True)
+            lines.append(t)
+        layers = tuple(int(v) for v in a.layers.split(',')) if a.layers else None
+        for arch in a.archs.split(','):
+            n = a.frames // 4 if arch == 'RN50x64' else a.frames
+            bench_precise(arch, n, a.chunk, a.precise_blocks.split(','), a.reps, layers,
+                          [int(v) for v in a.err_seeds.split(',')], say)
+        if a.precise_out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.precise_out)), exist_ok=True)
+            with open(a.precise_out, 'a') as f:
+                f.write('\n'.join(lines) + '\n')
+        return
     res = []
     for arch in a.archs.split(','):
         n = a.frames // 4 if arch == 'RN50x64' else a.frames
