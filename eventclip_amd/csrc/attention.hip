@@ -49,8 +49,9 @@ __device__ __forceinline__ void attn_stamp(int i)
 __device__ __forceinline__ void attn_stamp(int) {}
 #endif
 
-// Waves per workgroup: 8 when two workgroups fit a CU's LDS (K + V <= 80 KiB: S <= 320), 16 when the
-// sequence's K and V leave room for one workgroup only (S = 577: 148 KiB) -- four waves per SIMD either way.
+// Waves per workgroup, as dispatch() picks them: 8 while K + V and the 4224-byte merge area of a split tile stay within
+// 80 KiB, so that two workgroups fit a CU's LDS (nine 32-key steps: S <= 288), 16 from S = 289 on, where the sequence's K
+// and V leave room for one workgroup only (S = 577: 148 KiB) -- four waves per SIMD either way.
 
 struct AttnArgs {
     const void *qkv;  // [n_seq * S, 3W] 16-bit: q | k | v, heads are 64-wide column blocks
@@ -335,9 +336,9 @@ __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnA
     attn_stamp(0);
 
     // ---- stage K and V of this head: AT_THREADS / 8 rows x 8 chunks of 16 B per pass, at most five passes
-    // (S <= 320 on 8 waves, <= 640 on 16).  Every load of the head is requested before the first LDS
-    // write, so the staging costs one memory round trip instead of one per pass (a third of a workgroup's
-    // life at S = 257 otherwise) ----
+    // (room for 320 rows on 8 waves, 640 on 16; dispatch() sends S <= 288 to 8 waves and 289 .. 640 to 16).
+    // Every load of the head is requested before the first LDS write, so the staging costs one memory round
+    // trip instead of one per pass (a third of a workgroup's life at S = 257 otherwise) ----
     {
         const int r_in = threadIdx.x >> 3, ch = threadIdx.x & 7;
         u32x4 kv[5], vv[5];
