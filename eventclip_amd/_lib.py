@@ -236,6 +236,10 @@ SIGNATURES = {
                              c_float, c_void_p, c_void_p]),
     'ec_text_embed': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                               c_void_p]),
+    'ec_vit_embed_hl': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
+                                c_void_p, c_int, c_void_p]),
+    'ec_split_hl': (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p]),
+    'ec_join_hl_rows': (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p]),
     'ec_attention': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_void_p]),
     'ec_row_stats_merge': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]),

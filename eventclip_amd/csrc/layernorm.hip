@@ -20,6 +20,15 @@ using namespace ec;
 
 constexpr int LN_MAXV = 8;  // float4 per lane: width <= 2048
 
+// base pointers against the vector width a kernel reads or writes them with (NULL, an optional buffer left out, passes):
+// 16 bytes for fp32 (float4), 8 for a 16-bit plane (four elements), 4 for e4m3 (four bytes)
+inline bool aligned(const void *p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+inline bool aligned16(const void *a, const void *b = nullptr, const void *c = nullptr, const void *d = nullptr,
+                      const void *e = nullptr)
+{
+    return aligned(a, 16) && aligned(b, 16) && aligned(c, 16) && aligned(d, 16) && aligned(e, 16);
+}
+
 __device__ __forceinline__ float wave_sum(float v)
 {
 #pragma unroll
@@ -321,6 +330,8 @@ int vit_embed_hl(const float *patch, const float *cls, const float *pos, const f
 {
     EC_REQUIRE(width % 4 == 0 && width <= LN_MAXV * 256 && seq >= 2, "vit_embed_hl: bad shape");
     if (n_img == 0) return EC_OK;
+    EC_REQUIRE(patch && cls && pos && gamma && beta && x_hi && x_lo, "vit_embed_hl: null buffer");
+    EC_REQUIRE(aligned16(patch, cls, pos, gamma, beta) && aligned(x_hi, 8) && aligned(x_lo, 8), "vit_embed_hl: misaligned buffer");
     const long rows = (long)n_img * seq;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_EMBED, s, 0, (double)rows * width * 8.0);
@@ -342,6 +353,7 @@ int vit_embed_hl(const float *patch, const float *cls, const float *pos, const f
 int split_hl(const float *x, long n, void *x_hi, void *x_lo, int dtype, ec_stream_t stream)
 {
     EC_REQUIRE(n >= 0 && n % 4 == 0 && x && x_hi && x_lo, "split_hl: bad arguments");
+    EC_REQUIRE(aligned(x, 16) && aligned(x_hi, 8) && aligned(x_lo, 8), "split_hl: misaligned buffer");
     if (n == 0) return EC_OK;
     const unsigned grid = (unsigned)((n / 4 + 255) / 256 < 65536 ? (n / 4 + 255) / 256 : 65536);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -359,7 +371,9 @@ int split_hl(const float *x, long n, void *x_hi, void *x_lo, int dtype, ec_strea
 int join_hl_rows(const void *x_hi, const void *x_lo, long ld, int rows, int width, float *out, int dtype, ec_stream_t stream)
 {
     if (rows == 0) return EC_OK;
-    EC_REQUIRE(width % 4 == 0 && ld % 4 == 0, "join_hl_rows: bad shape");
+    EC_REQUIRE(rows > 0 && width > 0 && width % 4 == 0 && ld % 4 == 0 && ld >= width, "join_hl_rows: bad shape");
+    EC_REQUIRE(x_hi && x_lo && out, "join_hl_rows: null buffer");
+    EC_REQUIRE(aligned(x_hi, 8) && aligned(x_lo, 8) && aligned(out, 16), "join_hl_rows: misaligned buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long n4 = (long)rows * (width / 4);
     const unsigned grid = (unsigned)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
@@ -424,6 +438,7 @@ EC_API int ec_split16(const float *x, long n, int gelu, void *hi16, void *lo16, 
     EC_REQUIRE(n >= 0 && n % 4 == 0, "ec_split16: n=%ld must be a multiple of 4", n);
     if (n == 0) return EC_OK;
     EC_REQUIRE(x && hi16 && lo16, "ec_split16: null buffer");
+    EC_REQUIRE(aligned(x, 16) && aligned(hi16, 8) && aligned(lo16, 8), "ec_split16: misaligned buffer");
     const unsigned grid = (unsigned)((n / 4 + 255) / 256 < 65536 ? (n / 4 + 255) / 256 : 65536);
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)n * 8.0);
@@ -447,6 +462,7 @@ EC_API int ec_layernorm_split(const float *x, long ldx, const int32_t *row_idx, 
     if (rows == 0) return EC_OK;
     EC_REQUIRE(x && gamma && beta && out16, "ec_layernorm: null buffer");
     EC_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0, "ec_layernorm: strides must be multiples of 4");
+    EC_REQUIRE(aligned16(x, gamma, beta) && aligned(out16, 8) && aligned(out16_lo, 8), "ec_layernorm: misaligned buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid(ec::ceil_div(rows, 4)), block(256);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)rows * width * 6.0);
@@ -470,6 +486,8 @@ EC_API int ec_layernorm_hl(const void *x_hi, const void *x_lo, long ldx, const f
     if (rows == 0) return EC_OK;
     EC_REQUIRE(x_hi && x_lo && gamma && beta && out16 && out16_lo, "ec_layernorm_hl: null buffer");
     EC_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0, "ec_layernorm_hl: strides must be multiples of 4");
+    EC_REQUIRE(aligned(x_hi, 8) && aligned(x_lo, 8) && aligned16(gamma, beta) && aligned(out16, 8) && aligned(out16_lo, 8),
+               "ec_layernorm_hl: misaligned buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid(ec::ceil_div(rows, 4)), block(256);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)rows * width * 8.0);
@@ -495,6 +513,9 @@ EC_API int ec_layernorm_hl8(const void *x_hi, const void *x_lo, long ldx, const 
     if (rows == 0) return EC_OK;
     EC_REQUIRE(x_hi && x_lo && gamma && beta && out16 && out_lo8, "ec_layernorm_hl8: null buffer");
     EC_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0 && ldo >= width, "ec_layernorm_hl8: strides must be multiples of 4 (ldo >= width)");
+    EC_REQUIRE(aligned(x_hi, 8) && aligned(x_lo, 8) && aligned16(gamma, beta) && aligned(out16, 8) && aligned(out_lo8, 4) &&
+                   aligned(out_hi8, 4),
+               "ec_layernorm_hl8: misaligned buffer");
     EC_REQUIRE(lo_exp >= -60 && lo_exp <= 60 && hi_exp >= -60 && hi_exp <= 60, "ec_layernorm_hl8: exponents outside -60 .. 60");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid(ec::ceil_div(rows, 4)), block(256);
@@ -519,6 +540,8 @@ EC_API int ec_vit_embed_train(const float *patch, const float *cls, const float 
 {
     EC_REQUIRE(width % 4 == 0 && width <= LN_MAXV * 256 && seq >= 2, "ec_vit_embed: bad shape");
     if (n_img == 0) return EC_OK;
+    EC_REQUIRE(patch && cls && pos && gamma && beta && x, "ec_vit_embed: null buffer");
+    EC_REQUIRE(aligned16(patch, cls, pos, gamma, beta) && aligned16(x, pre), "ec_vit_embed: misaligned buffer");
     const long rows = (long)n_img * seq;
     ec::ProfScope prof(ec::PROF_EMBED, static_cast<hipStream_t>(stream), 0, (double)rows * width * 8.0);
     hipLaunchKernelGGL(vit_embed_kernel<-1>, dim3((unsigned)ec::ceil_div(rows, 4L)), dim3(256), 0,
@@ -528,11 +551,31 @@ EC_API int ec_vit_embed_train(const float *patch, const float *cls, const float 
     return EC_OK;
 }
 
+/* the tower drivers' internal entry points (tower_ops.h), exported so that they can be tested on their own */
+EC_API int ec_vit_embed_hl(const float *patch, const float *cls, const float *pos, const float *gamma, const float *beta,
+                           int n_img, int seq, int width, float eps, void *x_hi, void *x_lo, int dtype, ec_stream_t stream)
+{
+    return ec_tower::vit_embed_hl(patch, cls, pos, gamma, beta, n_img, seq, width, eps, x_hi, x_lo, dtype, stream);
+}
+
+EC_API int ec_split_hl(const float *x, long n, void *x_hi, void *x_lo, int dtype, ec_stream_t stream)
+{
+    return ec_tower::split_hl(x, n, x_hi, x_lo, dtype, stream);
+}
+
+EC_API int ec_join_hl_rows(const void *x_hi, const void *x_lo, long ld, int rows, int width, float *out, int dtype,
+                           ec_stream_t stream)
+{
+    return ec_tower::join_hl_rows(x_hi, x_lo, ld, rows, width, out, dtype, stream);
+}
+
 EC_API int ec_text_embed(const int32_t *tokens, const float *table, const float *pos, int n_txt,
                          int ctx, int width, int vocab, float *x, ec_stream_t stream)
 {
-    EC_REQUIRE(width % 4 == 0 && ctx > 0 && vocab > 0, "ec_text_embed: bad shape");
+    EC_REQUIRE(width > 0 && width % 4 == 0 && ctx > 0 && vocab > 0, "ec_text_embed: bad shape");
     if (n_txt == 0) return EC_OK;
+    EC_REQUIRE(tokens && table && pos && x, "ec_text_embed: null buffer");
+    EC_REQUIRE(aligned(tokens, 4) && aligned16(table, pos, x), "ec_text_embed: misaligned buffer");
     const long rows = (long)n_txt * ctx;
     ec::ProfScope prof(ec::PROF_EMBED, static_cast<hipStream_t>(stream), 0, (double)rows * width * 8.0);
     hipLaunchKernelGGL(text_embed_kernel, dim3((unsigned)ec::ceil_div(rows, 4L)), dim3(256), 0,

@@ -426,6 +426,18 @@ EC_API int ec_vit_embed_train(const float *patch, const float *cls, const float 
 EC_API int ec_text_embed(const int32_t *tokens, const float *table, const float *pos, int n_txt,
                          int ctx, int width, int vocab, float *x, ec_stream_t stream);
 
+/* The folded chain's hand-overs (ec_vit_weights.ln_folded), exported for the tests.  The residual stream as two planes
+ * x = hi + lo, hi in `dtype`, lo ALWAYS fp16:
+ *   ec_vit_embed_hl: ec_vit_embed with ln_pre's output written as the planes x_hi / x_lo [n_img, seq, width];
+ *   ec_split_hl:     fp32 [n] -> the planes (n % 4 == 0);
+ *   ec_join_hl_rows: `rows` rows of the planes at row stride ld (elements) -> fp32 [rows, width].
+ * Base pointers: 16-byte aligned where fp32, 8-byte aligned where 16-bit (as for every entry point of this group). */
+EC_API int ec_vit_embed_hl(const float *patch, const float *cls, const float *pos, const float *gamma, const float *beta,
+                           int n_img, int seq, int width, float eps, void *x_hi, void *x_lo, int dtype, ec_stream_t stream);
+EC_API int ec_split_hl(const float *x, long n, void *x_hi, void *x_lo, int dtype, ec_stream_t stream);
+EC_API int ec_join_hl_rows(const void *x_hi, const void *x_lo, long ld, int rows, int width, float *out, int dtype,
+                           ec_stream_t stream);
+
 /* Multi-head self-attention, head dim 64 (nn.MultiheadAttention of the CLIP
  * blocks).  qkv: 16-bit [n_seq * S, 3 * width] = q | k | v; out: 16-bit
  * [n_seq * S, width].  causal != 0 applies the text tower's mask. */
