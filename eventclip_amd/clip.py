@@ -25,10 +25,10 @@ from functools import lru_cache
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 from . import _lib
 from . import resnet as _resnet
+from .clip_base import ATTN_Q_SCALE, ClipBase, Packer, _assign, _block_keys   # noqa: F401 (re-exported)
 from .preprocess import Preprocess
 from .resnet import RESNET_ARCHS, resnet_config
 
@@ -63,18 +63,6 @@ def arch_config(arch, **override):
     cfg = dict(ARCHS[arch], context_length=CONTEXT_LENGTH, vocab_size=VOCAB_SIZE)
     cfg.update(override)
     return cfg
-
-
-def _block_keys(prefix, i):
-    p = f'{prefix}.resblocks.{i}.'
-    return [p + k for k in ('ln_1.weight', 'ln_1.bias', 'attn.in_proj_weight', 'attn.in_proj_bias',
-                            'attn.out_proj.weight', 'attn.out_proj.bias', 'ln_2.weight',
-                            'ln_2.bias', 'mlp.c_fc.weight', 'mlp.c_fc.bias', 'mlp.c_proj.weight',
-                            'mlp.c_proj.bias')]
-
-
-# log2(e) / sqrt(head dim 64): what ec_attention_scaled_q expects in the q columns (include/eventclip_hip.h)
-ATTN_Q_SCALE = 0.125 * 1.4426950408889634
 
 
 def random_state_dict(cfg, seed=0, qk_gain=1.0, branch_gain=1.0):
@@ -165,20 +153,6 @@ def config_from_state_dict(sd):
                 vocab_size=sd['token_embedding.weight'].shape[0])
 
 
-class _Holder(nn.Module):
-    """Plain container so parameters appear under OpenAI's dotted key names."""
-
-
-def _assign(root, key, tensor):
-    parts = key.split('.')
-    m = root
-    for p in parts[:-1]:
-        if p not in m._modules:
-            m.add_module(p, _Holder())
-        m = m._modules[p]
-    m.register_parameter(parts[-1], nn.Parameter(tensor.clone().float(), requires_grad=False))
-
-
 # of the split-operand blocks (image_precise_blocks), how many run fp32-class attention (+ the MLP activation as hi + lo):
 # (up to 288 tokens, beyond) -- measured, profiles/r5_tolerance_sweep.txt: at S = 577 (configs[3], sharp attention over 2.2 x
 # the keys) five such blocks leave the logits at 1.0 - 1.4e-3, seven at 7e-4; at S = 257 five are enough
@@ -225,23 +199,13 @@ def tolerance_mode_kwargs(arch_or_cfg):
     return dict(image_precise_blocks=pb, image_precise_attn_blocks=min(pa, pb))
 
 
-class CLIP(nn.Module):
+class CLIP(ClipBase):
     """Frozen CLIP (ViT image tower + text tower) running on hand-written HIP kernels."""
 
     def __init__(self, cfg, state_dict, dtype='float16', chunk=2560, text_precise=True,
                  image_precise=False, full_last_block=None, low_latency=False, ln_folded=None, q_scaled=True,
                  image_precise_blocks=None, image_precise_attn_blocks=None, image_lo_fp8=None):
-        super().__init__()
-        self.cfg = dict(cfg)
-        for k in ('input_resolution', 'context_length', 'vocab_size'):
-            state_dict = {a: b for a, b in state_dict.items() if a != k}
-        for k, v in state_dict.items():
-            _assign(self, k, v)
-        self.visual.output_dim = cfg['embed_dim']
-        self.visual.input_resolution = cfg['image_size']
-        self.compute_dtype = {'float16': torch.float16, 'fp16': torch.float16,
-                              'bfloat16': torch.bfloat16, 'bf16': torch.bfloat16}[str(dtype)]
-        self.chunk = int(chunk)
+        super().__init__(cfg, state_dict, dtype, chunk)
         # split-precision (~fp32) arithmetic: on for the text tower (run once, cached by the
         # classifiers), off for the image tower (3x the GEMM work; validation only)
         self.text_precise, self.image_precise = bool(text_precise), bool(image_precise)
@@ -289,133 +253,16 @@ class CLIP(nn.Module):
         self.image_lo_fp8 = bool(image_lo_fp8) and self.image_precise_blocks > 0 and cfg['width'] % 128 == 0
         # bytes of tower scratch at most
         self.workspace_budget = 24 << 30
-        self._packed = None
-        self._ws = None
-
-    # ---- protocol bits the reference's classifiers read ----
-    @property
-    def dtype(self):
-        return self.logit_scale.dtype
-
-    @property
-    def device(self):
-        return self.logit_scale.device
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None          # .cuda() / .to(): repack lazily
-        self._ws = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, sd, strict=True):
-        self._packed = None
-        return super().load_state_dict(sd, strict=strict)
 
     # ---- device packing ----
     def _pack(self):
         if self._packed is not None:
             return self._packed
-        dev = _lib.require_gpu()
-        if self.logit_scale.device.type != 'cuda':
-            raise _lib.HipLibraryError('CLIP weights are on the CPU: call model.cuda() first '
-                                       '(there is no CPU fallback)')
+        dev = self._pack_device()
         sd = {k: v.detach() for k, v in self.state_dict().items()}
         cd = self.compute_dtype
-        code = _lib.EC_F16 if cd == torch.float16 else _lib.EC_BF16
-        keep = []   # owns every device tensor the structs point to
-
-        def dev32(t):
-            t = t.to(dev, torch.float32).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
-        def dev16(t):
-            t = t.to(dev, torch.float32).to(cd).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
-        exact = []          # per split-precision block matrix of the image tower: is it its 16-bit value?
-
-        def dev16_pair(t, null_if_exact=False):
-            # (hi, lo) = (round16(w), round16(w - hi)), the operands of a split-precision GEMM (ec_gemm_args.W_lo).  null_if_exact
-            # (ec_vit_weights.weights_exact16): a matrix that IS its 16-bit value -- a checkpoint stored in 16 bit --
-            # has no lo part: NULL, and the product with it is skipped
-            t32 = t.to(dev, torch.float32)
-            pair = torch.empty((2,) + tuple(t32.shape), dtype=cd, device=dev)
-            pair[0] = t32.to(cd)
-            pair[1] = (t32 - pair[0].float()).to(cd)
-            keep.append(pair)
-            if null_if_exact:
-                is_exact = bool((pair[1] == 0).all()) and not getattr(self, 'keep_zero_lo', False)   # (tests)
-                exact.append(is_exact)
-                if is_exact:
-                    return pair[0].data_ptr(), None
-            return pair[0].data_ptr(), pair[1].data_ptr()
-
-        def blocks(prefix, layers, precise_all, q_scaled_all=False, ln_folded=False, precise_first=0, lo_fp8=False):
-            from . import ops
-            arr = (_lib.EcBlockWeights * layers)()
-            for i in range(layers):
-                ks = _block_keys(prefix, i)
-                b = arr[i]
-                # precise_first (ec_vit_weights.precise_blocks): the first blocks are split-operand blocks -- PLAIN matrices
-                # (no softmax scale, no LayerNorm gain folded in) with their lo parts; the rest as asked
-                split_ops = i < precise_first and not precise_all
-                precise = precise_all or split_ops
-                q_scaled = q_scaled_all and not precise
-                b.ln1_g, b.ln1_b = dev32(sd[ks[0]]), dev32(sd[ks[1]])
-                wqkv, bqkv = sd[ks[2]], sd[ks[3]]
-                if q_scaled:
-                    # ec_vit_weights.q_scaled: softmax temperature and base change folded into the q rows in
-                    # fp32, before the one rounding to 16 bit
-                    width = wqkv.shape[1]
-                    heads = c.get('heads', width // 64) if prefix.startswith('visual') else c.get('text_heads', width // 64)
-                    assert width == 64 * heads, \
-                        'q_scaled folds log2(e) / sqrt(64) into in_proj: the attention kernels are built for head dim 64'
-                    wqkv, bqkv = wqkv.float().clone(), bqkv.float().clone()
-                    wqkv[:width] *= ATTN_Q_SCALE
-                    bqkv[:width] *= ATTN_Q_SCALE
-                vis = prefix.startswith('visual')
-                b.qkv_b = dev32(bqkv)
-                b.out_b = dev32(sd[ks[5]])
-                b.ln2_g, b.ln2_b = dev32(sd[ks[6]]), dev32(sd[ks[7]])
-                b.fc1_b, b.fc2_b = dev32(sd[ks[9]]), dev32(sd[ks[11]])
-                if precise:     # plain matrices with their lo parts (NULL where the matrix is its 16-bit value)
-                    b.qkv_w, b.qkv_w_lo = dev16_pair(wqkv, vis)
-                    b.out_w, b.out_w_lo = dev16_pair(sd[ks[4]], vis)
-                    b.fc1_w, b.fc1_w_lo = dev16_pair(sd[ks[8]], vis)
-                    b.fc2_w, b.fc2_w_lo = dev16_pair(sd[ks[10]], vis)
-                    if split_ops and lo_fp8:
-                        # e4m3 copies of the 16-bit matrices and of the lo parts that exist (ec_block_weights.*_w8 / *_wlo8)
-                        def f8(t32, lo):
-                            hi = t32.to(dev, torch.float32).to(cd)
-                            src = (t32.to(dev, torch.float32) - hi.float()).to(cd).float() if lo else hi.float()
-                            q, e = ops.quantize_e4m3(src)
-                            keep.append(q)
-                            return q.data_ptr(), e
-                        b.qkv_w8, b.qkv_w8_exp = f8(wqkv, False)
-                        b.fc1_w8, b.fc1_w8_exp = f8(sd[ks[8]], False)
-                        b.fc2_w8, b.fc2_w8_exp = f8(sd[ks[10]], False)
-                        if b.qkv_w_lo:
-                            b.qkv_wlo8, b.qkv_wlo8_exp = f8(wqkv, True)
-                        if b.fc1_w_lo:
-                            b.fc1_wlo8, b.fc1_wlo8_exp = f8(sd[ks[8]], True)
-                    continue
-                b.qkv_w = dev16(wqkv)
-                b.out_w, b.fc1_w, b.fc2_w = dev16(sd[ks[4]]), dev16(sd[ks[8]]), dev16(sd[ks[10]])
-                if ln_folded:
-                    # ec_vit_weights.ln_folded: W' = W diag(gamma) rounded once, its row sums AS ROUNDED, b + W beta
-                    def fold(wt, bias, gamma, beta):
-                        wt, bias = wt.float().to(dev), bias.float().to(dev)
-                        wp = (wt * gamma.float().to(dev)[None, :]).to(cd).contiguous()
-                        keep.append(wp)
-                        cs = wp.float().sum(1).contiguous()
-                        bf = (bias + wt @ beta.float().to(dev)).contiguous()
-                        keep.extend([cs, bf])
-                        return wp.data_ptr(), cs.data_ptr(), bf.data_ptr()
-                    b.qkv_w_ln, b.qkv_cs, b.qkv_bf = fold(wqkv, bqkv, sd[ks[0]], sd[ks[1]])
-                    b.fc1_w_ln, b.fc1_cs, b.fc1_bf = fold(sd[ks[8]], sd[ks[9]], sd[ks[6]], sd[ks[7]])
-            return arr
-
+        pk = Packer(sd, dev, cd, self.cfg, keep_zero_lo=getattr(self, 'keep_zero_lo', False))
+        dev32, dev16, dev16_pair = pk.dev32, pk.dev16, pk.dev16_pair
         c = self.cfg
         P, W = c['patch'], c['width']
         # a patch row carries every pixel value as hi + lo 16-bit parts, [hi | lo | 0] (kpad wide);
@@ -430,7 +277,7 @@ class CLIP(nn.Module):
         conv_lo = torch.zeros(W, klo)
         conv_lo[:, :k] = cw
         v = _lib.EcVitWeights()
-        v.dtype, v.image_size, v.patch, v.width = code, c['image_size'], P, W
+        v.dtype, v.image_size, v.patch, v.width = pk.code, c['image_size'], P, W
         v.layers, v.heads, v.out_dim, v.kpad = c['layers'], W // 64, c['embed_dim'], kpad
         v.conv_w = dev16(conv)
         v.cls, v.pos = dev32(sd['visual.class_embedding']), dev32(sd['visual.positional_embedding'])
@@ -451,31 +298,15 @@ class CLIP(nn.Module):
         v.precise_attn_blocks = self.image_precise_attn_blocks
         v.lo_fp8 = int(self.image_lo_fp8)
         v.conv_w_lo = dev16_pair(conv_lo, null_if_exact=True)[1]
-        vb = blocks('visual.transformer', c['layers'], self.image_precise, q_scaled_all=bool(v.q_scaled),
-                    ln_folded=bool(v.ln_folded), precise_first=self.image_precise_blocks, lo_fp8=self.image_lo_fp8)
+        vb = pk.blocks('visual.transformer', c['layers'], self.image_precise, q_scaled_all=bool(v.q_scaled),
+                       ln_folded=bool(v.ln_folded), precise_first=self.image_precise_blocks, lo_fp8=self.image_lo_fp8)
         v.blocks = ctypes.cast(vb, ctypes.POINTER(_lib.EcBlockWeights))
         # (a mixed checkpoint -- some matrices exact, some not -- sets the flag and relies on the per-matrix NULL lo
         # pointers: the C side checks every pointer it is about to use, the flag only says that NULL is allowed)
-        v.weights_exact16 = int(any(exact))
-        t = _lib.EcTextWeights()
-        t.dtype, t.ctx, t.vocab, t.width = code, c['context_length'], c['vocab_size'], c['text_width']
-        t.layers, t.heads, t.out_dim = c['text_layers'], c['text_heads'], c['embed_dim']
-        t.token_embedding = dev32(sd['token_embedding.weight'])
-        t.pos = dev32(sd['positional_embedding'])
-        t.ln_final_g, t.ln_final_b = dev32(sd['ln_final.weight']), dev32(sd['ln_final.bias'])
-        t.proj_w, proj_lo = dev16_pair(sd['text_projection'].t())
-        t.precise = int(self.text_precise)
-        if self.text_precise:
-            t.proj_w_lo = proj_lo
-        tb = blocks('transformer', c['text_layers'], self.text_precise)
-        t.blocks = ctypes.cast(tb, ctypes.POINTER(_lib.EcBlockWeights))
-        self._packed = dict(vit=v, text=t, keep=keep, vb=vb, tb=tb, kpad=kpad, code=code, dev=dev)
+        v.weights_exact16 = int(any(pk.exact))
+        t, tb = pk.text(self.text_precise)
+        self._packed = dict(vit=v, text=t, keep=pk.keep, vb=vb, tb=tb, kpad=kpad, code=pk.code, dev=dev)
         return self._packed
-
-    def _workspace(self, nbytes, dev):
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        return self._ws
 
     @property
     def kpad(self):
@@ -512,26 +343,6 @@ class CLIP(nn.Module):
                                     pk['code'], _lib.stream_ptr())
         _lib.check(rc, 'ec_patchify')
         return self.encode_patches(patches)
-
-    @torch.no_grad()
-    def encode_text(self, text):
-        """text: int tensor [K, 77] of BPE ids -> fp32 [K, D] (not normalised)."""
-        pk = self._pack()
-        c = self.cfg
-        if text.dim() != 2 or text.shape[1] != c['context_length']:
-            raise ValueError(f'encode_text expects [K, {c["context_length"]}]')
-        from . import torch_ops
-        tok = text.to(pk['dev'], torch.int32).contiguous()
-        return torch.ops.eventclip_hip.text_encode(tok, torch_ops.handle_of(self))
-
-    def forward(self, image, text):
-        """Cosine-similarity logits, as OpenAI's CLIP.forward."""
-        i = self.encode_image(image)
-        t = self.encode_text(text)
-        i = i / i.norm(dim=1, keepdim=True)
-        t = t / t.norm(dim=1, keepdim=True)
-        li = self.logit_scale.exp() * i @ t.t()
-        return li, li.t()
 
 
 def build_random(arch, seed=0, dtype='float16', device='cuda', chunk=2560, **override):

@@ -1265,15 +1265,6 @@ int ln_backward(const float *x, long ldx, const float *dy, long ldy, const float
     return EC_OK;
 }
 
-int gemm_x(int M, int N, int K, int dtype, int epi, const void *A, const void *W, void *C, const float *resid, void *aux,
-           const float *bias, ec_stream_t s)
-{
-    ec_gemm_args g = {};
-    g.M = M, g.N = N, g.K = K, g.dtype = dtype, g.epilogue = epi, g.variant = 0;
-    g.A = A, g.lda = K, g.W = W, g.ldw = K, g.bias = bias, g.C = C, g.ldc = N, g.resid = resid, g.aux = aux;
-    return ec_gemm(&g, s);
-}
-
 // C[m0 + m][n] = (resid ? resid : 0) + bias[n] + sum over K-batches of partial[s][m][n]
 __global__ __launch_bounds__(256) void tail_fixup_kernel(const float *partial, int splits, int rows, int N, const float *bias,
                                                          const float *resid, float *C)
@@ -1317,9 +1308,9 @@ int gemm_rows32(int M, int N, int K, int dtype, int epi, const void *A, const vo
     if (extra_round && K >= 2048)
         while (splits < 8 && tiles_n * splits * 2 <= cus && (K / 64) % (splits * 2) == 0 && K / (splits * 2) >= 256) splits *= 2;
     if (splits < 2 || (size_t)splits * rem * N > partial_floats || (epi != EC_EPI_STORE32 && epi != EC_EPI_RESID32))
-        return gemm_x(M, N, K, dtype, epi, A, W, C, resid, nullptr, bias, stream);
+        return Gemm(M, N, K, dtype, epi, A, W, bias, C).resid(resid).run(stream);
     const size_t esz = 2;
-    EC_TRY(gemm_x(full, N, K, dtype, epi, A, W, C, resid, nullptr, bias, stream));
+    EC_TRY(Gemm(full, N, K, dtype, epi, A, W, bias, C).resid(resid).run(stream));
     ec_gemm_args g = {};
     g.M = rem, g.N = N, g.K = K / splits, g.dtype = dtype, g.epilogue = EC_EPI_STORE32, g.variant = 0;
     g.A = static_cast<const unsigned char *>(A) + (size_t)full * K * esz, g.lda = K, g.W = W, g.ldw = K;
@@ -1393,17 +1384,17 @@ EC_API int ec_vit_train_forward(const ec_vit_weights *w, const void *patches, in
     for (int l = 0; l < L; l++) {
         const ec_block_weights &p = w->blocks[l];
         EC_TRY(ec_layernorm(b.x[l], W, nullptr, p.ln1_g, p.ln1_b, M, W, LN_EPS, b.h1[l], W, dt, stream));
-        EC_TRY(gemm_x(M, 3 * W, W, dt, EC_EPI_STORE16, b.h1[l], p.qkv_w, b.qkv[l], nullptr, nullptr, p.qkv_b, stream));
+        EC_TRY(Gemm(M, 3 * W, W, dt, EC_EPI_STORE16, b.h1[l], p.qkv_w, p.qkv_b, b.qkv[l]).run(stream));
         EC_TRY(ec_attention_train(b.qkv[l], b.att[l], b.lse[l], n_img, S, W, w->heads, dt, stream));
-        EC_TRY(gemm_x(M, W, W, dt, EC_EPI_RESID32, b.att[l], p.out_w, b.xm[l], b.x[l], nullptr, p.out_b, stream));
+        EC_TRY(Gemm(M, W, W, dt, EC_EPI_RESID32, b.att[l], p.out_w, p.out_b, b.xm[l]).resid(b.x[l]).run(stream));
         EC_TRY(ec_layernorm(b.xm[l], W, nullptr, p.ln2_g, p.ln2_b, M, W, LN_EPS, b.h2[l], W, dt, stream));
-        EC_TRY(gemm_x(M, 4 * W, W, dt, EC_EPI_GELU16_SAVE, b.h2[l], p.fc1_w, b.gact[l], nullptr, b.u[l], p.fc1_b, stream));
+        EC_TRY(Gemm(M, 4 * W, W, dt, EC_EPI_GELU16_SAVE, b.h2[l], p.fc1_w, p.fc1_b, b.gact[l]).aux(b.u[l]).run(stream));
         EC_TRY(gemm_rows32(M, W, 4 * W, dt, EC_EPI_RESID32, b.gact[l], p.fc2_w, b.x[l + 1], b.xm[l], p.fc2_b, b.part,
                            b.part_floats, stream));
     }
     EC_TRY(ec_layernorm_split(b.x[L], (long)S * W, nullptr, w->ln_post_g, w->ln_post_b, n_img, W, LN_EPS, b.cls_hi,
                               b.cls_lo, W, dt, stream));
-    return gemm3(n_img, w->out_dim, W, dt, false, b.cls_hi, b.cls_lo, w->proj_w, w->proj_w_lo, nullptr, feats, stream);
+    return Gemm(n_img, w->out_dim, W, dt, EC_EPI_STORE32, b.cls_hi, w->proj_w, nullptr, feats).lo(b.cls_lo, w->proj_w_lo).run(stream);
 }
 
 EC_API int ec_vit_train_backward(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches, int n_img,
@@ -1489,7 +1480,7 @@ EC_API int ec_vit_train_backward_stages(const ec_vit_weights *w, const ec_vit_tr
         // (b.dx16 is the 16-bit copy of b.dx: written by the LayerNorm backward that produced it)
         if (q.fc2_b) EC_TRY(bias_grad<float>(b.dx, W, M, W, b, q.fc2_b, s));
         if (q.fc2_w) EC_TRY(weight_grad_rows(dt, b.dx16, W, b.gact[l], 4L * W, W, 4 * W, M, b, q.fc2_w, stream));
-        EC_TRY(gemm_x(M, 4 * W, W, dt, EC_EPI_GELU_BWD16, b.dx16, pt.fc2_wt, b.g16, nullptr, b.u[l], nullptr, stream));
+        EC_TRY(Gemm(M, 4 * W, W, dt, EC_EPI_GELU_BWD16, b.dx16, pt.fc2_wt, nullptr, b.g16).aux(b.u[l]).run(stream));
         if (q.fc1_b) {
             if (dt == EC_F16) EC_TRY(bias_grad<_Float16>((const _Float16 *)b.g16, 4L * W, M, 4 * W, b, q.fc1_b, s));
             else EC_TRY(bias_grad<__bf16>((const __bf16 *)b.g16, 4L * W, M, 4 * W, b, q.fc1_b, s));
@@ -1502,7 +1493,7 @@ EC_API int ec_vit_train_backward_stages(const ec_vit_weights *w, const ec_vit_tr
         // xm = x[l] + out_proj(attention(in_proj(ln_1(x[l]))))
         if (q.out_b) EC_TRY(bias_grad<float>(b.dx, W, M, W, b, q.out_b, s));
         if (q.out_w) EC_TRY(weight_grad_rows(dt, b.dx16, W, b.att[l], W, W, W, M, b, q.out_w, stream));
-        EC_TRY(gemm_x(M, W, W, dt, EC_EPI_STORE16, b.dx16, pt.out_wt, b.da16, nullptr, nullptr, nullptr, stream));
+        EC_TRY(Gemm(M, W, W, dt, EC_EPI_STORE16, b.dx16, pt.out_wt, nullptr, b.da16).run(stream));
         EC_TRY(ec_attention_backward(b.qkv[l], b.att[l], b.lse[l], b.da16, b.g16, b.delta, n_img, S, W, w->heads, dt,
                                      stream));
         if (q.qkv_b) {

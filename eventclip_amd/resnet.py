@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .clip_base import ClipBase, Packer
 
 # layers, width w, image size, embed dim, text width / heads (text layers 12, context 77, vocab 49408 for all)
 RESNET_ARCHS = {
@@ -221,7 +222,7 @@ def config_from_state_dict(sd):
                 context_length=sd['positional_embedding'].shape[0], vocab_size=sd['token_embedding.weight'].shape[0])
 
 
-class ResNetCLIP(nn.Module):
+class ResNetCLIP(ClipBase):
     """Frozen ResNet CLIP on HIP kernels: the surface of ``clip.CLIP`` the classifiers read (encode_image,
     encode_text, visual.output_dim / input_resolution, logit_scale, state_dict in OpenAI's keys), plus
     ``encode_frames`` for the uint8 frames of ``ec_preprocess`` (EC_PRE_HWC_U8)."""
@@ -229,17 +230,7 @@ class ResNetCLIP(nn.Module):
     def __init__(self, cfg, state_dict, dtype='float16', chunk=64, precise_blocks=0, precise=False):
         """precise_blocks: 0, the 16-bit tower; n_blocks (or precise=True), the stem, every Bottleneck and the attention
         pool on split-precision (hi + lo) operands; 0 < n < n_blocks, the stem and the first n Bottlenecks."""
-        super().__init__()
-        from .clip import _assign
-        self.cfg = dict(cfg)
-        for k, v in state_dict.items():
-            if k not in ('input_resolution', 'context_length', 'vocab_size'):
-                _assign(self, k, v)
-        self.visual.output_dim = cfg['embed_dim']
-        self.visual.input_resolution = cfg['image_size']
-        self.compute_dtype = {'float16': torch.float16, 'fp16': torch.float16,
-                              'bfloat16': torch.bfloat16, 'bf16': torch.bfloat16}[str(dtype)]
-        self.chunk = int(chunk)        # images per pass through the tower (bounds the activation workspace)
+        super().__init__(cfg, state_dict, dtype, chunk)
         n_blocks = sum(cfg['vision_layers'])
         self.precise_blocks = n_blocks if precise else int(precise_blocks)
         if not 0 <= self.precise_blocks <= n_blocks:
@@ -247,43 +238,16 @@ class ResNetCLIP(nn.Module):
         if self.precise_blocks and self.compute_dtype != torch.float16:
             raise ValueError(f'precise_blocks={self.precise_blocks} needs dtype float16 (the split-precision kernels '
                              'carry f16 hi + lo planes; bfloat16 is not supported)')
-        self._packed = None
-        self._ws = None
-
-    @property
-    def dtype(self):
-        return self.logit_scale.dtype
-
-    @property
-    def device(self):
-        return self.logit_scale.device
 
     @property
     def dtype_code(self):
         return _lib.EC_F16 if self.compute_dtype == torch.float16 else _lib.EC_BF16
 
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        self._ws = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, sd, strict=True):
-        self._packed = None
-        return super().load_state_dict(sd, strict=strict)
-
-    def _workspace(self, nbytes, dev):
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        return self._ws
-
     # ---- device packing ----
     def _pack(self):
         if self._packed is not None:
             return self._packed
-        dev = _lib.require_gpu()
-        if self.logit_scale.device.type != 'cuda':
-            raise _lib.HipLibraryError('CLIP weights are on the CPU: call model.cuda() first '
-                                       '(there is no CPU fallback)')
+        dev = self._pack_device()
         sd = {k: v.detach().float().cpu() for k, v in self.state_dict().items()}
         cd = self.compute_dtype
         keep = []
@@ -358,51 +322,10 @@ class ResNetCLIP(nn.Module):
         rw.kv = linear(torch.cat([sd[a + 'k_proj.weight'], sd[a + 'v_proj.weight']]),
                        torch.cat([sd[a + 'k_proj.bias'], sd[a + 'v_proj.bias']]))
         rw.c = linear(sd[a + 'c_proj.weight'], sd[a + 'c_proj.bias'])
-        text, tb = self._pack_text(sd, dev, keep)
+        # the transformer text tower, split-precision (hi + lo) as CLIP packs it by default
+        text, tb = Packer(sd, dev, cd, c, keep=keep).text(precise=True)
         self._packed = dict(resnet=rw, blocks=blocks, text=text, tb=tb, keep=keep, dev=dev, code=self.dtype_code)
         return self._packed
-
-    def _pack_text(self, sd, dev, keep):
-        """ec_text_weights of the transformer text tower, split-precision (hi + lo) as CLIP packs it by default."""
-        from .clip import _block_keys
-        cd = self.compute_dtype
-
-        def dev32(t):
-            t = t.to(dev, torch.float32).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
-        def pair(t):
-            t32 = t.to(dev, torch.float32)
-            p = torch.empty((2,) + tuple(t32.shape), dtype=cd, device=dev)
-            p[0] = t32.to(cd)
-            p[1] = (t32 - p[0].float()).to(cd)
-            keep.append(p)
-            return p[0].data_ptr(), p[1].data_ptr()
-
-        c = self.cfg
-        arr = (_lib.EcBlockWeights * c['text_layers'])()
-        for i in range(c['text_layers']):
-            ks = _block_keys('transformer', i)
-            b = arr[i]
-            b.ln1_g, b.ln1_b = dev32(sd[ks[0]]), dev32(sd[ks[1]])
-            b.qkv_b, b.out_b = dev32(sd[ks[3]]), dev32(sd[ks[5]])
-            b.ln2_g, b.ln2_b = dev32(sd[ks[6]]), dev32(sd[ks[7]])
-            b.fc1_b, b.fc2_b = dev32(sd[ks[9]]), dev32(sd[ks[11]])
-            b.qkv_w, b.qkv_w_lo = pair(sd[ks[2]])
-            b.out_w, b.out_w_lo = pair(sd[ks[4]])
-            b.fc1_w, b.fc1_w_lo = pair(sd[ks[8]])
-            b.fc2_w, b.fc2_w_lo = pair(sd[ks[10]])
-        t = _lib.EcTextWeights()
-        t.dtype, t.ctx, t.vocab, t.width = self.dtype_code, c['context_length'], c['vocab_size'], c['text_width']
-        t.layers, t.heads, t.out_dim = c['text_layers'], c['text_heads'], c['embed_dim']
-        t.token_embedding = dev32(sd['token_embedding.weight'])
-        t.pos = dev32(sd['positional_embedding'])
-        t.ln_final_g, t.ln_final_b = dev32(sd['ln_final.weight']), dev32(sd['ln_final.bias'])
-        t.proj_w, t.proj_w_lo = pair(sd['text_projection'].t())
-        t.precise = 1
-        t.blocks = ctypes.cast(arr, ctypes.POINTER(_lib.EcBlockWeights))
-        return t, arr
 
     # ---- image tower ----
     def _encode(self, inp, mode):
@@ -427,22 +350,6 @@ class ResNetCLIP(nn.Module):
         if frames.dtype != torch.uint8 or tuple(frames.shape[1:]) != (R, R, 3) or not frames.is_cuda:
             raise ValueError(f'encode_frames expects uint8 CUDA [N, {R}, {R}, 3], got {tuple(frames.shape)}')
         return self._encode(frames.contiguous(), _lib.EC_PRE_HWC_U8)
-
-    @torch.no_grad()
-    def encode_text(self, text):
-        """text: int tensor [K, 77] of BPE ids -> fp32 [K, D] (not normalised)."""
-        pk = self._pack()
-        if text.dim() != 2 or text.shape[1] != self.cfg['context_length']:
-            raise ValueError(f'encode_text expects [K, {self.cfg["context_length"]}]')
-        from . import torch_ops
-        tok = text.to(pk['dev'], torch.int32).contiguous()
-        return torch.ops.eventclip_hip.text_encode(tok, torch_ops.handle_of(self))
-
-    def forward(self, image, text):
-        i = F.normalize(self.encode_image(image), dim=1)
-        t = F.normalize(self.encode_text(text), dim=1)
-        li = self.logit_scale.exp() * i @ t.t()
-        return li, li.t()
 
 
 def padded_flop_overhead(cfg):

@@ -611,3 +611,43 @@ def test_folded_layernorm_tower_matches_the_plain_chain_and_the_oracle(hip, arch
     print(f'\n[{arch}] feature error vs the fp32 oracle: plain chain {e_plain:.2e}, folded {e_fold:.2e}')
     assert e_fold < 1e-3 and e_fold < 1.5 * e_plain + 1e-4
     assert torch.equal(folded, every)
+
+
+# per profiler class (gemm.hip groups the epilogues: STORE16 with STORE16_LN, GELU16 with GELU16_LN, RESID32 with RESID_HL;
+# LayerNorm, the statistics kernels and ec_split16 share a class), 4 blocks, the last one on the class rows only:
+#   STORE16   one QKV launch per full block, k | v + q in the last one
+#   RESID32   out_proj and c_proj of every block + the lo half of the patch embedding;  STORE32: patch embedding, proj
+#   layernorm plain: 2 per block + ln_post.  folded: ec_row_stats once, a merge behind every residual GEMM that a default
+#             block follows (2 + 2 + 2 + 1), ln_post.  three split-operand blocks: 2 per block, one merge behind the
+#             last of them, one in the default block, ln_post.  precise: 2 + ec_split16 per block, ln_post
+_BLOCK_CHAIN_LAUNCHES = {'gemm_kernel<STORE16>': 5, 'gemm_kernel<GELU16>': 4, 'gemm_kernel<RESID32>': 9, 'gemm_kernel<STORE32>': 2,
+                         'layernorm_kernel': 9, 'attention_kernel': 4, 'embed_kernel': 1}
+_PRECISE_LAUNCHES = {'gemm_kernel<STORE16>': 4, 'gemm_kernel<RESID32>': 9, 'gemm_kernel<STORE32>': 6,
+                     'layernorm_kernel': 13, 'attention_kernel': 4, 'embed_kernel': 1}
+
+
+@pytest.mark.parametrize('kw,want', [
+    (dict(), _BLOCK_CHAIN_LAUNCHES),
+    (dict(ln_folded=False), _BLOCK_CHAIN_LAUNCHES),
+    (dict(image_precise=True), _PRECISE_LAUNCHES),
+    (dict(image_precise_blocks=3, image_precise_attn_blocks=2, image_lo_fp8=True), _BLOCK_CHAIN_LAUNCHES),
+    (dict(image_precise_blocks=3, image_precise_attn_blocks=2, image_lo_fp8=False), _BLOCK_CHAIN_LAUNCHES),
+], ids=['folded', 'plain', 'precise', 'split_lo8', 'split_lo16'])
+def test_tower_launch_counts_by_mode(kw, want, hip):
+    """The launches of one ec_vit_encode call (ViT-B/32 with 4 blocks, 3 images, one chunk) per profiler class are what
+    the per-block launch lists in csrc/towers.hip say.  The numbers were recorded from the library before the block
+    drivers were rewritten and checked by hand against those lists (the three block chains happen to agree per class)."""
+    import torch
+    from eventclip_amd import _lib
+    from eventclip_amd import clip as eclip
+    cfg = eclip.arch_config('ViT-B/32', layers=4, text_layers=1, vocab_size=1024)
+    m = eclip.CLIP(cfg, eclip.random_state_dict(cfg, seed=3), **kw).cuda().eval()
+    patches = torch.randn(3, 49, m.kpad, generator=torch.Generator().manual_seed(5)).half().cuda()
+    m.encode_patches(patches)           # packs the weights, allocates the workspace
+    torch.cuda.synchronize()
+    _lib.profile_begin()
+    feats = m.encode_patches(patches)
+    torch.cuda.synchronize()
+    got = {e['name']: e['launches'] for e in _lib.profile_end() if e['launches']}
+    assert torch.isfinite(feats).all()
+    assert got == want, (got, want)
