@@ -216,6 +216,18 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
     'ec_dropout_mask': (c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int64, ctypes.c_float, c_void_p,
                                 c_void_p]),
+    'ec_adapter_train_tape_bytes': (ctypes.c_size_t, [c_int] * 7),
+    'ec_adapter_train_backward_workspace_bytes': (ctypes.c_size_t, [c_int] * 5),
+    'ec_adapter_train_forward': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(EcAdapterTrainParams),
+                                         ctypes.c_float, ctypes.c_uint64, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    'ec_adapter_train_backward': (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(EcAdapterTrainParams), ctypes.c_float,
+                                          ctypes.c_uint64, c_void_p, ctypes.c_size_t, c_void_p,
+                                          ctypes.POINTER(EcAdapterTrainParams), c_void_p, c_void_p, ctypes.c_size_t,
+                                          c_void_p]),
+    'ec_classify_backward_workspace_bytes': (ctypes.c_size_t, [c_int] * 4),
+    'ec_classify_backward': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
+                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     ctypes.c_size_t, c_void_p]),
     'ec_adam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, ctypes.c_float,
                              ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_int, c_void_p]),
     'ec_gemm': (c_int, [ctypes.POINTER(EcGemmArgs), c_void_p]),
@@ -325,7 +337,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 602      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
+ABI_VERSION = 603      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
 
 
 class HipLibraryError(RuntimeError):

@@ -3,7 +3,9 @@
 ``TransformerAdapter`` keeps its parameters in the same torch modules as the
 reference (``in_proj``, ``transformer_encoder.layers.{i}.*``, ``out_proj``) so that
 checkpoints written by the reference's trainer load key for key; those modules are
-parameter holders only -- ``forward`` runs ``ec_adapter_forward``.  fp32, eval only.
+parameter holders only -- ``forward`` runs ``ec_adapter_forward`` (fp32, the fused inference kernel) in eval mode
+or with grad disabled, and the differentiable ``eventclip_hip::adapter_train_fwd`` (``ec_adapter_train_forward`` /
+``_backward``, with the encoder layers' dropout of 0.1) in train mode with grad enabled.
 """
 import ctypes
 
@@ -89,6 +91,8 @@ class TransformerAdapter(Adapter):
         self.out_proj = nn.Linear(d_model, in_dim)
         self._packed = None
 
+    TRAIN_DROPOUT = 0.1       # nn.TransformerEncoderLayer's default, what the reference trains with
+
     def _apply(self, fn, *a, **k):
         self._packed = None
         return super()._apply(fn, *a, **k)
@@ -97,8 +101,13 @@ class TransformerAdapter(Adapter):
         self._packed = None
         return super().load_state_dict(*a, **k)
 
+    def _param_key(self):
+        """Changes when a parameter is updated in place (an optimiser step bumps ``_version``) or replaced."""
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
     def _pack(self):
-        if self._packed is not None:
+        key = self._param_key()
+        if self._packed is not None and self._packed['key'] == key:
             return self._packed
         dev = _lib.require_gpu()
         if self.in_proj.weight.device.type != 'cuda':
@@ -126,23 +135,40 @@ class TransformerAdapter(Adapter):
         w.in_w_t, w.in_b = d(self.in_proj.weight, True), d(self.in_proj.bias)
         w.out_w_t, w.out_b = d(self.out_proj.weight, True), d(self.out_proj.bias)
         w.layer = ctypes.cast(layers, ctypes.POINTER(_lib.EcAdapterLayer))
-        self._packed = dict(w=w, layers=layers, keep=keep)
+        self._packed = dict(w=w, layers=layers, keep=keep, key=key)
         return self._packed
 
     @torch.no_grad()
     def forward_rows(self, feats, row_idx):
+        """The fused inference kernel, in every mode (FSCLIPClassifier's eval forward and the trainers' checks)."""
         from . import torch_ops
         self._pack()
         return torch.ops.eventclip_hip.adapter_fwd(feats.float().contiguous(), row_idx.contiguous(),
                                                     torch_ops.handle_of(self))
 
-    @torch.no_grad()
+    def train_rows(self, rows, idx):
+        """The differentiable forward: rows fp32 [B * T, C] with zero rows on padded views, idx int32 [B, T] (-1 =
+        padded) -> [B, T, C], with autograd into every parameter that requires grad (and into ``rows``).  Dropout is
+        ``TRAIN_DROPOUT`` while this module is in train mode, seeded once per call from torch's default generator
+        (``torch.manual_seed`` reproduces a run), else 0: the deterministic eval-mode function."""
+        from . import torch_ops
+        names = [n for n, _ in self.named_parameters()]
+        assert names == torch_ops.adapter_param_names(self.num_layers), names
+        p = self.TRAIN_DROPOUT if self.training else 0.
+        seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0. else 0
+        out, _ = torch.ops.eventclip_hip.adapter_train_fwd(rows.contiguous(), idx.contiguous(), list(self.parameters()),
+                                                           self.d_model, self.num_heads, self.ffn_dim, self.num_layers,
+                                                           float(self.residual), p, seed)
+        return out
+
     def forward(self, feats, valid_masks):
         """feats [B, T, C], valid_masks [B, T] (True = valid view), as adapter.py:82-105.
         Padded views must hold zeros, which is what the reference's classifier passes."""
         B, T, C = feats.shape
         idx = torch.where(valid_masks, torch.arange(B * T, device=feats.device).view(B, T),
                           torch.full((B, T), -1, device=feats.device)).to(torch.int32)
+        if self.training and torch.is_grad_enabled():
+            return self.train_rows(feats.float().reshape(B * T, C), idx)
         return self.forward_rows(feats.reshape(B * T, C), idx)
 
     @property

@@ -6,9 +6,12 @@ Mirror of /root/reference/models/clip_cls.py: ``ZSCLIPClassifier`` (:14-219) and
 ``get_img_feats``, ``get_text_feats``, ``state_dict`` / ``load_state_dict`` that
 leave the frozen CLIP weights out, and ``load_weight``.  The arithmetic (image tower,
 text tower, adapter, logits, aggregation) is done by libeventclip_hip.so; torch is
-used for tensors and the nn.Module plumbing only.  ``forward`` is the inference path; the
-training losses of the reference (calc_train_loss, :164-175) and their gradients live in
-``eventclip_amd.train`` (cached-feature few-shot training).
+used for tensors and the nn.Module plumbing only.  In eval mode or under ``no_grad`` ``forward``
+is the inference path.  ``FSCLIPClassifier.forward`` in train mode with grad enabled is differentiable
+(``eventclip_hip::adapter_train_fwd`` and ``::classify`` carry autograd formulas over HIP backward kernels), so the
+reference's loop trains it as it is: ``out = clf(data)``, ``clf.calc_train_loss(data, out)['ce_loss'].backward()``,
+any ``torch.optim`` optimiser.  The fused "loss + gradients + Adam" steps of ``eventclip_amd.train`` on cached
+features stay the fast path.
 
 ``forward`` accepts the reference's batch (``img`` [B, T, 3, R, R] + ``valid_mask``)
 or the fused batch of ``Event2ImagePipeline`` (``patches`` + ``row_idx`` +
@@ -18,6 +21,7 @@ import copy
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from . import clip as eclip
@@ -128,26 +132,38 @@ class ZSCLIPClassifier(nn.Module):
             row_idx = row_idx.to(torch.int32).reshape(valid_masks.shape)
         return feats.float().contiguous(), row_idx.contiguous(), valid_masks
 
-    def _classify(self, feats, row_idx, normalize):
+    def _classify(self, feats, row_idx, normalize, text_t=None):
         from . import torch_ops  # noqa: F401  (registers eventclip_hip::classify)
-        return torch.ops.eventclip_hip.classify(feats, row_idx, self._text_transposed(),
+        return torch.ops.eventclip_hip.classify(feats, row_idx, self._text_transposed() if text_t is None else text_t,
                                                 float(self.logit_scale), _AGG[self.agg_func],
                                                 bool(normalize))
 
     @torch.no_grad()
     def forward(self, data_dict):
-        """clip_cls.py:131-162."""
+        """clip_cls.py:131-162.  Nothing here is trainable: no graph in any mode."""
         feats, row_idx, valid_masks = self._view_feats(data_dict)
         # logits = logit_scale * img_feats @ text_feats.T with UN-normalised image feats (:148)
         full_logits, logits, probs = self._classify(feats, row_idx, normalize=False)
         return dict(full_logits=full_logits, valid_masks=valid_masks, logits=logits, probs=probs)
 
+    def calc_train_loss(self, data_dict, out_dict):
+        """clip_cls.py:164-175: CE on the aggregated logits, or NLL of log(probs + 1e-6), as ``loss_dict`` selects."""
+        labels = data_dict['label']
+        loss_dict = {}
+        if self.use_logits_loss:
+            loss_dict['ce_loss'] = F.cross_entropy(out_dict['logits'], labels)
+        if self.use_probs_loss:
+            loss_dict['ce_loss'] = F.nll_loss((out_dict['probs'] + 1e-6).log(), labels)
+        return loss_dict
+
     @torch.no_grad()
     def calc_eval_loss(self, data_dict, out_dict):
-        """Accuracies of clip_cls.py:177-192 (the CE terms belong to training)."""
+        """clip_cls.py:177-192: the training loss terms and the two accuracies."""
+        loss_dict = self.calc_train_loss(data_dict, out_dict)
         y = data_dict['label']
         hit = lambda scores: (scores.argmax(-1) == y).float().mean()     # noqa: E731
-        return dict(probs_acc=hit(out_dict['probs']), logits_acc=hit(out_dict['logits']))
+        loss_dict.update(probs_acc=hit(out_dict['probs']), logits_acc=hit(out_dict['logits']))
+        return loss_dict
 
     dtype = property(lambda self: self.model.logit_scale.dtype)          # clip_cls.py:194-200
     device = property(lambda self: self.model.logit_scale.device)
@@ -221,9 +237,17 @@ class FSCLIPClassifier(ZSCLIPClassifier):
     def get_img_feats(self, imgs):
         return self._adjust_dtype(super().get_img_feats(imgs))
 
-    @torch.no_grad()
     def forward(self, data_dict):
-        """clip_cls.py:308-350."""
+        """clip_cls.py:308-350.  In train mode with grad enabled the output carries a graph into the adapter's
+        parameters and ``text_feats`` (``_forward_train``); in eval mode or under ``no_grad`` it is the inference path."""
+        if self.training and torch.is_grad_enabled() and self._differentiable:
+            return self._forward_train(data_dict)
+        with torch.no_grad():
+            return self._forward_eval(data_dict)
+
+    _differentiable = True
+
+    def _forward_eval(self, data_dict):
         feats, row_idx, valid_masks = self._view_feats(data_dict)
         B, T = valid_masks.shape
         C = feats.shape[-1]
@@ -234,6 +258,23 @@ class FSCLIPClassifier(ZSCLIPClassifier):
                           torch.full((B, T), -1, device=feats.device)).to(torch.int32)
         full_logits, logits, probs = self._classify(full_img_feats.reshape(B * T, C).contiguous(),
                                                     idx.contiguous(), normalize=True)
+        return dict(full_logits=full_logits, valid_masks=valid_masks, logits=logits, probs=probs)
+
+    def _forward_train(self, data_dict):
+        """The same function with autograd: the frozen encoder and the zero scatter under ``no_grad`` (:313-321), the
+        adapter through ``adapter_train_fwd`` (dropout 0.1 while ``self.adapter.training``; the identity adapter needs
+        no op), ``text_feats = F.normalize(parameter)`` in torch (:285-288), then ``classify`` with the live text."""
+        with torch.no_grad():
+            feats, row_idx, valid_masks = self._view_feats(data_dict)
+            B, T = valid_masks.shape
+            C = feats.shape[-1]
+            rows = IdentityAdapter.forward_rows(None, feats.float(), row_idx).reshape(B * T, C)
+            idx = torch.where(valid_masks, torch.arange(B * T, device=feats.device).view(B, T),
+                              torch.full((B, T), -1, device=feats.device)).to(torch.int32).contiguous()
+        if self.adapter_type == 'trans':
+            rows = self.adapter.train_rows(rows, idx).reshape(B * T, C)
+        text_t = self.get_text_feats().float().t().contiguous()          # [C, K], differentiable under prompt tuning
+        full_logits, logits, probs = self._classify(rows.contiguous(), idx, normalize=True, text_t=text_t)
         return dict(full_logits=full_logits, valid_masks=valid_masks, logits=logits, probs=probs)
 
     @torch.no_grad()

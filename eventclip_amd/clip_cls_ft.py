@@ -22,7 +22,12 @@ FT_LOSS_DEFAULTS = dict(use_logits_loss=True, use_probs_loss=False)
 
 
 class FTCLIPClassifier(FSCLIPClassifier):
-    """Fine-tuned CLIP for few-shot classification (clip_cls_ft.py:15-333)."""
+    """Fine-tuned CLIP for few-shot classification (clip_cls_ft.py:15-333).
+
+    ``forward`` is the inference path in every mode, train mode with grad enabled included: it builds no autograd
+    graph.  What this class trains is the vision tower, and that goes through ``eventclip_amd.ft.FTTrainer``."""
+
+    _differentiable = False
 
     def __init__(self, adapter_dict=None, clip_dict=None, loss_dict=None):
         ad = dict(FT_ADAPTER_DEFAULTS if adapter_dict is None else adapter_dict)

@@ -72,18 +72,23 @@ __global__ __launch_bounds__(64) void text_norm_kernel(const float *t, int D, fl
 }
 
 // F.normalize per view, invalid views zero (clip_cls.py:325-329): one wave per view row.
-// row_idx (optional): the features are compact over the valid views, row_idx[b, v] = their row
+// row_idx (optional): the features are compact over the valid views, row_idx[b, v] = their row.  valid == nullptr:
+// a view is valid iff its row_idx names one of the n_rows rows.  normalize == 0: the rows are only gathered and masked.
 __global__ __launch_bounds__(TR_THREADS) void fs_normalize_kernel(const float *feats, const unsigned char *valid,
-                                                                  const int *row_idx, int R, int D, float *Fn)
+                                                                  const int *row_idx, int n_rows, int normalize, int R,
+                                                                  int D, float *Fn)
 {
     const int lane = threadIdx.x & 63, r = blockIdx.x * TR_WAVES + (threadIdx.x >> 6);
     if (r >= R) return;
-    const bool ok = valid[r] != 0;
-    const long frow = row_idx ? (ok ? row_idx[r] : 0) : (long)r;
+    const int ri = row_idx ? row_idx[r] : r;
+    const bool ok = valid ? valid[r] != 0 : (ri >= 0 && ri < n_rows);
+    const long frow = row_idx ? (ok ? ri : 0) : (long)r;
     const float *f = feats + frow * D;
     float s = 0.f;
-    for (int d = lane; d < D; d += 64) s += f[d] * f[d];
-    const float inv = ok ? 1.f / fmaxf(__builtin_sqrtf(wave_sum_f(s)), 1e-12f) : 0.f;
+    if (ok && normalize)
+        for (int d = lane; d < D; d += 64) s += f[d] * f[d];
+    float inv = ok ? 1.f / fmaxf(__builtin_sqrtf(wave_sum_f(s)), 1e-12f) : 0.f;
+    if (ok && !normalize) inv = 1.f;
     for (int d = lane; d < D; d += 64) Fn[(long)r * D + d] = ok ? f[d] * inv : 0.f;
 }
 
@@ -476,22 +481,92 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float *f, long n, f
         g[i] = f[i] > 0.f ? g[i] * scale : 0.f;
 }
 // through F.normalize + the validity mask (clip_cls.py:325-329): dm = valid ? (dfn - fn (fn . dfn)) / |m| : 0,
-// scaled by `scale` (the (1 - residual) of Adapter.residual_add on the way to out_proj)
+// scaled by `scale` (the (1 - residual) of Adapter.residual_add on the way to out_proj).
+// row_idx (optional): mixed / dmixed are compact rows, view r lives in row row_idx[r]; only the rows that a valid view
+// names are written (the caller clears dmixed first).  valid == nullptr: valid iff row_idx names one of the n_rows rows.
+// normalize == 0: the forward only gathered and masked, dm = valid ? dfn * scale : 0.
 __global__ __launch_bounds__(256) void normalize_bwd_kernel(const float *mixed, const float *fn, const float *dfn,
-                                                            const unsigned char *valid, int R, int D, float scale,
-                                                            float *dmixed)
+                                                            const unsigned char *valid, const int *row_idx, int n_rows,
+                                                            int normalize, int R, int D, float scale, float *dmixed)
 {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (r >= R) return;
+    const int ri = row_idx ? row_idx[r] : r;
+    const bool ok = valid ? valid[r] != 0 : (ri >= 0 && ri < n_rows);
+    if (row_idx && !ok) return;
+    const long mr = row_idx ? (long)ri : (long)r;
     float s = 0.f, dot = 0.f;
     for (int j = lane; j < D; j += 64) {
-        const float m = mixed[(long)r * D + j];
+        const float m = mixed[mr * D + j];
         s += m * m, dot += fn[(long)r * D + j] * dfn[(long)r * D + j];
     }
-    const float inv = valid[r] ? scale / fmaxf(__builtin_sqrtf(wave_sum_f(s)), 1e-12f) : 0.f;
+    float inv = ok ? scale / fmaxf(__builtin_sqrtf(wave_sum_f(s)), 1e-12f) : 0.f;
     dot = wave_sum_f(dot);
+    if (!normalize) inv = ok ? scale : 0.f, dot = 0.f;
     for (int j = lane; j < D; j += 64)
-        dmixed[(long)r * D + j] = (dfn[(long)r * D + j] - fn[(long)r * D + j] * dot) * inv;
+        dmixed[mr * D + j] = (dfn[(long)r * D + j] - fn[(long)r * D + j] * dot) * inv;
+}
+
+// The three upstream gradients of ec_classify_v2's outputs folded into dZ = d loss / d full_logits [B, T, K]; one
+// workgroup per sample.  A null upstream gradient is zero.  Valid view v, class k:
+//   dZ = d_full                                                        identity
+//      + d_logits | d_logits / n_valid | d_logits on the maximal view   _aggregate_logits (clip_cls.py:104-121); max: over
+//                                                                      l - 1e6 [invalid], the lowest index on a tie
+//      + p (d_probs - <d_probs, p>) / n_valid,  p = softmax_k(full[v]) _aggregate_probs (:123-129)
+// Invalid views get zero: their logits are the constant 0 of the scatter (:151-152).
+__global__ __launch_bounds__(TR_THREADS) void classify_dz_kernel(const float *full, const int *row_idx, int n_rows, int T,
+                                                                 int K, int agg, const float *d_full,
+                                                                 const float *d_logits, const float *d_probs, float *dZ)
+{
+    __shared__ float vmax[AD_MAXT], vsum[AD_MAXT], vdot[AD_MAXT];
+    __shared__ int ok[AD_MAXT];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x < T) {
+        const int r = row_idx[b * T + threadIdx.x];
+        ok[threadIdx.x] = r >= 0 && r < n_rows;
+    }
+    __syncthreads();
+    float nv = 0.f;
+    for (int v = 0; v < T; v++) nv += ok[v] ? 1.f : 0.f;
+    const float *fl = full + (long)b * T * K;
+    if (d_probs) {
+        const float *g = d_probs + (long)b * K;
+        for (int v = wave; v < T; v += TR_WAVES) {       // a wave per view: its softmax statistics and <g, p>
+            if (!ok[v]) continue;
+            float mx = -INFINITY;
+            for (int k = lane; k < K; k += 64) mx = fmaxf(mx, fl[(long)v * K + k]);
+            mx = wave_max_f(mx);
+            float se = 0.f, dot = 0.f;
+            for (int k = lane; k < K; k += 64) {
+                const float e = expf(fl[(long)v * K + k] - mx);
+                se += e, dot += g[k] * e;
+            }
+            se = wave_sum_f(se), dot = wave_sum_f(dot);
+            if (lane == 0) vmax[v] = mx, vsum[v] = se, vdot[v] = dot / se;
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += TR_THREADS) {
+        const float gl = d_logits ? d_logits[(long)b * K + k] : 0.f;
+        const float gp = d_probs ? d_probs[(long)b * K + k] : 0.f;
+        int amax = -1;
+        if (d_logits && agg == EC_AGG_MAX) {
+            float best = -INFINITY;
+            for (int v = 0; v < T; v++) {
+                const float l = fl[(long)v * K + k] - (ok[v] ? 0.f : 1.f) * 1e6f;
+                if (l > best) best = l, amax = v;
+            }
+        }
+        for (int v = 0; v < T; v++) {
+            float z = 0.f;
+            if (ok[v]) {
+                if (d_full) z = d_full[((long)b * T + v) * K + k];
+                if (d_logits) z += agg == EC_AGG_SUM ? gl : (agg == EC_AGG_MEAN ? gl / nv : (v == amax ? gl : 0.f));
+                if (d_probs) z += expf(fl[(long)v * K + k] - vmax[v]) / vsum[v] * (gp - vdot[v]) / nv;
+            }
+            dZ[((long)b * T + v) * K + k] = z;
+        }
+    }
 }
 
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
@@ -553,7 +628,7 @@ int ec::fs_text_loss_grad(const float *img_feats, const int32_t *row_idx, const 
     }
     hipLaunchKernelGGL(text_norm_kernel, dim3(K), dim3(64), 0, s, text_param, D, u, inv_norm);
     hipLaunchKernelGGL(fs_normalize_kernel, dim3((unsigned)((R + TR_WAVES - 1) / TR_WAVES)), dim3(TR_THREADS), 0, s, img_feats, valid,
-                       row_idx, (int)R, D, Fn);
+                       row_idx, 0, 1, (int)R, D, Fn);
     // full_logits [R, K] = logit_scale * Fn u^T, into the dL rows
     hipLaunchKernelGGL(sgemm_kernel<false>, dim3((K + 63) / 64, (unsigned)((R + 63) / 64)), dim3(256), 0, s, Fn, (long)D, 1L, u, 1L,
                        (long)D, (int)R, K, D, logit_scale, 0.f, static_cast<const float *>(nullptr), dL, (long)K);
@@ -589,9 +664,12 @@ extern "C" EC_API int ec_adam_step(float *param, const float *grad, float *exp_a
 // ---------------------------------------------------------------------------------------------------
 // 'text-trans': TransformerAdapter (models/adapter.py:52-110) + text_feats.  Layer-wise over all
 // R = B * T view rows: every nn.Linear is one sgemm_kernel launch (x W^T forward, dy W and dy^T x
-// backward), the saved activations live in the workspace.  Dropout (p = 0.1 inside
-// nn.TransformerEncoderLayer) is not applied: this is the deterministic function the eval-mode module
-// computes, the same one the golden gradients differentiate.
+// backward), the saved activations live in the workspace.  dropout_p = 0 is the deterministic function the
+// eval-mode module computes, the one the golden gradients differentiate; dropout_p > 0 adds the four train-mode
+// dropouts of nn.TransformerEncoderLayer from a stateless hash.  The adapter's forward and backward are written once
+// (adapter_train_fwd_launches / adapter_train_bwd_launches): ec_fs_trans_loss_grad runs them around its loss head,
+// ec_adapter_train_forward / _backward run them as two calls over a caller-owned tape (torch autograd), and
+// ec_classify_backward is the classifier tail's backward for an arbitrary upstream gradient.
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
@@ -610,27 +688,51 @@ struct LayerBufs {
     float *xhat1, *rstd1, *a, *qkv, *P, *o, *h1, *xhat2, *rstd2, *bn, *f;
 };
 
-struct TransBufs {
-    float *h0, *hfin, *y, *mixed, *dfn, *dy, *dh, *dh1, *dtmp_d, *dqkv, *df;
+// What the adapter's forward leaves for its backward (hfin and the layers' saved activations) and its own scratch
+// (h0, y, ftmp): the backward half only reads it.
+struct AdapterTape {
+    float *h0, *hfin, *y, *ftmp;
     LayerBufs L[8];
+};
+// Everything the adapter's backward overwrites.  dy = d loss / d out_proj's output on entry.
+struct AdapterScratch {
+    float *dy, *dh, *dh1, *dtmp_d, *dqkv, *df;
+};
+
+struct TransBufs {
+    float *mixed, *dfn;
+    AdapterTape tape;
+    AdapterScratch bw;
     // shared with the text-identity path
     float *Fn, *dL, *u, *dU, *inv_norm, *loss_b;
 };
 
-size_t carve_trans(Carve &c, int B, int T, int D, int K, int d, int ffn, int heads, int layers, TransBufs &t)
+void carve_tape(Carve &c, int B, int T, int D, int d, int ffn, int heads, int layers, AdapterTape &t)
 {
     const size_t R = (size_t)B * T;
-    t.Fn = c.f(R * D), t.dL = c.f(R * K), t.u = c.f((size_t)K * D), t.dU = c.f((size_t)K * D);
-    t.inv_norm = c.f(K), t.loss_b = c.f(B);
-    t.h0 = c.f(R * d), t.hfin = c.f(R * d), t.y = c.f(R * D), t.mixed = c.f(R * D), t.dfn = c.f(R * D);
-    t.dy = c.f(R * D), t.dh = c.f(R * d), t.dh1 = c.f(R * d), t.dtmp_d = c.f(R * d), t.dqkv = c.f(R * 3 * d);
-    t.df = c.f(R * ffn);
+    t.h0 = c.f(R * d), t.hfin = c.f(R * d), t.y = c.f(R * D), t.ftmp = c.f(R * d);
     for (int l = 0; l < layers; l++) {
         LayerBufs &b = t.L[l];
         b.xhat1 = c.f(R * d), b.rstd1 = c.f(R), b.a = c.f(R * d), b.qkv = c.f(R * 3 * d);
         b.P = c.f((size_t)B * heads * T * T), b.o = c.f(R * d), b.h1 = c.f(R * d), b.xhat2 = c.f(R * d);
         b.rstd2 = c.f(R), b.bn = c.f(R * d), b.f = c.f(R * ffn);
     }
+}
+void carve_scratch(Carve &c, int B, int T, int D, int d, int ffn, AdapterScratch &t)
+{
+    const size_t R = (size_t)B * T;
+    t.dy = c.f(R * D), t.dh = c.f(R * d), t.dh1 = c.f(R * d), t.dtmp_d = c.f(R * d), t.dqkv = c.f(R * 3 * d);
+    t.df = c.f(R * ffn);
+}
+
+size_t carve_trans(Carve &c, int B, int T, int D, int K, int d, int ffn, int heads, int layers, TransBufs &t)
+{
+    const size_t R = (size_t)B * T;
+    t.Fn = c.f(R * D), t.dL = c.f(R * K), t.u = c.f((size_t)K * D), t.dU = c.f((size_t)K * D);
+    t.inv_norm = c.f(K), t.loss_b = c.f(B);
+    t.mixed = c.f(R * D), t.dfn = c.f(R * D);
+    carve_tape(c, B, T, D, d, ffn, heads, layers, t.tape);
+    carve_scratch(c, B, T, D, d, ffn, t.bw);
     return c.off;
 }
 
@@ -651,15 +753,130 @@ void linear_fwd(hipStream_t s, const float *x, const float *W, const float *b, i
 {
     gemm(s, relu, x, in, 1, W, 1, in, R, out, in, 1.f, beta, b, y);
 }
-// dx[R, in] = dy[R, out] W (+ beta dx);  dW[out, in] = dy^T x;  db[out] = colsum(dy)
+// dx[R, in] = dy[R, out] W (+ beta dx);  dW[out, in] = dy^T x;  db[out] = colsum(dy).  A null output is skipped.
 void linear_bwd(hipStream_t s, const float *x, const float *W, const float *dy, int R, int in, int out, float *dx,
                 float dx_beta, float *dW, float *db)
 {
     if (dx) gemm(s, false, dy, out, 1, W, in, 1, R, in, out, 1.f, dx_beta, nullptr, dx);
-    gemm(s, false, dy, 1, out, x, in, 1, out, in, R, 1.f, 0.f, nullptr, dW);
-    hipLaunchKernelGGL(colsum_kernel, dim3((out + 63) / 64), dim3(256), 0, s, dy, (const float *)nullptr, R, out, db);
+    if (dW) gemm(s, false, dy, 1, out, x, in, 1, out, in, R, 1.f, 0.f, nullptr, dW);
+    if (db) hipLaunchKernelGGL(colsum_kernel, dim3((out + 63) / 64), dim3(256), 0, s, dy, (const float *)nullptr, R, out, db);
+}
+// d gamma[j] = sum_r dy[r, j] xhat[r, j], d beta[j] = sum_r dy[r, j]; a null output is skipped
+void ln_param_bwd(hipStream_t s, const float *dy, const float *xhat, int R, int d, float *dg, float *db)
+{
+    if (dg) hipLaunchKernelGGL(colsum_kernel, dim3((d + 63) / 64), dim3(256), 0, s, dy, xhat, R, d, dg);
+    if (db) hipLaunchKernelGGL(colsum_kernel, dim3((d + 63) / 64), dim3(256), 0, s, dy, (const float *)nullptr, R, d, db);
 }
 unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
+
+bool adapter_geometry_ok(const ec_adapter_train_params *w, int T)
+{
+    return w->in_dim > 0 && w->d_model > 0 && w->d_model <= 1024 && w->ffn_dim > 0 && w->heads > 0 &&
+           w->d_model % w->heads == 0 && w->layers >= 1 && w->layers <= 8 && T <= AD_MAXT;
+}
+
+// dropout sites of layer l (nn.TransformerEncoderLayer, norm_first): 4 l + {0 attention weights,
+// 1 dropout1 after out_proj, 2 dropout inside the MLP, 3 dropout2 after linear2}
+
+// The adapter's forward (adapter.py:82-105) over all R = B * T view rows, saving what the backward reads:
+// mixed [R, D] = r img_feats + (1 - r) out_proj(encoder(in_proj(img_feats))).  The one launch sequence behind
+// ec_fs_trans_loss_grad and ec_adapter_train_forward.
+void adapter_train_fwd_launches(hipStream_t s, const float *img_feats, const unsigned char *valid, int B, int T,
+                                const ec_adapter_train_params *w, float dp, unsigned long long seed, AdapterTape &t,
+                                float *mixed)
+{
+    const int D = w->in_dim, d = w->d_model, ffn = w->ffn_dim, heads = w->heads, layers = w->layers, R = B * T;
+    const float r = w->residual;
+    const unsigned ln_grid = (unsigned)((R + 3) / 4);
+    linear_fwd(s, img_feats, w->in_w, w->in_b, R, D, d, t.h0);
+    const float *h = t.h0;
+    for (int l = 0; l < layers; l++) {
+        const ec_adapter_train_layer &p = w->blocks[l];
+        LayerBufs &b = t.L[l];
+        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, h, p.ln1_g, p.ln1_b, R, d, b.a, b.xhat1, b.rstd1);
+        linear_fwd(s, b.a, p.qkv_w, p.qkv_b, R, d, 3 * d, b.qkv);
+        hipLaunchKernelGGL(adapter_attn_fwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, valid, T, d, heads, b.P, b.o,
+                           dp, seed, (unsigned)(4 * l));
+        if (dp > 0.f) {
+            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, t.ftmp);
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, t.ftmp,
+                               (long)R * d, dp, seed, (unsigned)(4 * l + 1), b.h1);   // h1 = h + dropout1(out_proj(o))
+        } else {
+            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, (const float *)nullptr,
+                               (long)R * d, 1.f, 0.f, b.h1);
+            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, b.h1, 1.f);                   // h1 = h + out_proj(o)
+        }
+        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, b.h1, p.ln2_g, p.ln2_b, R, d, b.bn, b.xhat2,
+                           b.rstd2);
+        linear_fwd(s, b.bn, p.w1, p.b1, R, d, ffn, b.f, 0.f, true);                   // relu(linear1)
+        if (dp > 0.f)
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s,
+                               (const float *)nullptr, b.f, (long)R * ffn, dp, seed, (unsigned)(4 * l + 2), b.f);
+        if (dp > 0.f) {
+            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.ftmp);
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.h1, t.ftmp,
+                               (long)R * d, dp, seed, (unsigned)(4 * l + 3), t.hfin);  // h = h1 + dropout2(linear2(f))
+        } else {
+            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.h1, (const float *)nullptr,
+                               (long)R * d, 1.f, 0.f, t.hfin);
+            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.hfin, 1.f);                   // h = h1 + linear2(f)
+        }
+        h = t.hfin;      // this layer's input is dead (ln_1 consumed it, h1 took its copy): reuse its slot
+    }
+    linear_fwd(s, h, w->out_w, w->out_b, R, d, D, t.y);
+    hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * D)), dim3(256), 0, s, img_feats, t.y, (long)R * D, r,
+                       1.f - r, mixed);                                             // Adapter.residual_add
+}
+
+// The adapter's backward from x.dy = d loss / d out_proj's output: every non-null gradient of g, and (d_img non-null)
+// d_img = d_img_beta * d_img + d h0 in_proj.weight.  Reads the tape, writes only x and the gradients.  The one launch
+// sequence behind ec_fs_trans_loss_grad and ec_adapter_train_backward.
+void adapter_train_bwd_launches(hipStream_t s, const float *img_feats, int B, int T, const ec_adapter_train_params *w,
+                                const ec_adapter_train_params *g, float dp, unsigned long long seed,
+                                const AdapterTape &t, const AdapterScratch &x, float *d_img, float d_img_beta)
+{
+    const int D = w->in_dim, d = w->d_model, ffn = w->ffn_dim, heads = w->heads, layers = w->layers, R = B * T;
+    const unsigned ln_grid = (unsigned)((R + 3) / 4);
+    const float keep_scale = 1.f / (1.f - dp);
+    linear_bwd(s, t.hfin, w->out_w, x.dy, R, d, D, x.dh, 0.f, g->out_w, g->out_b);
+    for (int l = layers - 1; l >= 0; l--) {
+        const ec_adapter_train_layer &p = w->blocks[l];
+        const ec_adapter_train_layer &q = g->blocks[l];
+        const LayerBufs &b = t.L[l];
+        // h = h1 + dropout2(linear2(dropout(relu(linear1(ln2(h1))))))
+        const float *dlin2 = x.dh;
+        if (dp > 0.f) {
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
+                               (const float *)nullptr, x.dh, (long)R * d, dp, seed, (unsigned)(4 * l + 3), x.dtmp_d);
+            dlin2 = x.dtmp_d;
+        }
+        linear_bwd(s, b.f, p.w2, dlin2, R, ffn, d, x.df, 0.f, q.w2, q.b2);
+        hipLaunchKernelGGL(relu_bwd_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s, b.f, (long)R * ffn,
+                           keep_scale, x.df);
+        linear_bwd(s, b.bn, p.w1, x.df, R, d, ffn, x.dtmp_d, 0.f, q.w1, q.b1);
+        ln_param_bwd(s, x.dtmp_d, b.xhat2, R, d, q.ln2_g, q.ln2_b);
+        hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, x.dh, (const float *)nullptr,
+                           (long)R * d, 1.f, 0.f, x.dh1);
+        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, x.dtmp_d, b.xhat2, b.rstd2, p.ln2_g, R, d, x.dh1,
+                           1);
+        // h1 = h + dropout1(out_proj(attn(in_proj(ln1(h)))))
+        const float *dlin_o = x.dh1;
+        if (dp > 0.f) {
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
+                               (const float *)nullptr, x.dh1, (long)R * d, dp, seed, (unsigned)(4 * l + 1), x.dh);
+            dlin_o = x.dh;        // dh is rebuilt from dh1 below
+        }
+        linear_bwd(s, b.o, p.o_w, dlin_o, R, d, d, x.dtmp_d, 0.f, q.o_w, q.o_b);
+        hipLaunchKernelGGL(adapter_attn_bwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, b.P, x.dtmp_d, T, d, heads,
+                           x.dqkv, dp, seed, (unsigned)(4 * l));
+        linear_bwd(s, b.a, p.qkv_w, x.dqkv, R, d, 3 * d, x.dtmp_d, 0.f, q.qkv_w, q.qkv_b);
+        ln_param_bwd(s, x.dtmp_d, b.xhat1, R, d, q.ln1_g, q.ln1_b);
+        hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, x.dh1, (const float *)nullptr,
+                           (long)R * d, 1.f, 0.f, x.dh);
+        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, x.dtmp_d, b.xhat1, b.rstd1, p.ln1_g, R, d, x.dh, 1);
+    }
+    linear_bwd(s, img_feats, w->in_w, x.dh, R, D, d, d_img, d_img_beta, g->in_w, g->in_b);
+}
 
 }  // namespace
 
@@ -685,8 +902,8 @@ extern "C" EC_API int ec_fs_trans_loss_grad(const float *img_feats, const uint8_
     EC_REQUIRE(w && g && w->blocks && g->blocks, "ec_fs_trans_loss_grad: null parameter / gradient structs");
     EC_REQUIRE(agg == EC_AGG_SUM || agg == EC_AGG_MEAN, "ec_fs_trans_loss_grad: agg must be sum or mean");
     const int d = w->d_model, ffn = w->ffn_dim, heads = w->heads, layers = w->layers;
-    EC_REQUIRE(w->in_dim == D && d > 0 && d <= 1024 && heads > 0 && d % heads == 0 && layers >= 1 && layers <= 8 &&
-                   T <= AD_MAXT, "ec_fs_trans_loss_grad: unsupported adapter geometry (T <= %d, layers <= 8)", AD_MAXT);
+    EC_REQUIRE(w->in_dim == D && adapter_geometry_ok(w, T),
+               "ec_fs_trans_loss_grad: unsupported adapter geometry (T <= %d, layers <= 8)", AD_MAXT);
     EC_REQUIRE(img_feats && valid && labels && text_param && loss && grad_text && workspace,
                "ec_fs_trans_loss_grad: null buffer");
     Carve c{static_cast<unsigned char *>(workspace), 0};
@@ -705,56 +922,13 @@ extern "C" EC_API int ec_fs_trans_loss_grad(const float *img_feats, const uint8_
     }
     const int R = B * T;
     const float r = w->residual;
-    const unsigned ln_grid = (unsigned)((R + 3) / 4);
-    const float dp = dropout_p, keep_scale = 1.f / (1.f - dropout_p);
-    const unsigned long long seed = dropout_seed;
-    // dropout sites of layer l (nn.TransformerEncoderLayer, norm_first): 4 l + {0 attention weights,
-    // 1 dropout1 after out_proj, 2 dropout inside the MLP, 3 dropout2 after linear2}
 
-    // ---------------- forward (adapter.py:82-105) ----------------
-    linear_fwd(s, img_feats, w->in_w, w->in_b, R, D, d, t.h0);
-    const float *h = t.h0;
-    for (int l = 0; l < layers; l++) {
-        const ec_adapter_train_layer &p = w->blocks[l];
-        LayerBufs &b = t.L[l];
-        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, h, p.ln1_g, p.ln1_b, R, d, b.a, b.xhat1, b.rstd1);
-        linear_fwd(s, b.a, p.qkv_w, p.qkv_b, R, d, 3 * d, b.qkv);
-        hipLaunchKernelGGL(adapter_attn_fwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, valid, T, d, heads, b.P, b.o,
-                           dp, seed, (unsigned)(4 * l));
-        if (dp > 0.f) {
-            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, t.dtmp_d);
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, t.dtmp_d,
-                               (long)R * d, dp, seed, (unsigned)(4 * l + 1), b.h1);   // h1 = h + dropout1(out_proj(o))
-        } else {
-            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, (const float *)nullptr,
-                               (long)R * d, 1.f, 0.f, b.h1);
-            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, b.h1, 1.f);                   // h1 = h + out_proj(o)
-        }
-        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, b.h1, p.ln2_g, p.ln2_b, R, d, b.bn, b.xhat2,
-                           b.rstd2);
-        linear_fwd(s, b.bn, p.w1, p.b1, R, d, ffn, b.f, 0.f, true);                   // relu(linear1)
-        if (dp > 0.f)
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s,
-                               (const float *)nullptr, b.f, (long)R * ffn, dp, seed, (unsigned)(4 * l + 2), b.f);
-        if (dp > 0.f) {
-            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.dtmp_d);
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.h1, t.dtmp_d,
-                               (long)R * d, dp, seed, (unsigned)(4 * l + 3), t.hfin);  // h = h1 + dropout2(linear2(f))
-        } else {
-            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.h1, (const float *)nullptr,
-                               (long)R * d, 1.f, 0.f, t.hfin);
-            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.hfin, 1.f);                   // h = h1 + linear2(f)
-        }
-        h = t.hfin;      // this layer's input is dead (ln_1 consumed it, h1 took its copy): reuse its slot
-    }
-    linear_fwd(s, h, w->out_w, w->out_b, R, d, D, t.y);
-    hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * D)), dim3(256), 0, s, img_feats, t.y, (long)R * D, r,
-                       1.f - r, t.mixed);                                           // Adapter.residual_add
+    adapter_train_fwd_launches(s, img_feats, valid, B, T, w, dropout_p, dropout_seed, t.tape, t.mixed);
 
     // ---------------- loss, dL, text gradient (shared with 'text-identity') ----------------
     hipLaunchKernelGGL(text_norm_kernel, dim3(K), dim3(64), 0, s, text_param, D, t.u, t.inv_norm);
     hipLaunchKernelGGL(fs_normalize_kernel, dim3((unsigned)((R + TR_WAVES - 1) / TR_WAVES)), dim3(TR_THREADS), 0, s, t.mixed, valid,
-                       (const int *)nullptr, R, D, t.Fn);
+                       (const int *)nullptr, 0, 1, R, D, t.Fn);
     hipLaunchKernelGGL(sgemm_kernel<false>, dim3((K + 63) / 64, (unsigned)((R + 63) / 64)), dim3(256), 0, s, t.Fn, (long)D, 1L, t.u,
                        1L, (long)D, R, K, D, logit_scale, 0.f, static_cast<const float *>(nullptr), t.dL, (long)K);
     hipLaunchKernelGGL(fs_loss_grad_kernel, dim3(B), dim3(TR_THREADS), lds, s, valid, labels, B, T, K, agg, use_probs_loss, t.dL,
@@ -766,53 +940,132 @@ extern "C" EC_API int ec_fs_trans_loss_grad(const float *img_feats, const uint8_
 
     // ---------------- backward into the adapter ----------------
     gemm(s, false, t.dL, K, 1, t.u, D, 1, R, D, K, logit_scale, 0.f, nullptr, t.dfn);   // dFn = s dL u
-    hipLaunchKernelGGL(normalize_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, t.mixed, t.Fn, t.dfn, valid, R, D, 1.f - r,
-                       t.dy);                                                        // dY = (1 - r) dMixed
-    linear_bwd(s, h, w->out_w, t.dy, R, d, D, t.dh, 0.f, g->out_w, g->out_b);
-    for (int l = layers - 1; l >= 0; l--) {
-        const ec_adapter_train_layer &p = w->blocks[l];
-        const ec_adapter_train_layer &q = g->blocks[l];
-        LayerBufs &b = t.L[l];
-        // h = h1 + dropout2(linear2(dropout(relu(linear1(ln2(h1))))))
-        const float *dlin2 = t.dh;
-        if (dp > 0.f) {
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
-                               (const float *)nullptr, t.dh, (long)R * d, dp, seed, (unsigned)(4 * l + 3), t.dtmp_d);
-            dlin2 = t.dtmp_d;
-        }
-        linear_bwd(s, b.f, p.w2, dlin2, R, ffn, d, t.df, 0.f, const_cast<float *>(q.w2), const_cast<float *>(q.b2));
-        hipLaunchKernelGGL(relu_bwd_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s, b.f, (long)R * ffn,
-                           keep_scale, t.df);
-        linear_bwd(s, b.bn, p.w1, t.df, R, d, ffn, t.dtmp_d, 0.f, const_cast<float *>(q.w1), const_cast<float *>(q.b1));
-        hipLaunchKernelGGL(colsum_kernel, dim3((d + 63) / 64), dim3(256), 0, s, t.dtmp_d, b.xhat2, R, d,
-                           const_cast<float *>(q.ln2_g));
-        hipLaunchKernelGGL(colsum_kernel, dim3((d + 63) / 64), dim3(256), 0, s, t.dtmp_d, (const float *)nullptr, R, d,
-                           const_cast<float *>(q.ln2_b));
-        hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, t.dh, (const float *)nullptr,
-                           (long)R * d, 1.f, 0.f, t.dh1);
-        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, t.dtmp_d, b.xhat2, b.rstd2, p.ln2_g, R, d, t.dh1,
-                           1);
-        // h1 = h + dropout1(out_proj(attn(in_proj(ln1(h)))))
-        const float *dlin_o = t.dh1;
-        if (dp > 0.f) {
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
-                               (const float *)nullptr, t.dh1, (long)R * d, dp, seed, (unsigned)(4 * l + 1), t.dh);
-            dlin_o = t.dh;        // dh is rebuilt from dh1 below
-        }
-        linear_bwd(s, b.o, p.o_w, dlin_o, R, d, d, t.dtmp_d, 0.f, const_cast<float *>(q.o_w), const_cast<float *>(q.o_b));
-        hipLaunchKernelGGL(adapter_attn_bwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, b.P, t.dtmp_d, T, d, heads,
-                           t.dqkv, dp, seed, (unsigned)(4 * l));
-        linear_bwd(s, b.a, p.qkv_w, t.dqkv, R, d, 3 * d, t.dtmp_d, 0.f, const_cast<float *>(q.qkv_w),
-                   const_cast<float *>(q.qkv_b));
-        hipLaunchKernelGGL(colsum_kernel, dim3((d + 63) / 64), dim3(256), 0, s, t.dtmp_d, b.xhat1, R, d,
-                           const_cast<float *>(q.ln1_g));
-        hipLaunchKernelGGL(colsum_kernel, dim3((d + 63) / 64), dim3(256), 0, s, t.dtmp_d, (const float *)nullptr, R, d,
-                           const_cast<float *>(q.ln1_b));
-        hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, t.dh1, (const float *)nullptr,
-                           (long)R * d, 1.f, 0.f, t.dh);
-        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, t.dtmp_d, b.xhat1, b.rstd1, p.ln1_g, R, d, t.dh, 1);
+    hipLaunchKernelGGL(normalize_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, t.mixed, t.Fn, t.dfn, valid,
+                       (const int *)nullptr, 0, 1, R, D, 1.f - r, t.bw.dy);            // dY = (1 - r) dMixed
+    adapter_train_bwd_launches(s, img_feats, B, T, w, g, dropout_p, dropout_seed, t.tape, t.bw, nullptr, 0.f);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
+// ---- the same forward and backward as two calls over a caller-owned tape (torch autograd) ----
+extern "C" EC_API size_t ec_adapter_train_tape_bytes(int B, int T, int D, int d_model, int ffn_dim, int heads, int layers)
+{
+    if (B <= 0 || T <= 0 || D <= 0 || d_model <= 0 || ffn_dim <= 0 || heads <= 0 || layers <= 0 || layers > 8) return 0;
+    Carve c{nullptr, 0};
+    AdapterTape t;
+    carve_tape(c, B, T, D, d_model, ffn_dim, heads, layers, t);
+    return c.off;
+}
+
+extern "C" EC_API size_t ec_adapter_train_backward_workspace_bytes(int B, int T, int D, int d_model, int ffn_dim)
+{
+    if (B <= 0 || T <= 0 || D <= 0 || d_model <= 0 || ffn_dim <= 0) return 0;
+    Carve c{nullptr, 0};
+    AdapterScratch x;
+    carve_scratch(c, B, T, D, d_model, ffn_dim, x);
+    return c.off;
+}
+
+extern "C" EC_API int ec_adapter_train_forward(const float *img_feats, const uint8_t *valid, int B, int T,
+                                               const ec_adapter_train_params *w, float dropout_p,
+                                               uint64_t dropout_seed, float *out, void *tape, size_t tape_bytes,
+                                               ec_stream_t stream)
+{
+    EC_REQUIRE(B > 0 && T > 0, "ec_adapter_train_forward: bad shape B=%d T=%d", B, T);
+    EC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "ec_adapter_train_forward: dropout_p=%g", (double)dropout_p);
+    EC_REQUIRE(w && w->blocks, "ec_adapter_train_forward: null parameter struct");
+    EC_REQUIRE(adapter_geometry_ok(w, T), "ec_adapter_train_forward: unsupported adapter geometry (T <= %d, layers <= 8)",
+               AD_MAXT);
+    EC_REQUIRE(img_feats && valid && out && tape, "ec_adapter_train_forward: null buffer");
+    Carve c{static_cast<unsigned char *>(tape), 0};
+    AdapterTape t;
+    carve_tape(c, B, T, w->in_dim, w->d_model, w->ffn_dim, w->heads, w->layers, t);
+    if (c.off > tape_bytes)
+        return ec::fail(EC_ERR_WORKSPACE, "ec_adapter_train_forward: tape %zu < %zu bytes", tape_bytes, c.off);
+    adapter_train_fwd_launches(static_cast<hipStream_t>(stream), img_feats, valid, B, T, w, dropout_p, dropout_seed, t, out);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
+extern "C" EC_API int ec_adapter_train_backward(const float *img_feats, int B, int T, const ec_adapter_train_params *w,
+                                                float dropout_p, uint64_t dropout_seed, const void *tape,
+                                                size_t tape_bytes, const float *d_out,
+                                                const ec_adapter_train_params *g, float *d_img_feats, void *workspace,
+                                                size_t workspace_bytes, ec_stream_t stream)
+{
+    EC_REQUIRE(B > 0 && T > 0, "ec_adapter_train_backward: bad shape B=%d T=%d", B, T);
+    EC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "ec_adapter_train_backward: dropout_p=%g", (double)dropout_p);
+    EC_REQUIRE(w && g && w->blocks && g->blocks, "ec_adapter_train_backward: null parameter / gradient structs");
+    EC_REQUIRE(adapter_geometry_ok(w, T), "ec_adapter_train_backward: unsupported adapter geometry (T <= %d, layers <= 8)",
+               AD_MAXT);
+    EC_REQUIRE(img_feats && tape && d_out && workspace, "ec_adapter_train_backward: null buffer");
+    const int D = w->in_dim, R = B * T;
+    Carve ct{static_cast<unsigned char *>(const_cast<void *>(tape)), 0};
+    AdapterTape t;
+    carve_tape(ct, B, T, D, w->d_model, w->ffn_dim, w->heads, w->layers, t);
+    if (ct.off > tape_bytes)
+        return ec::fail(EC_ERR_WORKSPACE, "ec_adapter_train_backward: tape %zu < %zu bytes", tape_bytes, ct.off);
+    Carve cx{static_cast<unsigned char *>(workspace), 0};
+    AdapterScratch x;
+    carve_scratch(cx, B, T, D, w->d_model, w->ffn_dim, x);
+    if (cx.off > workspace_bytes)
+        return ec::fail(EC_ERR_WORKSPACE, "ec_adapter_train_backward: workspace %zu < %zu bytes", workspace_bytes, cx.off);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const float r = w->residual;
+    // out = r img_feats + (1 - r) y (Adapter.residual_add): dY = (1 - r) d_out, d_img_feats = r d_out + (through in_proj)
+    hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * D)), dim3(256), 0, s, d_out, (const float *)nullptr,
+                       (long)R * D, 1.f - r, 0.f, x.dy);
+    if (d_img_feats)
+        hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * D)), dim3(256), 0, s, d_out, (const float *)nullptr,
+                           (long)R * D, r, 0.f, d_img_feats);
+    adapter_train_bwd_launches(s, img_feats, B, T, w, g, dropout_p, dropout_seed, t, x, d_img_feats, 1.f);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
+// ---- the VJP of ec_classify_v2 (csrc/classify.hip) with respect to feats and text_t ----
+extern "C" EC_API size_t ec_classify_backward_workspace_bytes(int B, int T, int C, int K)
+{
+    if (B <= 0 || T <= 0 || C <= 0 || K <= 0) return 0;
+    const size_t R = (size_t)B * T;
+    return 2 * align256(R * C * 4) + align256(R * K * 4);
+}
+
+extern "C" EC_API int ec_classify_backward(const float *feats, int n_rows, const int32_t *row_idx, const float *text_t,
+                                           int B, int T, int C, int K, float logit_scale, int agg, int normalize,
+                                           const float *full_logits, const float *d_full_logits, const float *d_logits,
+                                           const float *d_probs, float *d_feats, float *d_text_t, void *workspace,
+                                           size_t workspace_bytes, ec_stream_t stream)
+{
+    EC_REQUIRE(B >= 0 && T > 0 && T <= AD_MAXT && C > 0 && C % 4 == 0 && K >= 2 && n_rows >= 0,
+               "ec_classify_backward: bad shape n_rows=%d B=%d T=%d C=%d K=%d (T <= %d, C a multiple of 4, K >= 2)", n_rows,
+               B, T, C, K, AD_MAXT);
+    EC_REQUIRE(agg == EC_AGG_SUM || agg == EC_AGG_MEAN || agg == EC_AGG_MAX, "ec_classify_backward: unknown agg %d", agg);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // rows of feats that no valid view names keep a zero gradient: normalize_bwd_kernel writes the others
+    if (d_feats && n_rows > 0) EC_CHECK_HIP(hipMemsetAsync(d_feats, 0, (size_t)n_rows * C * 4, s));
+    if (B == 0 || n_rows == 0) {
+        if (d_text_t) EC_CHECK_HIP(hipMemsetAsync(d_text_t, 0, (size_t)C * K * 4, s));
+        return EC_OK;
     }
-    linear_bwd(s, img_feats, w->in_w, t.dh, R, D, d, nullptr, 0.f, g->in_w, g->in_b);
+    EC_REQUIRE(feats && row_idx && text_t && full_logits && workspace, "ec_classify_backward: null buffer");
+    const size_t need = ec_classify_backward_workspace_bytes(B, T, C, K);
+    if (workspace_bytes < need)
+        return ec::fail(EC_ERR_WORKSPACE, "ec_classify_backward: workspace %zu < %zu bytes", workspace_bytes, need);
+    const int R = B * T;
+    Carve c{static_cast<unsigned char *>(workspace), 0};
+    float *Fn = c.f((size_t)R * C), *dFn = c.f((size_t)R * C), *dZ = c.f((size_t)R * K);
+    hipLaunchKernelGGL(classify_dz_kernel, dim3(B), dim3(TR_THREADS), 0, s, full_logits, row_idx, n_rows, T, K, agg,
+                       d_full_logits, d_logits, d_probs, dZ);
+    hipLaunchKernelGGL(fs_normalize_kernel, dim3((unsigned)((R + TR_WAVES - 1) / TR_WAVES)), dim3(TR_THREADS), 0, s, feats,
+                       (const unsigned char *)nullptr, row_idx, n_rows, normalize, R, C, Fn);
+    if (d_text_t)       // d text_t [C, K] = scale Fn^T dZ: the reduction runs over the R view rows
+        gemm(s, false, Fn, 1, C, dZ, K, 1, C, K, R, logit_scale, 0.f, nullptr, d_text_t);
+    if (d_feats) {
+        gemm(s, false, dZ, K, 1, text_t, 1, K, R, C, K, logit_scale, 0.f, nullptr, dFn);   // dFn = scale dZ text
+        hipLaunchKernelGGL(normalize_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, feats, Fn, dFn,
+                           (const unsigned char *)nullptr, row_idx, n_rows, normalize, R, C, 1.f, d_feats);
+    }
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }

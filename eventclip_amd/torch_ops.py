@@ -12,15 +12,23 @@ mirrors of the reference's interface (vis / preprocess / clip / adapter / clip_c
     torch.ops.eventclip_hip.text_encode        ec_text_encode                  models/clip_cls.py:84
     torch.ops.eventclip_hip.adapter_fwd        ec_adapter_forward              models/adapter.py:82-105
     torch.ops.eventclip_hip.classify           ec_classify_v2                   models/clip_cls.py:139-154, :319-343
+    torch.ops.eventclip_hip.classify_bwd       ec_classify_backward            its vector-Jacobian product (loss.backward())
+    torch.ops.eventclip_hip.adapter_train_fwd  ec_adapter_train_forward        models/adapter.py:82-105 in train mode
+    torch.ops.eventclip_hip.adapter_train_bwd  ec_adapter_train_backward       its backward, over the forward's tape
     torch.ops.eventclip_hip.resnet_encode      ec_resnet_encode                models/clip_cls.py:101 (ResNet backbones)
 
 Weights live in packed C structs owned by the Python modules; an op receives them as an integer
 handle into a registry of live modules (tensors-only signatures keep the ops traceable, and the
 registered fake kernels give their output shapes without touching the device).
+
+``classify`` and ``adapter_train_fwd`` carry autograd formulas (``torch.library.register_autograd``) whose backward
+passes are the ``*_bwd`` ops, so ``loss.backward()`` reaches ``text_feats`` and the adapter's parameters, which
+``adapter_train_fwd`` takes as real tensor inputs.  The ``*_bwd`` ops have no formula of their own: there is no double
+backward, and asking for one raises.
 """
 import ctypes
 import weakref
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -254,6 +262,183 @@ def _(feats, row_idx, text_t, logit_scale, agg, normalize):
     return feats.new_empty((B, T, K)), feats.new_empty((B, K)), feats.new_empty((B, K))
 
 
+def _f32c(t):
+    return None if t is None else t.float().contiguous()
+
+
+@custom_op(f'{NAMESPACE}::classify_bwd', mutates_args=(), device_types='cuda')
+def classify_bwd(feats: torch.Tensor, row_idx: torch.Tensor, text_t: torch.Tensor, full_logits: torch.Tensor,
+                 d_full_logits: Optional[torch.Tensor], d_logits: Optional[torch.Tensor], d_probs: Optional[torch.Tensor],
+                 logit_scale: float, agg: int, normalize: bool, need_feats: bool,
+                 need_text: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The vector-Jacobian product of ``classify``: (d_feats [Nv, C], d_text_t [C, K]); an upstream gradient that is
+    None is zero, a gradient that is not needed comes back as an empty tensor and costs no launch."""
+    B, T = row_idx.shape
+    C, K = text_t.shape
+    n_rows = int(feats.shape[0])
+    feats, text_t, full_logits = _f32c(feats), _f32c(text_t), _f32c(full_logits)
+    row_idx = row_idx.contiguous()
+    ups = [_f32c(g) for g in (d_full_logits, d_logits, d_probs)]
+    d_feats = torch.empty((n_rows, C) if need_feats else (0,), dtype=torch.float32, device=feats.device)
+    d_text = torch.empty((C, K) if need_text else (0,), dtype=torch.float32, device=feats.device)
+    ws = torch.empty(max(int(_lib.lib().ec_classify_backward_workspace_bytes(B, T, C, K)), 256), dtype=torch.uint8,
+                     device=feats.device)
+    rc = _lib.lib().ec_classify_backward(_lib.ptr(feats), n_rows, _lib.ptr(row_idx), _lib.ptr(text_t), B, T, C, K,
+                                         logit_scale, agg, int(normalize), _lib.ptr(full_logits), _lib.ptr(ups[0]),
+                                         _lib.ptr(ups[1]), _lib.ptr(ups[2]), _lib.ptr(d_feats) if need_feats else None,
+                                         _lib.ptr(d_text) if need_text else None, _lib.ptr(ws), ws.numel(),
+                                         _lib.stream_ptr())
+    _lib.check(rc, 'ec_classify_backward')
+    return d_feats, d_text
+
+
+@classify_bwd.register_fake
+def _(feats, row_idx, text_t, full_logits, d_full_logits, d_logits, d_probs, logit_scale, agg, normalize, need_feats,
+      need_text):
+    return (feats.new_empty(tuple(feats.shape) if need_feats else (0,), dtype=torch.float32),
+            feats.new_empty(tuple(text_t.shape) if need_text else (0,), dtype=torch.float32))
+
+
+def _classify_setup(ctx, inputs, output):
+    feats, row_idx, text_t, logit_scale, agg, normalize = inputs
+    ctx.save_for_backward(feats, row_idx, text_t, output[0])
+    ctx.tail = (logit_scale, agg, normalize)
+    ctx.set_materialize_grads(False)          # an output the loss does not use sends None, not a tensor of zeros
+
+
+def _classify_backward(ctx, d_full_logits, d_logits, d_probs):
+    feats, row_idx, text_t, full_logits = ctx.saved_tensors
+    need_feats, need_text = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+    d_feats, d_text = torch.ops.eventclip_hip.classify_bwd(feats, row_idx, text_t, full_logits, d_full_logits, d_logits,
+                                                           d_probs, *ctx.tail, need_feats, need_text)
+    return d_feats if need_feats else None, None, d_text if need_text else None, None, None, None
+
+
+classify.register_autograd(_classify_backward, setup_context=_classify_setup)
+
+
+# ---- the transformer adapter under autograd: forward and backward as two ops with a tape between them ----
+_ADAPTER_LAYER_PARAMS = ('self_attn.in_proj_weight', 'self_attn.in_proj_bias', 'self_attn.out_proj.weight',
+                         'self_attn.out_proj.bias', 'linear1.weight', 'linear1.bias', 'linear2.weight', 'linear2.bias',
+                         'norm1.weight', 'norm1.bias', 'norm2.weight', 'norm2.bias')
+
+
+def adapter_param_names(layers):
+    """``TransformerAdapter.named_parameters()`` order: the order of the ``params`` list of the two ops below."""
+    return [f'transformer_encoder.layers.{i}.{n}' for i in range(layers) for n in _ADAPTER_LAYER_PARAMS] + \
+        ['in_proj.weight', 'in_proj.bias', 'out_proj.weight', 'out_proj.bias']
+
+
+class _Geometry:
+    def __init__(self, in_dim, d_model, heads, ffn_dim, layers, residual):
+        self.in_dim, self.d_model, self.num_heads, self.ffn_dim = in_dim, d_model, heads, ffn_dim
+        self.num_layers, self.residual = layers, residual
+
+
+def _train_struct(params, geo):
+    from .train import _adapter_struct
+    names = adapter_param_names(geo.num_layers)
+    if len(params) != len(names):
+        raise RuntimeError(f'{NAMESPACE}: {len(params)} adapter parameters, {len(names)} expected (named_parameters() order)')
+    return _adapter_struct(geo, dict(zip(names, params)))
+
+
+@custom_op(f'{NAMESPACE}::adapter_train_fwd', mutates_args=(), device_types='cuda')
+def adapter_train_fwd(feats: torch.Tensor, row_idx: torch.Tensor, params: List[torch.Tensor], d_model: int, heads: int,
+                      ffn_dim: int, layers: int, residual: float, dropout_p: float,
+                      seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """feats fp32 [B * T, C] with zero rows on invalid views, row_idx int32 [B, T] (< 0 = invalid view), params the
+    adapter's parameters in ``adapter_param_names`` order -> (out [B, T, C], the residual mix of adapter.py:22-25;
+    tape uint8 [n]: the saved activations ``adapter_train_bwd`` reads)."""
+    B, T = row_idx.shape
+    C = int(feats.shape[-1])
+    if tuple(feats.shape) != (B * T, C):
+        raise RuntimeError(f'{NAMESPACE}::adapter_train_fwd: feats {tuple(feats.shape)} is not [B * T = {B * T}, C]')
+    feats = _f32c(feats)
+    params = [_f32c(p) for p in params]
+    w, keep = _train_struct(params, _Geometry(C, d_model, heads, ffn_dim, layers, residual))   # noqa: F841 (alive over the call)
+    valid = (row_idx >= 0).to(torch.uint8).contiguous()
+    out = torch.empty((B, T, C), dtype=torch.float32, device=feats.device)
+    need = int(_lib.lib().ec_adapter_train_tape_bytes(B, T, C, d_model, ffn_dim, heads, layers))
+    tape = torch.zeros((max(need, 256),), dtype=torch.uint8, device=feats.device)   # its alignment gaps too: an output
+    rc = _lib.lib().ec_adapter_train_forward(_lib.ptr(feats), _lib.ptr(valid), B, T, ctypes.byref(w), dropout_p, seed,
+                                             _lib.ptr(out), _lib.ptr(tape), tape.numel(), _lib.stream_ptr())
+    _lib.check(rc, 'ec_adapter_train_forward')
+    return out, tape
+
+
+def _tape_numel(B, T, C, d_model, heads, ffn_dim, layers):
+    """ec_adapter_train_tape_bytes restated for the fake kernel (no library call while tracing)."""
+    R, up = B * T, lambda n: (n * 4 + 255) // 256 * 256
+    per_layer = 6 * up(R * d_model) + 2 * up(R) + up(R * 3 * d_model) + up(B * heads * T * T) + up(R * ffn_dim)
+    return max(3 * up(R * d_model) + up(R * C) + layers * per_layer, 256)
+
+
+@adapter_train_fwd.register_fake
+def _(feats, row_idx, params, d_model, heads, ffn_dim, layers, residual, dropout_p, seed):
+    B, T = row_idx.shape
+    C = feats.shape[-1]
+    return (feats.new_empty((B, T, C), dtype=torch.float32),
+            feats.new_empty((_tape_numel(B, T, C, d_model, heads, ffn_dim, layers),), dtype=torch.uint8))
+
+
+@custom_op(f'{NAMESPACE}::adapter_train_bwd', mutates_args=(), device_types='cuda')
+def adapter_train_bwd(feats: torch.Tensor, row_idx: torch.Tensor, params: List[torch.Tensor], tape: torch.Tensor,
+                      d_out: torch.Tensor, d_model: int, heads: int, ffn_dim: int, layers: int, residual: float,
+                      dropout_p: float, seed: int, need_mask: int) -> List[torch.Tensor]:
+    """The backward of ``adapter_train_fwd`` over its tape (only read: a second call gives the same bits).  Returns
+    len(params) + 1 tensors: the gradient of params[i] where bit i of need_mask is set, d_feats [B * T, C] where bit
+    len(params) is set, an empty tensor (and no launch) otherwise."""
+    B, T = row_idx.shape
+    C = int(feats.shape[-1])
+    feats, d_out = _f32c(feats), _f32c(d_out)
+    params = [_f32c(p) for p in params]
+    n = len(params)
+    grads = [torch.empty_like(p) if need_mask >> i & 1 else None for i, p in enumerate(params)]
+    d_feats = torch.empty_like(feats) if need_mask >> n & 1 else None
+    geo = _Geometry(C, d_model, heads, ffn_dim, layers, residual)
+    w, keep_w = _train_struct(params, geo)      # noqa: F841
+    g, keep_g = _train_struct(grads, geo)       # noqa: F841
+    ws = torch.empty((max(int(_lib.lib().ec_adapter_train_backward_workspace_bytes(B, T, C, d_model, ffn_dim)), 256),),
+                     dtype=torch.uint8, device=feats.device)
+    rc = _lib.lib().ec_adapter_train_backward(_lib.ptr(feats), B, T, ctypes.byref(w), dropout_p, seed, _lib.ptr(tape),
+                                              tape.numel(), _lib.ptr(d_out), ctypes.byref(g), _lib.ptr(d_feats),
+                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    _lib.check(rc, 'ec_adapter_train_backward')
+    empty = feats.new_empty((0,))
+    return [empty.clone() if t is None else t for t in grads + [d_feats]]
+
+
+@adapter_train_bwd.register_fake
+def _(feats, row_idx, params, tape, d_out, d_model, heads, ffn_dim, layers, residual, dropout_p, seed, need_mask):
+    like = list(params) + [feats]
+    return [feats.new_empty(tuple(t.shape) if need_mask >> i & 1 else (0,), dtype=torch.float32)
+            for i, t in enumerate(like)]
+
+
+def _adapter_setup(ctx, inputs, output):
+    feats, row_idx, params = inputs[:3]
+    ctx.save_for_backward(feats, row_idx, output[1], *params)
+    ctx.tail = tuple(inputs[3:])
+    ctx.mark_non_differentiable(output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _adapter_backward(ctx, d_out, d_tape):
+    feats, row_idx, tape, *params = ctx.saved_tensors
+    n = len(params)
+    need = list(ctx.needs_input_grad[2]) + [ctx.needs_input_grad[0]]
+    if d_out is None or not any(need):
+        return (None, None, [None] * n) + (None,) * 7
+    mask = sum(1 << i for i, b in enumerate(need) if b)
+    got = torch.ops.eventclip_hip.adapter_train_bwd(feats, row_idx, params, tape, d_out, *ctx.tail, mask)
+    grads = [t if b else None for t, b in zip(got, need)]
+    return (grads[n], None, grads[:n]) + (None,) * 7
+
+
+adapter_train_fwd.register_autograd(_adapter_backward, setup_context=_adapter_setup)
+
+
 @custom_op(f'{NAMESPACE}::resnet_encode', mutates_args=(), device_types='cuda')
 def resnet_encode(inp: torch.Tensor, input_mode: int, clip_handle: int) -> torch.Tensor:
     """ResNet image tower: fp32 [N, 3, R, R] (EC_PRE_CHW_F32) or uint8 [N, R, R, 3] (EC_PRE_HWC_U8) -> fp32 [N, D].
@@ -281,4 +466,5 @@ def _(inp, input_mode, clip_handle):
     return inp.new_empty((inp.shape[0], _resolve(clip_handle, 'resnet_encode').cfg['embed_dim']), dtype=torch.float32)
 
 
-OPS = ('events_to_frames', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode')
+OPS = ('events_to_frames', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode',
+       'classify_bwd', 'adapter_train_fwd', 'adapter_train_bwd')

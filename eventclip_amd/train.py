@@ -55,8 +55,13 @@ _LAYER_FIELDS = (('ln1_g', 'norm1.weight'), ('ln1_b', 'norm1.bias'), ('qkv_w', '
 
 
 def _adapter_struct(adapter, tensors):
-    """ec_adapter_train_params over `tensors` (name -> fp32 CUDA tensor, the adapter's state-dict names)."""
+    """ec_adapter_train_params over `tensors` (name -> fp32 CUDA tensor, the adapter's state-dict names; None -> NULL,
+    a gradient the split backward skips)."""
     import ctypes
+
+    class _Null:
+        data_ptr = staticmethod(lambda: None)
+    tensors = {k: _Null if v is None else v for k, v in tensors.items()}
     layers = (_lib.EcAdapterTrainLayer * adapter.num_layers)()
     for i in range(adapter.num_layers):
         for field, name in _LAYER_FIELDS:

@@ -51,12 +51,14 @@ EC_API const char *ec_last_error(void);
  *   601  + ec_vit_train_layout (additive: no struct or argument list changed)
  *   602  ec_resnet_conv_w + w_lo, ec_resnet_weights + precise_blocks (the ResNet towers' split-precision form); + the
  *        ec_resnet_*_hl entry points
+ *   603  + ec_classify_backward, ec_adapter_train_forward / _backward and their size functions (additive: no struct or
+ *        argument list changed)
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does, with its ctypes mirrors.) */
-#define EC_ABI_VERSION 602
+#define EC_ABI_VERSION 603
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);
@@ -739,6 +741,40 @@ EC_API int ec_fs_trans_loss_grad(const float *img_feats, const uint8_t *valid, c
                                  ec_stream_t stream);
 EC_API int ec_dropout_mask(uint64_t seed, uint32_t site, int64_t n, float p, uint8_t *mask,
                            ec_stream_t stream);
+
+/* The forward half and the backward half of ec_fs_trans_loss_grad's adapter as two calls with a caller-owned tape between
+ * them (torch autograd: eventclip_hip::adapter_train_fwd / adapter_train_bwd) -- the same kernels in the same order.
+ *   forward   img_feats fp32 [B, T, in_dim] with ZERO rows on invalid views, valid uint8 [B, T] -> out [B, T, in_dim],
+ *             the residual mix r * img_feats + (1 - r) * out_proj(encoder(in_proj(img_feats))) (adapter.py:22-25), and
+ *             the saved activations in tape (ec_adapter_train_tape_bytes, 256-byte aligned).
+ *   backward  d_out [B, T, in_dim] -> the parameter gradients into `grads` (a NULL pointer there skips that gradient
+ *             and its launch; `blocks` must be a host array) and, when d_img_feats is not NULL, d loss / d img_feats.
+ *             params, img_feats, dropout_p and dropout_seed are the forward's.  The tape is only read: everything
+ *             the backward overwrites lives in workspace (ec_adapter_train_backward_workspace_bytes), so a second
+ *             backward over the same tape gives the same bits. */
+EC_API size_t ec_adapter_train_tape_bytes(int B, int T, int D, int d_model, int ffn_dim, int heads, int layers);
+EC_API size_t ec_adapter_train_backward_workspace_bytes(int B, int T, int D, int d_model, int ffn_dim);
+EC_API int ec_adapter_train_forward(const float *img_feats, const uint8_t *valid, int B, int T,
+                                    const ec_adapter_train_params *params, float dropout_p, uint64_t dropout_seed,
+                                    float *out, void *tape, size_t tape_bytes, ec_stream_t stream);
+EC_API int ec_adapter_train_backward(const float *img_feats, int B, int T, const ec_adapter_train_params *params,
+                                     float dropout_p, uint64_t dropout_seed, const void *tape, size_t tape_bytes,
+                                     const float *d_out, const ec_adapter_train_params *grads, float *d_img_feats,
+                                     void *workspace, size_t workspace_bytes, ec_stream_t stream);
+
+/* The vector-Jacobian product of ec_classify_v2 with respect to feats and text_t, fp32 throughout.
+ *   feats [n_rows, C], row_idx [B, T], text_t [C, K] (the fp32 tensor, not the prepared planes), logit_scale, agg,
+ *   normalize: the forward's arguments;  full_logits [B, T, K]: the forward's output.
+ *   d_full_logits [B, T, K], d_logits [B, K], d_probs [B, K]: upstream gradients, each may be NULL (= zero).
+ *   d_feats [n_rows, C], d_text_t [C, K]: outputs, each may be NULL (skipped).  Rows of feats that no valid view names
+ *   get exact zeros; a view is valid iff 0 <= row_idx < n_rows, and two views must not name the same row.
+ * T <= 16, C a multiple of 4, K >= 2; EC_AGG_MAX sends d_logits to the maximal valid view, the lowest index on a tie.
+ * workspace: ec_classify_backward_workspace_bytes(B, T, C, K) bytes, 256-byte aligned. */
+EC_API size_t ec_classify_backward_workspace_bytes(int B, int T, int C, int K);
+EC_API int ec_classify_backward(const float *feats, int n_rows, const int32_t *row_idx, const float *text_t, int B, int T,
+                                int C, int K, float logit_scale, int agg, int normalize, const float *full_logits,
+                                const float *d_full_logits, const float *d_logits, const float *d_probs, float *d_feats,
+                                float *d_text_t, void *workspace, size_t workspace_bytes, ec_stream_t stream);
 
 /* C[M, N] (row stride ldc) = alpha * sum_k A(m, k) B(k, n) + beta * C with A(m, k) = A[m * sam + k * sak],
  * B(k, n) = B[k * sbk + n * sbn]: fp32, any layout, for the SMALL products around the towers (LoRA factors

@@ -8,7 +8,12 @@ views T, D = 768.
 One JSON line per (adapter type, geometry): ms per step and samples/s, and `cpu_baseline`: the oracle's step (loss +
 gradients in float64 -- numpy for `text-identity`, torch CPU autograd over the explicit forward for `text-trans` --
 plus its numpy Adam over every trained tensor) on the same batch, on the box's host cores.  Synthetic features,
-seeded weights.  The CPU leg is the only place the oracle is touched."""
+seeded weights.  The CPU leg is the only place the oracle is touched.
+
+Next to each fused step, `autograd`: the same batch through the reference's own loop -- `out = clf(data)`,
+`clf.calc_train_loss(data, out)['ce_loss'].backward()`, `torch.optim.Adam.step()` -- with the cached features standing
+in for the frozen encoder: ms per step, and the step's three parts timed on their own with a device sync after each
+(their sum exceeds the step: the syncs keep host and device from overlapping)."""
 import argparse
 import json
 import os
@@ -43,6 +48,53 @@ def cpu_step(kind, clf, feats, valid, labels, repeat=3):
         best = min(best, time.perf_counter() - t0)
     return dict(ms_per_step=round(best * 1e3, 2), kind='port', dtype='float64', threads=torch.get_num_threads(),
                 sample='the same batch, best of %d steps' % repeat)
+
+
+def autograd_step_ms(clf, feats, valid, labels, steps):
+    """forward + calc_train_loss + backward + torch.optim.Adam on the cached features (dropout as in training)."""
+    flat = valid.reshape(-1)
+    row_idx = torch.where(flat, torch.cumsum(flat.int(), 0) - 1, torch.full_like(flat, -1, dtype=torch.int64))
+    row_idx = row_idx.to(torch.int32).reshape(valid.shape)
+    compact = feats[valid].contiguous()
+    clf._view_feats = lambda data_dict: (compact, row_idx, valid)          # the frozen encoder's cached outputs
+    clf.train()
+    opt = torch.optim.Adam([p for p in clf.parameters() if p.requires_grad], lr=2e-5)
+    data = {'valid_mask': valid, 'label': labels}
+    parts = dict(forward_loss=0., backward=0., optimizer=0.)
+
+    def step(timed):
+        t = [time.perf_counter()]
+
+        def lap():
+            if timed:
+                torch.cuda.synchronize()
+                t.append(time.perf_counter())
+        opt.zero_grad(set_to_none=True)
+        loss = clf.calc_train_loss(data, clf(data))['ce_loss']
+        lap()
+        loss.backward()
+        lap()
+        opt.step()
+        lap()
+        if timed:
+            for k, a, b in zip(parts, t, t[1:]):
+                parts[k] += b - a
+        return loss
+
+    for _ in range(5):
+        step(False)
+    torch.cuda.synchronize()
+    dt = float('inf')
+    for _ in range(2):
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            loss = step(False)
+        torch.cuda.synchronize()
+        dt = min(dt, (time.perf_counter() - t0) / steps)
+    for _ in range(steps):
+        step(True)
+    return dict(ms_per_step=round(dt * 1e3, 3), loss=round(float(loss.detach()), 4), tensors=len(opt.param_groups[0]['params']),
+                synced_parts_ms={k: round(v / steps * 1e3, 3) for k, v in parts.items()})
 
 
 def main():
@@ -86,13 +138,14 @@ def main():
                     worst = max(worst, time.perf_counter() - t1)
                 torch.cuda.synchronize()
                 dt = min(dt, (time.perf_counter() - t0) / a.steps)
-            cases.append((kind, name, B, T, K, dt, float(loss), clf, feats, valid, labels, worst))
-    for kind, name, B, T, K, dt, loss, clf, feats, valid, labels, worst in cases:
+            ag = autograd_step_ms(clf, feats, valid, labels, a.steps)
+            cases.append((kind, name, B, T, K, dt, float(loss), clf, feats, valid, labels, worst, ag))
+    for kind, name, B, T, K, dt, loss, clf, feats, valid, labels, worst, ag in cases:
         cb = cpu_step(kind, clf, feats, valid, labels)
         cb['speedup'] = round(cb['ms_per_step'] / (dt * 1e3), 1)
         print(json.dumps(dict(adapter_type=kind, geometry=name, batch=B, views=T, classes=K,
                               ms_per_step=round(dt * 1e3, 3), samples_per_s=round(B / dt, 1),
-                              loss=round(loss, 4), slowest_call_ms=round(worst * 1e3, 3), cpu_baseline=cb)), flush=True)
+                              loss=round(loss, 4), slowest_call_ms=round(worst * 1e3, 3), autograd=ag, cpu_baseline=cb)), flush=True)
 
 
 if __name__ == '__main__':
