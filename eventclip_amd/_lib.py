@@ -4,7 +4,11 @@ There is no CPU fallback: if the library is missing or no MI355X is visible the
 callers raise.  torch is used only to own device memory and streams.
 """
 import ctypes
+import math
 import os
+
+import numpy as np
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EVENTCLIP_HIP_LIB: tools/ point it at libeventclip_hip_diag.so (python -m eventclip_amd.build --diag),
@@ -356,7 +360,6 @@ def lib():
         # libamdhip64.so.7).  Load it first so that this library's NEEDED entry
         # binds to the same runtime instead of pulling a second copy from
         # /opt/rocm, whose streams and device state torch would not share.
-        import torch
         bundled = os.path.join(os.path.dirname(torch.__file__), 'lib', 'libamdhip64.so')
         if os.path.exists(bundled):
             ctypes.CDLL(bundled, mode=ctypes.RTLD_GLOBAL)
@@ -384,7 +387,6 @@ def check(rc, what=''):
 
 def require_gpu():
     """The device every op runs on; raises when there is none."""
-    import torch
     if not torch.cuda.is_available():
         raise HipLibraryError('eventclip_amd needs an MI355X (gfx950) device: '
                               'torch.cuda.is_available() is False and there is no CPU fallback.')
@@ -392,15 +394,71 @@ def require_gpu():
 
 
 def stream_ptr():
-    import torch
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def ptr(t):
-    """Device pointer of a torch tensor (None -> NULL)."""
+    """Device pointer of a torch tensor (None -> NULL), for tests and tools that call the ABI directly; code in this
+    package passes the tensor itself to ``launch``, which also keeps it alive over the call."""
     if t is None:
         return None
     return ctypes.c_void_p(t.data_ptr())
+
+
+_PLAIN = frozenset({int, float, type(None)})
+
+
+def launch(name, *args):
+    """Call the stream-taking entry ``name`` on torch's current stream and raise under its name when it fails.
+    A tensor goes as its device pointer, None as NULL, a ctypes Structure by reference, anything else (a ``byref``,
+    a scalar, a host address) as it is.  ``args`` holds every tensor until the call has returned, so temporaries are
+    safe to pass; the arrays behind a struct's pointer FIELDS are raw addresses and stay the caller's to keep."""
+    conv = []
+    for a in args:
+        if type(a) in _PLAIN:                     # most of any argument list: told by exact type, before the isinstance tests
+            pass
+        elif isinstance(a, torch.Tensor):
+            a = a.data_ptr()
+        elif isinstance(a, ctypes.Structure):
+            a = ctypes.byref(a)
+        conv.append(a)
+    check(getattr(lib(), name)(*conv, stream_ptr()), name)
+
+
+def scratch(nbytes, device):
+    """A fresh uint8 device buffer of at least ``nbytes`` (never empty: the kernels want a real pointer)."""
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
+class Scratch:
+    """Grow-only uint8 device buffer, reused from call to call: ``get`` reallocates only for more bytes or another
+    device, and drops the old block first so the two never coexist.  ``device`` must carry its index (``require_gpu()``,
+    ``tensor.device``): a bare ``torch.device('cuda')`` never equals the buffer's device and would reallocate every call."""
+
+    def __init__(self):
+        self.buf = None
+
+    def get(self, nbytes, device):
+        if self.buf is None or self.buf.numel() < nbytes or self.buf.device != device:
+            self.buf = None
+            self.buf = torch.empty((int(nbytes),), dtype=torch.uint8, device=device)
+        return self.buf
+
+
+def device_table(items):
+    """ctypes array of structs -> device copy (uint8 CUDA tensor) for the batched kernels' item tables."""
+    return torch.from_numpy(np.frombuffer(items, dtype=np.uint8).copy()).cuda()
+
+
+def flat_views(shapes, device, min_numel=0):
+    """{name: shape} -> (flat, {name: view}): one zeroed fp32 buffer (a single all-reduce / unscale covers it) and a
+    view of it per name, laid out in mapping order; views[name].storage_offset() is the name's offset in ``flat``."""
+    flat = torch.zeros((max(sum(math.prod(s) for s in shapes.values()), min_numel),), dtype=torch.float32, device=device)
+    views, off = {}, 0
+    for name, shape in shapes.items():
+        views[name] = flat[off:off + math.prod(shape)].view(tuple(shape))
+        off += math.prod(shape)
+    return flat, views
 
 
 def profile_begin():

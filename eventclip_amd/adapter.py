@@ -6,6 +6,10 @@ checkpoints written by the reference's trainer load key for key; those modules a
 parameter holders only -- ``forward`` runs ``ec_adapter_forward`` (fp32, the fused inference kernel) in eval mode
 or with grad disabled, and the differentiable ``eventclip_hip::adapter_train_fwd`` (``ec_adapter_train_forward`` /
 ``_backward``, with the encoder layers' dropout of 0.1) in train mode with grad enabled.
+
+The map from a parameter to its C struct field (``LAYER_PARAMS`` / ``PROJ_PARAMS``, ``adapter_param_names``,
+``_adapter_struct``) lives here, next to the module whose ``named_parameters()`` order it restates; ``train`` and
+``torch_ops`` import it from here, which is why this module reaches ``torch_ops`` only inside its methods.
 """
 import ctypes
 
@@ -51,6 +55,56 @@ def _scatter(feats, row_idx):
     valid = row_idx >= 0
     full[valid] = feats[row_idx[valid].long()]
     return full, valid
+
+
+def compact_row_idx(valid):
+    """valid bool [B, T] -> int32 [B, T]: a valid view's rank among the valid views (its row in a compact [Nv, C]
+    feature matrix), -1 on padded views."""
+    flat = valid.reshape(-1)
+    idx = torch.where(flat, torch.cumsum(flat.int(), 0) - 1, torch.full_like(flat, -1, dtype=torch.int64))
+    return idx.to(torch.int32).reshape(valid.shape)
+
+
+def dense_row_idx(valid):
+    """valid bool [B, T] -> int32 [B, T]: a valid view's own position b * T + t (its row in the [B * T, C] matrix with
+    zero rows on padded views), -1 on padded views."""
+    B, T = valid.shape
+    return torch.where(valid, torch.arange(B * T, device=valid.device).view(B, T),
+                       torch.full((B, T), -1, device=valid.device)).to(torch.int32)
+
+
+# The parameters of one encoder layer in ``named_parameters()`` order: (leaf under transformer_encoder.layers.{i}., field
+# of EcAdapterTrainLayer, is it a matrix -- EcAdapterLayer, the inference struct, reads the transposed copy ``<field>_t``).
+# The four projection tensors follow the layers: (leaf, field of EcAdapterTrainParams, matrix).
+LAYER_PARAMS = (('self_attn.in_proj_weight', 'qkv_w', True), ('self_attn.in_proj_bias', 'qkv_b', False),
+                ('self_attn.out_proj.weight', 'o_w', True), ('self_attn.out_proj.bias', 'o_b', False),
+                ('linear1.weight', 'w1', True), ('linear1.bias', 'b1', False),
+                ('linear2.weight', 'w2', True), ('linear2.bias', 'b2', False),
+                ('norm1.weight', 'ln1_g', False), ('norm1.bias', 'ln1_b', False),
+                ('norm2.weight', 'ln2_g', False), ('norm2.bias', 'ln2_b', False))
+PROJ_PARAMS = (('in_proj.weight', 'in_w', True), ('in_proj.bias', 'in_b', False),
+               ('out_proj.weight', 'out_w', True), ('out_proj.bias', 'out_b', False))
+
+
+def adapter_param_names(layers):
+    """``TransformerAdapter.named_parameters()`` order: the order of the ``params`` list of the two training ops."""
+    return [f'transformer_encoder.layers.{i}.{leaf}' for i in range(layers) for leaf, _, _ in LAYER_PARAMS] + \
+        [leaf for leaf, _, _ in PROJ_PARAMS]
+
+
+def _adapter_struct(tensors, in_dim, d_model, heads, ffn_dim, layers, residual):
+    """EcAdapterTrainParams over ``tensors`` (fp32 CUDA tensors in ``adapter_param_names`` order; None -> NULL, a
+    gradient the split backward skips) -> (struct, the layer array its ``blocks`` points to)."""
+    tensors = iter(tensors)
+    blocks = (_lib.EcAdapterTrainLayer * layers)()
+    p = _lib.EcAdapterTrainParams()
+    p.in_dim, p.d_model, p.heads, p.ffn_dim, p.layers, p.residual = in_dim, d_model, heads, ffn_dim, layers, float(residual)
+    for dst, table in [(b, LAYER_PARAMS) for b in blocks] + [(p, PROJ_PARAMS)]:
+        for _, field, _ in table:
+            t = next(tensors)
+            setattr(dst, field, None if t is None else t.data_ptr())
+    p.blocks = ctypes.cast(blocks, ctypes.POINTER(_lib.EcAdapterTrainLayer))
+    return p, blocks
 
 
 class IdentityAdapter(Adapter):
@@ -121,19 +175,13 @@ class TransformerAdapter(Adapter):
             return t.data_ptr()
 
         layers = (_lib.EcAdapterLayer * self.num_layers)()
-        for i, lyr in enumerate(self.transformer_encoder.layers):
-            e = layers[i]
-            e.ln1_g, e.ln1_b = d(lyr.norm1.weight), d(lyr.norm1.bias)
-            e.qkv_w_t, e.qkv_b = d(lyr.self_attn.in_proj_weight, True), d(lyr.self_attn.in_proj_bias)
-            e.o_w_t, e.o_b = d(lyr.self_attn.out_proj.weight, True), d(lyr.self_attn.out_proj.bias)
-            e.ln2_g, e.ln2_b = d(lyr.norm2.weight), d(lyr.norm2.bias)
-            e.w1_t, e.b1 = d(lyr.linear1.weight, True), d(lyr.linear1.bias)
-            e.w2_t, e.b2 = d(lyr.linear2.weight, True), d(lyr.linear2.bias)
         w = _lib.EcAdapterWeights()
         w.in_dim, w.d_model, w.heads, w.ffn = self.in_dim, self.d_model, self.num_heads, self.ffn_dim
         w.layers, w.residual = self.num_layers, float(self.residual)
-        w.in_w_t, w.in_b = d(self.in_proj.weight, True), d(self.in_proj.bias)
-        w.out_w_t, w.out_b = d(self.out_proj.weight, True), d(self.out_proj.bias)
+        for dst, mod, table in [(e, m, LAYER_PARAMS) for e, m in zip(layers, self.transformer_encoder.layers)] + \
+                [(w, self, PROJ_PARAMS)]:
+            for leaf, field, matrix in table:
+                setattr(dst, field + ('_t' if matrix else ''), d(mod.get_parameter(leaf), matrix))
         w.layer = ctypes.cast(layers, ctypes.POINTER(_lib.EcAdapterLayer))
         self._packed = dict(w=w, layers=layers, keep=keep, key=key)
         return self._packed
@@ -151,9 +199,9 @@ class TransformerAdapter(Adapter):
         padded) -> [B, T, C], with autograd into every parameter that requires grad (and into ``rows``).  Dropout is
         ``TRAIN_DROPOUT`` while this module is in train mode, seeded once per call from torch's default generator
         (``torch.manual_seed`` reproduces a run), else 0: the deterministic eval-mode function."""
-        from . import torch_ops
+        from . import torch_ops  # noqa: F401  (registers eventclip_hip::adapter_train_fwd)
         names = [n for n, _ in self.named_parameters()]
-        assert names == torch_ops.adapter_param_names(self.num_layers), names
+        assert names == adapter_param_names(self.num_layers), names
         p = self.TRAIN_DROPOUT if self.training else 0.
         seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0. else 0
         out, _ = torch.ops.eventclip_hip.adapter_train_fwd(rows.contiguous(), idx.contiguous(), list(self.parameters()),
@@ -165,8 +213,7 @@ class TransformerAdapter(Adapter):
         """feats [B, T, C], valid_masks [B, T] (True = valid view), as adapter.py:82-105.
         Padded views must hold zeros, which is what the reference's classifier passes."""
         B, T, C = feats.shape
-        idx = torch.where(valid_masks, torch.arange(B * T, device=feats.device).view(B, T),
-                          torch.full((B, T), -1, device=feats.device)).to(torch.int32)
+        idx = dense_row_idx(valid_masks)
         if self.training and torch.is_grad_enabled():
             return self.train_rows(feats.float().reshape(B * T, C), idx)
         return self.forward_rows(feats.reshape(B * T, C), idx)

@@ -36,9 +36,7 @@ def augment_events_device(events, n_events, params, resolution):
     out = torch.empty_like(events)
     counts = torch.empty((B,), dtype=torch.int64, device=dev)
     H, W = resolution
-    rc = _lib.lib().ec_augment_events(_lib.ptr(events), _lib.ptr(sr), B, _lib.ptr(prm), int(H), int(W),
-                                      _lib.ptr(out), _lib.ptr(counts), _lib.stream_ptr())
-    _lib.check(rc, 'ec_augment_events')
+    _lib.launch('ec_augment_events', events, sr, B, prm, int(H), int(W), out, counts)
     return out, counts.cpu().tolist(), offs[:-1].tolist()
 
 

@@ -339,9 +339,7 @@ class CLIP(ClipBase):
         n = img.shape[0]
         patches = torch.empty((n, (R // P) ** 2, pk['kpad']), dtype=self.compute_dtype,
                               device=pk['dev'])
-        rc = _lib.lib().ec_patchify(_lib.ptr(img), n, R, P, pk['kpad'], _lib.ptr(patches),
-                                    pk['code'], _lib.stream_ptr())
-        _lib.check(rc, 'ec_patchify')
+        _lib.launch('ec_patchify', img, n, R, P, pk['kpad'], patches, pk['code'])
         return self.encode_patches(patches)
 
 

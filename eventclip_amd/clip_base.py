@@ -172,7 +172,7 @@ class ClipBase(nn.Module):
                               'bfloat16': torch.bfloat16, 'bf16': torch.bfloat16}[str(dtype)]
         self.chunk = int(chunk)        # images per pass through the tower (bounds the activation workspace)
         self._packed = None
-        self._ws = None
+        self._ws = _lib.Scratch()      # the towers' activation workspace
 
     # ---- protocol bits the reference's classifiers read ----
     @property
@@ -185,7 +185,7 @@ class ClipBase(nn.Module):
 
     def _apply(self, fn, *a, **k):
         self._packed = None          # .cuda() / .to(): repack lazily
-        self._ws = None
+        self._ws.buf = None
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, sd, strict=True):
@@ -198,11 +198,6 @@ class ClipBase(nn.Module):
             raise _lib.HipLibraryError('CLIP weights are on the CPU: call model.cuda() first '
                                        '(there is no CPU fallback)')
         return dev
-
-    def _workspace(self, nbytes, dev):
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        return self._ws
 
     @torch.no_grad()
     def encode_text(self, text):

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import clip as eclip
-from .adapter import IdentityAdapter, TransformerAdapter
+from .adapter import IdentityAdapter, TransformerAdapter, compact_row_idx, dense_row_idx
 
 _AGG = {'sum': _lib.EC_AGG_SUM, 'mean': _lib.EC_AGG_MEAN, 'max': _lib.EC_AGG_MAX}
 
@@ -126,10 +126,7 @@ class ZSCLIPClassifier(nn.Module):
             imgs = data_dict['img']                                      # [B, T, C, H, W]
             valid_imgs = imgs[valid_masks]                               # clip_cls.py:139
             feats = self.get_img_feats(valid_imgs)
-            flat = valid_masks.reshape(-1)
-            row_idx = torch.where(flat, torch.cumsum(flat.int(), 0) - 1,
-                                  torch.full_like(flat, -1, dtype=torch.int64))
-            row_idx = row_idx.to(torch.int32).reshape(valid_masks.shape)
+            row_idx = compact_row_idx(valid_masks)
         return feats.float().contiguous(), row_idx.contiguous(), valid_masks
 
     def _classify(self, feats, row_idx, normalize, text_t=None):
@@ -254,10 +251,8 @@ class FSCLIPClassifier(ZSCLIPClassifier):
         # scatter to [B, T, C] with zero rows for padded views (:319-321), adapter (:322)
         full_img_feats = self.adapter.forward_rows(feats, row_idx)       # [B, T, C] fp32
         # F.normalize + mask + logits + aggregation (:326-343) in ec_classify
-        idx = torch.where(valid_masks, torch.arange(B * T, device=feats.device).view(B, T),
-                          torch.full((B, T), -1, device=feats.device)).to(torch.int32)
         full_logits, logits, probs = self._classify(full_img_feats.reshape(B * T, C).contiguous(),
-                                                    idx.contiguous(), normalize=True)
+                                                    dense_row_idx(valid_masks), normalize=True)
         return dict(full_logits=full_logits, valid_masks=valid_masks, logits=logits, probs=probs)
 
     def _forward_train(self, data_dict):
@@ -269,8 +264,7 @@ class FSCLIPClassifier(ZSCLIPClassifier):
             B, T = valid_masks.shape
             C = feats.shape[-1]
             rows = IdentityAdapter.forward_rows(None, feats.float(), row_idx).reshape(B * T, C)
-            idx = torch.where(valid_masks, torch.arange(B * T, device=feats.device).view(B, T),
-                              torch.full((B, T), -1, device=feats.device)).to(torch.int32).contiguous()
+            idx = dense_row_idx(valid_masks)
         if self.adapter_type == 'trans':
             rows = self.adapter.train_rows(rows, idx).reshape(B * T, C)
         text_t = self.get_text_feats().float().t().contiguous()          # [C, K], differentiable under prompt tuning

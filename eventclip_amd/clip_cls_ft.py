@@ -55,8 +55,7 @@ class FTCLIPClassifier(FSCLIPClassifier):
         t = self._tower
         x = imgs.to(t.dev, torch.float32).contiguous()
         patches = torch.empty((x.shape[0], t.G, t.kpad), dtype=t.cd, device=t.dev)
-        _lib.check(_lib.lib().ec_patchify(_lib.ptr(x), x.shape[0], t.cfg['image_size'], t.P, t.kpad, _lib.ptr(patches),
-                                          t.code, _lib.stream_ptr()), 'ec_patchify')
+        _lib.launch('ec_patchify', x, x.shape[0], t.cfg['image_size'], t.P, t.kpad, patches, t.code)
         return self._adjust_dtype(t.encode_patches(patches))
 
     # ---- checkpoints: model.visual.* travels with the classifier (clip_cls_ft.py:313-333) ----

@@ -23,7 +23,9 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .train import _AGG, cosine_warmup_lr
+from ._lib import device_table
+from .adapter import compact_row_idx
+from .train import _AGG, adam_table, cosine_warmup_lr
 
 _BLOCK = (('ln1_g', 'ln_1.weight'), ('ln1_b', 'ln_1.bias'), ('qkv_w', 'attn.in_proj_weight'),
           ('qkv_b', 'attn.in_proj_bias'), ('out_w', 'attn.out_proj.weight'), ('out_b', 'attn.out_proj.bias'),
@@ -39,22 +41,26 @@ def _block_name(i, leaf):
     return f'transformer.resblocks.{i}.{leaf}'
 
 
-def pack_weights16(jobs, dtype_code):
-    """jobs: list of (w fp32 CUDA [rows, cols], hi, lo, hi_t) with 16-bit outputs or None, all the same shape ->
-    one ``ec_pack_weight16_batched`` launch."""
-    if not jobs:
-        return
-    rows, cols = jobs[0][0].shape
+def pack_table(jobs):
+    """jobs: list of (w fp32 CUDA [rows, cols], hi, lo, hi_t) with 16-bit outputs or None, all the same shape -> the
+    device item table of ``ec_pack_weight16_batched``."""
     items = (_lib.EcPackItem * len(jobs))()
     for it, (w, hi, lo, hi_t) in zip(items, jobs):
-        assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (rows, cols)
+        assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.shape == jobs[0][0].shape
         it.w = w.data_ptr()
         it.hi = hi.data_ptr() if hi is not None else None
         it.lo = lo.data_ptr() if lo is not None else None
         it.hi_t = hi_t.data_ptr() if hi_t is not None else None
-    table = device_table(items)
-    rc = _lib.lib().ec_pack_weight16_batched(_lib.ptr(table), len(jobs), rows, cols, dtype_code, _lib.stream_ptr())
-    _lib.check(rc, 'ec_pack_weight16_batched')
+    return device_table(items)
+
+
+def pack_weights16(jobs, dtype_code):
+    """jobs as ``pack_table`` takes them -> one ``ec_pack_weight16_batched`` launch."""
+    if not jobs:
+        return
+    rows, cols = jobs[0][0].shape
+    table = pack_table(jobs)
+    _lib.launch('ec_pack_weight16_batched', table, len(jobs), rows, cols, dtype_code)
     return table
 
 
@@ -69,17 +75,9 @@ def sgemm(a, b, out, alpha=1.0, beta=0.0):
     M, K = a.shape
     K2, N = b.shape
     assert K == K2 and tuple(out.shape) == (M, N) and out.stride(1) == 1
-    rc = _lib.lib().ec_sgemm(_lib.ptr(a), a.stride(0), a.stride(1), _lib.ptr(b), b.stride(0), b.stride(1), M, N, K,
-                             float(alpha), float(beta), _lib.ptr(out), out.stride(0), _lib.stream_ptr())
-    _lib.check(rc, 'ec_sgemm')
+    _lib.launch('ec_sgemm', a, a.stride(0), a.stride(1), b, b.stride(0), b.stride(1), M, N, K, float(alpha), float(beta),
+                out, out.stride(0))
     return out
-
-
-def device_table(items):
-    """ctypes array of structs -> device copy (uint8 CUDA tensor) for the batched kernels' item tables."""
-    import numpy as np
-    host = np.frombuffer(items, dtype=np.uint8).copy()
-    return torch.from_numpy(host).cuda()
 
 
 class VisualTower:
@@ -126,7 +124,7 @@ class VisualTower:
         self._pack_plans = {}
         self._build_structs()
         self.pack()
-        self._ws = None
+        self._ws = _lib.Scratch()
         self._tape = None
         self._grad_slots = {}
         self._grad_structs = {}
@@ -185,21 +183,10 @@ class VisualTower:
                                                          pk['conv_lo_tmp'], None))
             if 'proj' in todo:
                 groups.setdefault(('proj',), []).append((src('proj'), None, pk['proj_lo_tmp'], pk['proj_t']))
-            plan = []
-            for jobs in groups.values():
-                rows, cols = jobs[0][0].shape
-                items = (_lib.EcPackItem * len(jobs))()
-                for it, (w, hi, lo, hi_t) in zip(items, jobs):
-                    assert w.is_contiguous() and w.dtype == torch.float32
-                    it.w = w.data_ptr()
-                    it.hi = hi.data_ptr() if hi is not None else None
-                    it.lo = lo.data_ptr() if lo is not None else None
-                    it.hi_t = hi_t.data_ptr() if hi_t is not None else None
-                plan.append((device_table(items), len(jobs), rows, cols))
-            self._pack_plans[todo] = plan
+            plan = self._pack_plans[todo] = [(pack_table(jobs), len(jobs)) + tuple(jobs[0][0].shape)
+                                             for jobs in groups.values()]
         for table, n, rows, cols in plan:
-            rc = _lib.lib().ec_pack_weight16_batched(_lib.ptr(table), n, rows, cols, self.code, _lib.stream_ptr())
-            _lib.check(rc, 'ec_pack_weight16_batched')
+            _lib.launch('ec_pack_weight16_batched', table, n, rows, cols, self.code)
         if 'conv1.weight' in todo:
             pk['conv'][:, :self.k] = pk['conv_hi_tmp']                          # [w_hi | w_hi | 0]
             pk['conv'][:, self.k:2 * self.k] = pk['conv_hi_tmp']
@@ -210,11 +197,7 @@ class VisualTower:
 
     # ---- passes ----
     def _workspace(self, n):
-        need = int(_lib.lib().ec_vit_train_workspace_bytes(ctypes.byref(self._vit), n))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=self.dev)
-        return self._ws
+        return self._ws.get(int(_lib.lib().ec_vit_train_workspace_bytes(ctypes.byref(self._vit), n)), self.dev)
 
     def forward(self, patches):
         """patches: 16-bit CUDA [N, G, kpad] -> fp32 features [N, D]; keeps the tape for ``backward``."""
@@ -223,9 +206,7 @@ class VisualTower:
         assert tuple(patches.shape) == (n, self.G, self.kpad), f'patches {tuple(patches.shape)}'
         ws = self._workspace(n)
         feats = torch.empty((n, self.D), dtype=torch.float32, device=self.dev)
-        rc = _lib.lib().ec_vit_train_forward(ctypes.byref(self._vit), _lib.ptr(patches), n, _lib.ptr(feats),
-                                             _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, 'ec_vit_train_forward')
+        _lib.launch('ec_vit_train_forward', self._vit, patches, n, feats, ws, ws.numel())
         self._tape = (patches, n)
         return feats
 
@@ -236,15 +217,14 @@ class VisualTower:
         need = int(_lib.lib().ec_vit_workspace_bytes(ctypes.byref(self._vit), min(n, 256)))
         ws = torch.empty((need,), dtype=torch.uint8, device=self.dev)
         feats = torch.empty((n, self.D), dtype=torch.float32, device=self.dev)
-        rc = _lib.lib().ec_vit_encode(ctypes.byref(self._vit), _lib.ptr(patches), n, _lib.ptr(feats), _lib.ptr(ws),
-                                      ws.numel(), min(n, 256), _lib.stream_ptr())
-        _lib.check(rc, 'ec_vit_encode')
+        _lib.launch('ec_vit_encode', self._vit, patches, n, feats, ws, ws.numel(), min(n, 256))
         return feats
 
     def workspace_views(self, n):
         """Typed views of the training workspace of the last ``forward`` over n images (``ec_vit_train_layout``): the
         tape and the backward pass's state between stages, for tests.  -> (tower-wide {name: view}, [block {name: view}])"""
-        assert self._ws is not None, 'workspace_views before a forward'
+        ws = self._ws.buf
+        assert ws is not None, 'workspace_views before a forward'
         L, W, M, H, cd = self.L, self.W, n * self.S, self.W // 64, self.cd
         cnt = _lib.EC_VT_BLOCK0 + _lib.EC_VT_PER_BLOCK * L
         offs = (ctypes.c_int64 * cnt)()
@@ -257,8 +237,8 @@ class VisualTower:
                 numel *= s
             nbytes = numel * torch.empty((), dtype=dtype).element_size()
             o = offs[slot]
-            assert 0 <= o and o + nbytes <= self._ws.numel()
-            return self._ws[o:o + nbytes].view(dtype).view(shape)
+            assert 0 <= o and o + nbytes <= ws.numel()
+            return ws[o:o + nbytes].view(dtype).view(shape)
         f32 = torch.float32
         top = dict(pre=view(_lib.EC_VT_PRE, f32, M, W), x_last=view(_lib.EC_VT_X_LAST, f32, M, W),
                    dx=view(_lib.EC_VT_DX, f32, M, W), dx16=view(_lib.EC_VT_DX16, cd, M, W),
@@ -279,13 +259,7 @@ class VisualTower:
         """One flat fp32 buffer with a slot per wanted gradient (a single all-reduce / unscale covers it)."""
         key = tuple(want)
         if key not in self._grad_slots:
-            sizes = [self.master[n].numel() for n in want]
-            flat = torch.zeros((max(sum(sizes), 4),), dtype=torch.float32, device=self.dev)
-            views, off = {}, 0
-            for n, sz in zip(want, sizes):
-                views[n] = flat[off:off + sz].view(self.master[n].shape)
-                off += sz
-            self._grad_slots[key] = (flat, views)
+            self._grad_slots[key] = _lib.flat_views({n: self.master[n].shape for n in want}, self.dev, min_numel=4)
         return self._grad_slots[key]
 
     def _grad_struct(self, want):
@@ -297,10 +271,8 @@ class VisualTower:
             g = _lib.EcVitGrads()
             top = {leaf: f for f, leaf in _TOP}
             blk = {leaf: f for f, leaf in _BLOCK}
-            spans, off = {}, 0
+            spans = {name: (t.storage_offset(), t.numel()) for name, t in views.items()}
             for name, t in views.items():
-                spans[name] = (off, t.numel())
-                off += t.numel()
                 if name in top:
                     setattr(g, top[name], t.data_ptr())
                 else:
@@ -325,11 +297,8 @@ class VisualTower:
         g, views, flat, _ = self._grad_struct(want)
         sb, se = (0, self.L + 2) if stages is None else stages
         ws = self._workspace(n)
-        rc = _lib.lib().ec_vit_train_backward_stages(ctypes.byref(self._vit), ctypes.byref(self._vit_t), _lib.ptr(patches),
-                                                     n, _lib.ptr(d_feats), ctypes.byref(g),
-                                                     ctypes.byref(lora) if lora is not None else None, int(sb), int(se),
-                                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, 'ec_vit_train_backward_stages')
+        _lib.launch('ec_vit_train_backward_stages', self._vit, self._vit_t, patches, n, d_feats, g, lora, int(sb), int(se),
+                    ws, ws.numel())
         return views, flat
 
     def canonical(self, names):
@@ -483,21 +452,12 @@ class LoraFactors:
         """effective = base + up @ down for every projection (lora.py:138-150, :50-52) and the repack of those
         matrices; the factors' own 16-bit copies (the backward pass's operands) follow."""
         t = self.tower
-        rc = _lib.lib().ec_lora_merge_batched(_lib.ptr(self._items), self._n_items, t.W, t.W, self.r, _lib.stream_ptr())
-        _lib.check(rc, 'ec_lora_merge_batched')
+        _lib.launch('ec_lora_merge_batched', self._items, self._n_items, t.W, t.W, self.r)
         t.pack(self.merged_names)
         if self._pack_tables is None:
-            def table(jobs):
-                items = (_lib.EcPackItem * len(jobs))()
-                for it, (w, hi, lo, hi_t) in zip(items, jobs):
-                    it.w = w.data_ptr()
-                    it.hi = hi.data_ptr() if hi is not None else None
-                    it.hi_t = hi_t.data_ptr() if hi_t is not None else None
-                return device_table(items)
-            self._pack_tables = (table(self._pack_down), table(self._pack_up))
+            self._pack_tables = (pack_table(self._pack_down), pack_table(self._pack_up))
         for tbl, (rows, cols) in zip(self._pack_tables, ((self.r, t.W), (t.W, self.r))):
-            rc = _lib.lib().ec_pack_weight16_batched(_lib.ptr(tbl), self._n_items, rows, cols, t.code, _lib.stream_ptr())
-            _lib.check(rc, 'ec_pack_weight16_batched')
+            _lib.launch('ec_pack_weight16_batched', tbl, self._n_items, rows, cols, t.code)
 
     def state_dict_entries(self):
         """The tower's attention entries as the reference's LoRA-injected modules name them."""
@@ -554,8 +514,6 @@ def ft_loss_grad(img_feats, valid, labels, text_param, logit_scale, agg='mean', 
         assert f.dim() == 2 and tuple(row_idx.shape) == (B, T)
     t = text_param.detach().float().contiguous()
     K = t.shape[0]
-    v8 = valid.to(torch.uint8).contiguous()
-    lab = labels.to(torch.int32).contiguous()
     need = int(_lib.lib().ec_fs_text_train_workspace_bytes(B, T, D, K)) + max(B * T, K) * D * 4
     ws = torch.empty((need,), dtype=torch.uint8, device=dev)
     loss = torch.empty((1,), dtype=torch.float32, device=dev)
@@ -565,12 +523,9 @@ def ft_loss_grad(img_feats, valid, labels, text_param, logit_scale, agg='mean', 
         gtext = text_grad_out if text_grad_out is not None else torch.empty((K, D), dtype=torch.float32, device=dev)
         assert gtext.is_contiguous() and tuple(gtext.shape) == (K, D) and gtext.dtype == torch.float32
     logits = torch.empty((B, K), dtype=torch.float32, device=dev)
-    rc = _lib.lib().ec_ft_loss_grad(_lib.ptr(f), _lib.ptr(row_idx), _lib.ptr(v8), _lib.ptr(lab), _lib.ptr(t), B, T, D, K,
-                                    float(logit_scale), _AGG[agg], int(bool(use_probs_loss)), float(grad_scale),
-                                    _lib.ptr(step_scalars), _lib.ptr(loss), _lib.ptr(gtext), _lib.ptr(gimg),
-                                    _lib.ptr(logits), _lib.ptr(ws),
-                                    ws.numel(), _lib.stream_ptr())
-    _lib.check(rc, 'ec_ft_loss_grad')
+    _lib.launch('ec_ft_loss_grad', f, row_idx, valid.to(torch.uint8).contiguous(), labels.to(torch.int32).contiguous(), t,
+                B, T, D, K, float(logit_scale), _AGG[agg], int(bool(use_probs_loss)), float(grad_scale), step_scalars,
+                loss, gtext, gimg, logits, ws, ws.numel())
     return loss[0], gimg, gtext, logits
 
 
@@ -617,12 +572,8 @@ class FTTrainer:
         self._found = torch.zeros((1,), dtype=torch.int32, device=self.tower.dev)
         self._lora_grads = {}
         if self.lora:                                   # the factor gradients share one flat buffer too
-            total = sum(p.numel() for p in self.lora.params.values())
-            self._lora_flat = torch.zeros((total,), dtype=torch.float32, device=self.tower.dev)
-            off = 0
-            for n, p in self.lora.params.items():
-                self._lora_grads[n] = self._lora_flat[off:off + p.numel()].view(p.shape)
-                off += p.numel()
+            self._lora_flat, self._lora_grads = _lib.flat_views({n: p.shape for n, p in self.lora.params.items()},
+                                                                self.tower.dev)
         # gradients live at fixed addresses: views of the tower's flat buffer, the factor gradients, text_feats'
         self._grads = {}
         self._flat, views = self.tower.grad_buffer(self.want)
@@ -635,13 +586,8 @@ class FTTrainer:
             self.lora.merge()
         if classifier.prompt_tuning:
             self._grads['text_feats'] = torch.zeros_like(classifier.text_feats.data)
-        items = (_lib.EcAdamItem * len(self.tensors))()
-        for it, (k, p) in zip(items, self.tensors.items()):
-            assert p.is_contiguous() and self._grads[k].is_contiguous()
-            m, v = self.state[k]
-            it.param, it.grad, it.exp_avg, it.exp_avg_sq = p.data_ptr(), self._grads[k].data_ptr(), m.data_ptr(), v.data_ptr()
-            it.n, it.group = p.numel(), int(k.startswith('model.visual.'))
-        self._adam_items = device_table(items) if len(self.tensors) else None
+        self._adam_items = adam_table(self.tensors, self._grads, self.state,
+                                      group=lambda k: int(k.startswith('model.visual.'))) if self.tensors else None
         self._adam_max = max([p.numel() for p in self.tensors.values()] + [0])
         # the scaler's verdict on a step is read back asynchronously (pinned host word + event) and applied
         # before the next step needs the scale: the host never waits for the step it has just queued
@@ -738,17 +684,13 @@ class FTTrainer:
         valid = data_dict['valid_mask'].to(self.tower.dev)
         if 'patches' in data_dict:
             return data_dict['patches'], valid, data_dict['row_idx']
-        flat = valid.reshape(-1)
-        row_idx = torch.where(flat, torch.cumsum(flat.int(), 0) - 1, torch.full_like(flat, -1, dtype=torch.int64))
-        row_idx = row_idx.to(torch.int32).reshape(valid.shape)
+        row_idx = compact_row_idx(valid)
         imgs = data_dict['img']
         t = self.tower
         x = imgs[valid].to(t.dev, torch.float32).contiguous()
         R = t.cfg['image_size']
         patches = torch.empty((x.shape[0], t.G, t.kpad), dtype=t.cd, device=t.dev)
-        rc = _lib.lib().ec_patchify(_lib.ptr(x), x.shape[0], R, t.P, t.kpad, _lib.ptr(patches), t.code,
-                                    _lib.stream_ptr())
-        _lib.check(rc, 'ec_patchify')
+        _lib.launch('ec_patchify', x, x.shape[0], R, t.P, t.kpad, patches, t.code)
         return patches, valid, row_idx
 
     def resolve(self):
@@ -811,17 +753,13 @@ class FTTrainer:
             for buf in ([flat] if self.want else []) + ([self._lora_flat] if self.lora else []):
                 if ddp and buf is not flat:
                     dist.all_reduce(buf)              # the LoRA factors' gradients: one small collective
-                rc = _lib.lib().ec_grad_unscale_check(_lib.ptr(buf), buf.numel(), 1.0, _lib.ptr(self._found), _lib.ptr(sc),
-                                                      _lib.stream_ptr())
-                _lib.check(rc, 'ec_grad_unscale_check')
+                _lib.launch('ec_grad_unscale_check', buf, buf.numel(), 1.0, self._found, sc)
         if clf.prompt_tuning and ddp:
             dist.all_reduce(gtext)
             gtext /= world                      # (not scaled: the head's text gradient never sees the loss scale)
         if self._adam_items is not None:
-            rc = _lib.lib().ec_adam_step_multi(_lib.ptr(self._adam_items), len(self.tensors), self._adam_max, 0., 0.,
-                                               self.betas[0], self.betas[1], self.eps, 0., 0,
-                                               _lib.ptr(self._found) if check else None, _lib.ptr(sc), _lib.stream_ptr())
-            _lib.check(rc, 'ec_adam_step_multi')
+            _lib.launch('ec_adam_step_multi', self._adam_items, len(self.tensors), self._adam_max, 0., 0., self.betas[0],
+                        self.betas[1], self.eps, 0., 0, self._found if check else None, sc)
             if self.lora:
                 self.lora.merge()
             if self._moved:
@@ -863,8 +801,6 @@ class FTTrainer:
             loss, logits, feats = self._body(patches, valid, labels, row_idx, ddp, world)
         self.last = dict(logits=logits, feats=feats, grads=self._grads, skipped=False)
         self.steps += 1
-        if hasattr(clf, '_invalidate_text_cache') and self._adam_items is not None:
-            clf._invalidate_text_cache()
         if check:
             self._pending = torch.cuda.Event()
             self._pending.record()

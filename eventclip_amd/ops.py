@@ -3,8 +3,6 @@
 Tensors are torch CUDA tensors used as plain device buffers; everything runs on
 torch's current stream.  No CPU fallback.
 """
-import ctypes
-
 from . import _lib
 
 
@@ -15,6 +13,20 @@ def dtype_code(t):
     if t == torch.bfloat16:
         return _lib.EC_BF16
     raise TypeError(f'16-bit dtype expected, got {t}')
+
+
+def _gemm_args(A, W, out, M, N, K, epilogue, splits):
+    """EcGemmArgs with what every call sets: the problem, the operands and the output with their row strides, the
+    K split's partial-product stride."""
+    a = _lib.EcGemmArgs()
+    a.M, a.N, a.K = M, N, K
+    a.dtype, a.epilogue = dtype_code(A.dtype), epilogue
+    a.A, a.lda = A.data_ptr(), A.stride(0)
+    a.W, a.ldw = W.data_ptr(), W.stride(0)
+    a.C, a.ldc = out.data_ptr(), out.stride(-2)
+    if splits > 1:
+        a.splits, a.split_stride = splits, out.stride(0)
+    return a
 
 
 def gemm(A, W, bias=None, epilogue='store16', out=None, variant=0, diag=None, resid=None, aux=None,
@@ -53,13 +65,9 @@ def gemm(A, W, bias=None, epilogue='store16', out=None, variant=0, diag=None, re
     assert (epilogue != 'resid_hl' or aux is not None) and (not epilogue.endswith('_ln') or row_stats is not None)
     assert out.dtype == want and tuple(out.shape) == shape and out.stride(-1) == 1, \
         f'{epilogue} writes a {want} {shape} tensor, got {out.dtype} {tuple(out.shape)}'
-    a = _lib.EcGemmArgs()
-    a.M, a.N, a.K = M, N, K
-    a.dtype, a.epilogue, a.variant = dtype_code(A.dtype), epi, variant
-    a.A, a.lda = A.data_ptr(), A.stride(0)
-    a.W, a.ldw = W.data_ptr(), W.stride(0)
+    a = _gemm_args(A, W, out, M, N, K, epi, splits)
+    a.variant = variant
     a.bias = bias.data_ptr() if bias is not None else None
-    a.C, a.ldc = out.data_ptr(), out.stride(-2)
     a.diag = diag.data_ptr() if diag is not None else None    # EC_GEMM_DIAG builds only
     if resid is not None:
         assert resid.dtype == torch.float32 and tuple(resid.shape) == (M, N) and resid.stride(0) == out.stride(-2)
@@ -90,12 +98,10 @@ def gemm(A, W, bias=None, epilogue='store16', out=None, variant=0, diag=None, re
         t, e = aux8
         assert t.dtype == torch.uint8 and tuple(t.shape) == (M, 2 * N) and t.stride(0) == 2 * out.stride(-2) and aux is None
         a.aux, a.aux_e4m3, a.aux_exp = t.data_ptr(), 1, int(e)
-    if splits > 1:
-        a.splits, a.split_stride = splits, out.stride(0)
     if ws is not None:                       # fp32 scratch: an under-filled launch runs K-batched (low latency)
         assert ws.is_cuda and ws.is_contiguous()
         a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
-    _lib.check(_lib.lib().ec_gemm(ctypes.byref(a), _lib.stream_ptr()), 'ec_gemm')
+    _lib.launch('ec_gemm', a)
     return out
 
 
@@ -136,16 +142,9 @@ def gemm_rows(A, W, splits=1, out=None):
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=A.device)
     assert out.dtype == torch.float32 and tuple(out.shape) == shape and out.stride(-1) == 1
-    a = _lib.EcGemmArgs()
-    a.M, a.N, a.K = M, N, K
-    a.dtype, a.epilogue, a.variant = dtype_code(A.dtype), _lib.EC_EPI_STORE32, 0
-    a.A, a.lda = A.data_ptr(), A.stride(0)
-    a.W, a.ldw = W.data_ptr(), W.stride(0)
-    a.C, a.ldc = out.data_ptr(), out.stride(-2)
+    a = _gemm_args(A, W, out, M, N, K, _lib.EC_EPI_STORE32, splits)
     a.transposed, a.k_rows = 1, rows
-    if splits > 1:
-        a.splits, a.split_stride = splits, out.stride(0)
-    _lib.check(_lib.lib().ec_gemm(ctypes.byref(a), _lib.stream_ptr()), 'ec_gemm')
+    _lib.launch('ec_gemm', a)
     return out
 
 
@@ -156,9 +155,8 @@ def layernorm_hl(x_hi, x_lo, gamma, beta, eps=1e-5):
     rows, width = x_hi.shape
     assert x_lo.dtype == torch.float16 and x_lo.shape == x_hi.shape and x_lo.stride() == x_hi.stride()
     out = torch.empty((2, rows, width), dtype=x_hi.dtype, device=x_hi.device)
-    _lib.check(_lib.lib().ec_layernorm_hl(x_hi.data_ptr(), x_lo.data_ptr(), x_hi.stride(0), gamma.data_ptr(), beta.data_ptr(),
-                                          rows, width, float(eps), out[0].data_ptr(), out[1].data_ptr(), width,
-                                          dtype_code(x_hi.dtype), _lib.stream_ptr()), 'ec_layernorm_hl')
+    _lib.launch('ec_layernorm_hl', x_hi, x_lo, x_hi.stride(0), gamma, beta, rows, width, float(eps), out[0], out[1], width,
+                dtype_code(x_hi.dtype))
     return out[0], out[1]
 
 
@@ -169,8 +167,7 @@ def row_stats(x16, eps=1e-5):
     rows, width = x16.shape
     assert x16.stride(1) == 1
     out = torch.zeros((rows + 1, 2), dtype=torch.float32, device=x16.device)[:rows]   # readable to an even row count
-    _lib.check(_lib.lib().ec_row_stats(x16.data_ptr(), x16.stride(0), rows, width, float(eps), out.data_ptr(),
-                                       dtype_code(x16.dtype), _lib.stream_ptr()), 'ec_row_stats')
+    _lib.launch('ec_row_stats', x16, x16.stride(0), rows, width, float(eps), out, dtype_code(x16.dtype))
     return out
 
 
@@ -179,6 +176,5 @@ def row_stats_merge(row_sums, width, eps=1e-5):
     import torch
     rows, groups = row_sums.shape[0], row_sums.shape[1]
     out = torch.zeros((rows + 1, 2), dtype=torch.float32, device=row_sums.device)[:rows]   # readable to an even row count
-    _lib.check(_lib.lib().ec_row_stats_merge(row_sums.data_ptr(), rows, groups, width, float(eps), out.data_ptr(),
-                                             _lib.stream_ptr()), 'ec_row_stats_merge')
+    _lib.launch('ec_row_stats_merge', row_sums, rows, groups, width, float(eps), out)
     return out

@@ -69,9 +69,7 @@ def preprocess_frames(frames, n_px=224, mode='chw', patch=None, kpad=None, dtype
         from . import torch_ops  # noqa: F401  (registers eventclip_hip::preprocess)
         return torch.ops.eventclip_hip.preprocess(frames, int(n_px), m, int(patch), int(kpad), code)
     assert out.dtype == odt and out.is_contiguous() and out.numel() >= int(np.prod(shape))
-    rc = _lib.lib().ec_preprocess(_lib.ptr(frames), F, host.ctypes.data, _lib.ptr(plan),
-                                  _lib.ptr(out), m, patch, kpad, code, _lib.stream_ptr())
-    _lib.check(rc, 'ec_preprocess')
+    _lib.launch('ec_preprocess', frames, F, host.ctypes.data, plan, out, m, patch, kpad, code)
     return out
 
 

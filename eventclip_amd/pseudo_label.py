@@ -24,10 +24,8 @@ def select(probs, conf_thresh, tta=False, tta_consistent=False, tta_min_prob=Fal
     pred = torch.empty((B,), dtype=torch.int32, device=dev)
     mx = torch.empty((B,), dtype=torch.float32, device=dev)
     sel = torch.empty((B,), dtype=torch.uint8, device=dev)
-    rc = _lib.lib().ec_pseudo_label(_lib.ptr(p), B, V, K, float(conf_thresh), int(bool(tta_consistent)),
-                                    int(bool(tta_min_prob)), _lib.ptr(mean), _lib.ptr(pred),
-                                    _lib.ptr(mx), _lib.ptr(sel), _lib.stream_ptr())
-    _lib.check(rc, 'ec_pseudo_label')
+    _lib.launch('ec_pseudo_label', p, B, V, K, float(conf_thresh), int(bool(tta_consistent)), int(bool(tta_min_prob)),
+                mean, pred, mx, sel)
     return dict(probs=mean, pred=pred.long(), max_prob=mx, selected=sel.bool())
 
 

@@ -146,10 +146,7 @@ def apply_ops(frames, per_frame_ops, fill):
     need = int(_lib.lib().ec_randaugment_workspace_bytes(F, H, W, num_ops))
     ws = torch.empty((need,), dtype=torch.uint8, device=dev)
     fill_c = (ctypes.c_uint8 * 3)(*[int(v) for v in fill])
-    rc = _lib.lib().ec_randaugment(_lib.ptr(frames), _lib.ptr(out), F, H, W, _lib.ptr(ops_d), num_ops,
-                                   ctypes.cast(fill_c, ctypes.c_void_p), _lib.ptr(ws), need,
-                                   _lib.stream_ptr())
-    _lib.check(rc, 'ec_randaugment')
+    _lib.launch('ec_randaugment', frames, out, F, H, W, ops_d, num_ops, ctypes.cast(fill_c, ctypes.c_void_p), ws, need)
     return out
 
 

@@ -30,11 +30,11 @@ import ctypes
 import weakref
 from typing import List, Optional, Tuple
 
-import numpy as np
 import torch
 from torch.library import custom_op
 
 from . import _lib
+from .adapter import _adapter_struct, adapter_param_names
 
 NAMESPACE = 'eventclip_hip'
 
@@ -73,20 +73,11 @@ def events_to_frames(events: torch.Tensor, frame_range: torch.Tensor, H: int, W:
     from . import vis
     F = int(frame_range.shape[0])
     frames = torch.empty((F, H, W, 3), dtype=torch.uint8, device=events.device)
-    prm = _lib.EcEventsParams()
-    prm.H, prm.W, prm.thresh = H, W, thresh
-    prm.count_non_zero, prm.background_mask = int(count_non_zero), int(background_mask)
-    prm.max_frame_events = max_frame_events
-    prm.flip_x, prm.negate_p = int(flip_x), int(negate_p)
-    prm.float32_stage, prm.total_events = int(float32_stage), total_events
-    for c in range(3):
-        prm.red[c], prm.blue[c] = red[c], blue[c]
-    ws = vis.attach_sort_workspace(prm, events.device, True)   # noqa: F841 (alive over the call)
-    packed = vis.is_packed(events)
-    entry = _lib.lib().ec_events_to_frames_packed if packed else _lib.lib().ec_events_to_frames
-    rc = entry(_lib.ptr(events), _lib.ptr(frame_range), F, ctypes.byref(prm), _lib.ptr(frames), None,
-               None, None, _lib.stream_ptr())
-    _lib.check(rc, 'ec_events_to_frames')
+    prm = vis.events_params((H, W), red, blue, thresh, count_non_zero, background_mask, max_frame_events, flip_x,
+                            negate_p, float32_stage, total_events)
+    vis.attach_sort_workspace(prm, events.device, True)
+    _lib.launch('ec_events_to_frames_packed' if vis.is_packed(events) else 'ec_events_to_frames', events, frame_range,
+                F, prm, frames, None, None, None)
     return frames
 
 
@@ -107,9 +98,7 @@ def preprocess(frames: torch.Tensor, n_px: int, mode: int, patch: int, kpad: int
     F, H, W, _ = frames.shape
     host, plan = _plans()._plan(H, W, n_px, frames.device)
     out = frames.new_empty(_pre_shape(F, n_px, mode, patch, kpad), dtype=_pre_dtype(mode, dtype_code))
-    rc = _lib.lib().ec_preprocess(_lib.ptr(frames), F, host.ctypes.data, _lib.ptr(plan), _lib.ptr(out),
-                                  mode, max(patch, 1), kpad, dtype_code, _lib.stream_ptr())
-    _lib.check(rc, 'ec_preprocess')
+    _lib.launch('ec_preprocess', frames, F, host.ctypes.data, plan, out, mode, max(patch, 1), kpad, dtype_code)
     return out
 
 
@@ -152,10 +141,8 @@ def vit_encode(patches: torch.Tensor, clip_handle: int) -> torch.Tensor:
     if need > m.workspace_budget:     # keep the scratch bounded (e.g. 336-px inputs)
         chunk = max(1, int(chunk * m.workspace_budget / need))
         need = _lib.lib().ec_vit_workspace_bytes(ctypes.byref(pk['vit']), chunk)
-    ws = m._workspace(need, pk['dev'])
-    rc = _lib.lib().ec_vit_encode(ctypes.byref(pk['vit']), _lib.ptr(patches), n, _lib.ptr(feats),
-                                  _lib.ptr(ws), ws.numel(), chunk, _lib.stream_ptr())
-    _lib.check(rc, 'ec_vit_encode')
+    ws = m._ws.get(need, pk['dev'])
+    _lib.launch('ec_vit_encode', pk['vit'], patches, n, feats, ws, ws.numel(), chunk)
     return feats
 
 
@@ -176,10 +163,8 @@ def text_encode(tokens: torch.Tensor, clip_handle: int) -> torch.Tensor:
         return feats
     chunk = max(1, min(512, n))
     need = _lib.lib().ec_text_workspace_bytes(ctypes.byref(pk['text']), chunk)
-    ws = m._workspace(need, pk['dev'])
-    rc = _lib.lib().ec_text_encode(ctypes.byref(pk['text']), _lib.ptr(tokens), n, _lib.ptr(feats),
-                                   _lib.ptr(ws), ws.numel(), chunk, _lib.stream_ptr())
-    _lib.check(rc, 'ec_text_encode')
+    ws = m._ws.get(need, pk['dev'])
+    _lib.launch('ec_text_encode', pk['text'], tokens, n, feats, ws, ws.numel(), chunk)
     return feats
 
 
@@ -199,9 +184,7 @@ def adapter_fwd(feats: torch.Tensor, row_idx: torch.Tensor, adapter_handle: int)
     pk = a._pack()
     B, T = row_idx.shape
     out = torch.empty((B, T, a.in_dim), dtype=torch.float32, device=feats.device)
-    rc = _lib.lib().ec_adapter_forward(ctypes.byref(pk['w']), _lib.ptr(feats), _lib.ptr(row_idx), B, T,
-                                       _lib.ptr(out), _lib.stream_ptr())
-    _lib.check(rc, 'ec_adapter_forward')
+    _lib.launch('ec_adapter_forward', pk['w'], feats, row_idx, B, T, out)
     return out
 
 
@@ -223,10 +206,8 @@ def _text_planes(text_t):
     hit = _TEXT_PLANES.get(key)
     if hit is not None and hit[1]() is text_t:
         return hit[0]
-    import weakref
-    ws = torch.empty(max(int(_lib.lib().ec_classify_text_bytes(C, K)), 256), dtype=torch.uint8, device=text_t.device)
-    rc = _lib.lib().ec_classify_prep_text(_lib.ptr(text_t), C, K, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-    _lib.check(rc, 'ec_classify_prep_text')
+    ws = _lib.scratch(_lib.lib().ec_classify_text_bytes(C, K), text_t.device)
+    _lib.launch('ec_classify_prep_text', text_t, C, K, ws, ws.numel())
     for k in [k for k, v in _TEXT_PLANES.items() if v[1]() is None]:        # tensors that are gone
         del _TEXT_PLANES[k]
     while len(_TEXT_PLANES) >= _TEXT_PLANES_MAX:
@@ -247,11 +228,9 @@ def classify(feats: torch.Tensor, row_idx: torch.Tensor, text_t: torch.Tensor, l
     probs = torch.empty((B, K), dtype=torch.float32, device=feats.device)
     n_rows = int(feats.shape[0])
     text_ws = _text_planes(text_t)
-    ws = torch.empty(max(int(_lib.lib().ec_classify_v2_workspace_bytes(n_rows, C, K)), 256), dtype=torch.uint8, device=feats.device)
-    rc = _lib.lib().ec_classify_v2(_lib.ptr(feats), n_rows, _lib.ptr(row_idx), _lib.ptr(text_ws), B, T, C, K,
-                                   logit_scale, agg, int(normalize), _lib.ptr(full), _lib.ptr(logits),
-                                   _lib.ptr(probs), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-    _lib.check(rc, 'ec_classify_v2')
+    ws = _lib.scratch(_lib.lib().ec_classify_v2_workspace_bytes(n_rows, C, K), feats.device)
+    _lib.launch('ec_classify_v2', feats, n_rows, row_idx, text_ws, B, T, C, K, logit_scale, agg, int(normalize), full,
+                logits, probs, ws, ws.numel())
     return full, logits, probs
 
 
@@ -281,14 +260,9 @@ def classify_bwd(feats: torch.Tensor, row_idx: torch.Tensor, text_t: torch.Tenso
     ups = [_f32c(g) for g in (d_full_logits, d_logits, d_probs)]
     d_feats = torch.empty((n_rows, C) if need_feats else (0,), dtype=torch.float32, device=feats.device)
     d_text = torch.empty((C, K) if need_text else (0,), dtype=torch.float32, device=feats.device)
-    ws = torch.empty(max(int(_lib.lib().ec_classify_backward_workspace_bytes(B, T, C, K)), 256), dtype=torch.uint8,
-                     device=feats.device)
-    rc = _lib.lib().ec_classify_backward(_lib.ptr(feats), n_rows, _lib.ptr(row_idx), _lib.ptr(text_t), B, T, C, K,
-                                         logit_scale, agg, int(normalize), _lib.ptr(full_logits), _lib.ptr(ups[0]),
-                                         _lib.ptr(ups[1]), _lib.ptr(ups[2]), _lib.ptr(d_feats) if need_feats else None,
-                                         _lib.ptr(d_text) if need_text else None, _lib.ptr(ws), ws.numel(),
-                                         _lib.stream_ptr())
-    _lib.check(rc, 'ec_classify_backward')
+    ws = _lib.scratch(_lib.lib().ec_classify_backward_workspace_bytes(B, T, C, K), feats.device)
+    _lib.launch('ec_classify_backward', feats, n_rows, row_idx, text_t, B, T, C, K, logit_scale, agg, int(normalize),
+                full_logits, *ups, d_feats if need_feats else None, d_text if need_text else None, ws, ws.numel())
     return d_feats, d_text
 
 
@@ -318,29 +292,12 @@ classify.register_autograd(_classify_backward, setup_context=_classify_setup)
 
 
 # ---- the transformer adapter under autograd: forward and backward as two ops with a tape between them ----
-_ADAPTER_LAYER_PARAMS = ('self_attn.in_proj_weight', 'self_attn.in_proj_bias', 'self_attn.out_proj.weight',
-                         'self_attn.out_proj.bias', 'linear1.weight', 'linear1.bias', 'linear2.weight', 'linear2.bias',
-                         'norm1.weight', 'norm1.bias', 'norm2.weight', 'norm2.bias')
-
-
-def adapter_param_names(layers):
-    """``TransformerAdapter.named_parameters()`` order: the order of the ``params`` list of the two ops below."""
-    return [f'transformer_encoder.layers.{i}.{n}' for i in range(layers) for n in _ADAPTER_LAYER_PARAMS] + \
-        ['in_proj.weight', 'in_proj.bias', 'out_proj.weight', 'out_proj.bias']
-
-
-class _Geometry:
-    def __init__(self, in_dim, d_model, heads, ffn_dim, layers, residual):
-        self.in_dim, self.d_model, self.num_heads, self.ffn_dim = in_dim, d_model, heads, ffn_dim
-        self.num_layers, self.residual = layers, residual
-
-
-def _train_struct(params, geo):
-    from .train import _adapter_struct
-    names = adapter_param_names(geo.num_layers)
-    if len(params) != len(names):
-        raise RuntimeError(f'{NAMESPACE}: {len(params)} adapter parameters, {len(names)} expected (named_parameters() order)')
-    return _adapter_struct(geo, dict(zip(names, params)))
+def _train_struct(params, *geometry):
+    """_adapter_struct over an op's ``params`` list (geometry: in_dim, d_model, heads, ffn_dim, layers, residual)."""
+    want = len(adapter_param_names(geometry[4]))
+    if len(params) != want:
+        raise RuntimeError(f'{NAMESPACE}: {len(params)} adapter parameters, {want} expected (named_parameters() order)')
+    return _adapter_struct(params, *geometry)
 
 
 @custom_op(f'{NAMESPACE}::adapter_train_fwd', mutates_args=(), device_types='cuda')
@@ -356,14 +313,12 @@ def adapter_train_fwd(feats: torch.Tensor, row_idx: torch.Tensor, params: List[t
         raise RuntimeError(f'{NAMESPACE}::adapter_train_fwd: feats {tuple(feats.shape)} is not [B * T = {B * T}, C]')
     feats = _f32c(feats)
     params = [_f32c(p) for p in params]
-    w, keep = _train_struct(params, _Geometry(C, d_model, heads, ffn_dim, layers, residual))   # noqa: F841 (alive over the call)
-    valid = (row_idx >= 0).to(torch.uint8).contiguous()
+    w, keep = _train_struct(params, C, d_model, heads, ffn_dim, layers, residual)   # noqa: F841 (the struct's layer array)
     out = torch.empty((B, T, C), dtype=torch.float32, device=feats.device)
     need = int(_lib.lib().ec_adapter_train_tape_bytes(B, T, C, d_model, ffn_dim, heads, layers))
-    tape = torch.zeros((max(need, 256),), dtype=torch.uint8, device=feats.device)   # its alignment gaps too: an output
-    rc = _lib.lib().ec_adapter_train_forward(_lib.ptr(feats), _lib.ptr(valid), B, T, ctypes.byref(w), dropout_p, seed,
-                                             _lib.ptr(out), _lib.ptr(tape), tape.numel(), _lib.stream_ptr())
-    _lib.check(rc, 'ec_adapter_train_forward')
+    tape = _lib.scratch(need, feats.device).zero_()       # its alignment gaps too: an output
+    _lib.launch('ec_adapter_train_forward', feats, (row_idx >= 0).to(torch.uint8).contiguous(), B, T, w, dropout_p, seed,
+                out, tape, tape.numel())
     return out, tape
 
 
@@ -396,15 +351,12 @@ def adapter_train_bwd(feats: torch.Tensor, row_idx: torch.Tensor, params: List[t
     n = len(params)
     grads = [torch.empty_like(p) if need_mask >> i & 1 else None for i, p in enumerate(params)]
     d_feats = torch.empty_like(feats) if need_mask >> n & 1 else None
-    geo = _Geometry(C, d_model, heads, ffn_dim, layers, residual)
-    w, keep_w = _train_struct(params, geo)      # noqa: F841
-    g, keep_g = _train_struct(grads, geo)       # noqa: F841
-    ws = torch.empty((max(int(_lib.lib().ec_adapter_train_backward_workspace_bytes(B, T, C, d_model, ffn_dim)), 256),),
-                     dtype=torch.uint8, device=feats.device)
-    rc = _lib.lib().ec_adapter_train_backward(_lib.ptr(feats), B, T, ctypes.byref(w), dropout_p, seed, _lib.ptr(tape),
-                                              tape.numel(), _lib.ptr(d_out), ctypes.byref(g), _lib.ptr(d_feats),
-                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-    _lib.check(rc, 'ec_adapter_train_backward')
+    geometry = (C, d_model, heads, ffn_dim, layers, residual)
+    w, keep_w = _train_struct(params, *geometry)      # noqa: F841 (the struct's layer array)
+    g, keep_g = _train_struct(grads, *geometry)       # noqa: F841
+    ws = _lib.scratch(_lib.lib().ec_adapter_train_backward_workspace_bytes(B, T, C, d_model, ffn_dim), feats.device)
+    _lib.launch('ec_adapter_train_backward', feats, B, T, w, dropout_p, seed, tape, tape.numel(), d_out, g, d_feats, ws,
+                ws.numel())
     empty = feats.new_empty((0,))
     return [empty.clone() if t is None else t for t in grads + [d_feats]]
 
@@ -454,10 +406,8 @@ def resnet_encode(inp: torch.Tensor, input_mode: int, clip_handle: int) -> torch
     need = _lib.lib().ec_resnet_workspace_bytes(ctypes.byref(pk['resnet']), chunk)
     if need == 0:
         _lib.check(_lib.EC_ERR_INVALID, 'ec_resnet_workspace_bytes')
-    ws = m._workspace(need, pk['dev'])
-    rc = _lib.lib().ec_resnet_encode(ctypes.byref(pk['resnet']), _lib.ptr(inp), int(input_mode), n, _lib.ptr(feats),
-                                     _lib.ptr(ws), ws.numel(), chunk, _lib.stream_ptr())
-    _lib.check(rc, 'ec_resnet_encode')
+    ws = m._ws.get(need, pk['dev'])
+    _lib.launch('ec_resnet_encode', pk['resnet'], inp, int(input_mode), n, feats, ws, ws.numel(), chunk)
     return feats
 
 

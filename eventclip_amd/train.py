@@ -8,15 +8,17 @@ and ``adam_step`` (torch.optim.Adam, ``ec_adam_step``).  ``TextFeatTrainer`` str
 the warm-up + cosine schedule of method.py:82-98 and, across ranks, an all-reduce of the K x D
 gradient (the only trainable tensor of this adapter type).
 """
+import collections
 import math
 
 import torch
 import torch.distributed as dist
 
 from . import _lib
+from .adapter import _adapter_struct
 
 _AGG = {'sum': _lib.EC_AGG_SUM, 'mean': _lib.EC_AGG_MEAN}
-_WS = {}
+_scratch = collections.defaultdict(_lib.Scratch)      # device index -> the loss kernels' workspace
 
 
 def fs_text_loss_grad(img_feats, valid, labels, text_param, logit_scale, agg='sum', use_probs_loss=False,
@@ -34,45 +36,13 @@ def fs_text_loss_grad(img_feats, valid, labels, text_param, logit_scale, agg='su
     v8 = valid.to(torch.uint8).contiguous()
     lab = labels.to(torch.int32).contiguous()
     need = int(_lib.lib().ec_fs_text_train_workspace_bytes(B, T, D, K))
-    ws = _WS.get(dev.index)
-    if ws is None or ws.numel() < need:
-        ws = _WS[dev.index] = torch.empty((need,), dtype=torch.uint8, device=dev)
+    ws = _scratch[dev.index].get(need, dev)
     loss = torch.empty((1,), dtype=torch.float32, device=dev)
     grad = torch.empty((K, D), dtype=torch.float32, device=dev)
     logits = torch.empty((B, K), dtype=torch.float32, device=dev) if return_logits else None
-    rc = _lib.lib().ec_fs_text_loss_grad(_lib.ptr(f), _lib.ptr(v8), _lib.ptr(lab), _lib.ptr(t), B, T, D, K,
-                                         float(logit_scale), _AGG[agg], int(bool(use_probs_loss)),
-                                         _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(logits), _lib.ptr(ws),
-                                         ws.numel(), _lib.stream_ptr())
-    _lib.check(rc, 'ec_fs_text_loss_grad')
+    _lib.launch('ec_fs_text_loss_grad', f, v8, lab, t, B, T, D, K, float(logit_scale), _AGG[agg],
+                int(bool(use_probs_loss)), loss, grad, logits, ws, ws.numel())
     return (loss[0], grad, logits) if return_logits else (loss[0], grad)
-
-
-_LAYER_FIELDS = (('ln1_g', 'norm1.weight'), ('ln1_b', 'norm1.bias'), ('qkv_w', 'self_attn.in_proj_weight'),
-                 ('qkv_b', 'self_attn.in_proj_bias'), ('o_w', 'self_attn.out_proj.weight'),
-                 ('o_b', 'self_attn.out_proj.bias'), ('ln2_g', 'norm2.weight'), ('ln2_b', 'norm2.bias'),
-                 ('w1', 'linear1.weight'), ('b1', 'linear1.bias'), ('w2', 'linear2.weight'), ('b2', 'linear2.bias'))
-
-
-def _adapter_struct(adapter, tensors):
-    """ec_adapter_train_params over `tensors` (name -> fp32 CUDA tensor, the adapter's state-dict names; None -> NULL,
-    a gradient the split backward skips)."""
-    import ctypes
-
-    class _Null:
-        data_ptr = staticmethod(lambda: None)
-    tensors = {k: _Null if v is None else v for k, v in tensors.items()}
-    layers = (_lib.EcAdapterTrainLayer * adapter.num_layers)()
-    for i in range(adapter.num_layers):
-        for field, name in _LAYER_FIELDS:
-            setattr(layers[i], field, tensors[f'transformer_encoder.layers.{i}.{name}'].data_ptr())
-    p = _lib.EcAdapterTrainParams()
-    p.in_dim, p.d_model, p.heads = adapter.in_dim, adapter.d_model, adapter.num_heads
-    p.ffn_dim, p.layers, p.residual = adapter.ffn_dim, adapter.num_layers, float(adapter.residual)
-    p.in_w, p.in_b = tensors['in_proj.weight'].data_ptr(), tensors['in_proj.bias'].data_ptr()
-    p.out_w, p.out_b = tensors['out_proj.weight'].data_ptr(), tensors['out_proj.bias'].data_ptr()
-    p.blocks = ctypes.cast(layers, ctypes.POINTER(_lib.EcAdapterTrainLayer))
-    return p, layers
 
 
 def dropout_mask(seed, site, n, p):
@@ -80,8 +50,7 @@ def dropout_mask(seed, site, n, p):
     out_proj, 2 inside the MLP, 3 after linear2} as ``fs_trans_loss_grad`` draws it."""
     dev = _lib.require_gpu()
     m = torch.empty((int(n),), dtype=torch.uint8, device=dev)
-    _lib.check(_lib.lib().ec_dropout_mask(int(seed), int(site), int(n), float(p), _lib.ptr(m), _lib.stream_ptr()),
-               'ec_dropout_mask')
+    _lib.launch('ec_dropout_mask', int(seed), int(site), int(n), float(p), m)
     return m
 
 
@@ -94,7 +63,6 @@ def fs_trans_loss_grad(img_feats, valid, labels, text_param, logit_scale, adapte
     stateless hash of (seed, site, element); 0: the deterministic eval-mode function.
     out (optional): {name: tensor} to receive the gradients (every adapter name and 'text_feats'; a trainer's
     fixed buffers -- nothing is allocated for them then)."""
-    import ctypes
     dev = _lib.require_gpu()
     if agg not in _AGG:
         raise NotImplementedError(f'agg_func {agg!r}: the reference trains with sum / mean')
@@ -106,25 +74,19 @@ def fs_trans_loss_grad(img_feats, valid, labels, text_param, logit_scale, adapte
     for k, v in params.items():
         assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous(), k
     grads = {k: out[k] for k in params} if out is not None else {k: torch.empty_like(v) for k, v in params.items()}
-    ps, keep_p = _adapter_struct(adapter, params)
-    gs, keep_g = _adapter_struct(adapter, grads)
+    geometry = (adapter.in_dim, adapter.d_model, adapter.num_heads, adapter.ffn_dim, adapter.num_layers, adapter.residual)
+    ps, keep_p = _adapter_struct(params.values(), *geometry)
+    gs, keep_g = _adapter_struct(grads.values(), *geometry)
     need = int(_lib.lib().ec_fs_trans_train_workspace_bytes(B, T, D, K, adapter.d_model, adapter.ffn_dim,
                                                             adapter.num_heads, adapter.num_layers))
-    ws = _WS.get(dev.index)
-    if ws is None or ws.numel() < need:
-        ws = _WS[dev.index] = torch.empty((need,), dtype=torch.uint8, device=dev)
+    ws = _scratch[dev.index].get(need, dev)
     loss = torch.empty((1,), dtype=torch.float32, device=dev)
     gtext = out['text_feats'] if out is not None and 'text_feats' in out else torch.empty((K, D), dtype=torch.float32, device=dev)
     assert gtext.is_contiguous() and tuple(gtext.shape) == (K, D) and gtext.dtype == torch.float32
     logits = torch.empty((B, K), dtype=torch.float32, device=dev) if return_logits else None
-    v8 = valid.to(torch.uint8).contiguous()       # named: a temporary's block would be handed to the next one
-    lab = labels.to(torch.int32).contiguous()
-    rc = _lib.lib().ec_fs_trans_loss_grad(
-        _lib.ptr(f), _lib.ptr(v8), _lib.ptr(lab),
-        _lib.ptr(t), B, T, D, K, float(logit_scale), _AGG[agg], int(bool(use_probs_loss)), ctypes.byref(ps),
-        ctypes.byref(gs), float(dropout_p), int(seed), _lib.ptr(loss), _lib.ptr(gtext), _lib.ptr(logits), _lib.ptr(ws), ws.numel(),
-        _lib.stream_ptr())
-    _lib.check(rc, 'ec_fs_trans_loss_grad')
+    _lib.launch('ec_fs_trans_loss_grad', f, valid.to(torch.uint8).contiguous(), labels.to(torch.int32).contiguous(), t,
+                B, T, D, K, float(logit_scale), _AGG[agg], int(bool(use_probs_loss)), ps, gs, float(dropout_p), int(seed),
+                loss, gtext, logits, ws, ws.numel())
     grads['text_feats'] = gtext
     return (loss[0], grads, logits) if return_logits else (loss[0], grads)
 
@@ -134,16 +96,20 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), ep
     _lib.require_gpu()
     for x in (param, grad, exp_avg, exp_avg_sq):
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == param.numel()
-    rc = _lib.lib().ec_adam_step(_lib.ptr(param), _lib.ptr(grad), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq),
-                                 param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                 float(weight_decay), int(step), _lib.stream_ptr())
-    _lib.check(rc, 'ec_adam_step')
+    _lib.launch('ec_adam_step', param, grad, exp_avg, exp_avg_sq, param.numel(), float(lr), float(betas[0]),
+                float(betas[1]), float(eps), float(weight_decay), int(step))
 
 
-def _device_table(items):
-    """ctypes array of structs -> device copy (uint8 CUDA tensor) for the batched kernels' item tables."""
-    import numpy as np
-    return torch.from_numpy(np.frombuffer(items, dtype=np.uint8).copy()).cuda()
+def adam_table(tensors, grads, state, group=lambda name: 0):
+    """The device item table of ``ec_adam_step_multi`` over {name: parameter}, with ``grads[name]`` and
+    ``state[name]`` = (exp_avg, exp_avg_sq) at fixed addresses; ``group(name)`` picks the learning rate (0 or 1)."""
+    items = (_lib.EcAdamItem * len(tensors))()
+    for it, (k, p) in zip(items, tensors.items()):
+        assert p.is_contiguous() and grads[k].is_contiguous()
+        m, v = state[k]
+        it.param, it.grad, it.exp_avg, it.exp_avg_sq = p.data_ptr(), grads[k].data_ptr(), m.data_ptr(), v.data_ptr()
+        it.n, it.group = p.numel(), group(k)
+    return _lib.device_table(items)
 
 
 def cosine_warmup_lr(step, total_steps, max_lr, min_lr, warmup_steps):
@@ -182,8 +148,6 @@ class TextFeatTrainer:
         self.steps += 1
         adam_step(clf.text_feats.data, grad, self.exp_avg, self.exp_avg_sq, self.steps, lr, self.betas,
                   self.eps, self.weight_decay)
-        if hasattr(clf, '_invalidate_text_cache'):
-            clf._invalidate_text_cache()
         return loss
 
 
@@ -207,21 +171,11 @@ class AdapterTrainer:
         self.state = {k: (torch.zeros_like(v), torch.zeros_like(v)) for k, v in self.tensors.items()}
         self.steps = 0
         # gradients at fixed addresses (views of one flat buffer: one all-reduce) and one Adam launch over all of them
-        total = sum(v.numel() for v in self.tensors.values())
-        self._flat = torch.zeros((total,), dtype=torch.float32, device=next(iter(self.tensors.values())).device)
-        self._grads, off = {}, 0
-        for k, v in self.tensors.items():
-            assert v.is_contiguous()
-            self._grads[k] = self._flat[off:off + v.numel()].view(v.shape)
-            off += v.numel()
+        self._flat, self._grads = _lib.flat_views({k: v.shape for k, v in self.tensors.items()},
+                                                  next(iter(self.tensors.values())).device)
         if not classifier.prompt_tuning:
             self._grads['text_feats'] = torch.empty_like(classifier.get_text_feats().float())   # computed, not trained
-        items = (_lib.EcAdamItem * len(self.tensors))()
-        for it, (k, p) in zip(items, self.tensors.items()):
-            m, v = self.state[k]
-            it.param, it.grad, it.exp_avg, it.exp_avg_sq = p.data_ptr(), self._grads[k].data_ptr(), m.data_ptr(), v.data_ptr()
-            it.n, it.group = p.numel(), 0
-        self._items = _device_table(items)
+        self._items = adam_table(self.tensors, self._grads, self.state)
         self._max_n = max(p.numel() for p in self.tensors.values())
 
     @torch.no_grad()
@@ -236,9 +190,7 @@ class AdapterTrainer:
             self._flat /= dist.get_world_size()
         lr = cosine_warmup_lr(self.steps, self.total_steps, self.lr, self.lr / 100., self.warmup_steps)
         self.steps += 1
-        rc = _lib.lib().ec_adam_step_multi(_lib.ptr(self._items), len(self.tensors), self._max_n, float(lr), float(lr),
-                                           float(self.betas[0]), float(self.betas[1]), self.eps, self.weight_decay,
-                                           int(self.steps), None, None, _lib.stream_ptr())
-        _lib.check(rc, 'ec_adam_step_multi')
+        _lib.launch('ec_adam_step_multi', self._items, len(self.tensors), self._max_n, float(lr), float(lr),
+                    float(self.betas[0]), float(self.betas[1]), self.eps, self.weight_decay, int(self.steps), None, None)
         clf.adapter._packed = None          # the forward kernel's transposed copies are stale now
         return loss

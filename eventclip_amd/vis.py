@@ -10,6 +10,7 @@ Same names and argument meaning as the reference:
 plus the batched device entry ``events_to_frames_device`` used by the pipeline.
 There is no CPU fallback.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -76,18 +77,28 @@ def colour_map(grayscale=True):
 def make_params(shape, grayscale=True, thresh=10., count_non_zero=False, background_mask=True,
                 max_frame_events=0, flip_x=False, negate_p=False, float_stage=DEFAULT_FLOAT_STAGE,
                 total_events=0):
-    H, W = shape
     red, blue = colour_map(grayscale)
+    return events_params(shape, red, blue, thresh, count_non_zero, background_mask, max_frame_events, flip_x, negate_p,
+                         _float32_stage(float_stage), total_events)
+
+
+def _float32_stage(float_stage):
+    if float_stage not in ('float64', 'float32'):
+        raise ValueError(f'float_stage {float_stage!r}: float64 (numpy >= 2) or float32 (numpy 1.x)')
+    return float_stage == 'float32'
+
+
+def events_params(shape, red, blue, thresh, count_non_zero, background_mask, max_frame_events, flip_x, negate_p,
+                  float32_stage, total_events):
+    """EcEventsParams with the (red, blue) colours given: what ``make_params`` and the custom op both fill."""
     p = _lib.EcEventsParams()
-    p.H, p.W = int(H), int(W)
+    p.H, p.W = int(shape[0]), int(shape[1])
     p.thresh = float(thresh)
     p.count_non_zero = int(bool(count_non_zero))
     p.background_mask = int(bool(background_mask))
     p.max_frame_events = int(max_frame_events)
     p.flip_x, p.negate_p = int(bool(flip_x)), int(bool(negate_p))
-    if float_stage not in ('float64', 'float32'):
-        raise ValueError(f'float_stage {float_stage!r}: float64 (numpy >= 2) or float32 (numpy 1.x)')
-    p.float32_stage = int(float_stage == 'float32')
+    p.float32_stage = int(bool(float32_stage))
     p.total_events = int(total_events)
     for c in range(3):
         p.red[c] = int(red[c])
@@ -95,7 +106,7 @@ def make_params(shape, grayscale=True, thresh=10., count_non_zero=False, backgro
     return p
 
 
-_SORT_WS = {}   # device index -> uint8 CUDA tensor (grown as needed, reused by every call)
+_sort_scratch = collections.defaultdict(_lib.Scratch)   # device index -> the sort workspace, reused by every call
 
 
 def attach_sort_workspace(prm, device, enable=True):
@@ -106,9 +117,7 @@ def attach_sort_workspace(prm, device, enable=True):
     if need <= 0:
         return None
     key = device.index if device.index is not None else torch.cuda.current_device()
-    ws = _SORT_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _SORT_WS[key] = torch.empty((need,), dtype=torch.uint8, device=device)
+    ws = _sort_scratch[key].get(need, device)
     prm.sort_workspace, prm.sort_workspace_bytes = ws.data_ptr(), ws.numel()
     return ws
 
@@ -173,8 +182,7 @@ def pack_events_device(events, return_bad=False):
     n = int(events.shape[0])
     out = torch.empty((n,), dtype=torch.int64, device=dev)
     bad = torch.zeros((1,), dtype=torch.int32, device=dev)
-    rc = _lib.lib().ec_pack_events(_lib.ptr(events), n, _lib.ptr(out), _lib.ptr(bad), _lib.stream_ptr())
-    _lib.check(rc, 'ec_pack_events')
+    _lib.launch('ec_pack_events', events, n, out, bad)
     return (out, int(bad.item())) if return_bad else out
 
 
@@ -206,12 +214,10 @@ def events_to_frames_device(events, frame_range, shape, grayscale=True, thresh=1
         # the production form: the registered custom op (eventclip_hip::events_to_frames)
         from . import torch_ops  # noqa: F401  (registers the namespace)
         red, blue = colour_map(grayscale)
-        if float_stage not in ('float64', 'float32'):
-            raise ValueError(f'float_stage {float_stage!r}: float64 (numpy >= 2) or float32 (numpy 1.x)')
         return torch.ops.eventclip_hip.events_to_frames(
             events, frame_range, int(H), int(W), float(thresh), [int(v) for v in red],
             [int(v) for v in blue], bool(count_non_zero), bool(background_mask), int(max_frame_events),
-            bool(flip_x), bool(negate_p), float_stage == 'float32', int(total_events))
+            bool(flip_x), bool(negate_p), _float32_stage(float_stage), int(total_events))
     # debug form (raw / kept counts, per-frame statistics, caller-owned output): straight to the C ABI
     frames = out if out is not None else torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
     raw = kept = stats = None
@@ -222,11 +228,9 @@ def events_to_frames_device(events, frame_range, shape, grayscale=True, thresh=1
         stats = torch.zeros((F, ctypes.sizeof(_lib.EcFrameStats)), dtype=torch.uint8, device=dev)
     prm = make_params(shape, grayscale, thresh, count_non_zero, background_mask, max_frame_events,
                       flip_x, negate_p, float_stage, total_events)
-    ws = attach_sort_workspace(prm, events.device, sort_workspace)   # noqa: F841 (kept alive over the call)
-    entry = _lib.lib().ec_events_to_frames_packed if packed else _lib.lib().ec_events_to_frames
-    rc = entry(_lib.ptr(events), _lib.ptr(frame_range), F, ctypes.byref(prm), _lib.ptr(frames),
-               _lib.ptr(raw), _lib.ptr(kept), _lib.ptr(stats), _lib.stream_ptr())
-    _lib.check(rc, 'ec_events_to_frames')
+    attach_sort_workspace(prm, events.device, sort_workspace)
+    _lib.launch('ec_events_to_frames_packed' if packed else 'ec_events_to_frames', events, frame_range, F, prm, frames,
+                raw, kept, stats)
     res = [frames]
     if return_counts:
         res += [raw, kept]
@@ -275,11 +279,8 @@ def center_events_device(events, sample_range, resolution):
     assert events.is_cuda and events.is_contiguous() and (packed or events.dtype == torch.float32)
     assert sample_range.is_cuda and sample_range.dtype == torch.int64
     H, W = resolution
-    entry = _lib.lib().ec_center_events_packed if packed else _lib.lib().ec_center_events
-    sample_range = sample_range.contiguous()
-    rc = entry(_lib.ptr(events), _lib.ptr(sample_range), int(sample_range.shape[0]),
-               int(H), int(W), _lib.stream_ptr())
-    _lib.check(rc, 'ec_center_events')
+    _lib.launch('ec_center_events_packed' if packed else 'ec_center_events', events, sample_range.contiguous(),
+                int(sample_range.shape[0]), int(H), int(W))
     return events
 
 

@@ -229,6 +229,17 @@ def test_sgemm_any_layout(hip):
     torch.testing.assert_close(ft.sgemm(at.t(), bt.t(), o2), at.t() @ bt.t(), rtol=1e-5, atol=1e-5)
 
 
+def test_launch_keeps_temporaries_alive(hip):
+    """Two same-sized operands passed to ``_lib.launch`` as temporaries, never bound to a name: the argument tuple
+    holds both until the call has returned, so the second clone cannot be handed the first one's block."""
+    from eventclip_amd import _lib
+    torch.manual_seed(4)
+    a0, b0 = torch.randn(32, 32, device='cuda'), torch.randn(32, 32, device='cuda')
+    out = torch.empty(32, 32, device='cuda')
+    _lib.launch('ec_sgemm', a0.clone(), 32, 1, b0.clone(), 32, 1, 32, 32, 32, 1.0, 0.0, out, 32)
+    torch.testing.assert_close(out, a0 @ b0, rtol=1e-5, atol=1e-5)
+
+
 @pytest.mark.parametrize('rows,cols,r,n_items', [(64, 64, 2, 1), (1024, 1024, 16, 5), (768, 768, 4, 3), (200, 136, 64, 2)])
 def test_lora_merge_and_chain_rule(hip, rows, cols, r, n_items):
     from eventclip_amd import _lib, ft

@@ -103,7 +103,7 @@ def main():
             flops = 2 * lin + 2.0 * M * 4 * W * W * L + 3.5 * att      # dX everywhere, dW for q k v o only
         else:
             flops = 2 * lin + 3.5 * att
-        ws_gb = t._ws.numel() / 2 ** 30
+        ws_gb = t._ws.buf.numel() / 2 ** 30
         print(json.dumps(dict(mode=mode, arch=a.arch, frames_per_step=n, classes=K, dtype=a.dtype,
                               graph=bool(a.graph), ms_per_step=round(dt * 1e3, 2), frames_per_s=round(n / dt, 1),
                               algorithmic_tflop_per_step=round(flops / 1e12, 2),
