@@ -530,7 +530,7 @@ __device__ __forceinline__ void epilogue16_buf(const GemmArgs &g, f32x4 (&acc)[T
         *reinterpret_cast<u32x4 *>(buf + lr * PITCH + q * 32 + 16) = *reinterpret_cast<const u32x4 *>(&o[8]);
     };
     if constexpr (LOUT) {
-        // Split output (ec_gemm_args.aux with an *_LN epilogue): C = hi = round16(v), aux = lo = round16(v - hi), the
+        // Split output (ec_gemm_args.aux with STORE16 / GELU16 in a split-operand launch): C = hi = round16(v), aux = lo = round16(v - hi), the
         // operand pair of a split-precision consumer (ec_gemm_args.A_lo; the attention of the split-operand blocks).
         // One scratch buffer per part, no pipelining of the row groups (this form runs in a few blocks of the tolerance
         // mode only); twice the stores.
@@ -1583,6 +1583,13 @@ extern "C" EC_API int ec_gemm(const ec_gemm_args *a, ec_stream_t stream)
     EC_REQUIRE((((uintptr_t)a->row_stats | (uintptr_t)a->col_sums) & 15) == 0, "ec_gemm: row_stats / col_sums must be 16-byte aligned");
     EC_REQUIRE(!a->row_stats || a->M < (1 << 27), "ec_gemm: row_stats addresses its pairs with 32-bit byte offsets (M = %d)", a->M);
     EC_REQUIRE(((uintptr_t)a->row_sums & 7) == 0, "ec_gemm: row_sums must be 8-byte aligned");
+    // an option the dispatched kernel would not read is refused, not ignored
+    const bool ln_epi = a->epilogue == EC_EPI_STORE16_LN || a->epilogue == EC_EPI_GELU16_LN;
+    EC_REQUIRE(!a->aux || !(a->epilogue == EC_EPI_STORE32 || a->epilogue == EC_EPI_RESID32 || ln_epi),
+               "ec_gemm: args.aux goes with the STORE16, GELU16, GELU16_SAVE, GELU_BWD16 and RESID_HL epilogues (epilogue %d)", a->epilogue);
+    EC_REQUIRE(!a->row_sums || a->epilogue == EC_EPI_RESID_HL, "ec_gemm: args.row_sums goes with EC_EPI_RESID_HL (epilogue %d)", a->epilogue);
+    EC_REQUIRE((!a->row_stats && !a->col_sums) || ln_epi,
+               "ec_gemm: args.row_stats / col_sums go with EC_EPI_STORE16_LN / EC_EPI_GELU16_LN (epilogue %d)", a->epilogue);
     if (a->epilogue == EC_EPI_RESID_HL && a->row_sums) {
         EC_REQUIRE(a->N % 64 == 0, "ec_gemm: row_sums needs N %% 64 == 0 (N = %d)", a->N);
         g.stat_out = a->row_sums, g.stat_groups = a->N / 64;

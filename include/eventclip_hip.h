@@ -297,7 +297,9 @@ typedef struct {
     /* The rest serves the training path (variant 0 only); all zero = the plain GEMM above. */
     long ldw;          /* row stride of W in elements (0 = K) */
     const float *resid;/* EC_EPI_RESID32: C = resid + acc + bias with resid [M, N] at stride ldc (NULL = C, in place) */
-    void *aux;         /* 16-bit [M, N] at stride ldc: second output of GELU16_SAVE / input of GELU_BWD16 */
+    void *aux;         /* 16-bit [M, N] at stride ldc: second output of GELU16_SAVE / input of GELU_BWD16 (the lo plane of
+                          RESID_HL, the lo output of STORE16 / GELU16 with split operands: below).  With EC_EPI_STORE32,
+                          EC_EPI_RESID32 or an *_LN epilogue, which would not read it: EC_ERR_INVALID (refused, not ignored) */
     int splits;        /* > 1: that many independent products over consecutive K-column ranges of A and W
                           (batch s reads columns s*K .. (s+1)*K - 1 and writes C + s * split_stride elements):
                           the partial sums of a weight gradient whose reduction dimension is the batch */
@@ -314,13 +316,13 @@ typedef struct {
                           copies).  K = rows per batch (a multiple of 64), batch s reads rows s*K ..; EC_EPI_STORE32,
                           no bias, variant 0, M a multiple of 8. */
     int k_rows;        /* transposed: the rows that exist (<= splits * K); rows past it read as zero */
-    /* EC_EPI_STORE16_LN / EC_EPI_GELU16_LN: */
+    /* EC_EPI_STORE16_LN / EC_EPI_GELU16_LN (row_stats or col_sums with any other epilogue: EC_ERR_INVALID): */
     const float *row_stats;   /* fp32 pairs (rstd, -rstd * mean) of the A rows; row m at row_stats + 2 * m * row_stats_stride.
                                  16-byte aligned, M pairs: at stride 1 the kernel fetches them two at a time through a
                                  descriptor whose range ends at pair M - 1 (nothing past the array is read); M < 2^27 */
     long row_stats_stride;    /* in rows (0 = 1): the class-token rows of a [n, S] statistics array are S apart */
     const float *col_sums;    /* fp32 [N]: sum over k of W[n][k] as rounded to 16 bit */
-    /* EC_EPI_RESID_HL, optional (N % 64 == 0): */
+    /* EC_EPI_RESID_HL, optional (N % 64 == 0; with any other epilogue: EC_ERR_INVALID): */
     float *row_sums;          /* fp32 [M][N / 64][2]: (sum, sum of squares) of the NEW hi plane over each 64-column group
                                  of every row; ec_row_stats_merge turns them into the row statistics of the GEMM that
                                  follows, so no pass over the hi plane is needed */
