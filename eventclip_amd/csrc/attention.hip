@@ -155,6 +155,27 @@ __device__ __forceinline__ void attn_move(float d, float d_log2, bool down, f32x
 // (conflict-free for the fragment reads of a 16-query tile)
 __device__ __forceinline__ int kkey(int row) { return row & 7; }
 __device__ __forceinline__ int vkey(int row) { return (row >> 1) & 3; }
+// ... as byte offsets inside the row, which lies at image + 128 row (the hi + lo kernels keep four planes in this layout)
+__device__ __forceinline__ int k_chunk(int row, int c) { return (c ^ kkey(row)) << 4; }
+__device__ __forceinline__ int v_slot(int row, int u) { return (u ^ vkey(row)) * 8; }
+// Stage 16-byte chunk ch (the 8-byte slots 2 ch, 2 ch + 1) of a V row: slot u -> u ^ vkey(row), so the chunk moves by
+// bit 1 of the key (bit 2 of the row) and its halves swap by bit 0 (bit 1 of the row)
+__device__ __forceinline__ void v_put(unsigned char *ldsV, int row, int ch, u32x4 t)
+{
+    if ((row >> 1) & 1) t = u32x4{t[2], t[3], t[0], t[1]};
+    *reinterpret_cast<u32x4 *>(ldsV + row * 128 + ((ch ^ ((row >> 2) & 1)) << 4)) = t;
+}
+
+// A vector of ones (the fifth "V^T" tile: the row sum from the matrix pipe), pinned: it stays in four VGPRs (else
+// rebuilt from SGPRs in every block)
+template <int DT> __device__ __forceinline__ typename T16<DT>::v8 ones16()
+{
+    typename T16<DT>::v8 ones;
+#pragma unroll
+    for (int j = 0; j < 8; j++) ones[j] = to16(1.f, typename T16<DT>::elem());
+    asm volatile("" : "+v"(ones));
+    return ones;
+}
 
 // One block of KSTEPS 32-key steps.  `down`: the tile has added nothing yet (m may move down too).
 template <int DT, int KSTEPS, bool MASK, int QM>
@@ -174,8 +195,8 @@ __device__ __forceinline__ void attn_block2(const unsigned char *ldsK, const uns
 #pragma unroll
     for (int kt = 0; kt < NT; kt++) {
         const int row = key0 + kt * 16 + c16;
-        const v8 k0 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((0 + g) ^ kkey(row)) << 4));
-        const v8 k1 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((4 + g) ^ kkey(row)) << 4));
+        const v8 k0 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + k_chunk(row, 0 + g));
+        const v8 k1 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + k_chunk(row, 4 + g));
         acc[kt] = mfma16(k0, qf[0], mneg);
         acc[kt] = mfma16(k1, qf[1], acc[kt]);
     }
@@ -213,9 +234,9 @@ __device__ __forceinline__ void attn_block2(const unsigned char *ldsK, const uns
 #pragma unroll
             for (int hh = 0; hh < 2; hh++) {
                 const int row = key0 + 32 * s + 16 * hh + 4 * g + (c16 >> 2);
-                const int u = ((c16 & 3) * 4 + dt) ^ vkey(row);
+                const int u = v_slot(row, (c16 & 3) * 4 + dt);
                 const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) s16x4 *)(ldsV + row * 128 + u * 8));
+                    (__attribute__((address_space(3))) s16x4 *)(ldsV + row * 128 + u));
                 const v4 tv = __builtin_bit_cast(v4, t);
                 vf[dt][4 * hh] = tv[0], vf[dt][4 * hh + 1] = tv[1], vf[dt][4 * hh + 2] = tv[2],
                             vf[dt][4 * hh + 3] = tv[3];
@@ -254,12 +275,12 @@ __device__ __forceinline__ void attn_odd_key(const unsigned char *ldsK, const un
     constexpr bool PRE = QM != QM_RAW;
     const float thr = PRE ? ATTN_THR : ATTN_THR / c, lo = PRE ? ATTN_LO : ATTN_LO / c;
     const int row = key + c16;
-    const v8 k0 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((0 + g) ^ kkey(row)) << 4));
-    const v8 k1 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + (((4 + g) ^ kkey(row)) << 4));
+    const v8 k0 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + k_chunk(row, 0 + g));
+    const v8 k1 = *reinterpret_cast<const v8 *>(ldsK + row * 128 + k_chunk(row, 4 + g));
     v4 vv[4];
 #pragma unroll
-    for (int dt = 0; dt < 4; dt++)   // logical 8-byte slot 4 g + dt of V's row, stored at slot ^ vkey(row)
-        vv[dt] = *reinterpret_cast<const v4 *>(ldsV + key * 128 + ((4 * g + dt) ^ vkey(key)) * 8);
+    for (int dt = 0; dt < 4; dt++)   // logical 8-byte slot 4 g + dt of V's row
+        vv[dt] = *reinterpret_cast<const v4 *>(ldsV + key * 128 + v_slot(key, 4 * g + dt));
     f32x4 acc = mfma16(k0, qf[0], mneg);
     acc = mfma16(k1, qf[1], acc);
     float sc = acc[0];
@@ -313,6 +334,48 @@ __host__ __device__ constexpr bool attn_lone_tile(int S, int causal, int waves)
     return !causal && (S & 15) == 1 && (S + 15) / 16 > waves && ((S + 15) / 16) % waves == 1;
 }
 
+// The split tile, shared by attention_kernel and attention_hl_kernel.  Its 32-key steps are dealt out evenly: wave w takes
+// [s0, s1) -- none, where there are fewer steps than waves -- and the last wave also what lies behind the last full step.
+template <int WAVES> __device__ __forceinline__ void lone_share(int S, int wave, int &s0, int &s1, bool &tail)
+{
+    const int steps = S >> 5;
+    s0 = wave * steps / WAVES, s1 = (wave + 1) * steps / WAVES;
+    tail = wave == WAVES - 1;
+}
+// This wave's partial (O, m in log2 units, l) of the tile's one valid query (row S - 1: lanes 0, 16, 32, 48, head dims
+// 16 g .. 16 g + 15 each) into the merge area; a barrier, then lone_merge
+__device__ __forceinline__ void lone_put(float *part, int wave, int g, int c16, const f32x4 (&o)[5], float m_log2, bool has_keys)
+{
+    if (c16 == 0) {
+        float *dst = part + wave * ATTN_PART;
+#pragma unroll
+        for (int dt = 0; dt < 4; dt++) *reinterpret_cast<f32x4 *>(dst + 16 * g + 4 * dt) = o[dt];
+        if (g == 0) {
+            dst[64] = has_keys ? m_log2 : -1e30f;   // a wave without keys: weight 0
+            dst[65] = o[4][0];
+        }
+    }
+}
+// One wave merges, lane = head dim: the output is num / den, the row's log-sum-exp (log2) m + log2 den
+struct LoneRow {
+    float num, den, m;
+};
+template <int WAVES> __device__ __forceinline__ LoneRow lone_merge(const float *part, int lane)
+{
+    float m = -1e30f;
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) m = fmaxf(m, part[w * ATTN_PART + 64]);
+    const float *col = part + lane;
+    float num = 0.f, den = 0.f;
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) {
+        const float f = __builtin_amdgcn_exp2f(part[w * ATTN_PART + 64] - m);
+        num = __builtin_fmaf(f, col[w * ATTN_PART], num);
+        den = __builtin_fmaf(f, part[w * ATTN_PART + 65], den);
+    }
+    return LoneRow{num, den, m};
+}
+
 template <int DT, int AT_WAVES, bool LSE = false, int QM = (DT == 0 ? QM_KERNEL : QM_RAW)>
 __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnArgs a)
 {
@@ -356,11 +419,8 @@ __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnA
         for (int p = 0; p < 5; p++) {
             const int row = r_in + p * (AT_THREADS / 8);
             if (row < SP) {
-                *reinterpret_cast<u32x4 *>(ldsK + row * 128 + ((ch ^ (row & 7)) << 4)) = kv[p];
-                // V: 8-byte slot u -> u ^ ((row>>1)&3): chunk moves by bit 1, halves swap by bit 0
-                u32x4 t = vv[p];
-                if ((row >> 1) & 1) t = u32x4{t[2], t[3], t[0], t[1]};
-                *reinterpret_cast<u32x4 *>(ldsV + row * 128 + ((ch ^ ((row >> 2) & 1)) << 4)) = t;
+                *reinterpret_cast<u32x4 *>(ldsK + row * 128 + k_chunk(row, ch)) = kv[p];
+                v_put(ldsV, row, ch, vv[p]);
             }
         }
     }
@@ -390,10 +450,7 @@ __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnA
     __syncthreads();
     attn_stamp(1);
 
-    v8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; j++) ones[j] = to16(1.f, elem());
-    asm volatile("" : "+v"(ones));   // stays in four VGPRs (else rebuilt from SGPRs in every block)
+    const v8 ones = ones16<DT>();
     // q <- q * log2(e) / sqrt(64), rounded to the operand type once per tile
     auto scale_q = [&](v8(&q)[2]) {
         if (QM != QM_KERNEL) return;
@@ -460,9 +517,9 @@ __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnA
     if (do_lone) {
         // ---- the tile left over: this wave's share of its keys, then the merge ----
         float *part = reinterpret_cast<float *>(smem + 2 * SP * 128);
-        const int steps = S >> 5;
-        const int s0 = wave * steps / AT_WAVES, s1 = (wave + 1) * steps / AT_WAVES;
-        const bool tail = wave == AT_WAVES - 1;
+        int s0, s1;
+        bool tail;
+        lone_share<AT_WAVES>(S, wave, s0, s1, tail);
         int g = g_lane, c16 = c_lane;
         asm volatile("" : "+v"(g), "+v"(c16));
         qf[0] = qn[0], qf[1] = qn[1];
@@ -472,33 +529,14 @@ __global__ __launch_bounds__(AT_WAVES * 64, 4) void attention_kernel(const AttnA
         for (int dt = 0; dt < 5; dt++) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         f32x4 mneg = f32x4{0.f, 0.f, 0.f, 0.f};
         attn_keys<DT, QM>(ldsK, ldsV, S, s0, s1, tail, qf, ones, a.scale_log2e, mneg, o, g, c16);
-        if (c16 == 0) {   // the tile's one valid query (row S - 1) lives in lanes 0, 16, 32, 48
-            float *dst = part + wave * ATTN_PART;
-#pragma unroll
-            for (int dt = 0; dt < 4; dt++)
-                *reinterpret_cast<f32x4 *>(dst + 16 * g + 4 * dt) = o[dt];
-            if (g == 0) {
-                const float mw = QM != QM_RAW ? -mneg[0] : -mneg[0] * a.scale_log2e;   // log2 units
-                dst[64] = (s1 > s0 || tail) ? mw : -1e30f;   // a wave without keys: weight 0
-                dst[65] = o[4][0];
-            }
-        }
+        lone_put(part, wave, g, c16, o, QM != QM_RAW ? -mneg[0] : -mneg[0] * a.scale_log2e, s1 > s0 || tail);
         __syncthreads();
-        if (wave == 0) {   // lane = head dim
-            float m = -1e30f;
-#pragma unroll
-            for (int w = 0; w < AT_WAVES; w++) m = fmaxf(m, part[w * ATTN_PART + 64]);
-            float num = 0.f, den = 0.f;
-#pragma unroll
-            for (int w = 0; w < AT_WAVES; w++) {
-                const float f = __builtin_amdgcn_exp2f(part[w * ATTN_PART + 64] - m);
-                num = __builtin_fmaf(f, part[w * ATTN_PART + lane], num);
-                den = __builtin_fmaf(f, part[w * ATTN_PART + 65], den);
-            }
+        if (wave == 0) {
+            const LoneRow r = lone_merge<AT_WAVES>(part, lane);
             const int qrow = S - 1;
-            ((elem *)a.out)[((long)seq * a.q_rows + qrow) * W + head * 64 + lane] = to16(num / den, elem());
+            ((elem *)a.out)[((long)seq * a.q_rows + qrow) * W + head * 64 + lane] = to16(r.num / r.den, elem());
             if (LSE && lane == 0)
-                a.lse[((long)seq * a.heads + head) * S + qrow] = m + __builtin_amdgcn_logf(den);
+                a.lse[((long)seq * a.heads + head) * S + qrow] = r.m + __builtin_amdgcn_logf(r.den);
         }
     }
     attn_stamp(2);
@@ -532,6 +570,8 @@ struct AttnHlArgs {
     int S, W, heads;
 };
 
+// attn_move's job in plain C++.  The two stay separate on purpose: attn_move is tied-operand asm, because attention_kernel's
+// accumulators must not leave their registers; here the MFMAs are builtins and the compiler is free to place O.
 __device__ __forceinline__ void hl_move(float d, bool down, f32x4 &mneg, f32x4 (&o)[5])
 {
     float alpha = __builtin_amdgcn_exp2f(-d);
@@ -552,7 +592,7 @@ __device__ __forceinline__ void attn_step_hl(const unsigned char *kh, const unsi
 #pragma unroll
     for (int kt = 0; kt < 2; kt++) {
         const int row = key0 + kt * 16 + c16;
-        const int o0 = row * 128 + (((0 + g) ^ (row & 7)) << 4), o1 = row * 128 + (((4 + g) ^ (row & 7)) << 4);
+        const int o0 = row * 128 + k_chunk(row, 0 + g), o1 = row * 128 + k_chunk(row, 4 + g);
         const f16x8 k0h = *reinterpret_cast<const f16x8 *>(kh + o0), k1h = *reinterpret_cast<const f16x8 *>(kh + o1);
         const f16x8 k0l = *reinterpret_cast<const f16x8 *>(kl + o0), k1l = *reinterpret_cast<const f16x8 *>(kl + o1);
         f32x4 a = mfma16(k0l, qh[0], mneg);       // the small products first
@@ -586,7 +626,7 @@ __device__ __forceinline__ void attn_step_hl(const unsigned char *kh, const unsi
 #pragma unroll
         for (int hh = 0; hh < 2; hh++) {
             const int row = key0 + 16 * hh + 4 * g + (c16 >> 2);
-            const int off = row * 128 + ((((c16 & 3) * 4 + dt) ^ ((row >> 1) & 3)) << 3);
+            const int off = row * 128 + v_slot(row, (c16 & 3) * 4 + dt);
             const f16x4 th = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vh + off)));
             const f16x4 tl = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(vl + off)));
 #pragma unroll
@@ -620,13 +660,13 @@ __device__ __forceinline__ void attn_odd_key_hl(const unsigned char *kh, const u
                                                 bool down, f32x4 &mneg, f32x4 (&o)[5], int g, int c16)
 {
     const int row = key + c16;
-    const int o0 = row * 128 + (((0 + g) ^ (row & 7)) << 4), o1 = row * 128 + (((4 + g) ^ (row & 7)) << 4);
+    const int o0 = row * 128 + k_chunk(row, 0 + g), o1 = row * 128 + k_chunk(row, 4 + g);
     const f16x8 k0h = *reinterpret_cast<const f16x8 *>(kh + o0), k1h = *reinterpret_cast<const f16x8 *>(kh + o1);
     const f16x8 k0l = *reinterpret_cast<const f16x8 *>(kl + o0), k1l = *reinterpret_cast<const f16x8 *>(kl + o1);
     f16x4 vvh[4], vvl[4];
 #pragma unroll
-    for (int dt = 0; dt < 4; dt++) {      // logical 8-byte slot 4 g + dt of V's row, stored at slot ^ ((key >> 1) & 3)
-        const int off = key * 128 + ((4 * g + dt) ^ ((key >> 1) & 3)) * 8;
+    for (int dt = 0; dt < 4; dt++) {      // logical 8-byte slot 4 g + dt of V's row
+        const int off = key * 128 + v_slot(key, 4 * g + dt);
         vvh[dt] = *reinterpret_cast<const f16x4 *>(vh + off), vvl[dt] = *reinterpret_cast<const f16x4 *>(vl + off);
     }
     f32x4 a = mfma16(k0l, qh[0], mneg);
@@ -669,9 +709,81 @@ __device__ __forceinline__ void attn_keys_hl(const unsigned char *kh, const unsi
 }
 
 constexpr int HL_WAVES = 8;
+
+// Stage K_hi, K_lo, V_hi, V_lo of the keys [key0, key0 + n_keys) of the workgroup's head (`base`: its first q element) into
+// `rows` LDS rows per plane; the rows behind the last key are copies of it.  HL_WAVES x 8 rows x 8 chunks of 16 B per pass,
+// every load of a pass pair in flight before its LDS writes.
+__device__ __forceinline__ void stage_hl(const AttnHlArgs &a, long base, unsigned char *kh, unsigned char *kl, unsigned char *vh,
+                                         unsigned char *vl, int key0, int n_keys, int rows)
+{
+    constexpr int PASS = HL_WAVES * 64 / 8;
+    const int W = a.W;
+    const long ld = 3L * W;
+    const int r_in = threadIdx.x >> 3, ch = threadIdx.x & 7;
+    for (int p0 = 0; p0 < rows; p0 += 2 * PASS) {
+        u32x4 t[2][4];
+#pragma unroll
+        for (int p = 0; p < 2; p++) {
+            const int row = p0 + r_in + p * PASS;
+            if (row < rows) {
+                const long src = base + (long)(key0 + (row < n_keys ? row : n_keys - 1)) * ld + ch * 8;
+                t[p][0] = *reinterpret_cast<const u32x4 *>(a.qkv_hi + src + W), t[p][1] = *reinterpret_cast<const u32x4 *>(a.qkv_lo + src + W);
+                t[p][2] = *reinterpret_cast<const u32x4 *>(a.qkv_hi + src + 2 * W), t[p][3] = *reinterpret_cast<const u32x4 *>(a.qkv_lo + src + 2 * W);
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < 2; p++) {
+            const int row = p0 + r_in + p * PASS;
+            if (row < rows) {
+                const int ko = row * 128 + k_chunk(row, ch);
+                *reinterpret_cast<u32x4 *>(kh + ko) = t[p][0];
+                *reinterpret_cast<u32x4 *>(kl + ko) = t[p][1];
+                v_put(vh, row, ch, t[p][2]);
+                v_put(vl, row, ch, t[p][3]);
+            }
+        }
+    }
+}
+
+// q of one tile: c (q_hi + q_lo) in fp32, split again (the softmax scale and the base change enter before the split)
+__device__ __forceinline__ void load_q_hl(const AttnHlArgs &a, long base, int qt, int c_lane, int g_lane, f16x8 (&qh)[2],
+                                          f16x8 (&ql)[2])
+{
+    constexpr float C = 0.125f * 1.4426950408889634f;
+    const long ld = 3L * a.W;
+    int qsrc = qt * 16 + c_lane;
+    qsrc = qsrc < a.S ? qsrc : a.S - 1;
+#pragma unroll
+    for (int ks = 0; ks < 2; ks++) {
+        const f16x8 h = *reinterpret_cast<const f16x8 *>(a.qkv_hi + base + (long)qsrc * ld + ks * 32 + g_lane * 8);
+        const f16x8 l = *reinterpret_cast<const f16x8 *>(a.qkv_lo + base + (long)qsrc * ld + ks * 32 + g_lane * 8);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            _Float16 xh, xl;
+            split16(((float)h[j] + (float)l[j]) * C, xh, xl);
+            qh[ks][j] = xh, ql[ks][j] = xl;
+        }
+    }
+}
+
+// normalise a query's 16 head dims 16 g .. 16 g + 15 and store them as hi + lo; `row`: the query's row of out
+__device__ __forceinline__ void store_hl(const AttnHlArgs &a, long row, int head, int g, const f32x4 (&o)[5])
+{
+    const float inv = 1.f / o[4][0];
+    _Float16 hi[16], lo[16];
+#pragma unroll
+    for (int dt = 0; dt < 4; dt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) split16(o[dt][r] * inv, hi[4 * dt + r], lo[4 * dt + r]);
+    const long off = row * a.W + head * 64 + g * 16;
+    *reinterpret_cast<u32x4 *>(a.out_hi + off) = *reinterpret_cast<const u32x4 *>(&hi[0]);
+    *reinterpret_cast<u32x4 *>(a.out_hi + off + 8) = *reinterpret_cast<const u32x4 *>(&hi[8]);
+    *reinterpret_cast<u32x4 *>(a.out_lo + off) = *reinterpret_cast<const u32x4 *>(&lo[0]);
+    *reinterpret_cast<u32x4 *>(a.out_lo + off + 8) = *reinterpret_cast<const u32x4 *>(&lo[8]);
+}
+
 __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl_kernel(const AttnHlArgs a)
 {
-    constexpr int THREADS = HL_WAVES * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int S = a.S, W = a.W;
     const int SP = 32 * ((S + 31) / 32);
@@ -680,82 +792,16 @@ __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl_kernel(const At
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g_lane = lane >> 4, c_lane = lane & 15;
     const int head = blockIdx.x % a.heads, seq = blockIdx.x / a.heads;
-    const long ld = 3L * W;
-    const long base = (long)seq * S * ld + head * 64;
-    {   // stage the four planes: every load of a pass pair in flight before its LDS writes
-        const int r_in = threadIdx.x >> 3, ch = threadIdx.x & 7;
-        for (int p0 = 0; p0 < SP; p0 += 2 * (THREADS / 8)) {
-            u32x4 t[2][4];
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const int row = p0 + r_in + p * (THREADS / 8);
-                if (row < SP) {
-                    const long src = base + (long)(row < S ? row : S - 1) * ld + ch * 8;   // rows behind the last key: copies of it
-                    t[p][0] = *reinterpret_cast<const u32x4 *>(a.qkv_hi + src + W), t[p][1] = *reinterpret_cast<const u32x4 *>(a.qkv_lo + src + W);
-                    t[p][2] = *reinterpret_cast<const u32x4 *>(a.qkv_hi + src + 2 * W), t[p][3] = *reinterpret_cast<const u32x4 *>(a.qkv_lo + src + 2 * W);
-                }
-            }
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const int row = p0 + r_in + p * (THREADS / 8);
-                if (row < SP) {
-                    const int ko = row * 128 + ((ch ^ (row & 7)) << 4), vo = row * 128 + ((ch ^ ((row >> 2) & 1)) << 4);
-                    *reinterpret_cast<u32x4 *>(kh + ko) = t[p][0];
-                    *reinterpret_cast<u32x4 *>(kl + ko) = t[p][1];
-                    u32x4 x = t[p][2], y = t[p][3];
-                    if ((row >> 1) & 1) x = u32x4{x[2], x[3], x[0], x[1]}, y = u32x4{y[2], y[3], y[0], y[1]};
-                    *reinterpret_cast<u32x4 *>(vh + vo) = x;
-                    *reinterpret_cast<u32x4 *>(vl + vo) = y;
-                }
-            }
-        }
-    }
+    const long base = (long)seq * S * (3L * W) + head * 64;
+    stage_hl(a, base, kh, kl, vh, vl, 0, S, SP);
     const int n_qt_all = (S + 15) / 16;
     const bool lone = attn_lone_tile(S, 0, HL_WAVES);
     const int n_qt = lone ? n_qt_all - 1 : n_qt_all;
-    constexpr float C = 0.125f * 1.4426950408889634f;
-    // q of one tile: c (q_hi + q_lo) in fp32, split again (the softmax scale and the base change enter before the split)
-    auto load_q = [&](int qt, f16x8(&qh)[2], f16x8(&ql)[2]) {
-        int qsrc = qt * 16 + c_lane;
-        qsrc = qsrc < S ? qsrc : S - 1;
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-            const f16x8 h = *reinterpret_cast<const f16x8 *>(a.qkv_hi + base + (long)qsrc * ld + ks * 32 + g_lane * 8);
-            const f16x8 l = *reinterpret_cast<const f16x8 *>(a.qkv_lo + base + (long)qsrc * ld + ks * 32 + g_lane * 8);
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                float x = ((float)h[j] + (float)l[j]) * C;
-                asm volatile("" : "+v"(x));
-                qh[ks][j] = (_Float16)x;
-                ql[ks][j] = (_Float16)(x - (float)qh[ks][j]);
-            }
-        }
-    };
-    f16x8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; j++) ones[j] = (_Float16)1.f;
-    asm volatile("" : "+v"(ones));
+    const f16x8 ones = ones16<EC_F16>();
     __syncthreads();
-    auto store = [&](int qrow, int g, const f32x4(&o)[5], float inv) {
-        _Float16 hi[16], lo[16];
-#pragma unroll
-        for (int dt = 0; dt < 4; dt++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                float x = o[dt][r] * inv;
-                asm volatile("" : "+v"(x));      // ONE rounded fp32 value for both parts (see attention_f32m_kernel)
-                hi[4 * dt + r] = (_Float16)x;
-                lo[4 * dt + r] = (_Float16)(x - (float)hi[4 * dt + r]);
-            }
-        const long off = ((long)seq * S + qrow) * W + head * 64 + g * 16;
-        *reinterpret_cast<u32x4 *>(a.out_hi + off) = *reinterpret_cast<const u32x4 *>(&hi[0]);
-        *reinterpret_cast<u32x4 *>(a.out_hi + off + 8) = *reinterpret_cast<const u32x4 *>(&hi[8]);
-        *reinterpret_cast<u32x4 *>(a.out_lo + off) = *reinterpret_cast<const u32x4 *>(&lo[0]);
-        *reinterpret_cast<u32x4 *>(a.out_lo + off + 8) = *reinterpret_cast<const u32x4 *>(&lo[8]);
-    };
     for (int qt = wave; qt < n_qt; qt += HL_WAVES) {
         f16x8 qh[2], ql[2];
-        load_q(qt, qh, ql);
+        load_q_hl(a, base, qt, c_lane, g_lane, qh, ql);
         int g = g_lane, c16 = c_lane;
         asm volatile("" : "+v"(g), "+v"(c16));
         f32x4 o[5];
@@ -764,15 +810,16 @@ __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl_kernel(const At
         f32x4 mneg = f32x4{0.f, 0.f, 0.f, 0.f};
         attn_keys_hl(kh, kl, vh, vl, S, 0, S >> 5, true, qh, ql, ones, mneg, o, g, c16);
         const int qrow = qt * 16 + c16;
-        if (qrow < S) store(qrow, g, o, 1.f / o[4][0]);
+        if (qrow < S) store_hl(a, (long)seq * S + qrow, head, g, o);
     }
     if (lone) {
         // the tile left over (one query row): this wave's share of its keys, then the merge through LDS
         float *part = reinterpret_cast<float *>(smem + 4 * SP * 128);
-        const int steps = S >> 5, s0 = wave * steps / HL_WAVES, s1 = (wave + 1) * steps / HL_WAVES;
-        const bool tail = wave == HL_WAVES - 1;
+        int s0, s1;
+        bool tail;
+        lone_share<HL_WAVES>(S, wave, s0, s1, tail);
         f16x8 qh[2], ql[2];
-        load_q(n_qt_all - 1, qh, ql);
+        load_q_hl(a, base, n_qt_all - 1, c_lane, g_lane, qh, ql);
         int g = g_lane, c16 = c_lane;
         asm volatile("" : "+v"(g), "+v"(c16));
         f32x4 o[5];
@@ -780,33 +827,15 @@ __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl_kernel(const At
         for (int dt = 0; dt < 5; dt++) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         f32x4 mneg = f32x4{0.f, 0.f, 0.f, 0.f};
         attn_keys_hl(kh, kl, vh, vl, S, s0, s1, tail, qh, ql, ones, mneg, o, g, c16);
-        if (c16 == 0) {   // the tile's one valid query (row S - 1) lives in lanes 0, 16, 32, 48
-            float *dst = part + wave * ATTN_PART;
-#pragma unroll
-            for (int dt = 0; dt < 4; dt++) *reinterpret_cast<f32x4 *>(dst + 16 * g + 4 * dt) = o[dt];
-            if (g == 0) {
-                dst[64] = (s1 > s0 || tail) ? -mneg[0] : -1e30f;   // a wave without keys: weight 0
-                dst[65] = o[4][0];
-            }
-        }
+        lone_put(part, wave, g, c16, o, -mneg[0], s1 > s0 || tail);
         __syncthreads();
-        if (wave == 0) {   // lane = head dim
-            float m = -1e30f;
-#pragma unroll
-            for (int w = 0; w < HL_WAVES; w++) m = fmaxf(m, part[w * ATTN_PART + 64]);
-            float num = 0.f, den = 0.f;
-#pragma unroll
-            for (int w = 0; w < HL_WAVES; w++) {
-                const float f = __builtin_amdgcn_exp2f(part[w * ATTN_PART + 64] - m);
-                num = __builtin_fmaf(f, part[w * ATTN_PART + lane], num);
-                den = __builtin_fmaf(f, part[w * ATTN_PART + 65], den);
-            }
-            float x = num / den;
-            asm volatile("" : "+v"(x));
-            const _Float16 h = (_Float16)x;
+        if (wave == 0) {
+            const LoneRow r = lone_merge<HL_WAVES>(part, lane);
+            _Float16 h, l;
+            split16(r.num / r.den, h, l);
             const long off = ((long)seq * S + S - 1) * W + head * 64 + lane;
             a.out_hi[off] = h;
-            a.out_lo[off] = (_Float16)(x - (float)h);
+            a.out_lo[off] = l;
         }
     }
 }
@@ -819,7 +848,6 @@ __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl_kernel(const At
 constexpr int HL2_TILES = 5;      // query tiles per wave at most: S <= 8 x 5 x 16 = 640
 __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl2_kernel(const AttnHlArgs a, int split, int SPL)
 {
-    constexpr int THREADS = HL_WAVES * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int S = a.S, W = a.W;
     unsigned char *kh = smem, *kl = smem + SPL * 128, *vh = smem + 2 * SPL * 128, *vl = smem + 3 * SPL * 128;
@@ -827,30 +855,9 @@ __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl2_kernel(const A
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g_lane = lane >> 4, c_lane = lane & 15;
     const int head = blockIdx.x % a.heads, seq = blockIdx.x / a.heads;
-    const long ld = 3L * W;
-    const long base = (long)seq * S * ld + head * 64;
+    const long base = (long)seq * S * (3L * W) + head * 64;
     const int n_qt = (S + 15) / 16;
-    constexpr float C = 0.125f * 1.4426950408889634f;
-    auto load_q = [&](int qt, f16x8(&qh)[2], f16x8(&ql)[2]) {
-        int qsrc = qt * 16 + c_lane;
-        qsrc = qsrc < S ? qsrc : S - 1;
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-            const f16x8 h = *reinterpret_cast<const f16x8 *>(a.qkv_hi + base + (long)qsrc * ld + ks * 32 + g_lane * 8);
-            const f16x8 l = *reinterpret_cast<const f16x8 *>(a.qkv_lo + base + (long)qsrc * ld + ks * 32 + g_lane * 8);
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                float x = ((float)h[j] + (float)l[j]) * C;
-                asm volatile("" : "+v"(x));
-                qh[ks][j] = (_Float16)x;
-                ql[ks][j] = (_Float16)(x - (float)qh[ks][j]);
-            }
-        }
-    };
-    f16x8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; j++) ones[j] = (_Float16)1.f;
-    asm volatile("" : "+v"(ones));
+    const f16x8 ones = ones16<EC_F16>();
     f32x4 o[HL2_TILES][5];
     float mneg[HL2_TILES];          // (-m of a tile: one register between the passes, the MFMA's C operand inside one)
 #pragma unroll
@@ -862,41 +869,14 @@ __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl2_kernel(const A
     for (int half = 0; half < 2; half++) {
         const int key0 = half ? split : 0, Sl = half ? S - split : split;
         if (half) __syncthreads();      // every wave is done with the first pass's planes
-        {
-            const int r_in = threadIdx.x >> 3, ch = threadIdx.x & 7;
-            for (int p0 = 0; p0 < SPL; p0 += 2 * (THREADS / 8)) {
-                u32x4 t[2][4];
-#pragma unroll
-                for (int p = 0; p < 2; p++) {
-                    const int row = p0 + r_in + p * (THREADS / 8);
-                    if (row < SPL) {
-                        const long src = base + (long)(key0 + (row < Sl ? row : Sl - 1)) * ld + ch * 8;
-                        t[p][0] = *reinterpret_cast<const u32x4 *>(a.qkv_hi + src + W), t[p][1] = *reinterpret_cast<const u32x4 *>(a.qkv_lo + src + W);
-                        t[p][2] = *reinterpret_cast<const u32x4 *>(a.qkv_hi + src + 2 * W), t[p][3] = *reinterpret_cast<const u32x4 *>(a.qkv_lo + src + 2 * W);
-                    }
-                }
-#pragma unroll
-                for (int p = 0; p < 2; p++) {
-                    const int row = p0 + r_in + p * (THREADS / 8);
-                    if (row < SPL) {
-                        const int ko = row * 128 + ((ch ^ (row & 7)) << 4), vo = row * 128 + ((ch ^ ((row >> 2) & 1)) << 4);
-                        *reinterpret_cast<u32x4 *>(kh + ko) = t[p][0];
-                        *reinterpret_cast<u32x4 *>(kl + ko) = t[p][1];
-                        u32x4 x = t[p][2], y = t[p][3];
-                        if ((row >> 1) & 1) x = u32x4{x[2], x[3], x[0], x[1]}, y = u32x4{y[2], y[3], y[0], y[1]};
-                        *reinterpret_cast<u32x4 *>(vh + vo) = x;
-                        *reinterpret_cast<u32x4 *>(vl + vo) = y;
-                    }
-                }
-            }
-        }
+        stage_hl(a, base, kh, kl, vh, vl, key0, Sl, SPL);
         __syncthreads();
 #pragma unroll
         for (int t = 0; t < HL2_TILES; t++) {
             const int qt = wave + HL_WAVES * t;
             if (qt < n_qt) {      // (wave-uniform)
                 f16x8 qh[2], ql[2];
-                load_q(qt, qh, ql);
+                load_q_hl(a, base, qt, c_lane, g_lane, qh, ql);
                 int g = g_lane, c16 = c_lane;
                 asm volatile("" : "+v"(g), "+v"(c16));
                 f32x4 mn = f32x4{mneg[t], mneg[t], mneg[t], mneg[t]};
@@ -908,59 +888,46 @@ __global__ __launch_bounds__(HL_WAVES * 64, 1) void attention_hl2_kernel(const A
 #pragma unroll
     for (int t = 0; t < HL2_TILES; t++) {
         const int qt = wave + HL_WAVES * t, qrow = qt * 16 + c_lane;
-        if (qt < n_qt && qrow < S) {
-            const float inv = 1.f / o[t][4][0];
-            _Float16 hi[16], lo[16];
-#pragma unroll
-            for (int dt = 0; dt < 4; dt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    float x = o[t][dt][r] * inv;
-                    asm volatile("" : "+v"(x));
-                    hi[4 * dt + r] = (_Float16)x;
-                    lo[4 * dt + r] = (_Float16)(x - (float)hi[4 * dt + r]);
-                }
-            const long off = ((long)seq * S + qrow) * W + head * 64 + g_lane * 16;
-            *reinterpret_cast<u32x4 *>(a.out_hi + off) = *reinterpret_cast<const u32x4 *>(&hi[0]);
-            *reinterpret_cast<u32x4 *>(a.out_hi + off + 8) = *reinterpret_cast<const u32x4 *>(&hi[8]);
-            *reinterpret_cast<u32x4 *>(a.out_lo + off) = *reinterpret_cast<const u32x4 *>(&lo[0]);
-            *reinterpret_cast<u32x4 *>(a.out_lo + off + 8) = *reinterpret_cast<const u32x4 *>(&lo[8]);
-        }
+        if (qt < n_qt && qrow < S) store_hl(a, (long)seq * S + qrow, head, g_lane, o[t]);
     }
 }
 
-template <int DT> int dispatch(const AttnArgs &a, int n_seq, int heads, hipStream_t s)
+template <int DT> int dispatch(const AttnArgs &a, int n_seq, hipStream_t s)
 {
     const int n32 = (a.S + 31) / 32;
     // K and V images, plus the merge area of a tile whose keys are split over the waves -- reserved only where the
     // kernel can take that path for this S (its `lone` condition: not causal, S = 16 n + 1, the tile count one more
     // than a multiple of the wave count), so that S = 609 .. 640 (n32 = 20: exactly 160 KiB of K and V) still fits
     const int kv = 32 * n32 * 128 * 2;
-    const int waves_if = kv + 16 * ATTN_PART * 4 > 80 * 1024 ? 16 : 8;      // the wave count the full carve would pick
-    const bool may_split = attn_lone_tile(a.S, a.causal, waves_if);
+    // Waves per workgroup: 16 when K + V (and the merge area: the full carve) leave room for one workgroup per CU only,
+    // else 8.  (9..12 waves, which would spread the 17 query tiles of S = 257 over two even passes, measure 0.22 ms
+    // against 0.17 ms for 8: the second workgroup no longer co-resides.)
+    const bool wide = kv + 16 * ATTN_PART * 4 > 80 * 1024;
+    const bool may_split = attn_lone_tile(a.S, a.causal, wide ? 16 : 8);
     const int lds = kv + (may_split ? 16 * ATTN_PART * 4 : 0);
     if (lds > 160 * 1024)
         return ec::fail(EC_ERR_UNSUPPORTED, "ec_attention: sequence length %d needs %d bytes of LDS (K and V images%s), "
                         "the CU has 163840: S <= 640%s", a.S, lds, may_split ? " + the split-tile merge area" : "",
                         may_split ? " (608 for this S, whose last query tile is split over the waves)" : "");
-    // Waves per workgroup: 16 when K + V leave room for one workgroup per CU only, else 8.  (9..12 waves,
-    // which would spread the 17 query tiles of S = 257 over two even passes, measure 0.22 ms against
-    // 0.17 ms for 8: the second workgroup no longer co-resides.)
-    const bool wide = kv + 16 * ATTN_PART * 4 > 80 * 1024;
-    void (*kern)(const AttnArgs) = a.lse ? (wide ? attention_kernel<DT, 16, true> : attention_kernel<DT, 8, true>)
-                                         : (wide ? attention_kernel<DT, 16> : attention_kernel<DT, 8>);
-    if (a.q_scaled == 1)   // the inference towers (never with a log-sum-exp)
-        kern = wide ? attention_kernel<DT, 16, false, QM_INPUT> : attention_kernel<DT, 8, false, QM_INPUT>;
-    if (a.q_scaled == 2)   // a plain q, every score scaled in fp32: q is rounded ONCE (the split-operand blocks behind the
-                           // fp32-attention ones; QM_KERNEL's second rounding of q cost configs[2] 30 % there)
-        kern = wide ? attention_kernel<DT, 16, false, QM_RAW> : attention_kernel<DT, 8, false, QM_RAW>;
+    // The kernel by [q_scaled, or 3 for a log-sum-exp][wide]:
+    //  0  the type's default QM
+    //  1  the inference towers (never with a log-sum-exp)
+    //  2  a plain q, every score scaled in fp32: q is rounded ONCE (the split-operand blocks behind the
+    //     fp32-attention ones; QM_KERNEL's second rounding of q cost configs[2] 30 % there)
+    //  3  the type's default QM with the log-sum-exp (ec_attention_train: q_scaled = 0)
+    static void (*const table[4][2])(const AttnArgs) = {
+        {attention_kernel<DT, 8>, attention_kernel<DT, 16>},
+        {attention_kernel<DT, 8, false, QM_INPUT>, attention_kernel<DT, 16, false, QM_INPUT>},
+        {attention_kernel<DT, 8, false, QM_RAW>, attention_kernel<DT, 16, false, QM_RAW>},
+        {attention_kernel<DT, 8, true>, attention_kernel<DT, 16, true>}};
+    void (*const kern)(const AttnArgs) = table[a.lse && a.q_scaled == 0 ? 3 : a.q_scaled][wide];
     const int nw = wide ? 16 : 8;
     // always the full carve (one attribute call per kernel and device, thread-safe)
     if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024)) return rc;
     // algorithmic work: QK^T and PV, 2 * 2 * S^2 * 64 flops per head; bytes: read qkv, write out
-    ec::ProfScope prof(ec::PROF_ATTENTION, s, 4.0 * a.q_rows * a.S * 64.0 * heads * n_seq,
+    ec::ProfScope prof(ec::PROF_ATTENTION, s, 4.0 * a.q_rows * a.S * 64.0 * a.heads * n_seq,
                        (double)n_seq * a.W * 2.0 * (2.0 * a.S + 2.0 * a.q_rows));
-    hipLaunchKernelGGL(kern, dim3((unsigned)heads * (unsigned)n_seq), dim3(nw * 64), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.heads * (unsigned)n_seq), dim3(nw * 64), lds, s, a);
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }
@@ -1128,14 +1095,9 @@ __global__ __launch_bounds__(256) void attention_f32m_kernel(const void *qkv_v, 
                 v4 hi, lo;
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    // the product as ONE rounded fp32 value for both parts: with -ffp-contract=fast hipcc otherwise
-                    // rounds hi from fl(o inv) but takes lo against a hi of its own rounded straight from the exact
-                    // product (v_fma_mixlo_f16), and where the two differ (a near-tie) lo comes out with the wrong
-                    // sign: one element in ~2000 off by a 16-bit ulp
-                    float x = o[dt][r] * inv;
-                    asm volatile("" : "+v"(x));
-                    hi[r] = to16(x, elem());
-                    lo[r] = to16(x - (float)hi[r], elem());
+                    elem h, l;
+                    split16(o[dt][r] * inv, h, l);
+                    hi[r] = h, lo[r] = l;
                 }
                 const long off = ((long)seq * S + query) * W + head * 64 + 16 * dt + 4 * g;
                 *reinterpret_cast<v4 *>((elem *)out_hi + off) = hi;
@@ -1155,29 +1117,49 @@ extern "C" __attribute__((visibility("default"))) int ec_attn_stamps_read(unsign
 }
 #endif
 
-static int attention_rows(const void *qkv, void *out, int n_seq, int S, int width, int heads, int causal, int q_rows,
-                          int q_scaled, int dtype, ec_stream_t stream)
+// the checks every entry point makes first, under the entry point's own name
+static int check_shape(const char *api, int n_seq, int S, int width, int heads)
+{
+    EC_REQUIRE(n_seq >= 0 && S > 0 && heads > 0, "%s: bad shape", api);
+    EC_REQUIRE(width == heads * 64, "%s: head dim must be 64 (width %d, heads %d)", api, width, heads);
+    return EC_OK;
+}
+
+static AttnArgs make_args(const void *qkv, void *out, float *lse, int S, int width, int heads, int causal, int q_rows, int q_scaled)
 {
     AttnArgs a;
     a.qkv = qkv, a.out = out, a.S = S, a.W = width, a.heads = heads, a.causal = causal;
     a.q_rows = q_rows;
-    a.lse = nullptr;
+    a.lse = lse;
     a.scale_log2e = 0.125f * 1.4426950408889634f;
     a.q_scaled = q_scaled;
+    return a;
+}
+
+static int launch16(const char *api, const AttnArgs &a, int n_seq, int dtype, ec_stream_t stream)
+{
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == EC_F16) return dispatch<EC_F16>(a, n_seq, heads, s);
-    if (dtype == EC_BF16) return dispatch<EC_BF16>(a, n_seq, heads, s);
-    return ec::fail(EC_ERR_INVALID, "ec_attention: unknown dtype %d", dtype);
+    if (dtype == EC_F16) return dispatch<EC_F16>(a, n_seq, s);
+    if (dtype == EC_BF16) return dispatch<EC_BF16>(a, n_seq, s);
+    return ec::fail(EC_ERR_INVALID, "%s: unknown dtype %d", api, dtype);
+}
+
+// ec_attention_rows and ec_attention_scaled_q
+static int attention_rows(const char *api, const void *qkv, void *out, int n_seq, int S, int width, int heads, int causal,
+                          int q_rows, int q_scaled, int dtype, ec_stream_t stream)
+{
+    if (int rc = check_shape(api, n_seq, S, width, heads)) return rc;
+    EC_REQUIRE(q_rows >= 1 && q_rows <= S, "%s: q_rows=%d outside 1..%d", api, q_rows, S);
+    if (n_seq == 0) return EC_OK;
+    EC_REQUIRE(qkv && out, "%s: null buffer", api);
+    return launch16(api, make_args(qkv, out, nullptr, S, width, heads, causal, q_rows, q_scaled), n_seq, dtype, stream);
 }
 
 // tower_ops.h: a plain q whose scores are scaled in fp32 (no second rounding of q), no mask
 int ec_tower::attention_exact_scale(const void *qkv, void *out, int n_seq, int S, int width, int heads, int dtype,
                                     ec_stream_t stream)
 {
-    EC_REQUIRE(n_seq >= 0 && S > 0 && heads > 0 && width == heads * 64, "attention_exact_scale: bad shape");
-    if (n_seq == 0) return EC_OK;
-    EC_REQUIRE(qkv && out, "attention_exact_scale: null buffer");
-    return attention_rows(qkv, out, n_seq, S, width, heads, 0, S, 2, dtype, stream);
+    return attention_rows("attention_exact_scale", qkv, out, n_seq, S, width, heads, 0, S, 2, dtype, stream);
 }
 
 extern "C" EC_API int ec_attention(const void *qkv, void *out, int n_seq, int S, int width,
@@ -1190,51 +1172,29 @@ extern "C" EC_API int ec_attention_rows(const void *qkv, void *out, int n_seq, i
                                         int heads, int causal, int q_rows, int dtype,
                                         ec_stream_t stream)
 {
-    EC_REQUIRE(n_seq >= 0 && S > 0 && heads > 0, "ec_attention: bad shape");
-    EC_REQUIRE(q_rows >= 1 && q_rows <= S, "ec_attention: q_rows=%d outside 1..%d", q_rows, S);
-    EC_REQUIRE(width == heads * 64, "ec_attention: head dim must be 64 (width %d, heads %d)", width,
-               heads);
-    if (n_seq == 0) return EC_OK;
-    EC_REQUIRE(qkv && out, "ec_attention: null buffer");
-    return attention_rows(qkv, out, n_seq, S, width, heads, causal, q_rows, 0, dtype, stream);
+    return attention_rows("ec_attention", qkv, out, n_seq, S, width, heads, causal, q_rows, 0, dtype, stream);
 }
 
 extern "C" EC_API int ec_attention_scaled_q(const void *qkv, void *out, int n_seq, int S, int width, int heads,
                                             int causal, int q_rows, int dtype, ec_stream_t stream)
 {
-    EC_REQUIRE(n_seq >= 0 && S > 0 && heads > 0, "ec_attention_scaled_q: bad shape");
-    EC_REQUIRE(q_rows >= 1 && q_rows <= S, "ec_attention_scaled_q: q_rows=%d outside 1..%d", q_rows, S);
-    EC_REQUIRE(width == heads * 64, "ec_attention_scaled_q: head dim must be 64 (width %d, heads %d)", width, heads);
-    if (n_seq == 0) return EC_OK;
-    EC_REQUIRE(qkv && out, "ec_attention_scaled_q: null buffer");
-    return attention_rows(qkv, out, n_seq, S, width, heads, causal, q_rows, 1, dtype, stream);
+    return attention_rows("ec_attention_scaled_q", qkv, out, n_seq, S, width, heads, causal, q_rows, 1, dtype, stream);
 }
 
 extern "C" EC_API int ec_attention_train(const void *qkv, void *out, float *lse, int n_seq, int S, int width,
                                          int heads, int dtype, ec_stream_t stream)
 {
-    EC_REQUIRE(n_seq >= 0 && S > 0 && heads > 0, "ec_attention_train: bad shape");
-    EC_REQUIRE(width == heads * 64, "ec_attention_train: head dim must be 64 (width %d, heads %d)", width, heads);
+    if (int rc = check_shape("ec_attention_train", n_seq, S, width, heads)) return rc;
     if (n_seq == 0) return EC_OK;
     EC_REQUIRE(qkv && out && lse, "ec_attention_train: null buffer");
-    AttnArgs a;
-    a.qkv = qkv, a.out = out, a.S = S, a.W = width, a.heads = heads, a.causal = 0;
-    a.q_rows = S;
-    a.lse = lse;
-    a.scale_log2e = 0.125f * 1.4426950408889634f;
-    a.q_scaled = 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == EC_F16) return dispatch<EC_F16>(a, n_seq, heads, s);
-    if (dtype == EC_BF16) return dispatch<EC_BF16>(a, n_seq, heads, s);
-    return ec::fail(EC_ERR_INVALID, "ec_attention_train: unknown dtype %d", dtype);
+    return launch16("ec_attention_train", make_args(qkv, out, lse, S, width, heads, 0, S, 0), n_seq, dtype, stream);
 }
 
 extern "C" EC_API int ec_attention_f32(const float *qkv, void *out_hi, void *out_lo, int n_seq, int S,
                                        int width, int heads, int causal, int dtype,
                                        ec_stream_t stream)
 {
-    EC_REQUIRE(n_seq >= 0 && S > 0 && heads > 0, "ec_attention_f32: bad shape");
-    EC_REQUIRE(width == heads * 64, "ec_attention_f32: head dim must be 64");
+    if (int rc = check_shape("ec_attention_f32", n_seq, S, width, heads)) return rc;
     if (n_seq == 0) return EC_OK;
     EC_REQUIRE(qkv && out_hi && out_lo, "ec_attention_f32: null buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1253,45 +1213,55 @@ extern "C" EC_API int ec_attention_f32(const float *qkv, void *out_hi, void *out
     return EC_OK;
 }
 
+// Which kernel ec_attention_split takes and its LDS carve: the only place these predicates live (tests/attention_ref.hl_path
+// restates them).  `plain_f16`: f16 planes with a plain q -- three products per tile on the 16-bit matrix instruction:
+//  HL_ONE   the four planes (and the merge area of a split last tile) fit the CU's LDS: attention_hl_kernel
+//  HL_TWO   they fit in two passes over the keys, [0, split) and [split, S), of `spl` LDS rows per plane (the longer second
+//           pass: whole 32-key steps, or behind an odd key its 16 copies), and a wave has at most HL2_TILES query tiles
+//           (S <= 608): attention_hl2_kernel
+//  HL_FP32  anything longer, a pre-scaled q, bf16 planes: attention_f32m_kernel on v_mfma_f32_16x16x4_f32
+struct HlPlan {
+    enum { HL_ONE, HL_TWO, HL_FP32 } kind;
+    int lds, split, spl;
+};
+static HlPlan hl_plan(int S, bool plain_f16)
+{
+    if (!plain_f16) return {HlPlan::HL_FP32, 0, 0, 0};
+    const int sp = 32 * ((S + 31) / 32);
+    const int one = 4 * sp * 128 + (attn_lone_tile(S, 0, HL_WAVES) ? HL_WAVES * ATTN_PART * 4 : 0);
+    if (one <= 160 * 1024) return {HlPlan::HL_ONE, one, 0, 0};
+    const int split = (S / 2) & ~31, sl = S - split;
+    const int spl = (sl & 31) == 1 ? ((sl + 15 + 15) / 16) * 16 : ((sl + 31) / 32) * 32;
+    if (split >= 32 && 4 * spl * 128 <= 160 * 1024 && (S + 15) / 16 <= HL_WAVES * HL2_TILES) return {HlPlan::HL_TWO, 4 * spl * 128, split, spl};
+    return {HlPlan::HL_FP32, 0, 0, 0};
+}
+
 extern "C" EC_API int ec_attention_split(const void *qkv_hi, const void *qkv_lo, void *out_hi, void *out_lo, int n_seq, int S,
                                          int width, int heads, int q_prescaled, int dtype, ec_stream_t stream)
 {
-    EC_REQUIRE(n_seq >= 0 && S > 0 && heads > 0, "ec_attention_split: bad shape");
-    EC_REQUIRE(width == heads * 64, "ec_attention_split: head dim must be 64");
+    if (int rc = check_shape("ec_attention_split", n_seq, S, width, heads)) return rc;
     if (n_seq == 0) return EC_OK;
     EC_REQUIRE(qkv_hi && qkv_lo && out_hi && out_lo, "ec_attention_split: null buffer");
     EC_REQUIRE((((uintptr_t)qkv_hi | (uintptr_t)qkv_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15) == 0,
                "ec_attention_split: buffers must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_ATTENTION, s, 4.0 * S * S * 64.0 * heads * n_seq, (double)n_seq * S * width * 2.0 * 8.0);
-    // a plain f16 q and a sequence whose four planes fit the CU's LDS: three products per tile on the 16-bit matrix
-    // instruction (attention_hl_kernel); anything else: fp32 on v_mfma_f32_16x16x4_f32
-    const int sp = 32 * ((S + 31) / 32);
-    const int hl_lds = 4 * sp * 128 + (attn_lone_tile(S, 0, HL_WAVES) ? HL_WAVES * ATTN_PART * 4 : 0);
-    if (dtype == EC_F16 && !q_prescaled && hl_lds <= 160 * 1024) {
+    const HlPlan plan = hl_plan(S, dtype == EC_F16 && !q_prescaled);
+    if (plan.kind != HlPlan::HL_FP32) {
         AttnHlArgs h;
         h.qkv_hi = static_cast<const _Float16 *>(qkv_hi), h.qkv_lo = static_cast<const _Float16 *>(qkv_lo);
         h.out_hi = static_cast<_Float16 *>(out_hi), h.out_lo = static_cast<_Float16 *>(out_lo);
         h.S = S, h.W = width, h.heads = heads;
-        if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(attention_hl_kernel), 160 * 1024)) return rc;
-        hipLaunchKernelGGL(attention_hl_kernel, dim3((unsigned)heads * (unsigned)n_seq), dim3(HL_WAVES * 64), hl_lds, s, h);
+        const dim3 grid((unsigned)heads * (unsigned)n_seq), block(HL_WAVES * 64);
+        if (plan.kind == HlPlan::HL_ONE) {
+            if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(attention_hl_kernel), 160 * 1024)) return rc;
+            hipLaunchKernelGGL(attention_hl_kernel, grid, block, plan.lds, s, h);
+        } else {
+            if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(attention_hl2_kernel), 160 * 1024)) return rc;
+            hipLaunchKernelGGL(attention_hl2_kernel, grid, block, plan.lds, s, h, plan.split, plan.spl);
+        }
         EC_CHECK_HIP(hipGetLastError());
         return EC_OK;
-    }
-    // ... or whose planes fit in two passes over the keys (S <= 608): attention_hl2_kernel
-    {
-        const int split = (S / 2) & ~31, sl = S - split;
-        const int spl = (sl & 31) == 1 ? ((sl + 15 + 15) / 16) * 16 : ((sl + 31) / 32) * 32;     // the odd key's 16 copies, else whole steps
-        if (dtype == EC_F16 && !q_prescaled && split >= 32 && 4 * spl * 128 <= 160 * 1024 && (S + 15) / 16 <= HL_WAVES * HL2_TILES) {
-            AttnHlArgs h;
-            h.qkv_hi = static_cast<const _Float16 *>(qkv_hi), h.qkv_lo = static_cast<const _Float16 *>(qkv_lo);
-            h.out_hi = static_cast<_Float16 *>(out_hi), h.out_lo = static_cast<_Float16 *>(out_lo);
-            h.S = S, h.W = width, h.heads = heads;
-            if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(attention_hl2_kernel), 160 * 1024)) return rc;
-            hipLaunchKernelGGL(attention_hl2_kernel, dim3((unsigned)heads * (unsigned)n_seq), dim3(HL_WAVES * 64), 4 * spl * 128, s, h, split, spl);
-            EC_CHECK_HIP(hipGetLastError());
-            return EC_OK;
-        }
     }
     const long blocks = (long)n_seq * heads * ((S + 63) / 64);
     EC_REQUIRE(blocks < (1L << 31), "ec_attention_split: %ld workgroups", blocks);

@@ -555,7 +555,7 @@ __device__ __forceinline__ void epilogue16_buf(const GemmArgs &g, f32x4 (&acc)[T
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     float x = v[r];
-                    asm volatile("" : "+v"(x));      // ONE rounded fp32 value for both parts (see attention_f32m_kernel)
+                    asm volatile("" : "+v"(x));      // ONE rounded fp32 value for both parts (see mfma.h's split16; lo stays fp32 here)
                     o[4 * j + r] = to16(x, elem());
                     l32[4 * j + r] = x - (float)o[4 * j + r];
                     l[4 * j + r] = to16(l32[4 * j + r], elem());

@@ -42,6 +42,18 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c)
 __device__ __forceinline__ _Float16 to16(float x, _Float16) { return (_Float16)x; }
 __device__ __forceinline__ __bf16 to16(float x, __bf16) { return (__bf16)x; }
 
+// x as hi + lo 16-bit parts (T = _Float16 or __bf16): hi rounded from x, lo from x - hi.  x is pinned first, so that
+// it is ONE rounded fp32 value for both parts: with -ffp-contract=fast hipcc otherwise rounds hi from fl(a b) (x is
+// usually a product, o * 1 / l) but takes lo against a hi of its own rounded straight from the exact product
+// (v_fma_mixlo_f16), and where the two differ (a near-tie) lo comes out with the wrong sign: one element in ~2000
+// off by a 16-bit ulp.  (A vector's element does not bind to T &: split into scalars, then assign.)
+template <typename T> __device__ __forceinline__ void split16(float x, T &hi, T &lo)
+{
+    asm volatile("" : "+v"(x));
+    hi = (T)x;
+    lo = (T)(x - (float)hi);
+}
+
 // 16-byte global -> LDS DMA (no VGPR destination).  lds must be wave-uniform: the
 // hardware writes lane i's 16 bytes at lds + 16*i.
 __device__ __forceinline__ void glds16(const void *g, void *lds)

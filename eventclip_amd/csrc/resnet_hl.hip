@@ -23,7 +23,7 @@ constexpr int CB_M = 128, CB_N = 128, CB_K = 64, CB_LD = CB_K + 8;   // as conv_
 constexpr float LO_UP = 2048.f, LO_DOWN = 1.f / 2048.f;
 
 __device__ __forceinline__ float join_hl(_Float16 hi, _Float16 lo) { return (float)hi + (float)lo * LO_DOWN; }
-__device__ __forceinline__ void split_hl(float v, _Float16 &hi, _Float16 &lo)
+__device__ __forceinline__ void split_hl(float v, _Float16 &hi, _Float16 &lo)   // mfma.h's split16 with lo scaled up
 {
     hi = (_Float16)v;
     lo = (_Float16)((v - (float)hi) * LO_UP);
