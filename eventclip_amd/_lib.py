@@ -138,6 +138,10 @@ class EcPackItem(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ('w', 'hi', 'lo', 'hi_t')]
 
 
+class EcSpanItem(ctypes.Structure):
+    _fields_ = [('ptr', c_void_p), ('n', ctypes.c_int64)]
+
+
 class EcAdamItem(ctypes.Structure):
     _fields_ = [('param', c_void_p), ('grad', c_void_p), ('exp_avg', c_void_p), ('exp_avg_sq', c_void_p),
                 ('n', ctypes.c_int64), ('group', c_int)]
@@ -301,8 +305,13 @@ SIGNATURES = {
     'ec_vit_train_backward_stages': (c_int, [ctypes.POINTER(EcVitWeights), ctypes.POINTER(EcVitTrainWeights), c_void_p,
                                              c_int, c_void_p, ctypes.POINTER(EcVitGrads), ctypes.POINTER(EcVitLora), c_int,
                                              c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    'ec_vit_train_backward_scratch_bytes': (ctypes.c_size_t, [ctypes.POINTER(EcVitWeights), c_int]),
+    'ec_vit_train_backward_over': (c_int, [ctypes.POINTER(EcVitWeights), ctypes.POINTER(EcVitTrainWeights), c_void_p,
+                                           c_int, c_void_p, ctypes.POINTER(EcVitGrads), ctypes.POINTER(EcVitLora), c_void_p,
+                                           ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p]),
     'ec_vit_train_layout': (c_int, [ctypes.POINTER(EcVitWeights), c_int, c_void_p, c_int]),
     'ec_pack_weight16_batched': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'ec_fingerprint_batched': (c_int, [c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p]),
     'ec_layernorm_backward_partials': (ctypes.c_size_t, [c_int, c_int]),
     'ec_layernorm_backward': (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_float,
                                       c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -341,7 +350,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 603      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
+ABI_VERSION = 604      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
 
 
 class HipLibraryError(RuntimeError):

@@ -260,6 +260,13 @@ class CLIP(ClipBase):
             return self._packed
         dev = self._pack_device()
         sd = {k: v.detach() for k, v in self.state_dict().items()}
+        if any('.lora_' in k for k in sd):
+            # an autograd-enabled FTCLIPClassifier injected LoRA modules into ``visual``: the inference copies hold the
+            # effective weights base + up @ down under the plain names
+            from .lora import merge_lora_visual
+            vis = merge_lora_visual({k[len('visual.'):]: v for k, v in sd.items() if k.startswith('visual.')})
+            sd = {k: v for k, v in sd.items() if not k.startswith('visual.')}
+            sd.update({'visual.' + k: v for k, v in vis.items()})
         cd = self.compute_dtype
         pk = Packer(sd, dev, cd, self.cfg, keep_zero_lo=getattr(self, 'keep_zero_lo', False))
         dev32, dev16, dev16_pair = pk.dev32, pk.dev16, pk.dev16_pair

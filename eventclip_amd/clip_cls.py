@@ -284,8 +284,9 @@ class FSCLIPClassifier(ZSCLIPClassifier):
 
 
 def build_model(params):
-    """models/__init__.py:5-21.  'FTCLIP' gives the serving form of FTCLIPClassifier (forward and
-    checkpoints; fine-tuning of CLIP itself is out of scope)."""
+    """models/__init__.py:5-21.  ``params.clip_dict`` goes to the classifier untouched: 'FTCLIP' gives the serving
+    form of FTCLIPClassifier (forward and checkpoints; ``eventclip_amd.ft.FTTrainer`` fine-tunes it), and with
+    ``clip_dict['autograd'] = True`` the form the reference's own loop trains with ``loss.backward()``."""
     kind = params.model
     if kind == 'ZSCLIP':
         return ZSCLIPClassifier(clip_dict=params.clip_dict)

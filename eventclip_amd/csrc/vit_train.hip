@@ -406,6 +406,20 @@ __global__ __launch_bounds__(256) void pack_weight_kernel(const ec_pack_item *it
     }
 }
 
+// Fingerprint of a list of fp32 tensors: per tensor, the sum over its words of bits * (an odd multiplier of the word's
+// position) modulo 2^64.  Changing any one word changes the sum; integer addition commutes, so the order in which the
+// workgroups arrive does not matter.  `out` is zero on entry.
+__global__ __launch_bounds__(256) void fingerprint_kernel(const ec_span_item *items, unsigned long long *out)
+{
+    const ec_span_item it = items[blockIdx.y];
+    const uint32_t *w = static_cast<const uint32_t *>(it.ptr);
+    unsigned long long acc = 0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < it.n; i += (long)gridDim.x * 256)
+        acc += (unsigned long long)w[i] * (0x9E3779B97F4A7C15ull * (2ull * (unsigned long long)i + 1ull));
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out + blockIdx.y, acc);
+}
+
 // ------------------------------------------------------------------------------------------
 // LoRA (models/lora.py): the factors act through merged weights W + up @ down and receive their gradients
 // from the merged weight's: d up = dW down^T, d down = up^T dW.  r <= 64; fp32; a few MB per matrix.
@@ -966,37 +980,41 @@ struct TrainBufs {
     int lr_slab, lr_slabs;
 };
 
-size_t carve_train(Scratch &sc, const ec_vit_weights *w, int n, TrainBufs &b)
+// own: the scratch of the passes comes from a buffer of its own instead of following the tape in `sc` (a backward pass
+// that leaves the tape's buffer untouched); the return value is then the tape's bytes alone, own->off the scratch's
+size_t carve_train(Scratch &tape, const ec_vit_weights *w, int n, TrainBufs &b, Scratch *own = nullptr)
 {
     const int g = w->image_size / w->patch, G = g * g, S = G + 1, W = w->width, L = w->layers;
     const size_t M = (size_t)n * S;
     const int Mp = padded_rows((int)M);
     b.Mp = Mp;
-    b.pre = (float *)sc.take(M * W * 4);
-    for (int l = 0; l <= L; l++) b.x[l] = (float *)sc.take(M * W * 4);
+    b.pre = (float *)tape.take(M * W * 4);
+    for (int l = 0; l <= L; l++) b.x[l] = (float *)tape.take(M * W * 4);
     for (int l = 0; l < L; l++) {
-        b.xm[l] = (float *)sc.take(M * W * 4);
-        b.qkv[l] = sc.take(M * 3 * W * 2);
-        b.att[l] = sc.take(M * W * 2);
-        b.u[l] = sc.take(M * 4 * W * 2);
-        b.gact[l] = sc.take(M * 4 * W * 2);
-        b.h1[l] = sc.take(M * W * 2);
-        b.h2[l] = sc.take(M * W * 2);
-        b.lse[l] = (float *)sc.take((size_t)n * w->heads * S * 4);
+        b.xm[l] = (float *)tape.take(M * W * 4);
+        b.qkv[l] = tape.take(M * 3 * W * 2);
+        b.att[l] = tape.take(M * W * 2);
+        b.u[l] = tape.take(M * 4 * W * 2);
+        b.gact[l] = tape.take(M * 4 * W * 2);
+        b.h1[l] = tape.take(M * W * 2);
+        b.h2[l] = tape.take(M * W * 2);
+        b.lse[l] = (float *)tape.take((size_t)n * w->heads * S * 4);
     }
-    b.g16 = sc.take(M * 4 * W * 2);          // >= n G W 4 bytes: also the patch GEMM's fp32 output
-    b.cls_hi = sc.take((size_t)n * W * 2);
-    b.cls_lo = sc.take((size_t)n * W * 2);
-    b.dx = (float *)sc.take(M * W * 4);
-    b.dh32 = (float *)sc.take(M * W * 4);
-    b.delta = (float *)sc.take((size_t)n * w->heads * S * 4);
-    b.clsln = (float *)sc.take((size_t)n * W * 4);
-    b.dclsln = (float *)sc.take((size_t)n * W * 4);
-    b.dx16 = sc.take(M * W * 2);
-    b.da16 = sc.take(M * W * 2);
+    const size_t tape_bytes = tape.off;
+    Scratch &scr = own ? *own : tape;
+    b.g16 = scr.take(M * 4 * W * 2);          // >= n G W 4 bytes: also the patch GEMM's fp32 output
+    b.cls_hi = scr.take((size_t)n * W * 2);
+    b.cls_lo = scr.take((size_t)n * W * 2);
+    b.dx = (float *)scr.take(M * W * 4);
+    b.dh32 = (float *)scr.take(M * W * 4);
+    b.delta = (float *)scr.take((size_t)n * w->heads * S * 4);
+    b.clsln = (float *)scr.take((size_t)n * W * 4);
+    b.dclsln = (float *)scr.take((size_t)n * W * 4);
+    b.dx16 = scr.take(M * W * 2);
+    b.da16 = scr.take(M * W * 2);
     // transposed copies: only the patch embedding's weight gradient still takes them (its rows skip the class tokens)
-    b.ta = sc.take((size_t)W * Mp * 2);
-    b.tb = sc.take((size_t)w->kpad * Mp * 2);
+    b.ta = scr.take((size_t)W * Mp * 2);
+    b.tb = scr.take((size_t)w->kpad * Mp * 2);
     size_t pf = 0;
     const int shapes[5][2] = {{3 * W, W}, {W, W}, {4 * W, W}, {W, 4 * W}, {W, w->kpad}};
     for (int i = 0; i < 5; i++) {
@@ -1006,18 +1024,18 @@ size_t carve_train(Scratch &sc, const ec_vit_weights *w, int n, TrainBufs &b)
         pf = fr > pf ? fr : pf;
     }
     b.part_floats = pf;
-    b.part = (float *)sc.take(pf * 4);
+    b.part = (float *)scr.take(pf * 4);
     b.ln_wgs = (int)((M + 3) / 4 < 1024 ? (M + 3) / 4 : 1024);
-    b.lnpart = (float *)sc.take((size_t)b.ln_wgs * 2 * W * 4);
+    b.lnpart = (float *)scr.take((size_t)b.ln_wgs * 2 * W * 4);
     b.W = W;
     b.col_slabs = 256;
-    b.colpart = (float *)sc.take((size_t)b.col_slabs * 4 * W * 4);
+    b.colpart = (float *)scr.take((size_t)b.col_slabs * 4 * W * 4);
     b.lr_slab = 256;                                                       // the shortest row slab of an outer product
     b.lr_slabs = (int)((M + b.lr_slab - 1) / b.lr_slab);
-    b.lr_proj = sc.take((M + 32) * 64 * 2 * 2 * 4);                        // four [2][<= 64][Mp] 16-bit coefficient slots
-    b.lr_part = (float *)sc.take((size_t)b.lr_slabs * 64 * W * 4 * 4);     // four [slabs, <= 64, W] partial blocks
-    b.lr_frag = sc.take((size_t)8 * 64 * W * 2);                           // eight factors [<= 64, W] in fragment order
-    return sc.off;
+    b.lr_proj = scr.take((M + 32) * 64 * 2 * 2 * 4);                        // four [2][<= 64][Mp] 16-bit coefficient slots
+    b.lr_part = (float *)scr.take((size_t)b.lr_slabs * 64 * W * 4 * 4);     // four [slabs, <= 64, W] partial blocks
+    b.lr_frag = scr.take((size_t)8 * 64 * W * 2);                           // eight factors [<= 64, W] in fragment order
+    return own ? tape_bytes : tape.off;
 }
 
 int check_geometry(const ec_vit_weights *w, const char *who)
@@ -1408,10 +1426,45 @@ EC_API int ec_vit_train_backward(const ec_vit_weights *w, const ec_vit_train_wei
 // Stages: 0 = the head (ln_post, proj), 1 .. L = blocks L - 1 .. 0, L + 1 = the embedding.  The state between
 // stages (the residual-stream gradient and its 16-bit copy) lives in the workspace, so a caller can run a few
 // blocks, hand their finished gradients to a collective on another stream, and carry on.
+static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches, int n_img,
+                           const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora, int stage_begin,
+                           int stage_end, void *workspace, size_t workspace_bytes, void *scratch, size_t scratch_bytes,
+                           ec_stream_t stream);
+
 EC_API int ec_vit_train_backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
                                         int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
                                         int stage_begin, int stage_end, void *workspace, size_t workspace_bytes,
                                         ec_stream_t stream)
+{
+    return backward_stages(w, wt, patches, n_img, d_feats, gr, lora, stage_begin, stage_end, workspace, workspace_bytes,
+                           nullptr, 0, stream);
+}
+
+EC_API size_t ec_vit_train_backward_scratch_bytes(const ec_vit_weights *w, int n_img)
+{
+    if (!w || n_img <= 0 || w->patch <= 0 || w->layers < 1 || w->layers > 64) return 0;
+    Scratch tape{nullptr, 0, 0}, own{nullptr, 0, 0};
+    TrainBufs b;
+    carve_train(tape, w, n_img, b, &own);
+    return own.off;
+}
+
+// The whole pass with the tape only read: the scratch that ec_vit_train_backward keeps behind the tape in the same
+// buffer comes from the caller (ec_vit_train_backward_scratch_bytes), so the tape's buffer is not written at all.
+EC_API int ec_vit_train_backward_over(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
+                                      int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
+                                      const void *tape, size_t tape_bytes, void *scratch, size_t scratch_bytes,
+                                      ec_stream_t stream)
+{
+    EC_REQUIRE(scratch, "ec_vit_train_backward_over: null scratch");
+    return backward_stages(w, wt, patches, n_img, d_feats, gr, lora, 0, w ? w->layers + 2 : 0, const_cast<void *>(tape),
+                           tape_bytes, scratch, scratch_bytes, stream);
+}
+
+static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches, int n_img,
+                           const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora, int stage_begin,
+                           int stage_end, void *workspace, size_t workspace_bytes, void *scratch, size_t scratch_bytes,
+                           ec_stream_t stream)
 {
     EC_TRY(check_geometry(w, "ec_vit_train_backward"));
     EC_REQUIRE(stage_begin >= 0 && stage_begin <= stage_end && stage_end <= w->layers + 2,
@@ -1425,10 +1478,13 @@ EC_API int ec_vit_train_backward_stages(const ec_vit_weights *w, const ec_vit_tr
     const int M = n_img * S, D = w->out_dim;
     auto has_lora = [&](int l, int p) { return lora && lora->blocks[l].d_up[p] != nullptr; };
     Scratch sc{(unsigned char *)workspace, 0, workspace_bytes};
+    Scratch own{(unsigned char *)scratch, 0, scratch_bytes};
     TrainBufs b;
-    const size_t need = carve_train(sc, w, n_img, b);
+    const size_t need = carve_train(sc, w, n_img, b, scratch ? &own : nullptr);
     if (need > workspace_bytes)
         return ec::fail(EC_ERR_WORKSPACE, "ec_vit_train_backward: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (scratch && own.off > scratch_bytes)
+        return ec::fail(EC_ERR_WORKSPACE, "ec_vit_train_backward_over: scratch %zu < %zu bytes", scratch_bytes, own.off);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int Mp = b.Mp;
 
@@ -1561,6 +1617,23 @@ EC_API int ec_pack_weight16_batched(const ec_pack_item *items, int n_items, int 
         hipLaunchKernelGGL(pack_weight_kernel<EC_BF16>, grid, dim3(256), 0, s, items, rows, cols);
     else
         return ec::fail(EC_ERR_INVALID, "ec_pack_weight16_batched: unknown dtype %d", dtype);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
+EC_API int ec_fingerprint_batched(const ec_span_item *items, int n_items, int64_t max_n, uint64_t *out, ec_stream_t stream)
+{
+    EC_REQUIRE(n_items >= 0 && max_n >= 0, "ec_fingerprint_batched: %d items of at most %lld words", n_items, (long long)max_n);
+    if (n_items == 0) return EC_OK;
+    EC_REQUIRE(items && out, "ec_fingerprint_batched: null buffer");
+    EC_REQUIRE(n_items <= 65535, "ec_fingerprint_batched: %d items (at most 65535 per call)", n_items);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EC_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)n_items * sizeof(uint64_t), s));
+    long blocks = ((long)max_n + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks > 64 ? 64 : blocks);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit sums");
+    hipLaunchKernelGGL(fingerprint_kernel, dim3((unsigned)blocks, (unsigned)n_items), dim3(256), 0, s, items,
+                       reinterpret_cast<unsigned long long *>(out));
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }

@@ -14,6 +14,9 @@ train.py:121) -- is here three layers over the C ABI:
 ``FTTrainer``     one optimisation step: loss and feature gradients (``ec_ft_loss_grad``), the gradient scaler
                   of mixed precision (``ec_grad_unscale_check``), one all-reduce of the flat gradient buffer
                   across ranks, ``ec_adam_step`` per tensor with the warm-up + cosine schedule.
+Under torch autograd (``FTCLIPClassifier(clip_dict=dict(..., autograd=True))``, ``eventclip_hip::vit_train_fwd`` / ``_bwd``)
+the first two layers serve alone: the optimiser is torch's, and ``VisualTower.refresh`` keeps the operand copies behind
+whatever it writes.
 No CPU fallback: every numeric step is a HIP kernel.
 """
 import ctypes
@@ -39,6 +42,14 @@ _MATRICES = ('qkv_w', 'out_w', 'fc1_w', 'fc2_w')
 
 def _block_name(i, leaf):
     return f'transformer.resblocks.{i}.{leaf}'
+
+
+def plain_visual_name(name):
+    """A name under ``model.visual`` as the reference's LoRA-injected modules spell it (``inject_lora_modules``) ->
+    the plain state-dict name of that master; None for a LoRA factor."""
+    if '.lora_' in name:
+        return None
+    return name.replace('.in_proj_weight.merged_proj', '.in_proj_weight').replace('.out_proj.linear.', '.out_proj.')
 
 
 def pack_table(jobs):
@@ -102,11 +113,18 @@ class VisualTower:
         self.S = self.G + 1
         self.cd = clip_model.compute_dtype
         self.code = _lib.EC_F16 if self.cd == torch.float16 else _lib.EC_BF16
-        self.master = {}
+        self.master, self.param = {}, {}
         for name, p in clip_model.visual.named_parameters():
+            name = plain_visual_name(name)
+            if name is None:              # a factor of injected LoRA modules: ``LoraFactors`` takes those
+                continue
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 p.data = p.data.to(dev, torch.float32).contiguous()
             self.master[name] = p.data
+            self.param[name] = p          # the module's own Parameter: ``requires_grad`` says whether it trains
+        self.lora = None                  # the LoraFactors injected into this tower, if any
+        self._seen = self._fp = None      # the fingerprints ``refresh`` last packed; its item table
+        self._train_flags = self._train_names = None
         self.effective = {}
         k = 3 * self.P * self.P
         self.k, self.kpad, self.klo = k, ((2 * k + 63) // 64) * 64, ((k + 63) // 64) * 64
@@ -195,9 +213,64 @@ class VisualTower:
             pk['proj_lo_t'].copy_(pk['proj_lo_tmp'].t())
         self.clip._packed = None       # the inference copies of clip.py are stale once a master moved
 
+    def _fingerprints(self):
+        """One 64-bit fingerprint per master, then per LoRA factor (``ec_fingerprint_batched``: one launch; the
+        read-back waits for the stream, i.e. for whatever was still writing them)."""
+        lf = self.lora
+        if self._fp is None or self._fp[0] is not lf:
+            tensors = list(self.master.values()) + (list(lf.params.values()) if lf else [])
+            items = (_lib.EcSpanItem * len(tensors))()
+            for it, t in zip(items, tensors):
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                it.ptr, it.n = t.data_ptr(), t.numel()
+            self._fp = (lf, device_table(items), len(tensors), max(t.numel() for t in tensors),
+                        torch.empty((len(tensors),), dtype=torch.int64, device=self.dev), tensors)
+        _, table, n, max_n, out, _ = self._fp
+        _lib.launch('ec_fingerprint_batched', table, n, max_n, out)
+        return out.tolist()
+
+    def refresh(self):
+        """Bring the operand copies up to date under torch autograd, where anybody may write a master or a factor:
+        ``opt.step()``, ``load_state_dict``, ``p.mul_()`` under ``no_grad``, ``p.data.mul_()``.  The last of these moves no
+        version counter, so the tensors' contents are compared, as fingerprints: what changed since the last call is
+        re-merged (``ec_lora_merge_batched``) and repacked (``ec_pack_weight16_batched``, batched by shape as ``pack``
+        does).  Nothing changed: no repack.  -> whether anything was rebuilt."""
+        lf = self.lora
+        now = self._fingerprints()
+        if now == self._seen:
+            return False
+        if self._seen is None:            # __init__ packed every master; the factors have not been merged yet
+            moved, factors = set(), lf is not None
+        else:
+            moved = {n for n, a, b in zip(self.master, now, self._seen) if a != b}
+            factors = now[len(self.master):] != self._seen[len(self.master):]
+        todo = moved & set(self.matrix_names())
+        if lf and (factors or todo & set(lf.merged_names)):
+            if todo & set(lf.merged_names):
+                lf.copy_plain_rows()
+            lf.merge()
+            todo -= set(lf.merged_names)
+        if todo:
+            self.pack(todo)
+        self.clip._packed = None          # biases, LayerNorm terms and embeddings are read in place: only clip.py's copies
+        self._seen = now
+        return True
+
+    def trainable(self):
+        """The masters whose Parameter requires grad, in ``canonical()`` order (cached on the flags)."""
+        flags = tuple(p.requires_grad for p in self.param.values())
+        if flags != self._train_flags:
+            self._train_names = self.canonical([n for n, p in self.param.items() if p.requires_grad])
+            self._train_flags = flags
+        return self._train_names
+
     # ---- passes ----
+    def workspace_bytes(self, n):
+        """Bytes of the training workspace (tape + both passes' scratch) for n images."""
+        return int(_lib.lib().ec_vit_train_workspace_bytes(ctypes.byref(self._vit), n))
+
     def _workspace(self, n):
-        return self._ws.get(int(_lib.lib().ec_vit_train_workspace_bytes(ctypes.byref(self._vit), n)), self.dev)
+        return self._ws.get(self.workspace_bytes(n), self.dev)
 
     def forward(self, patches):
         """patches: 16-bit CUDA [N, G, kpad] -> fp32 features [N, D]; keeps the tape for ``backward``."""
@@ -262,25 +335,31 @@ class VisualTower:
             self._grad_slots[key] = _lib.flat_views({n: self.master[n].shape for n in want}, self.dev, min_numel=4)
         return self._grad_slots[key]
 
+    def grads_over(self, tensors):
+        """{state-dict name: fp32 CUDA tensor of the master's size} -> (EcVitGrads pointing at them, its block array:
+        the caller keeps both, and the tensors, alive over the launch)."""
+        bg = (_lib.EcBlockGrads * self.L)()
+        g = _lib.EcVitGrads()
+        top = {leaf: f for f, leaf in _TOP}
+        blk = {leaf: f for f, leaf in _BLOCK}
+        for name, t in tensors.items():
+            if name in top:
+                setattr(g, top[name], t.data_ptr())
+            else:
+                m = re.match(r'^transformer\.resblocks\.(\d+)\.(.+)$', name)
+                if not m or m.group(2) not in blk:
+                    raise KeyError(f'{name!r} is not a parameter of the vision tower')
+                setattr(bg[int(m.group(1))], blk[m.group(2)], t.data_ptr())
+        g.blocks = ctypes.cast(bg, ctypes.POINTER(_lib.EcBlockGrads))
+        return g, bg
+
     def _grad_struct(self, want):
         """(EcVitGrads over the flat buffer's views, views, flat, {name: (offset, numel)}) for a want list, cached."""
         key = tuple(want)
         if key not in self._grad_structs:
             flat, views = self.grad_buffer(want)
-            bg = (_lib.EcBlockGrads * self.L)()
-            g = _lib.EcVitGrads()
-            top = {leaf: f for f, leaf in _TOP}
-            blk = {leaf: f for f, leaf in _BLOCK}
             spans = {name: (t.storage_offset(), t.numel()) for name, t in views.items()}
-            for name, t in views.items():
-                if name in top:
-                    setattr(g, top[name], t.data_ptr())
-                else:
-                    m = re.match(r'^transformer\.resblocks\.(\d+)\.(.+)$', name)
-                    if not m or m.group(2) not in blk:
-                        raise KeyError(f'{name!r} is not a parameter of the vision tower')
-                    setattr(bg[int(m.group(1))], blk[m.group(2)], t.data_ptr())
-            g.blocks = ctypes.cast(bg, ctypes.POINTER(_lib.EcBlockGrads))
+            g, bg = self.grads_over(views)
             self._grad_structs[key] = (g, bg, views, flat, spans)
         g, _, views, flat, spans = self._grad_structs[key]
         return g, views, flat, spans
@@ -376,24 +455,43 @@ def trainable_visual(names, clip_dict):
     return [n for n in names if n in picked]
 
 
+def lora_factor_shapes(spec, layers, width):
+    """{key under ``model.visual.``: shape} of the factors a LoRA spec injects, in the order ``LoraFactors`` holds
+    them (per block: q, v[, k] down / up, then out_proj's)."""
+    r, lora_k, lora_o = parse_lora(spec)
+    out = {}
+    for i in range(layers):
+        pre = _block_name(i, 'attn')
+        for nm in ('q', 'v') + (('k',) if lora_k else ()):
+            out[f'{pre}.in_proj_weight.lora_down_{nm}'] = (r, width)
+            out[f'{pre}.in_proj_weight.lora_up_{nm}'] = (width, r)
+        if lora_o:
+            out[f'{pre}.out_proj.lora_down.weight'] = (r, width)
+            out[f'{pre}.out_proj.lora_up.weight'] = (width, r)
+    return out
+
+
 class LoraFactors:
     """Low-rank factors of every attention block, keyed like the reference's injected modules
     (``...attn.in_proj_weight.lora_down_q`` / ``lora_up_q`` / ``_k`` / ``_v``, ``...attn.out_proj.lora_down.weight``
     / ``lora_up.weight``), initialised as lora.py:8-11 (down ~ N(0, 1 / r), up = 0)."""
 
-    def __init__(self, tower, spec):
+    def __init__(self, tower, spec, params=None):
+        """params: the factors as somebody else owns them (the ``nn.Parameter``s of an autograd-enabled classifier),
+        keyed and shaped as ``lora_factor_shapes`` says; default: drawn here."""
         self.tower = tower
+        tower.lora = self
         self.r, self.lora_k, self.lora_o = parse_lora(spec)
         W, dev = tower.W, tower.dev
-        self.params = {}
-        for i in range(tower.L):
-            pre = _block_name(i, 'attn')
-            for nm in ('q', 'v') + (('k',) if self.lora_k else ()):
-                self.params[f'{pre}.in_proj_weight.lora_down_{nm}'] = (torch.randn(self.r, W) / self.r).to(dev)
-                self.params[f'{pre}.in_proj_weight.lora_up_{nm}'] = torch.zeros(W, self.r, device=dev)
-            if self.lora_o:
-                self.params[f'{pre}.out_proj.lora_down.weight'] = (torch.randn(self.r, W) / self.r).to(dev)
-                self.params[f'{pre}.out_proj.lora_up.weight'] = torch.zeros(W, self.r, device=dev)
+        shapes = lora_factor_shapes(spec, tower.L, W)
+        if params is None:
+            params = {k: ((torch.randn(shape) / self.r).to(dev) if '.lora_down' in k else torch.zeros(shape, device=dev))
+                      for k, shape in shapes.items()}
+        for k, shape in shapes.items():
+            p = params[k]
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and tuple(p.shape) == shape):
+                raise ValueError(f'LoRA factor {k}: fp32 contiguous CUDA {shape} expected')
+        self.params = {k: params[k] for k in shapes}
         self.merged_names = []
         for i in range(tower.L):
             names = [_block_name(i, 'attn.in_proj_weight')] + ([_block_name(i, 'attn.out_proj.weight')] if self.lora_o else [])
@@ -413,9 +511,10 @@ class LoraFactors:
                 out.append((i, None, pre + '.out_proj.lora_down.weight', pre + '.out_proj.lora_up.weight'))
         return out
 
-    def bind(self, factor_grads):
+    def bind(self, factor_grads=None):
         """Build the item tables and the gradient struct once: every pointer (masters, merged scratch, the
-        factors, their 16-bit operand copies and gradients) is stable for the life of the trainer."""
+        factors, their 16-bit operand copies and gradients) is stable for the life of the trainer.  Without
+        ``factor_grads`` the struct carries no gradient pointers: ``struct_for`` makes one per backward pass."""
         t, W, r = self.tower, self.tower.W, self.r
         proj = self.projections()
         items = (_lib.EcLoraItem * len(proj))()
@@ -433,7 +532,8 @@ class LoraFactors:
             it.up, it.down = self.params[ku].data_ptr(), self.params[kd].data_ptr()
             slot = 3 if j is None else j
             blocks[i].down16[slot], blocks[i].up16_t[slot] = self.down16[kd].data_ptr(), self.up16t[ku].data_ptr()
-            blocks[i].d_up[slot], blocks[i].d_down[slot] = factor_grads[ku].data_ptr(), factor_grads[kd].data_ptr()
+            if factor_grads is not None:
+                blocks[i].d_up[slot], blocks[i].d_down[slot] = factor_grads[ku].data_ptr(), factor_grads[kd].data_ptr()
         self._n_items = len(proj)
         self._items = device_table(items)
         self._blocks = blocks
@@ -443,10 +543,30 @@ class LoraFactors:
         self._pack_down = [(self.params[kd], self.down16[kd], None, None) for _, _, kd, _ in proj]
         self._pack_up = [(self.params[ku], None, None, self.up16t[ku]) for _, _, _, ku in proj]
         self._pack_tables = None
-        if not self.lora_k:       # the k rows of in_proj carry no factors: their merged rows are the base rows
+        self.copy_plain_rows()
+
+    def copy_plain_rows(self):
+        """The k rows of in_proj carry no factors without 'k' in the spec: their merged rows are the base rows."""
+        t, W = self.tower, self.tower.W
+        if not self.lora_k:
             for i in range(t.L):
                 n = _block_name(i, 'attn.in_proj_weight')
                 t.effective[n][W:2 * W].copy_(t.master[n][W:2 * W])
+
+    def struct_for(self, factor_grads):
+        """An ``EcVitLora`` of its own for one backward pass: the bound operand copies, gradients written to
+        ``factor_grads`` ({key: fp32 tensor}; a projection with neither of its two keys there is skipped).
+        -> (struct, its block array: keep both alive over the launch)."""
+        blocks = (_lib.EcBlockLora * self.tower.L)()
+        for i, j, kd, ku in self.projections():
+            slot = 3 if j is None else j
+            if ku in factor_grads or kd in factor_grads:
+                blocks[i].down16[slot], blocks[i].up16_t[slot] = self._blocks[i].down16[slot], self._blocks[i].up16_t[slot]
+                blocks[i].d_up[slot], blocks[i].d_down[slot] = factor_grads[ku].data_ptr(), factor_grads[kd].data_ptr()
+        st = _lib.EcVitLora()
+        st.rank = self.r
+        st.blocks = ctypes.cast(blocks, ctypes.POINTER(_lib.EcBlockLora))
+        return st, blocks
 
     def merge(self):
         """effective = base + up @ down for every projection (lora.py:138-150, :50-52) and the repack of those
@@ -470,6 +590,20 @@ class LoraFactors:
                 out[pre + '.out_proj.linear.bias'] = t.master[pre + '.out_proj.bias']
         out.update(self.params)
         return out
+
+
+def valid_patches(tower, data_dict):
+    """-> patches [Nv, G, kpad] of the valid views, valid [B, T], row_idx [B, T] (no host synchronisation when
+    the batch comes with its own 'patches' + 'row_idx', e.g. from Event2ImagePipeline)."""
+    t = tower
+    valid = data_dict['valid_mask'].to(t.dev)
+    if 'patches' in data_dict:
+        return data_dict['patches'], valid, data_dict['row_idx']
+    row_idx = compact_row_idx(valid)
+    x = data_dict['img'][valid].to(t.dev, torch.float32).contiguous()
+    patches = torch.empty((x.shape[0], t.G, t.kpad), dtype=t.cd, device=t.dev)
+    _lib.launch('ec_patchify', x, x.shape[0], t.cfg['image_size'], t.P, t.kpad, patches, t.code)
+    return patches, valid, row_idx
 
 
 class GradScaler:
@@ -543,6 +677,9 @@ class FTTrainer:
         if optimizer.lower() not in ('adam', 'adamw'):
             raise ValueError('Should use Adam or AdamW optimizer!')                     # method.py:160
         assert weight_decay == 0.                                                       # method.py:161
+        if getattr(classifier, 'autograd', False):
+            raise ValueError('this FTCLIPClassifier trains under torch autograd (clip_dict["autograd"]): it owns the '
+                             "tower's operand copies, and an FTTrainer on top of it would be their second owner")
         self.clf = classifier
         self.tower = VisualTower(classifier.model)
         cd = classifier.clip_dict
@@ -679,19 +816,7 @@ class FTTrainer:
         self._graph = None
 
     def _patches(self, data_dict):
-        """-> patches [Nv, G, kpad] of the valid views, valid [B, T], row_idx [B, T] (no host synchronisation when
-        the batch comes with its own 'patches' + 'row_idx', e.g. from Event2ImagePipeline)."""
-        valid = data_dict['valid_mask'].to(self.tower.dev)
-        if 'patches' in data_dict:
-            return data_dict['patches'], valid, data_dict['row_idx']
-        row_idx = compact_row_idx(valid)
-        imgs = data_dict['img']
-        t = self.tower
-        x = imgs[valid].to(t.dev, torch.float32).contiguous()
-        R = t.cfg['image_size']
-        patches = torch.empty((x.shape[0], t.G, t.kpad), dtype=t.cd, device=t.dev)
-        _lib.launch('ec_patchify', x, x.shape[0], R, t.P, t.kpad, patches, t.code)
-        return patches, valid, row_idx
+        return valid_patches(self.tower, data_dict)
 
     def resolve(self):
         """Apply the gradient scaler's verdict on the last queued step (waits for that step if it is still

@@ -16,14 +16,16 @@ mirrors of the reference's interface (vis / preprocess / clip / adapter / clip_c
     torch.ops.eventclip_hip.adapter_train_fwd  ec_adapter_train_forward        models/adapter.py:82-105 in train mode
     torch.ops.eventclip_hip.adapter_train_bwd  ec_adapter_train_backward       its backward, over the forward's tape
     torch.ops.eventclip_hip.resnet_encode      ec_resnet_encode                models/clip_cls.py:101 (ResNet backbones)
+    torch.ops.eventclip_hip.vit_train_fwd      ec_vit_train_forward            models/clip_cls_ft.py:196-243, the tower with a tape
+    torch.ops.eventclip_hip.vit_train_bwd      ec_vit_train_backward_over      its backward, over the forward's tape
 
 Weights live in packed C structs owned by the Python modules; an op receives them as an integer
 handle into a registry of live modules (tensors-only signatures keep the ops traceable, and the
 registered fake kernels give their output shapes without touching the device).
 
-``classify`` and ``adapter_train_fwd`` carry autograd formulas (``torch.library.register_autograd``) whose backward
-passes are the ``*_bwd`` ops, so ``loss.backward()`` reaches ``text_feats`` and the adapter's parameters, which
-``adapter_train_fwd`` takes as real tensor inputs.  The ``*_bwd`` ops have no formula of their own: there is no double
+``classify``, ``adapter_train_fwd`` and ``vit_train_fwd`` carry autograd formulas (``torch.library.register_autograd``)
+whose backward passes are the ``*_bwd`` ops, so ``loss.backward()`` reaches ``text_feats``, the adapter's parameters and
+the vision tower's, which ``adapter_train_fwd`` / ``vit_train_fwd`` take as real tensor inputs.  The ``*_bwd`` ops have no formula of their own: there is no double
 backward, and asking for one raises.
 """
 import ctypes
@@ -416,5 +418,113 @@ def _(inp, input_mode, clip_handle):
     return inp.new_empty((inp.shape[0], _resolve(clip_handle, 'resnet_encode').cfg['embed_dim']), dtype=torch.float32)
 
 
+# ---- the vision tower under autograd: forward and backward as two ops with a tape between them ----
+def _tower_params(t, params, what):
+    """-> (names of the masters among ``params``, keys of the LoRA factors among them): the fp32 masters of
+    ``clip.visual`` that require grad in ``VisualTower.canonical()`` order, then the factors.  They are inputs so that
+    autograd routes their gradients; the kernels read them where the tower bound them (and their operand copies)."""
+    names = t.trainable()
+    keys = list(t.lora.params) if t.lora is not None else []
+    own = [t.master[n] for n in names] + [t.lora.params[k] for k in keys]
+    if len(params) != len(own):
+        raise RuntimeError(f'{NAMESPACE}::{what}: {len(params)} parameters, {len(own)} expected (the trainable masters '
+                           'in canonical() order, then the LoRA factors)')
+    for i, (p, o) in enumerate(zip(params, own)):
+        if p.shape != o.shape or p.dtype != o.dtype:
+            raise RuntimeError(f'{NAMESPACE}::{what}: params[{i}] {tuple(p.shape)} is not the tower\'s '
+                               f'{(names + keys)[i]} {tuple(o.shape)}')
+    return names, keys
+
+
+@custom_op(f'{NAMESPACE}::vit_train_fwd', mutates_args=(), device_types='cuda')
+def vit_train_fwd(patches: torch.Tensor, params: List[torch.Tensor],
+                  tower_handle: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """patches 16-bit [N, G, kpad], params the trainable tensors of the ``ft.VisualTower`` behind ``tower_handle``
+    (``_tower_params``) -> (feats fp32 [N, D]; tape uint8 [ec_vit_train_workspace_bytes]: the saved activations
+    ``vit_train_bwd`` reads, followed by the scratch of both passes).  The tape is this call's own, so several forwards
+    may be alive at once.  Operand copies of masters or factors written since they were packed are rebuilt first
+    (``VisualTower.refresh``)."""
+    t = _resolve(tower_handle, 'vit_train_fwd')
+    _tower_params(t, params, 'vit_train_fwd')
+    t.refresh()
+    n = int(patches.shape[0])
+    if patches.dtype != t.cd or tuple(patches.shape) != (n, t.G, t.kpad) or n == 0:
+        raise RuntimeError(f'{NAMESPACE}::vit_train_fwd: patches {tuple(patches.shape)} {patches.dtype}, '
+                           f'[N > 0, {t.G}, {t.kpad}] {t.cd} expected')
+    patches = patches.contiguous()
+    feats = torch.empty((n, t.D), dtype=torch.float32, device=patches.device)
+    tape = _lib.scratch(t.workspace_bytes(n), patches.device).zero_()     # its alignment gaps and scratch too: an output
+    _lib.launch('ec_vit_train_forward', t._vit, patches, n, feats, tape, tape.numel())
+    return feats, tape
+
+
+@vit_train_fwd.register_fake
+def _(patches, params, tower_handle):
+    t = _resolve(tower_handle, 'vit_train_fwd')
+    n = patches.shape[0]
+    return (patches.new_empty((n, t.D), dtype=torch.float32),
+            patches.new_empty((max(t.workspace_bytes(n), 256),), dtype=torch.uint8))
+
+
+@custom_op(f'{NAMESPACE}::vit_train_bwd', mutates_args=(), device_types='cuda')
+def vit_train_bwd(patches: torch.Tensor, params: List[torch.Tensor], tape: torch.Tensor, d_feats: torch.Tensor,
+                  tower_handle: int, need: List[bool]) -> List[torch.Tensor]:
+    """The backward of ``vit_train_fwd`` over its tape: len(params) tensors, the gradient of params[i] where need[i], an
+    empty tensor otherwise; the pass stops at the lowest block a needed gradient lives in.  Every gradient is a fresh
+    allocation the caller owns.  The tape is only read (``ec_vit_train_backward_over``: the pass's scratch is this
+    call's own), so a second call gives the same bits."""
+    t = _resolve(tower_handle, 'vit_train_bwd')
+    names, keys = _tower_params(t, params, 'vit_train_bwd')
+    if len(need) != len(params):
+        raise RuntimeError(f'{NAMESPACE}::vit_train_bwd: need has {len(need)} entries for {len(params)} parameters')
+    n = int(patches.shape[0])
+    if tuple(d_feats.shape) != (n, t.D) or tape.numel() < t.workspace_bytes(n):
+        raise RuntimeError(f'{NAMESPACE}::vit_train_bwd: d_feats {tuple(d_feats.shape)} / tape of {tape.numel()} bytes do '
+                           f'not belong to a forward over {n} images')
+    patches, d_feats = patches.contiguous(), _f32c(d_feats)
+    grads = [torch.empty_like(p) if b else None for p, b in zip(params, need)]
+    tower_grads = {k: g for k, g in zip(names, grads) if g is not None}
+    factor_grads = {k: g for k, g in zip(keys, grads[len(names):]) if g is not None}
+    spare = []                       # the partner of a factor whose own gradient is not asked for: written, dropped
+    if factor_grads:
+        for _, _, kd, ku in t.lora.projections():
+            for a, b in ((kd, ku), (ku, kd)):
+                if a in factor_grads and b not in factor_grads:
+                    spare.append(b)
+                    factor_grads[b] = torch.empty_like(t.lora.params[b])
+    g, keep_g = t.grads_over(tower_grads)                                   # noqa: F841 (the struct's block array)
+    lora, keep_l = t.lora.struct_for(factor_grads) if factor_grads else (None, None)   # noqa: F841
+    if tower_grads or factor_grads:
+        ws = _lib.scratch(_lib.lib().ec_vit_train_backward_scratch_bytes(ctypes.byref(t._vit), n), patches.device)
+        _lib.launch('ec_vit_train_backward_over', t._vit, t._vit_t, patches, n, d_feats, g, lora, tape, tape.numel(), ws,
+                    ws.numel())
+    return [patches.new_empty((0,), dtype=torch.float32) if x is None else x for x in grads]
+
+
+@vit_train_bwd.register_fake
+def _(patches, params, tape, d_feats, tower_handle, need):
+    return [p.new_empty(tuple(p.shape) if b else (0,), dtype=torch.float32) for p, b in zip(params, need)]
+
+
+def _vit_setup(ctx, inputs, output):
+    patches, params, tower_handle = inputs
+    ctx.save_for_backward(patches, output[1], *params)
+    ctx.tower_handle = tower_handle
+    ctx.mark_non_differentiable(output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _vit_backward(ctx, d_feats, d_tape):
+    patches, tape, *params = ctx.saved_tensors
+    need = list(ctx.needs_input_grad[1])
+    if d_feats is None or not any(need):
+        return None, [None] * len(params), None
+    got = torch.ops.eventclip_hip.vit_train_bwd(patches, params, tape, d_feats, ctx.tower_handle, need)
+    return None, [g if b else None for g, b in zip(got, need)], None
+
+
+vit_train_fwd.register_autograd(_vit_backward, setup_context=_vit_setup)
+
+
 OPS = ('events_to_frames', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode',
-       'classify_bwd', 'adapter_train_fwd', 'adapter_train_bwd')
+       'classify_bwd', 'adapter_train_fwd', 'adapter_train_bwd', 'vit_train_fwd', 'vit_train_bwd')

@@ -53,12 +53,13 @@ EC_API const char *ec_last_error(void);
  *        ec_resnet_*_hl entry points
  *   603  + ec_classify_backward, ec_adapter_train_forward / _backward and their size functions (additive: no struct or
  *        argument list changed)
+ *   604  + ec_fingerprint_batched, ec_vit_train_backward_over / _scratch_bytes (additive)
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does, with its ctypes mirrors.) */
-#define EC_ABI_VERSION 603
+#define EC_ABI_VERSION 604
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);
@@ -890,6 +891,15 @@ enum {
 };
 enum { EC_VT_B_X = 0, EC_VT_B_XM, EC_VT_B_QKV, EC_VT_B_ATT, EC_VT_B_U, EC_VT_B_GACT, EC_VT_B_H1, EC_VT_B_H2, EC_VT_B_LSE,
        EC_VT_PER_BLOCK };
+/* The whole backward pass with the tape ONLY READ: ec_vit_train_backward keeps its scratch behind the saved activations
+ * in the forward's workspace; here it comes from the caller (`scratch`, ec_vit_train_backward_scratch_bytes), and the
+ * buffer the forward filled (`tape`, ec_vit_train_workspace_bytes) is not written.  Same launches, same bits.  A tape
+ * that torch autograd saved stays as it is: a second pass over it gives the same gradients. */
+EC_API size_t ec_vit_train_backward_scratch_bytes(const ec_vit_weights *w, int n_img);
+EC_API int ec_vit_train_backward_over(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
+                                      int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
+                                      const void *tape, size_t tape_bytes, void *scratch, size_t scratch_bytes,
+                                      ec_stream_t stream);
 EC_API int ec_vit_train_layout(const ec_vit_weights *w, int n_img, int64_t *offsets, int n_offsets);
 
 /* fp32 [rows, cols] -> any of: hi = round16(w) [rows, cols]; lo = round16(w - hi); hi_t = hi transposed
@@ -901,6 +911,18 @@ typedef struct {
 } ec_pack_item;
 EC_API int ec_pack_weight16_batched(const ec_pack_item *items, int n_items, int rows, int cols, int dtype,
                                     ec_stream_t stream);
+
+/* Has anybody written these tensors since their operand copies were packed?  out[i] = a 64-bit fingerprint of the n
+ * 32-bit words at items[i].ptr (`items`, `out`: DEVICE arrays; max_n: the largest n): the sum of word * (an odd
+ * multiplier of its position) modulo 2^64, so any single changed word changes it and two different contents collide
+ * with probability ~2^-64.  One launch for the whole list, the same value whatever the order of arrival.  Under torch
+ * autograd the masters are written by whoever holds them (an optimiser, load_state_dict, `p.data` -- which moves no
+ * version counter), so the training forward compares fingerprints instead of trusting a notification. */
+typedef struct {
+    const void *ptr;
+    int64_t n;
+} ec_span_item;
+EC_API int ec_fingerprint_batched(const ec_span_item *items, int n_items, int64_t max_n, uint64_t *out, ec_stream_t stream);
 
 /* LayerNorm backward (fp32): x rows at stride ldx (the forward input), dy rows at stride ldy.
  * dx rows at stride ldo: dx = (accumulate ? dx : 0) + dLN; d_gamma / d_beta [width] (NULL = skip; they need

@@ -3,14 +3,20 @@ configs/ftclip/ft_text_fsclip_nin_params*.py -- ViT-L/14, N-ImageNet geometry, 1
 2 views per GPU, K = 1000, Adam, `lora='qkvo-16'` or every visual parameter).
 
     python tools/bench_ft.py [--arch ViT-L/14] [--samples 32] [--views 2] [--classes 1000] [--steps 5]
-                             [--modes lora,full,bias] [--dtype float16]
+                             [--modes lora,full,bias] [--dtype float16] [--graph | --autograd]
 
 Prints one JSON line per mode: ms per step, frames/s, the split forward / loss / backward / update, the
 algorithmic flops (3 x the forward's 2 M N K for a full step; LoRA skips the MLP's weight gradients) and the
 rate they amount to, and `cpu_baseline`: forward + backward of the oracle's tower (torch CPU fp32 autograd over
 oracle/clip_ref.py, every visual gradient, no optimiser) on a few frames with the box's host cores.  Synthetic
 frames, seeded random weights (no datasets / checkpoints on the box).  The CPU leg is the only place the oracle is
-touched."""
+touched.
+
+`--autograd` prints one line per mode with the same step three ways, interleaved in one process: `FTTrainer` with eager
+launches, `FTTrainer(graph=True)`, and the reference's loop on `FTCLIPClassifier(clip_dict=dict(..., autograd=True))`
+(`clf(data)`, `calc_train_loss`, `torch.amp.GradScaler`, `loss.backward()`, `torch.optim.Adam` over the two parameter
+groups of method.py:165-180): ms per step (the median of `--rounds` rounds of `--steps` steps) and the host's share of
+it (until the last step is queued)."""
 import argparse
 import json
 import os
@@ -44,6 +50,78 @@ def cpu_baseline(arch, frames=4, repeat=2):
                 sample='%d frames, forward + backward of every visual parameter, best of %d (%.1f s)' % (frames, repeat, best))
 
 
+def _batch(t, B, T, K, dev):
+    torch.manual_seed(0)
+    n = B * T
+    patches = (torch.randn(n, t.G, t.kpad, device=dev) * 0.5).to(t.cd)
+    patches[:, :, 2 * t.k:] = 0
+    return {'patches': patches, 'row_idx': torch.arange(n, device=dev, dtype=torch.int32).view(B, T),
+            'valid_mask': torch.ones(B, T, dtype=torch.bool, device=dev), 'label': torch.randint(0, K, (B,), device=dev)}
+
+
+def autograd_rows(a):
+    """FTTrainer eager / hipGraph and the autograd loop on the same batch, interleaved round by round."""
+    import statistics
+    from eventclip_amd import _lib, clip as eclip, ft
+    from eventclip_amd.clip_cls_ft import FTCLIPClassifier
+    dev = _lib.require_gpu()
+    B, T, K = a.samples, a.views, a.classes
+    for mode in a.modes.split(','):
+        extra = dict(lora='qkvo-16') if mode == 'lora' else (dict(lora=-1, only_bias=True) if mode == 'bias' else dict(lora=-1))
+
+        def classifier(**more):
+            model = eclip.build_random(a.arch, seed=0, dtype=a.dtype)
+            cd = dict(clip_model=model, prompt='a point cloud image of a {}', class_names=[f'c{i}' for i in range(K)],
+                      agg_func='mean', class_tokens=eclip.synthetic_tokens(K), only_conv1=False, only_bias=False,
+                      only_ln=False, **extra, **more)
+            return FTCLIPClassifier(adapter_dict=dict(adapter_type='text-identity', residual=0.95), clip_dict=cd,
+                                    loss_dict=dict(use_logits_loss=True, use_probs_loss=False)).cuda().train()
+        kw = dict(lr=2e-5, clip_lr=2e-5, total_steps=1000, init_scale=4096.0)
+        trainers = {'trainer_eager': ft.FTTrainer(classifier(), **kw), 'trainer_graph': ft.FTTrainer(classifier(), graph=True, **kw)}
+        clf = classifier(autograd=True)
+        named = [(n, p) for n, p in clf.named_parameters() if p.requires_grad]
+        opt = torch.optim.Adam([{'params': [p for n, p in named if 'model.visual' not in n], 'lr': 2e-5},
+                                {'params': [p for n, p in named if 'model.visual' in n], 'lr': 2e-5}])
+        scaler = torch.amp.GradScaler('cuda', init_scale=4096.0)
+        data = _batch(trainers['trainer_eager'].tower, B, T, K, dev)
+
+        def autograd_step():
+            opt.zero_grad(set_to_none=True)
+            loss = clf.calc_train_loss(data, clf(data))['ce_loss']
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+            return loss.detach()
+        steps = {k: (lambda tr=tr: tr.step(data)) for k, tr in trainers.items()}
+        steps['autograd'] = autograd_step
+        for fn in steps.values():
+            for _ in range(max(a.warmup, 4)):
+                fn()
+        torch.cuda.synchronize()
+        total, host, loss = {k: [] for k in steps}, {k: [] for k in steps}, {}
+        for _ in range(a.rounds):
+            for k, fn in steps.items():
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    loss[k] = fn()
+                t1 = time.perf_counter()
+                if k in trainers:
+                    trainers[k].resolve()
+                torch.cuda.synchronize()
+                host[k].append((t1 - t0) / a.steps * 1e3)
+                total[k].append((time.perf_counter() - t0) / a.steps * 1e3)
+        print(json.dumps(dict(mode=mode, arch=a.arch, frames_per_step=B * T, classes=K, dtype=a.dtype, steps=a.steps,
+                              rounds=a.rounds, trainable_tensors=len(named),
+                              ms_per_step={k: round(statistics.median(v), 2) for k, v in total.items()},
+                              ms_per_step_rounds={k: [round(x, 2) for x in v] for k, v in total.items()},
+                              host_ms_per_step={k: round(statistics.median(v), 2) for k, v in host.items()},
+                              loss={k: round(float(v), 4) for k, v in loss.items()},
+                              loss_scale=dict(trainer_eager=trainers['trainer_eager'].scaler.scale,
+                                              autograd=scaler.get_scale()))), flush=True)
+        del trainers, clf, opt, steps
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--arch', default='ViT-L/14')
@@ -56,7 +134,12 @@ def main():
     ap.add_argument('--dtype', default='float16')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--graph', action='store_true', help='replay the step from a hipGraph (recorded after 2 eager steps)')
+    ap.add_argument('--autograd', action='store_true',
+                    help='the step through torch autograd beside FTTrainer eager and graph=True, interleaved')
+    ap.add_argument('--rounds', type=int, default=3, help='--autograd: rounds of --steps steps per path')
     a = ap.parse_args()
+    if a.autograd:
+        return autograd_rows(a)
     from eventclip_amd import _lib, clip as eclip, ft
     from eventclip_amd.clip_cls_ft import FTCLIPClassifier
     dev = _lib.require_gpu()
