@@ -203,6 +203,8 @@ def smooth(img):
     k = np.array([1, 1, 1, 1, 5, 1, 1, 1, 1], dtype=np.float32) / np.float32(13)
     H, W, _ = img.shape
     out = img.copy()
+    if H < 3 or W < 3:                # no interior: Pillow returns the image unchanged
+        return out
     src = img.astype(np.float32)
     acc = np.full((H - 2, W - 2, 3), np.float32(0.5), dtype=np.float32)
     # Filter.c sums the three kernel rows bottom-up is irrelevant for bit-exactness only if the
