@@ -88,6 +88,11 @@ EC_OK, EC_ERR_INVALID, EC_ERR_HIP, EC_ERR_UNSUPPORTED, EC_ERR_WORKSPACE = 0, -1,
  EC_VT_BLOCK0) = range(11)
 (EC_VT_B_X, EC_VT_B_XM, EC_VT_B_QKV, EC_VT_B_ATT, EC_VT_B_U, EC_VT_B_GACT, EC_VT_B_H1, EC_VT_B_H2, EC_VT_B_LSE,
  EC_VT_PER_BLOCK) = range(10)
+# ec_adapter_train_layout: the adapter tape's slots (adapter-wide, then EC_AT_PER_LAYER per layer) and the backward's scratch
+EC_AT_H0, EC_AT_HFIN, EC_AT_Y, EC_AT_FTMP, EC_AT_LAYER0 = range(5)
+(EC_AT_L_XHAT1, EC_AT_L_RSTD1, EC_AT_L_A, EC_AT_L_QKV, EC_AT_L_P, EC_AT_L_O, EC_AT_L_H1, EC_AT_L_XHAT2, EC_AT_L_RSTD2,
+ EC_AT_L_BN, EC_AT_L_F, EC_AT_PER_LAYER) = range(12)
+EC_AS_DY, EC_AS_DH, EC_AS_DH1, EC_AS_DTMP_D, EC_AS_DQKV, EC_AS_DF, EC_AS_COUNT = range(7)
 
 
 class EcBlockWeights(ctypes.Structure):
@@ -232,6 +237,7 @@ SIGNATURES = {
                                           ctypes.c_uint64, c_void_p, ctypes.c_size_t, c_void_p,
                                           ctypes.POINTER(EcAdapterTrainParams), c_void_p, c_void_p, ctypes.c_size_t,
                                           c_void_p]),
+    'ec_adapter_train_layout': (c_int, [c_int] * 7 + [c_void_p, c_int, c_void_p, c_int]),
     'ec_classify_backward_workspace_bytes': (ctypes.c_size_t, [c_int] * 4),
     'ec_classify_backward': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -350,7 +356,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 604      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
+ABI_VERSION = 605      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
 
 
 class HipLibraryError(RuntimeError):

@@ -966,6 +966,46 @@ extern "C" EC_API size_t ec_adapter_train_backward_workspace_bytes(int B, int T,
     return c.off;
 }
 
+// The offsets come from carve_tape / carve_scratch themselves, run on a sentinel base address (a null base would hand
+// out null pointers): the two cannot drift apart.
+extern "C" EC_API int ec_adapter_train_layout(int B, int T, int D, int d_model, int ffn_dim, int heads, int layers,
+                                              int64_t *tape_offsets, int n_tape, int64_t *scratch_offsets, int n_scratch)
+{
+    EC_REQUIRE(B > 0 && T > 0 && D > 0 && d_model > 0 && ffn_dim > 0 && heads > 0 && layers >= 1 && layers <= 8,
+               "ec_adapter_train_layout: bad geometry (B %d T %d layers %d)", B, T, layers);
+    const int need = EC_AT_LAYER0 + EC_AT_PER_LAYER * layers;
+    if (tape_offsets) {
+        EC_REQUIRE(n_tape >= need, "ec_adapter_train_layout: %d tape slots for %d", n_tape, need);
+        unsigned char *const sentinel = reinterpret_cast<unsigned char *>(uintptr_t(1) << 40);
+        auto off = [&](const void *p) { return (int64_t)(static_cast<const unsigned char *>(p) - sentinel); };
+        Carve c{sentinel, 0};
+        AdapterTape t;
+        carve_tape(c, B, T, D, d_model, ffn_dim, heads, layers, t);
+        tape_offsets[EC_AT_H0] = off(t.h0), tape_offsets[EC_AT_HFIN] = off(t.hfin), tape_offsets[EC_AT_Y] = off(t.y);
+        tape_offsets[EC_AT_FTMP] = off(t.ftmp);
+        for (int l = 0; l < layers; l++) {
+            int64_t *o = tape_offsets + EC_AT_LAYER0 + EC_AT_PER_LAYER * l;
+            const LayerBufs &b = t.L[l];
+            o[EC_AT_L_XHAT1] = off(b.xhat1), o[EC_AT_L_RSTD1] = off(b.rstd1), o[EC_AT_L_A] = off(b.a);
+            o[EC_AT_L_QKV] = off(b.qkv), o[EC_AT_L_P] = off(b.P), o[EC_AT_L_O] = off(b.o), o[EC_AT_L_H1] = off(b.h1);
+            o[EC_AT_L_XHAT2] = off(b.xhat2), o[EC_AT_L_RSTD2] = off(b.rstd2), o[EC_AT_L_BN] = off(b.bn);
+            o[EC_AT_L_F] = off(b.f);
+        }
+    }
+    if (scratch_offsets) {
+        EC_REQUIRE(n_scratch >= EC_AS_COUNT, "ec_adapter_train_layout: %d scratch slots for %d", n_scratch, EC_AS_COUNT);
+        unsigned char *const sentinel = reinterpret_cast<unsigned char *>(uintptr_t(1) << 40);
+        auto off = [&](const void *p) { return (int64_t)(static_cast<const unsigned char *>(p) - sentinel); };
+        Carve c{sentinel, 0};
+        AdapterScratch x;
+        carve_scratch(c, B, T, D, d_model, ffn_dim, x);
+        scratch_offsets[EC_AS_DY] = off(x.dy), scratch_offsets[EC_AS_DH] = off(x.dh), scratch_offsets[EC_AS_DH1] = off(x.dh1);
+        scratch_offsets[EC_AS_DTMP_D] = off(x.dtmp_d), scratch_offsets[EC_AS_DQKV] = off(x.dqkv);
+        scratch_offsets[EC_AS_DF] = off(x.df);
+    }
+    return need;
+}
+
 extern "C" EC_API int ec_adapter_train_forward(const float *img_feats, const uint8_t *valid, int B, int T,
                                                const ec_adapter_train_params *w, float dropout_p,
                                                uint64_t dropout_seed, float *out, void *tape, size_t tape_bytes,

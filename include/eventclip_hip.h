@@ -54,12 +54,13 @@ EC_API const char *ec_last_error(void);
  *   603  + ec_classify_backward, ec_adapter_train_forward / _backward and their size functions (additive: no struct or
  *        argument list changed)
  *   604  + ec_fingerprint_batched, ec_vit_train_backward_over / _scratch_bytes (additive)
+ *   605  + ec_adapter_train_layout (additive: no struct or argument list changed)
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does, with its ctypes mirrors.) */
-#define EC_ABI_VERSION 604
+#define EC_ABI_VERSION 605
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);
@@ -692,7 +693,8 @@ EC_API int ec_pseudo_label(const float *probs, int B, int V, int K, float conf_t
  *   agg         EC_AGG_SUM / EC_AGG_MEAN;  use_probs_loss: 0 = CE on the aggregated logits,
  *               1 = NLL of log(probs + 1e-6) (loss_dict.use_probs_loss)
  *   loss        fp32 [1] (out, batch mean);  grad_text fp32 [K, D] (out)
- *   agg_logits  optional fp32 [B, K] (out): the aggregated logits of the forward pass */
+ *   agg_logits  optional fp32 [B, K] (out): the aggregated logits of the forward pass
+ * Every sample keeps at least one valid view: a sample with none divides by zero (here and in the reference). */
 EC_API size_t ec_fs_text_train_workspace_bytes(int B, int T, int D, int K);
 EC_API int ec_fs_text_loss_grad(const float *img_feats, const uint8_t *valid, const int32_t *labels,
                                 const float *text_param, int B, int T, int D, int K, float logit_scale,
@@ -715,7 +717,8 @@ EC_API int ec_adam_step(float *param, const float *grad, float *exp_avg, float *
  * stateless hash of (dropout_seed, site, element) -- the same distribution as torch's, not its random
  * stream; site = 4 * layer + {0, 1, 2, 3} in that order, element = flat index into [B, heads, T, T] /
  * [B*T, d_model] / [B*T, ffn_dim] / [B*T, d_model].  ec_dropout_mask returns the keep mask of a site
- * (tests replay it in the oracle).  dropout_p = 0: the deterministic, eval-mode function. */
+ * (tests replay it in the oracle).  dropout_p = 0: the deterministic, eval-mode function.
+ * Every sample keeps at least one valid view: a sample with none divides by zero (here and in the reference). */
 typedef struct {
     float *ln1_g, *ln1_b;   /* norm1.weight / .bias [d] */
     float *qkv_w, *qkv_b;   /* self_attn.in_proj_weight [3d, d] / in_proj_bias [3d] */
@@ -754,7 +757,8 @@ EC_API int ec_dropout_mask(uint64_t seed, uint32_t site, int64_t n, float p, uin
  *             and its launch; `blocks` must be a host array) and, when d_img_feats is not NULL, d loss / d img_feats.
  *             params, img_feats, dropout_p and dropout_seed are the forward's.  The tape is only read: everything
  *             the backward overwrites lives in workspace (ec_adapter_train_backward_workspace_bytes), so a second
- *             backward over the same tape gives the same bits. */
+ *             backward over the same tape gives the same bits.
+ * Every sample keeps at least one valid view: a sample with none divides by zero (here and in the reference). */
 EC_API size_t ec_adapter_train_tape_bytes(int B, int T, int D, int d_model, int ffn_dim, int heads, int layers);
 EC_API size_t ec_adapter_train_backward_workspace_bytes(int B, int T, int D, int d_model, int ffn_dim);
 EC_API int ec_adapter_train_forward(const float *img_feats, const uint8_t *valid, int B, int T,
@@ -764,6 +768,28 @@ EC_API int ec_adapter_train_backward(const float *img_feats, int B, int T, const
                                      float dropout_p, uint64_t dropout_seed, const void *tape, size_t tape_bytes,
                                      const float *d_out, const ec_adapter_train_params *grads, float *d_img_feats,
                                      void *workspace, size_t workspace_bytes, ec_stream_t stream);
+/* Where the tape and the backward's workspace keep their slots: byte offsets from each buffer's start, for tests that
+ * check one stage against a restatement of it.  tape_offsets[EC_AT_*] are the adapter-wide slots, layer l's slot k
+ * (EC_AT_L_*) is tape_offsets[EC_AT_LAYER0 + EC_AT_PER_LAYER * l + k]; scratch_offsets[EC_AS_*].  Either array may be NULL
+ * (skipped).  Returns the tape's slot count (EC_AT_LAYER0 + EC_AT_PER_LAYER * layers) or an EC_ERR_* code.  All fp32;
+ * R = B * T, d = d_model.  After ec_adapter_train_forward:
+ *   h0    [R, d] in_proj's output, layer 0's input
+ *   hfin  [R, d] the last layer's output, out_proj's input (every layer writes it; layer l + 1 reads it as its input)
+ *   y     [R, D] out_proj's output before the residual mix       ftmp [R, d] dropout_p > 0: the last linear2 output
+ *   layer: xhat1, xhat2 [R, d] the normalised rows of norm1 / norm2 before gamma; rstd1, rstd2 [R] their 1 / sqrt(var + eps);
+ *          a [R, d] norm1's output; qkv [R, 3d] in_proj of self_attn; P [B, heads, T, T] the softmax, NOT dropped;
+ *          o [R, d] attention output (built from the dropped P); h1 [R, d] the layer input + dropout1(out_proj(o));
+ *          bn [R, d] norm2's output; f [R, ffn] relu(linear1), dropped and rescaled when dropout_p > 0
+ * After ec_adapter_train_backward (each is overwritten layer by layer; what the FIRST layer left):
+ *   dy     [R, D] (1 - residual) d_out                       dh   [R, d] d loss / d h0
+ *   dh1    [R, d] d loss / d h1 of layer 0                   dtmp_d [R, d] d loss / d a (norm1's output) of layer 0
+ *   dqkv   [R, 3d] d loss / d qkv of layer 0                 df   [R, ffn] d loss / d linear1's output of layer 0 */
+enum { EC_AT_H0 = 0, EC_AT_HFIN, EC_AT_Y, EC_AT_FTMP, EC_AT_LAYER0 };
+enum { EC_AT_L_XHAT1 = 0, EC_AT_L_RSTD1, EC_AT_L_A, EC_AT_L_QKV, EC_AT_L_P, EC_AT_L_O, EC_AT_L_H1, EC_AT_L_XHAT2,
+       EC_AT_L_RSTD2, EC_AT_L_BN, EC_AT_L_F, EC_AT_PER_LAYER };
+enum { EC_AS_DY = 0, EC_AS_DH, EC_AS_DH1, EC_AS_DTMP_D, EC_AS_DQKV, EC_AS_DF, EC_AS_COUNT };
+EC_API int ec_adapter_train_layout(int B, int T, int D, int d_model, int ffn_dim, int heads, int layers,
+                                   int64_t *tape_offsets, int n_tape, int64_t *scratch_offsets, int n_scratch);
 
 /* The vector-Jacobian product of ec_classify_v2 with respect to feats and text_t, fp32 throughout.
  *   feats [n_rows, C], row_idx [B, T], text_t [C, K] (the fp32 tensor, not the prepared planes), logit_scale, agg,
@@ -939,7 +965,8 @@ EC_API int ec_layernorm_backward(const float *x, long ldx, const float *dy, long
  * the valid views, exactly what the encoder produced and what ec_vit_train_backward takes -- the scatter
  * of :208-209 and its gather in the backward pass never materialise.
  * grad_text may be NULL (fixed text features).  Workspace: ec_fs_text_train_workspace_bytes(B, T, D, K) +
- * max(B * T, K) * D * 4 bytes. */
+ * max(B * T, K) * D * 4 bytes.
+ * Every sample keeps at least one valid view: a sample with none divides by zero (here and in the reference). */
 EC_API int ec_ft_loss_grad(const float *img_feats, const int32_t *row_idx, const uint8_t *valid,
                            const int32_t *labels, const float *text_param, int B, int T, int D, int K,
                            float logit_scale, int agg, int use_probs_loss, float grad_scale,
