@@ -46,7 +46,7 @@ class EcAdapterWeights(ctypes.Structure):
     _fields_ = [('in_dim', c_int), ('d_model', c_int), ('heads', c_int), ('ffn', c_int),
                 ('layers', c_int), ('residual', c_float), ('in_w_t', c_void_p), ('in_b', c_void_p),
                 ('out_w_t', c_void_p), ('out_b', c_void_p),
-                ('layer', ctypes.POINTER(EcAdapterLayer))]
+                ('layer', ctypes.POINTER(EcAdapterLayer)), ('post_norm', c_int)]
 
 
 class EcAugOp(ctypes.Structure):
@@ -111,7 +111,7 @@ class EcAdapterTrainLayer(ctypes.Structure):
 class EcAdapterTrainParams(ctypes.Structure):
     _fields_ = [('in_dim', c_int), ('d_model', c_int), ('heads', c_int), ('ffn_dim', c_int), ('layers', c_int),
                 ('residual', ctypes.c_float), ('in_w', c_void_p), ('in_b', c_void_p), ('out_w', c_void_p),
-                ('out_b', c_void_p), ('blocks', ctypes.POINTER(EcAdapterTrainLayer))]
+                ('out_b', c_void_p), ('blocks', ctypes.POINTER(EcAdapterTrainLayer)), ('post_norm', c_int)]
 
 
 class EcVitWeights(ctypes.Structure):
@@ -356,7 +356,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 605      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
+ABI_VERSION = 606      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
 
 
 class HipLibraryError(RuntimeError):

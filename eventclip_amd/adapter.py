@@ -5,7 +5,9 @@ reference (``in_proj``, ``transformer_encoder.layers.{i}.*``, ``out_proj``) so t
 checkpoints written by the reference's trainer load key for key; those modules are
 parameter holders only -- ``forward`` runs ``ec_adapter_forward`` (fp32, the fused inference kernel) in eval mode
 or with grad disabled, and the differentiable ``eventclip_hip::adapter_train_fwd`` (``ec_adapter_train_forward`` /
-``_backward``, with the encoder layers' dropout of 0.1) in train mode with grad enabled.
+``_backward``, with the encoder layers' dropout of 0.1) in train mode with grad enabled.  Both layouts of the encoder
+layer are built, ``norm_first=True`` (pre-LN, the reference configs') and ``norm_first=False`` (post-LN): the state-dict
+keys are the same, the C structs carry the layout as ``post_norm``.
 
 The map from a parameter to its C struct field (``LAYER_PARAMS`` / ``PROJ_PARAMS``, ``adapter_param_names``,
 ``_adapter_struct``) lives here, next to the module whose ``named_parameters()`` order it restates; ``train`` and
@@ -92,13 +94,15 @@ def adapter_param_names(layers):
         [leaf for leaf, _, _ in PROJ_PARAMS]
 
 
-def _adapter_struct(tensors, in_dim, d_model, heads, ffn_dim, layers, residual):
+def _adapter_struct(tensors, in_dim, d_model, heads, ffn_dim, layers, residual, post_norm=0):
     """EcAdapterTrainParams over ``tensors`` (fp32 CUDA tensors in ``adapter_param_names`` order; None -> NULL, a
-    gradient the split backward skips) -> (struct, the layer array its ``blocks`` points to)."""
+    gradient the split backward skips) -> (struct, the layer array its ``blocks`` points to).  post_norm: 0 the pre-LN
+    layer (norm_first=True), 1 the post-LN one."""
     tensors = iter(tensors)
     blocks = (_lib.EcAdapterTrainLayer * layers)()
     p = _lib.EcAdapterTrainParams()
     p.in_dim, p.d_model, p.heads, p.ffn_dim, p.layers, p.residual = in_dim, d_model, heads, ffn_dim, layers, float(residual)
+    p.post_norm = int(post_norm)
     for dst, table in [(b, LAYER_PARAMS) for b in blocks] + [(p, PROJ_PARAMS)]:
         for _, field, _ in table:
             t = next(tensors)
@@ -131,9 +135,8 @@ class TransformerAdapter(Adapter):
     def __init__(self, in_dim, d_model=256, num_heads=4, ffn_dim=256 * 4, norm_first=True,
                  num_layers=2, residual=False):
         super().__init__(residual=residual)
-        if not norm_first:
-            raise NotImplementedError('only the pre-LN layout of the reference configs is built')
         self.in_dim, self.d_model, self.num_heads = in_dim, d_model, num_heads
+        self.norm_first = bool(norm_first)
         self.ffn_dim, self.num_layers = ffn_dim, num_layers
         enc_layer = nn.TransformerEncoderLayer(d_model=d_model, nhead=num_heads,
                                                dim_feedforward=ffn_dim, norm_first=norm_first,
@@ -177,7 +180,7 @@ class TransformerAdapter(Adapter):
         layers = (_lib.EcAdapterLayer * self.num_layers)()
         w = _lib.EcAdapterWeights()
         w.in_dim, w.d_model, w.heads, w.ffn = self.in_dim, self.d_model, self.num_heads, self.ffn_dim
-        w.layers, w.residual = self.num_layers, float(self.residual)
+        w.layers, w.residual, w.post_norm = self.num_layers, float(self.residual), int(not self.norm_first)
         for dst, mod, table in [(e, m, LAYER_PARAMS) for e, m in zip(layers, self.transformer_encoder.layers)] + \
                 [(w, self, PROJ_PARAMS)]:
             for leaf, field, matrix in table:
@@ -206,7 +209,7 @@ class TransformerAdapter(Adapter):
         seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0. else 0
         out, _ = torch.ops.eventclip_hip.adapter_train_fwd(rows.contiguous(), idx.contiguous(), list(self.parameters()),
                                                            self.d_model, self.num_heads, self.ffn_dim, self.num_layers,
-                                                           float(self.residual), p, seed)
+                                                           float(self.residual), p, seed, int(not self.norm_first))
         return out
 
     def forward(self, feats, valid_masks):

@@ -1,10 +1,15 @@
 // Few-shot feature adapter forward (gfx950, fp32).
 //
 // Replaces TransformerAdapter.forward + Adapter.residual_add of the reference
-// (models/adapter.py:82-105, :22-25): in_proj Linear(D -> d_model), L x pre-LN
+// (models/adapter.py:82-105, :22-25): in_proj Linear(D -> d_model), L <= 8 x
 // nn.TransformerEncoderLayer (torch defaults: ReLU, LayerNorm eps 1e-5, no final
 // norm, dropout off in eval) with src_key_padding_mask = ~valid, out_proj
-// Linear(d_model -> D), then  in * r + new * (1 - r).
+// Linear(d_model -> D), then  in * r + new * (1 - r).  Both layouts of the layer,
+// as a compile-time variant of the one kernel (ec_adapter_weights.post_norm):
+//   pre-LN  (norm_first = True)   x = x + SA(norm1(x));  x = x + FF(norm2(x))
+//   post-LN (norm_first = False)  x = norm1(x + SA(x));  x = norm2(x + FF(x))
+// Post-LN normalises the residual stream in place (a wave owns a row and has read
+// all of it before it writes), so both use the same LDS.
 //
 // The reference issues ~25 tiny fp32 kernels over [B, T <= 10, 256] tensors and is
 // launch-latency bound.  Here one 256-thread workgroup owns one sample and walks
@@ -19,7 +24,7 @@ namespace {
 
 constexpr int AD_THREADS = 256;
 constexpr int AD_MAXT = 16;
-constexpr int AD_MAXL = 4;
+constexpr int AD_MAXL = 8;
 
 struct AdArgs {
     int in_dim, dm, heads, ffn, layers, B, T;
@@ -89,6 +94,7 @@ __device__ void layer_norm(const float *in, float *out, int T, int W, const floa
     __syncthreads();
 }
 
+template <bool POST>
 __global__ __launch_bounds__(AD_THREADS) void adapter_kernel(const AdArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -113,9 +119,14 @@ __global__ __launch_bounds__(AD_THREADS) void adapter_kernel(const AdArgs a)
     linear(x0, D, D, a.in_w_t, a.in_b, dm, T, h, dm, 0);                  // adapter.py:95
     for (int l = 0; l < a.layers; l++) {
         const ec_adapter_layer &w = a.L[l];
-        // x = x + SA(norm1(x)) with key padding mask
-        layer_norm(h, y, T, dm, w.ln1_g, w.ln1_b);
-        linear(y, dm, dm, w.qkv_w_t, w.qkv_b, 3 * dm, T, big, wide, 0);
+        if constexpr (POST) {
+            // x = norm1(x + SA(x)) with key padding mask
+            linear(h, dm, dm, w.qkv_w_t, w.qkv_b, 3 * dm, T, big, wide, 0);
+        } else {
+            // x = x + SA(norm1(x)) with key padding mask
+            layer_norm(h, y, T, dm, w.ln1_g, w.ln1_b);
+            linear(y, dm, dm, w.qkv_w_t, w.qkv_b, 3 * dm, T, big, wide, 0);
+        }
         const float scale = rsqrtf((float)hd);
         for (int i = threadIdx.x; i < a.heads * T * T; i += AD_THREADS) {
             const int hh = i / (T * T), r = i - hh * T * T, tq = r / T, tk = r - tq * T;
@@ -146,10 +157,18 @@ __global__ __launch_bounds__(AD_THREADS) void adapter_kernel(const AdArgs a)
         }
         __syncthreads();
         linear(y, dm, dm, w.o_w_t, w.o_b, dm, T, h, dm, 2);
-        // x = x + FF(norm2(x)), ReLU
-        layer_norm(h, y, T, dm, w.ln2_g, w.ln2_b);
-        linear(y, dm, dm, w.w1_t, w.b1, a.ffn, T, big, wide, 1);
-        linear(big, wide, a.ffn, w.w2_t, w.b2, dm, T, h, dm, 2);
+        if constexpr (POST) {
+            // x = norm2(x + FF(x)), ReLU
+            layer_norm(h, h, T, dm, w.ln1_g, w.ln1_b);
+            linear(h, dm, dm, w.w1_t, w.b1, a.ffn, T, big, wide, 1);
+            linear(big, wide, a.ffn, w.w2_t, w.b2, dm, T, h, dm, 2);
+            layer_norm(h, h, T, dm, w.ln2_g, w.ln2_b);
+        } else {
+            // x = x + FF(norm2(x)), ReLU
+            layer_norm(h, y, T, dm, w.ln2_g, w.ln2_b);
+            linear(y, dm, dm, w.w1_t, w.b1, a.ffn, T, big, wide, 1);
+            linear(big, wide, a.ffn, w.w2_t, w.b2, dm, T, h, dm, 2);
+        }
     }
     // out_proj, then in * r + new * (1 - r)   (adapter.py:102-105, :22-25)
     const float r = a.residual;
@@ -193,6 +212,7 @@ extern "C" EC_API int ec_adapter_forward(const ec_adapter_weights *w, const floa
                "ec_adapter_forward: bad dims");
     EC_REQUIRE(w->residual >= 0.f && w->residual <= 1.f, "ec_adapter_forward: residual %f",
                w->residual);   // adapter.py:17-18
+    EC_REQUIRE(w->post_norm == 0 || w->post_norm == 1, "ec_adapter_forward: post_norm %d", w->post_norm);
     if (B == 0) return EC_OK;
     EC_REQUIRE(feats && row_idx && out, "ec_adapter_forward: null buffer");
     AdArgs a;
@@ -205,13 +225,14 @@ extern "C" EC_API int ec_adapter_forward(const ec_adapter_weights *w, const floa
     const int lds = (T * a.in_dim + 2 * T * a.dm + T * wide + a.heads * T * T) * 4;
     EC_REQUIRE(lds <= 160 * 1024, "ec_adapter_forward: needs %d bytes of LDS", lds);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    void (*const kernel)(const AdArgs) = w->post_norm ? adapter_kernel<true> : adapter_kernel<false>;
     if (lds > 64 * 1024)
-        EC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(adapter_kernel),
+        EC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     // flops per sample: 2*T*(D*dm*2 + layers*(4*dm*dm + 2*dm*ffn)) + attention
     const double fl = 2.0 * T * (2.0 * a.in_dim * a.dm + a.layers * (4.0 * a.dm * a.dm + 2.0 * a.dm * a.ffn));
     ec::ProfScope prof(ec::PROF_ADAPTER, s, fl * B, 0);
-    hipLaunchKernelGGL(adapter_kernel, dim3(B), dim3(AD_THREADS), lds, s, a);
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(AD_THREADS), lds, s, a);
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }

@@ -5,7 +5,7 @@
 //   forward   FSCLIPClassifier.forward, models/clip_cls.py:302-350: identity adapter, F.normalize of
 //             the image features (:325-327), invalid views zeroed (:329), text_feats =
 //             F.normalize(parameter) (:285-288), full_logits = logit_scale * feats @ text^T (:332),
-//             aggregation (:104-129);
+//             aggregation (:104-129): sum, mean or max over the valid views;
 //   loss      calc_train_loss, :164-175: cross-entropy on the aggregated logits, or NLL of
 //             log(probs + 1e-6);
 //   backward  d loss / d text_feats (torch autograd upstream), written out in closed form here:
@@ -94,6 +94,8 @@ __global__ __launch_bounds__(TR_THREADS) void fs_normalize_kernel(const float *f
 
 // One workgroup per sample: its per-view logits (full_logits[v][k] = scale * fn_v . u_k, :332 -- an fp32 MFMA
 // product of all view rows at once, left in the dL rows) into LDS, loss and dL rows.
+// EC_AGG_MAX (:116-121, logits - 1e6 [invalid], then max): per class the maximum over the valid views; its gradient goes
+// to that view alone, the lowest index on a tie, every other view gets an exact zero (classify_dz_kernel's rule).
 // LDS: logits [T][K] | reduction scratch
 __global__ __launch_bounds__(TR_THREADS) void fs_loss_grad_kernel(
     const unsigned char *valid, const int *labels, int B, int T, int K, int agg, int probs_loss, float *dL,
@@ -117,8 +119,14 @@ __global__ __launch_bounds__(TR_THREADS) void fs_loss_grad_kernel(
         float mx = -INFINITY;
         for (int k = threadIdx.x; k < K; k += TR_THREADS) {
             float s = 0.f;
-            for (int v = 0; v < T; v++) s += lg[v * K + k];
-            s *= wv;
+            if (agg == EC_AGG_MAX) {
+                s = -INFINITY;
+                for (int v = 0; v < T; v++)
+                    if (valid[b * T + v]) s = fmaxf(s, lg[v * K + k]);
+            } else {
+                for (int v = 0; v < T; v++) s += lg[v * K + k];
+                s *= wv;
+            }
             lg[k] = s;                      // row 0 now holds the aggregated logits (each k by one thread)
             mx = fmaxf(mx, s);
         }
@@ -131,6 +139,17 @@ __global__ __launch_bounds__(TR_THREADS) void fs_loss_grad_kernel(
         for (int k = threadIdx.x; k < K; k += TR_THREADS) {
             const float g = (__expf(lg[k] - lse) - (k == y ? 1.f : 0.f)) / (float)B;
             if (agg_logits) agg_logits[(long)b * K + k] = lg[k];
+            if (agg == EC_AGG_MAX) {
+                // the dL rows still hold this class's logits (only this thread writes column k): find the winner again
+                int amax = -1;
+                float best = -INFINITY;
+                for (int v = 0; v < T; v++) {
+                    const float l = dL[((long)b * T + v) * K + k];
+                    if (valid[b * T + v] && l > best) best = l, amax = v;
+                }
+                for (int v = 0; v < T; v++) dL[((long)b * T + v) * K + k] = v == amax ? g : 0.f;
+                continue;
+            }
             for (int v = 0; v < T; v++) dL[((long)b * T + v) * K + k] = g * wv;
         }
     } else {
@@ -151,14 +170,16 @@ __global__ __launch_bounds__(TR_THREADS) void fs_loss_grad_kernel(
         loss = -__logf(Py + 1e-6f);
         const float dPy = -1.f / ((float)B * (Py + 1e-6f));
         for (int k = threadIdx.x; k < K; k += TR_THREADS) {
-            float agg_k = 0.f;
+            float agg_k = 0.f, max_k = -INFINITY;
             for (int v = 0; v < T; v++) {
                 const float p = __expf(lg[v * K + k] - vmax[v]) / vsum[v];
                 const float c = valid[b * T + v] ? dPy * pvy[v] / n_valid : 0.f;
                 dL[((long)b * T + v) * K + k] = c * ((k == y ? 1.f : 0.f) - p);
                 agg_k += lg[v * K + k];
+                if (valid[b * T + v]) max_k = fmaxf(max_k, lg[v * K + k]);
             }
-            if (agg_logits) agg_logits[(long)b * K + k] = agg == EC_AGG_MEAN ? agg_k / n_valid : agg_k;
+            if (agg_logits)
+                agg_logits[(long)b * K + k] = agg == EC_AGG_MAX ? max_k : (agg == EC_AGG_MEAN ? agg_k / n_valid : agg_k);
         }
     }
     if (threadIdx.x == 0) loss_b[b] = loss;
@@ -598,8 +619,7 @@ int ec::fs_text_loss_grad(const float *img_feats, const int32_t *row_idx, const 
                           size_t workspace_bytes, ec_stream_t stream)
 {
     EC_REQUIRE(B > 0 && T > 0 && D > 0 && K > 0, "ec_fs_text_loss_grad: bad shape");
-    EC_REQUIRE(agg == EC_AGG_SUM || agg == EC_AGG_MEAN,
-               "ec_fs_text_loss_grad: agg must be sum or mean ('max' raises in the reference, clip_cls.py:117)");
+    EC_REQUIRE(agg == EC_AGG_SUM || agg == EC_AGG_MEAN || agg == EC_AGG_MAX, "ec_fs_text_loss_grad: unknown agg %d", agg);
     EC_REQUIRE(img_feats && valid && labels && text_param && loss && grad_text && workspace,
                "ec_fs_text_loss_grad: null buffer");
     EC_REQUIRE(workspace_bytes >= ec_fs_text_train_workspace_bytes(B, T, D, K),
@@ -662,7 +682,7 @@ extern "C" EC_API int ec_adam_step(float *param, const float *grad, float *exp_a
 }
 
 // ---------------------------------------------------------------------------------------------------
-// 'text-trans': TransformerAdapter (models/adapter.py:52-110) + text_feats.  Layer-wise over all
+// 'text-trans': TransformerAdapter (models/adapter.py:52-110, norm_first or not) + text_feats.  Layer-wise over all
 // R = B * T view rows: every nn.Linear is one sgemm_kernel launch (x W^T forward, dy W and dy^T x
 // backward), the saved activations live in the workspace.  dropout_p = 0 is the deterministic function the
 // eval-mode module computes, the one the golden gradients differentiate; dropout_p > 0 adds the four train-mode
@@ -772,11 +792,21 @@ unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256 < 4096 ? (n + 25
 bool adapter_geometry_ok(const ec_adapter_train_params *w, int T)
 {
     return w->in_dim > 0 && w->d_model > 0 && w->d_model <= 1024 && w->ffn_dim > 0 && w->heads > 0 &&
-           w->d_model % w->heads == 0 && w->layers >= 1 && w->layers <= 8 && T <= AD_MAXT;
+           w->d_model % w->heads == 0 && w->layers >= 1 && w->layers <= 8 && T <= AD_MAXT &&
+           (w->post_norm == 0 || w->post_norm == 1);
 }
 
-// dropout sites of layer l (nn.TransformerEncoderLayer, norm_first): 4 l + {0 attention weights,
+// dropout sites of layer l (nn.TransformerEncoderLayer, either layout): 4 l + {0 attention weights,
 // 1 dropout1 after out_proj, 2 dropout inside the MLP, 3 dropout2 after linear2}
+//
+// w->post_norm picks the layer's layout; both are launch sequences over the same kernels, tape slots and scratch:
+//   pre-LN   h1 = h + drop1(out_proj(attn(in_proj(norm1(h))))),  h' = h1 + drop2(linear2(drop(relu(linear1(norm2(h1))))))
+//   post-LN  a = norm1(h + drop1(out_proj(attn(in_proj(h))))),   h' = norm2(a + drop2(linear2(drop(relu(linear1(a))))))
+// Post-LN keeps norm1's input in h1, norm1's output in a (linear1's input and the second residual base), norm2's output
+// in bn (the next layer's input; the last layer's also in hfin); norm2's input passes through hfin and is not kept.  Its
+// backward takes norm2's gradients from the layer's output gradient alone (no residual skips the norm), then linear2,
+// ReLU, linear1, d a = d f W1 + d s2, norm1, out_proj, attention, and in_proj_weight's gradient against the layer's INPUT
+// (h0, or the previous layer's bn), d h = d qkv Wqkv + d s1.
 
 // The adapter's forward (adapter.py:82-105) over all R = B * T view rows, saving what the backward reads:
 // mixed [R, D] = r img_feats + (1 - r) out_proj(encoder(in_proj(img_feats))).  The one launch sequence behind
@@ -790,7 +820,48 @@ void adapter_train_fwd_launches(hipStream_t s, const float *img_feats, const uns
     const unsigned ln_grid = (unsigned)((R + 3) / 4);
     linear_fwd(s, img_feats, w->in_w, w->in_b, R, D, d, t.h0);
     const float *h = t.h0;
-    for (int l = 0; l < layers; l++) {
+    for (int l = 0; l < layers && w->post_norm; l++) {
+        // post-LN: s1 = h + dropout1(out_proj(attn(in_proj(h)))), a = norm1(s1),
+        //          s2 = a + dropout2(linear2(dropout(relu(linear1(a))))), bn = norm2(s2) -- the next layer's input
+        const ec_adapter_train_layer &p = w->blocks[l];
+        LayerBufs &b = t.L[l];
+        linear_fwd(s, h, p.qkv_w, p.qkv_b, R, d, 3 * d, b.qkv);
+        hipLaunchKernelGGL(adapter_attn_fwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, valid, T, d, heads, b.P, b.o,
+                           dp, seed, (unsigned)(4 * l));
+        if (dp > 0.f) {
+            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, t.ftmp);
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, t.ftmp,
+                               (long)R * d, dp, seed, (unsigned)(4 * l + 1), b.h1);
+        } else {
+            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, (const float *)nullptr,
+                               (long)R * d, 1.f, 0.f, b.h1);
+            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, b.h1, 1.f);
+        }
+        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, b.h1, p.ln1_g, p.ln1_b, R, d, b.a, b.xhat1,
+                           b.rstd1);
+        linear_fwd(s, b.a, p.w1, p.b1, R, d, ffn, b.f, 0.f, true);
+        if (dp > 0.f)
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s,
+                               (const float *)nullptr, b.f, (long)R * ffn, dp, seed, (unsigned)(4 * l + 2), b.f);
+        if (dp > 0.f) {                 // s2 lives in hfin until norm2 has read it: it is not kept
+            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.ftmp);
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.a, t.ftmp,
+                               (long)R * d, dp, seed, (unsigned)(4 * l + 3), t.hfin);
+        } else {
+            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.a, (const float *)nullptr,
+                               (long)R * d, 1.f, 0.f, t.hfin);
+            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.hfin, 1.f);
+        }
+        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, t.hfin, p.ln2_g, p.ln2_b, R, d, b.bn, b.xhat2,
+                           b.rstd2);
+        h = b.bn;
+        if (l == layers - 1) {          // out_proj (and its backward) read the encoder's output from hfin, as pre-LN
+            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.bn, (const float *)nullptr,
+                               (long)R * d, 1.f, 0.f, t.hfin);
+            h = t.hfin;
+        }
+    }
+    for (int l = 0; l < layers && !w->post_norm; l++) {
         const ec_adapter_train_layer &p = w->blocks[l];
         LayerBufs &b = t.L[l];
         hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, h, p.ln1_g, p.ln1_b, R, d, b.a, b.xhat1, b.rstd1);
@@ -839,7 +910,42 @@ void adapter_train_bwd_launches(hipStream_t s, const float *img_feats, int B, in
     const unsigned ln_grid = (unsigned)((R + 3) / 4);
     const float keep_scale = 1.f / (1.f - dp);
     linear_bwd(s, t.hfin, w->out_w, x.dy, R, d, D, x.dh, 0.f, g->out_w, g->out_b);
-    for (int l = layers - 1; l >= 0; l--) {
+    for (int l = layers - 1; l >= 0 && w->post_norm; l--) {
+        // post-LN; x.dh = d loss / d bn (the layer's output) on entry, d loss / d the layer's input on exit
+        const ec_adapter_train_layer &p = w->blocks[l];
+        const ec_adapter_train_layer &q = g->blocks[l];
+        const LayerBufs &b = t.L[l];
+        const float *hin = l ? t.L[l - 1].bn : t.h0;
+        // bn = norm2(s2): nothing skips norm2, so its input gradient is d s2 alone
+        ln_param_bwd(s, x.dh, b.xhat2, R, d, q.ln2_g, q.ln2_b);
+        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, x.dh, b.xhat2, b.rstd2, p.ln2_g, R, d, x.dh1, 0);
+        // s2 = a + dropout2(linear2(dropout(relu(linear1(a)))))
+        const float *dlin2 = x.dh1;
+        if (dp > 0.f) {
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
+                               (const float *)nullptr, x.dh1, (long)R * d, dp, seed, (unsigned)(4 * l + 3), x.dtmp_d);
+            dlin2 = x.dtmp_d;
+        }
+        linear_bwd(s, b.f, p.w2, dlin2, R, ffn, d, x.df, 0.f, q.w2, q.b2);
+        hipLaunchKernelGGL(relu_bwd_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s, b.f, (long)R * ffn,
+                           keep_scale, x.df);
+        linear_bwd(s, b.a, p.w1, x.df, R, d, ffn, x.dh1, 1.f, q.w1, q.b1);          // d a = d f W1 + d s2
+        // a = norm1(s1)
+        ln_param_bwd(s, x.dh1, b.xhat1, R, d, q.ln1_g, q.ln1_b);
+        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, x.dh1, b.xhat1, b.rstd1, p.ln1_g, R, d, x.dh, 0);
+        // s1 = h + dropout1(out_proj(attn(in_proj(h)))); x.dh = d s1, the residual's share of d h
+        const float *dlin_o = x.dh;
+        if (dp > 0.f) {
+            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
+                               (const float *)nullptr, x.dh, (long)R * d, dp, seed, (unsigned)(4 * l + 1), x.dh1);
+            dlin_o = x.dh1;       // d a is consumed
+        }
+        linear_bwd(s, b.o, p.o_w, dlin_o, R, d, d, x.dtmp_d, 0.f, q.o_w, q.o_b);
+        hipLaunchKernelGGL(adapter_attn_bwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, b.P, x.dtmp_d, T, d, heads,
+                           x.dqkv, dp, seed, (unsigned)(4 * l));
+        linear_bwd(s, hin, p.qkv_w, x.dqkv, R, d, 3 * d, x.dh, 1.f, q.qkv_w, q.qkv_b);   // d h = d qkv Wqkv + d s1
+    }
+    for (int l = layers - 1; l >= 0 && !w->post_norm; l--) {
         const ec_adapter_train_layer &p = w->blocks[l];
         const ec_adapter_train_layer &q = g->blocks[l];
         const LayerBufs &b = t.L[l];
@@ -900,7 +1006,7 @@ extern "C" EC_API int ec_fs_trans_loss_grad(const float *img_feats, const uint8_
     EC_REQUIRE(B > 0 && T > 0 && D > 0 && K > 0, "ec_fs_trans_loss_grad: bad shape");
     EC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "ec_fs_trans_loss_grad: dropout_p=%g", (double)dropout_p);
     EC_REQUIRE(w && g && w->blocks && g->blocks, "ec_fs_trans_loss_grad: null parameter / gradient structs");
-    EC_REQUIRE(agg == EC_AGG_SUM || agg == EC_AGG_MEAN, "ec_fs_trans_loss_grad: agg must be sum or mean");
+    EC_REQUIRE(agg == EC_AGG_SUM || agg == EC_AGG_MEAN || agg == EC_AGG_MAX, "ec_fs_trans_loss_grad: unknown agg %d", agg);
     const int d = w->d_model, ffn = w->ffn_dim, heads = w->heads, layers = w->layers;
     EC_REQUIRE(w->in_dim == D && adapter_geometry_ok(w, T),
                "ec_fs_trans_loss_grad: unsupported adapter geometry (T <= %d, layers <= 8)", AD_MAXT);

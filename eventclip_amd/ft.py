@@ -637,7 +637,7 @@ def ft_loss_grad(img_feats, valid, labels, text_param, logit_scale, agg='mean', 
     aggregated logits [B, K])."""
     dev = _lib.require_gpu()
     if agg not in _AGG:
-        raise NotImplementedError(f'agg_func {agg!r}: the reference trains with sum / mean')
+        raise ValueError(f'agg_func {agg!r}: sum, mean or max')
     f = img_feats.float().contiguous()
     B, T = valid.shape
     D = f.shape[-1]

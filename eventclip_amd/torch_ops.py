@@ -295,7 +295,8 @@ classify.register_autograd(_classify_backward, setup_context=_classify_setup)
 
 # ---- the transformer adapter under autograd: forward and backward as two ops with a tape between them ----
 def _train_struct(params, *geometry):
-    """_adapter_struct over an op's ``params`` list (geometry: in_dim, d_model, heads, ffn_dim, layers, residual)."""
+    """_adapter_struct over an op's ``params`` list (geometry: in_dim, d_model, heads, ffn_dim, layers, residual,
+    post_norm)."""
     want = len(adapter_param_names(geometry[4]))
     if len(params) != want:
         raise RuntimeError(f'{NAMESPACE}: {len(params)} adapter parameters, {want} expected (named_parameters() order)')
@@ -305,17 +306,18 @@ def _train_struct(params, *geometry):
 @custom_op(f'{NAMESPACE}::adapter_train_fwd', mutates_args=(), device_types='cuda')
 def adapter_train_fwd(feats: torch.Tensor, row_idx: torch.Tensor, params: List[torch.Tensor], d_model: int, heads: int,
                       ffn_dim: int, layers: int, residual: float, dropout_p: float,
-                      seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
+                      seed: int, post_norm: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """feats fp32 [B * T, C] with zero rows on invalid views, row_idx int32 [B, T] (< 0 = invalid view), params the
     adapter's parameters in ``adapter_param_names`` order -> (out [B, T, C], the residual mix of adapter.py:22-25;
-    tape uint8 [n]: the saved activations ``adapter_train_bwd`` reads)."""
+    tape uint8 [n]: the saved activations ``adapter_train_bwd`` reads).  post_norm: 0 the pre-LN encoder layer
+    (norm_first=True), 1 the post-LN one; the tape has the same size for both."""
     B, T = row_idx.shape
     C = int(feats.shape[-1])
     if tuple(feats.shape) != (B * T, C):
         raise RuntimeError(f'{NAMESPACE}::adapter_train_fwd: feats {tuple(feats.shape)} is not [B * T = {B * T}, C]')
     feats = _f32c(feats)
     params = [_f32c(p) for p in params]
-    w, keep = _train_struct(params, C, d_model, heads, ffn_dim, layers, residual)   # noqa: F841 (the struct's layer array)
+    w, keep = _train_struct(params, C, d_model, heads, ffn_dim, layers, residual, post_norm)   # noqa: F841 (the layer array)
     out = torch.empty((B, T, C), dtype=torch.float32, device=feats.device)
     need = int(_lib.lib().ec_adapter_train_tape_bytes(B, T, C, d_model, ffn_dim, heads, layers))
     tape = _lib.scratch(need, feats.device).zero_()       # its alignment gaps too: an output
@@ -332,18 +334,28 @@ def _tape_numel(B, T, C, d_model, heads, ffn_dim, layers):
 
 
 @adapter_train_fwd.register_fake
-def _(feats, row_idx, params, d_model, heads, ffn_dim, layers, residual, dropout_p, seed):
+def _(feats, row_idx, params, d_model, heads, ffn_dim, layers, residual, dropout_p, seed, post_norm=0):
     B, T = row_idx.shape
     C = feats.shape[-1]
     return (feats.new_empty((B, T, C), dtype=torch.float32),
             feats.new_empty((_tape_numel(B, T, C, d_model, heads, ffn_dim, layers),), dtype=torch.uint8))
 
 
+_MASK_BITS = 62
+
+
+def _join_mask(lo, hi):
+    return int(lo) | (int(hi) << _MASK_BITS)
+
+
 @custom_op(f'{NAMESPACE}::adapter_train_bwd', mutates_args=(), device_types='cuda')
 def adapter_train_bwd(feats: torch.Tensor, row_idx: torch.Tensor, params: List[torch.Tensor], tape: torch.Tensor,
                       d_out: torch.Tensor, d_model: int, heads: int, ffn_dim: int, layers: int, residual: float,
-                      dropout_p: float, seed: int, need_mask: int) -> List[torch.Tensor]:
-    """The backward of ``adapter_train_fwd`` over its tape (only read: a second call gives the same bits).  Returns
+                      dropout_p: float, seed: int, need_mask: int, post_norm: int = 0,
+                      need_mask_hi: int = 0) -> List[torch.Tensor]:
+    """The backward of ``adapter_train_fwd`` over its tape (only read: a second call gives the same bits); post_norm is
+    the forward's.  need_mask holds bits 0 .. 61 of the mask below, need_mask_hi bits 62 and up (an adapter of more than 4
+    layers has more tensors than a 64-bit argument has bits).  Returns
     len(params) + 1 tensors: the gradient of params[i] where bit i of need_mask is set, d_feats [B * T, C] where bit
     len(params) is set, an empty tensor (and no launch) otherwise."""
     B, T = row_idx.shape
@@ -351,9 +363,10 @@ def adapter_train_bwd(feats: torch.Tensor, row_idx: torch.Tensor, params: List[t
     feats, d_out = _f32c(feats), _f32c(d_out)
     params = [_f32c(p) for p in params]
     n = len(params)
+    need_mask = _join_mask(need_mask, need_mask_hi)
     grads = [torch.empty_like(p) if need_mask >> i & 1 else None for i, p in enumerate(params)]
     d_feats = torch.empty_like(feats) if need_mask >> n & 1 else None
-    geometry = (C, d_model, heads, ffn_dim, layers, residual)
+    geometry = (C, d_model, heads, ffn_dim, layers, residual, post_norm)
     w, keep_w = _train_struct(params, *geometry)      # noqa: F841 (the struct's layer array)
     g, keep_g = _train_struct(grads, *geometry)       # noqa: F841
     ws = _lib.scratch(_lib.lib().ec_adapter_train_backward_workspace_bytes(B, T, C, d_model, ffn_dim), feats.device)
@@ -364,8 +377,10 @@ def adapter_train_bwd(feats: torch.Tensor, row_idx: torch.Tensor, params: List[t
 
 
 @adapter_train_bwd.register_fake
-def _(feats, row_idx, params, tape, d_out, d_model, heads, ffn_dim, layers, residual, dropout_p, seed, need_mask):
+def _(feats, row_idx, params, tape, d_out, d_model, heads, ffn_dim, layers, residual, dropout_p, seed, need_mask,
+      post_norm=0, need_mask_hi=0):
     like = list(params) + [feats]
+    need_mask = _join_mask(need_mask, need_mask_hi)
     return [feats.new_empty(tuple(t.shape) if need_mask >> i & 1 else (0,), dtype=torch.float32)
             for i, t in enumerate(like)]
 
@@ -373,7 +388,8 @@ def _(feats, row_idx, params, tape, d_out, d_model, heads, ffn_dim, layers, resi
 def _adapter_setup(ctx, inputs, output):
     feats, row_idx, params = inputs[:3]
     ctx.save_for_backward(feats, row_idx, output[1], *params)
-    ctx.tail = tuple(inputs[3:])
+    ctx.tail = tuple(inputs[3:10])          # d_model .. seed
+    ctx.post_norm = inputs[10]
     ctx.mark_non_differentiable(output[1])
     ctx.set_materialize_grads(False)
 
@@ -382,12 +398,15 @@ def _adapter_backward(ctx, d_out, d_tape):
     feats, row_idx, tape, *params = ctx.saved_tensors
     n = len(params)
     need = list(ctx.needs_input_grad[2]) + [ctx.needs_input_grad[0]]
+    # one None per scalar argument the call carried: the dispatcher drops a trailing post_norm that equals its default
+    tail = (None,) * (len(ctx.needs_input_grad) - 3)
     if d_out is None or not any(need):
-        return (None, None, [None] * n) + (None,) * 7
+        return (None, None, [None] * n) + tail
     mask = sum(1 << i for i, b in enumerate(need) if b)
-    got = torch.ops.eventclip_hip.adapter_train_bwd(feats, row_idx, params, tape, d_out, *ctx.tail, mask)
+    got = torch.ops.eventclip_hip.adapter_train_bwd(feats, row_idx, params, tape, d_out, *ctx.tail,
+                                                    mask & ((1 << _MASK_BITS) - 1), ctx.post_norm, mask >> _MASK_BITS)
     grads = [t if b else None for t, b in zip(got, need)]
-    return (grads[n], None, grads[:n]) + (None,) * 7
+    return (grads[n], None, grads[:n]) + tail
 
 
 adapter_train_fwd.register_autograd(_adapter_backward, setup_context=_adapter_setup)

@@ -17,17 +17,18 @@ import torch.distributed as dist
 from . import _lib
 from .adapter import _adapter_struct
 
-_AGG = {'sum': _lib.EC_AGG_SUM, 'mean': _lib.EC_AGG_MEAN}
+_AGG = {'sum': _lib.EC_AGG_SUM, 'mean': _lib.EC_AGG_MEAN, 'max': _lib.EC_AGG_MAX}
 _scratch = collections.defaultdict(_lib.Scratch)      # device index -> the loss kernels' workspace
 
 
 def fs_text_loss_grad(img_feats, valid, labels, text_param, logit_scale, agg='sum', use_probs_loss=False,
                       return_logits=False):
     """img_feats fp32 CUDA [B, T, D] (raw encoder outputs), valid bool [B, T], labels int [B],
-    text_param fp32 [K, D] (raw parameter).  Returns (loss 0-dim tensor, grad [K, D][, logits [B, K]])."""
+    text_param fp32 [K, D] (raw parameter), agg 'sum' | 'mean' | 'max' (the maximum over the valid views; its gradient
+    goes to the maximal view alone).  Returns (loss 0-dim tensor, grad [K, D][, logits [B, K]])."""
     dev = _lib.require_gpu()
     if agg not in _AGG:
-        raise NotImplementedError(f'agg_func {agg!r}: the reference trains with sum / mean')
+        raise ValueError(f'agg_func {agg!r}: sum, mean or max')
     f = img_feats.float().contiguous()
     B, T, D = f.shape
     t = text_param.detach().float().contiguous()
@@ -57,7 +58,8 @@ def dropout_mask(seed, site, n, p):
 def fs_trans_loss_grad(img_feats, valid, labels, text_param, logit_scale, adapter, agg='sum',
                        use_probs_loss=False, return_logits=False, dropout_p=0., seed=0, out=None):
     """The `text-trans` step: img_feats fp32 CUDA [B, T, D] with ZERO rows on invalid views
-    (clip_cls.py:319-321), ``adapter`` an eventclip_amd.adapter.TransformerAdapter on the GPU.
+    (clip_cls.py:319-321), ``adapter`` an eventclip_amd.adapter.TransformerAdapter on the GPU, pre- or post-LN
+    (``adapter.norm_first``); agg 'sum' | 'mean' | 'max'.
     Returns (loss, grads) with grads = {adapter state-dict name: tensor, 'text_feats': [K, D]}
     dropout_p > 0: the train-mode dropouts of nn.TransformerEncoderLayer (p = 0.1 upstream), masks from a
     stateless hash of (seed, site, element); 0: the deterministic eval-mode function.
@@ -65,7 +67,7 @@ def fs_trans_loss_grad(img_feats, valid, labels, text_param, logit_scale, adapte
     fixed buffers -- nothing is allocated for them then)."""
     dev = _lib.require_gpu()
     if agg not in _AGG:
-        raise NotImplementedError(f'agg_func {agg!r}: the reference trains with sum / mean')
+        raise ValueError(f'agg_func {agg!r}: sum, mean or max')
     f = img_feats.float().contiguous()
     B, T, D = f.shape
     t = text_param.detach().float().contiguous()
@@ -74,7 +76,8 @@ def fs_trans_loss_grad(img_feats, valid, labels, text_param, logit_scale, adapte
     for k, v in params.items():
         assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous(), k
     grads = {k: out[k] for k in params} if out is not None else {k: torch.empty_like(v) for k, v in params.items()}
-    geometry = (adapter.in_dim, adapter.d_model, adapter.num_heads, adapter.ffn_dim, adapter.num_layers, adapter.residual)
+    geometry = (adapter.in_dim, adapter.d_model, adapter.num_heads, adapter.ffn_dim, adapter.num_layers, adapter.residual,
+                int(not adapter.norm_first))
     ps, keep_p = _adapter_struct(params.values(), *geometry)
     gs, keep_g = _adapter_struct(grads.values(), *geometry)
     need = int(_lib.lib().ec_fs_trans_train_workspace_bytes(B, T, D, K, adapter.d_model, adapter.ffn_dim,

@@ -55,12 +55,15 @@ EC_API const char *ec_last_error(void);
  *        argument list changed)
  *   604  + ec_fingerprint_batched, ec_vit_train_backward_over / _scratch_bytes (additive)
  *   605  + ec_adapter_train_layout (additive: no struct or argument list changed)
+ *   606  ec_adapter_weights + post_norm, ec_adapter_train_params + post_norm (the post-LN encoder layout; 0 = pre-LN, what
+ *        every zero-initialised struct of an older caller meant); ec_adapter_forward takes 8 layers; the fused training
+ *        steps take EC_AGG_MAX
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does, with its ctypes mirrors.) */
-#define EC_ABI_VERSION 605
+#define EC_ABI_VERSION 606
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);
@@ -665,7 +668,9 @@ typedef struct {
     float residual;                /* r of in * r + new * (1 - r) */
     const float *in_w_t, *in_b;    /* in_proj.weight^T [in_dim, d_model] */
     const float *out_w_t, *out_b;  /* out_proj.weight^T [d_model, in_dim] */
-    const ec_adapter_layer *layer; /* host array [layers] */
+    const ec_adapter_layer *layer; /* host array [layers], layers <= 8 */
+    int post_norm;                 /* 0: norm_first = True (pre-LN), x + SA(norm1(x)), x + FF(norm2(x));
+                                      1: norm_first = False (post-LN), norm1(x + SA(x)), norm2(x + FF(x)) */
 } ec_adapter_weights;
 
 /* feats: fp32 [n_rows, in_dim]; row_idx: int32 [B, T] (row of feats or -1 = padded
@@ -690,8 +695,10 @@ EC_API int ec_pseudo_label(const float *probs, int B, int V, int K, float conf_t
  * loss :164-175, d loss / d text_feats (torch autograd upstream), torch.optim.Adam.
  *   img_feats   fp32 [B, T, D] encoder outputs, NOT normalised (any value on invalid views)
  *   valid       uint8 [B, T];  labels int32 [B];  text_param fp32 [K, D] (the nn.Parameter, raw)
- *   agg         EC_AGG_SUM / EC_AGG_MEAN;  use_probs_loss: 0 = CE on the aggregated logits,
- *               1 = NLL of log(probs + 1e-6) (loss_dict.use_probs_loss)
+ *   agg         EC_AGG_SUM / EC_AGG_MEAN / EC_AGG_MAX;  use_probs_loss: 0 = CE on the aggregated logits,
+ *               1 = NLL of log(probs + 1e-6) (loss_dict.use_probs_loss; probs are the masked mean whatever agg is).
+ *               EC_AGG_MAX: per class the maximum over the VALID views; its gradient goes to that view alone (the lowest
+ *               index on a tie), every other view and every invalid view gets an exact zero (as ec_classify_backward)
  *   loss        fp32 [1] (out, batch mean);  grad_text fp32 [K, D] (out)
  *   agg_logits  optional fp32 [B, K] (out): the aggregated logits of the forward pass
  * Every sample keeps at least one valid view: a sample with none divides by zero (here and in the reference). */
@@ -707,8 +714,8 @@ EC_API int ec_adam_step(float *param, const float *grad, float *exp_avg, float *
                         ec_stream_t stream);
 
 /* 'text-trans' (configs/fsclip/joint_adapter/): the same step with the TransformerAdapter
- * (models/adapter.py:52-110: in_proj -> nn.TransformerEncoder(norm_first, ReLU, key padding mask) ->
- * out_proj -> residual mix) in front of the normalisation, differentiated with respect to every
+ * (models/adapter.py:52-110: in_proj -> nn.TransformerEncoder(norm_first or not: params->post_norm, ReLU, key padding
+ * mask) -> out_proj -> residual mix) in front of the normalisation, differentiated with respect to every
  * adapter parameter and text_feats.  Parameter tensors are passed in torch's own layouts
  * ([out, in] weights, state-dict names in the comments), gradients come back in a second struct of the
  * same shape.  img_feats must hold ZERO rows for invalid views (clip_cls.py:319-321).
@@ -734,6 +741,7 @@ typedef struct {
     float *in_w, *in_b;                          /* in_proj.weight [d, in_dim] / .bias */
     float *out_w, *out_b;                        /* out_proj.weight [in_dim, d] / .bias */
     const ec_adapter_train_layer *blocks;        /* host array [layers] */
+    int post_norm;                               /* 0: pre-LN (norm_first = True), 1: post-LN; the gradient struct's is not read */
 } ec_adapter_train_params;
 
 EC_API size_t ec_fs_trans_train_workspace_bytes(int B, int T, int D, int K, int d_model, int ffn_dim,
@@ -783,7 +791,15 @@ EC_API int ec_adapter_train_backward(const float *img_feats, int B, int T, const
  * After ec_adapter_train_backward (each is overwritten layer by layer; what the FIRST layer left):
  *   dy     [R, D] (1 - residual) d_out                       dh   [R, d] d loss / d h0
  *   dh1    [R, d] d loss / d h1 of layer 0                   dtmp_d [R, d] d loss / d a (norm1's output) of layer 0
- *   dqkv   [R, 3d] d loss / d qkv of layer 0                 df   [R, ffn] d loss / d linear1's output of layer 0 */
+ *   dqkv   [R, 3d] d loss / d qkv of layer 0                 df   [R, ffn] d loss / d linear1's output of layer 0
+ * Under post_norm = 1 the same slots, of the same sizes, hold (s1 = x + dropout1(out_proj(o)), s2 = a + dropout2(linear2(f))):
+ *   hfin  [R, d] the last layer's norm2 output (a copy of its bn); while the forward runs, every layer's s2 (norm2's input,
+ *         not kept: a + the keep-scale of site 4 l + 3 times linear2(f) restates it)
+ *   layer: h1 = s1, norm1's INPUT; xhat1, rstd1, a = norm1's outputs, a also linear1's input and the second residual base;
+ *          qkv = in_proj of the layer's input (h0 for layer 0, the previous layer's bn otherwise); P, o, f as above;
+ *          xhat2, rstd2, bn = norm2's outputs, bn the layer's output and the next layer's input
+ *   dh    d loss / d h0       dh1  d loss / d a of layer 0 (dropout_p > 0: d loss / d out_proj's output, through dropout1)
+ *   dtmp_d  d loss / d o of layer 0                              dy, dqkv, df as above */
 enum { EC_AT_H0 = 0, EC_AT_HFIN, EC_AT_Y, EC_AT_FTMP, EC_AT_LAYER0 };
 enum { EC_AT_L_XHAT1 = 0, EC_AT_L_RSTD1, EC_AT_L_A, EC_AT_L_QKV, EC_AT_L_P, EC_AT_L_O, EC_AT_L_H1, EC_AT_L_XHAT2,
        EC_AT_L_RSTD2, EC_AT_L_BN, EC_AT_L_F, EC_AT_PER_LAYER };

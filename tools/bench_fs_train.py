@@ -3,7 +3,7 @@ shapes: `text-identity` (configs/fsclip/text_adapter: only text_feats trains) an
 (configs/fsclip/joint_adapter: TransformerAdapter d_model 256, 2 layers, 4 heads + text_feats), train_batch_size 128,
 views T, D = 768.
 
-    python tools/bench_fs_train.py [--batch 128] [--steps 50]
+    python tools/bench_fs_train.py [--batch 128] [--steps 50] [--variants pre:mean,post:mean,pre:max,post:max]
 
 One JSON line per (adapter type, geometry): ms per step and samples/s, and `cpu_baseline`: the oracle's step (loss +
 gradients in float64 -- numpy for `text-identity`, torch CPU autograd over the explicit forward for `text-trans` --
@@ -13,7 +13,12 @@ seeded weights.  The CPU leg is the only place the oracle is touched.
 Next to each fused step, `autograd`: the same batch through the reference's own loop -- `out = clf(data)`,
 `clf.calc_train_loss(data, out)['ce_loss'].backward()`, `torch.optim.Adam.step()` -- with the cached features standing
 in for the frozen encoder: ms per step, and the step's three parts timed on their own with a device sync after each
-(their sum exceeds the step: the syncs keep host and device from overlapping)."""
+(their sum exceeds the step: the syncs keep host and device from overlapping).
+
+`--variants` times further forms of the same steps beside the default `pre:mean` (the reference configs': pre-LN adapter,
+mean aggregation): `<layout>:<agg>` with layout pre | post (TransformerAdapter(norm_first); `text-identity` has no adapter
+and runs once per aggregation) and agg sum | mean | max.  Every line names its `norm_first` and `agg_func`; the float64
+`cpu_baseline` exists for the default variant only (the oracle restates the pre-LN adapter)."""
 import argparse
 import json
 import os
@@ -101,7 +106,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=128)
     ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--variants', default='pre:mean', help='comma-separated <pre|post>:<sum|mean|max>')
     a = ap.parse_args()
+    variants = [tuple(v.split(':')) for v in a.variants.split(',')]
+    assert all(len(v) == 2 and v[0] in ('pre', 'post') and v[1] in ('sum', 'mean', 'max') for v in variants), a.variants
     from eventclip_amd import _lib, clip as eclip, train
     from eventclip_amd.clip_cls import FSCLIPClassifier
     dev = _lib.require_gpu()
@@ -110,13 +118,18 @@ def main():
     # every device timing first, the CPU legs after: the oracle's torch-CPU worker threads keep spinning for a
     # while after their last parallel region and slow the launching thread of whatever is timed next
     cases = []
+    runs = []
+    for layout, agg in variants:
+        if ('text-identity', None, agg) not in runs:
+            runs.append(('text-identity', None, agg))
+        runs.append(('text-trans', layout, agg))
     for name, T, K in (('n_imagenet', 2, 1000), ('n_caltech', 10, 101), ('n_cars', 1, 2)):
-        for kind in ('text-identity', 'text-trans'):
+        for kind, layout, agg in runs:
             cd = dict(clip_model=model, prompt='a point cloud image of a {}', class_names=[f'c{i}' for i in range(K)],
-                      agg_func='mean', class_tokens=eclip.synthetic_tokens(K))
+                      agg_func=agg, class_tokens=eclip.synthetic_tokens(K))
             ad = dict(adapter_type=kind, residual=0.95)
             if kind == 'text-trans':
-                ad.update(in_dim=768, d_model=256, num_heads=4, ffn_dim=1024, norm_first=True, num_layers=2)
+                ad.update(in_dim=768, d_model=256, num_heads=4, ffn_dim=1024, norm_first=layout == 'pre', num_layers=2)
             clf = FSCLIPClassifier(adapter_dict=ad, clip_dict=cd, loss_dict=dict(use_logits_loss=True, use_probs_loss=False)).cuda()
             tr = (train.TextFeatTrainer if kind == 'text-identity' else train.AdapterTrainer)(clf, lr=2e-5, total_steps=10 ** 6)
             torch.manual_seed(0)
@@ -139,13 +152,17 @@ def main():
                 torch.cuda.synchronize()
                 dt = min(dt, (time.perf_counter() - t0) / a.steps)
             ag = autograd_step_ms(clf, feats, valid, labels, a.steps)
-            cases.append((kind, name, B, T, K, dt, float(loss), clf, feats, valid, labels, worst, ag))
-    for kind, name, B, T, K, dt, loss, clf, feats, valid, labels, worst, ag in cases:
-        cb = cpu_step(kind, clf, feats, valid, labels)
-        cb['speedup'] = round(cb['ms_per_step'] / (dt * 1e3), 1)
-        print(json.dumps(dict(adapter_type=kind, geometry=name, batch=B, views=T, classes=K,
-                              ms_per_step=round(dt * 1e3, 3), samples_per_s=round(B / dt, 1),
-                              loss=round(loss, 4), slowest_call_ms=round(worst * 1e3, 3), autograd=ag, cpu_baseline=cb)), flush=True)
+            form = dict(norm_first=layout == 'pre' if kind == 'text-trans' else None, agg_func=agg)
+            cases.append((kind, name, B, T, K, dt, float(loss), clf, feats, valid, labels, worst, ag, form))
+    for kind, name, B, T, K, dt, loss, clf, feats, valid, labels, worst, ag, form in cases:
+        line = dict(adapter_type=kind, geometry=name, batch=B, views=T, classes=K, **form,
+                    ms_per_step=round(dt * 1e3, 3), samples_per_s=round(B / dt, 1),
+                    loss=round(loss, 4), slowest_call_ms=round(worst * 1e3, 3), autograd=ag)
+        if form['agg_func'] == 'mean' and form['norm_first'] is not False:
+            cb = cpu_step(kind, clf, feats, valid, labels)
+            cb['speedup'] = round(cb['ms_per_step'] / (dt * 1e3), 1)
+            line['cpu_baseline'] = cb
+        print(json.dumps(line), flush=True)
 
 
 if __name__ == '__main__':
