@@ -68,6 +68,7 @@ class EcGemmArgs(ctypes.Structure):
                 ('variant', c_int), ('A', c_void_p), ('lda', c_long), ('W', c_void_p),
                 ('bias', c_void_p), ('C', c_void_p), ('ldc', c_long), ('diag', c_void_p),
                 ('ldw', c_long), ('resid', c_void_p), ('aux', c_void_p), ('splits', c_int),
+                ('activation', c_int),           # (the former alignment padding in front of split_stride)
                 ('split_stride', c_long), ('ws', c_void_p), ('ws_bytes', ctypes.c_size_t),
                 ('transposed', c_int), ('k_rows', c_int), ('row_stats', c_void_p), ('row_stats_stride', c_long),
                 ('col_sums', c_void_p), ('row_sums', c_void_p), ('A_lo', c_void_p), ('W_lo', c_void_p),
@@ -79,6 +80,20 @@ class EcGemmArgs(ctypes.Structure):
 EC_EPI_STORE16, EC_EPI_GELU16, EC_EPI_RESID32, EC_EPI_STORE32 = 0, 1, 2, 3
 EC_EPI_GELU16_SAVE, EC_EPI_GELU_BWD16 = 4, 5
 EC_EPI_RESID_HL, EC_EPI_STORE16_LN, EC_EPI_GELU16_LN = 6, 7, 8
+# ec_gemm_args / ec_*_weights .activation, by the config's name for it (cfg['activation'])
+EC_ACT_QUICK_GELU, EC_ACT_GELU = 0, 1
+ACTIVATIONS = {'quick_gelu': EC_ACT_QUICK_GELU, 'gelu': EC_ACT_GELU}
+
+
+def activation_code(name):
+    """cfg['activation'] (None = the default, QuickGELU) -> EC_ACT_*; anything else raises."""
+    if name is None:
+        return EC_ACT_QUICK_GELU
+    if name not in ACTIVATIONS:
+        raise ValueError(f"unknown activation {name!r}: one of {sorted(ACTIVATIONS)}")
+    return ACTIVATIONS[name]
+
+
 EC_STEP_LR0, EC_STEP_LR1, EC_STEP_BC1, EC_STEP_BC2_SQRT, EC_STEP_GRAD_SCALE, EC_STEP_INV_SCALE, EC_STEP_COUNT = 0, 1, 2, 3, 4, 5, 8
 EC_PRE_CHW_F32, EC_PRE_PATCHES16, EC_PRE_HWC_U8 = 0, 1, 2
 EC_AGG_SUM, EC_AGG_MEAN, EC_AGG_MAX = 0, 1, 2
@@ -123,7 +138,7 @@ class EcVitWeights(ctypes.Structure):
                 ('blocks', ctypes.POINTER(EcBlockWeights)), ('precise', c_int),
                 ('conv_w_lo', c_void_p), ('proj_w_lo', c_void_p), ('full_last_block', c_int),
                 ('low_latency', c_int), ('q_scaled', c_int), ('ln_folded', c_int), ('precise_blocks', c_int), ('weights_exact16', c_int),
-                ('precise_attn_blocks', c_int), ('lo_fp8', c_int)]
+                ('precise_attn_blocks', c_int), ('lo_fp8', c_int), ('activation', c_int)]
 
 
 class EcTextWeights(ctypes.Structure):
@@ -132,7 +147,7 @@ class EcTextWeights(ctypes.Structure):
                 ('token_embedding', c_void_p), ('pos', c_void_p), ('ln_final_g', c_void_p),
                 ('ln_final_b', c_void_p), ('proj_w', c_void_p),
                 ('blocks', ctypes.POINTER(EcBlockWeights)), ('precise', c_int),
-                ('proj_w_lo', c_void_p)]
+                ('proj_w_lo', c_void_p), ('activation', c_int)]
 
 
 class EcLoraItem(ctypes.Structure):
@@ -157,7 +172,7 @@ class EcBlockWeightsT(ctypes.Structure):
 
 
 class EcVitTrainWeights(ctypes.Structure):
-    _fields_ = [('blocks', ctypes.POINTER(EcBlockWeightsT)), ('proj', c_void_p)]
+    _fields_ = [('blocks', ctypes.POINTER(EcBlockWeightsT)), ('proj', c_void_p), ('activation', c_int)]
 
 
 BLOCK_GRAD_FIELDS = ('ln1_g', 'ln1_b', 'qkv_w', 'qkv_b', 'out_w', 'out_b', 'ln2_g', 'ln2_b', 'fc1_w', 'fc1_b',
@@ -356,7 +371,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 606      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
+ABI_VERSION = 607      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
 
 
 class HipLibraryError(RuntimeError):

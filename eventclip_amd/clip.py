@@ -48,20 +48,58 @@ ARCHS = {
 CONTEXT_LENGTH = 77
 VOCAB_SIZE = 49408
 
+# The MLP activation, cfg['activation']: 'quick_gelu' = x sigmoid(1.702 x), OpenAI's checkpoints and the default everywhere;
+# 'gelu' = x Phi(x), torch.nn.GELU(): every CLIP that open_clip trained without a -quickgelu suffix (LAION-400M / LAION-2B /
+# DataComp / CommonPool ViT-B/32, B/16, L/14) and Hugging Face configs with hidden_act "gelu".  The key layout of the two
+# families is the same and NOTHING in a state dict names the activation: the caller has to (build_from_state_dict / load
+# take activation=...; an open_clip architecture name or an HF config.json say it themselves).
+ACTIVATIONS = tuple(_lib.ACTIVATIONS)
+# open_clip's spellings -> (architecture here, activation)
+OPEN_CLIP_ARCHS = {
+    'ViT-B-32': ('ViT-B/32', 'gelu'), 'ViT-B-16': ('ViT-B/16', 'gelu'), 'ViT-L-14': ('ViT-L/14', 'gelu'),
+    'ViT-L-14-336': ('ViT-L/14@336px', 'gelu'),
+    'ViT-B-32-quickgelu': ('ViT-B/32', 'quick_gelu'), 'ViT-B-16-quickgelu': ('ViT-B/16', 'quick_gelu'),
+    'ViT-L-14-quickgelu': ('ViT-L/14', 'quick_gelu'), 'ViT-L-14-336-quickgelu': ('ViT-L/14@336px', 'quick_gelu'),
+}
+# open_clip towers whose attention heads are not 64 wide (width / heads): the attention kernels are built for 64
+_OTHER_HEAD_DIM = {'ViT-H-14': 80, 'ViT-g-14': 88, 'ViT-bigG-14': 104}
+
 
 def available_models():
-    return list(_RESNETS) + list(ARCHS)
+    return list(_RESNETS) + list(ARCHS) + list(OPEN_CLIP_ARCHS)
+
+
+def _check_activation(activation):
+    if activation not in ACTIVATIONS:
+        raise ValueError(f'unknown activation {activation!r}: one of {ACTIVATIONS}')
+    return activation
+
+
+def resolve_arch(name):
+    """An architecture name in OpenAI's or open_clip's spelling -> (name in ARCHS, the activation the name implies or None).
+    OpenAI's names and the ResNets imply nothing (None: the default, QuickGELU); open_clip's 'ViT-B-32' / 'ViT-B-16' / 'ViT-L-14'
+    say exact GELU, '...-quickgelu' says QuickGELU; ViT-H / g / bigG raise (head dimension 80 / 88 / 104)."""
+    base = name[:-len('-quickgelu')] if name.endswith('-quickgelu') else name
+    if base in _OTHER_HEAD_DIM:
+        raise NotImplementedError(f'{name}: its attention heads are {_OTHER_HEAD_DIM[base]} wide and the attention kernels are '
+                                  'built for a head dimension of 64 (ViT-B/32, B/16, L/14)')
+    if name in OPEN_CLIP_ARCHS:
+        return OPEN_CLIP_ARCHS[name]
+    return name, None
 
 
 def arch_config(arch, **override):
-    """Config of a ViT architecture; ResNet names raise (their configs come from resnet_config)."""
+    """Config of a ViT architecture (OpenAI's name, or open_clip's, which also sets cfg['activation']); ResNet names raise
+    (their configs come from resnet_config)."""
     if arch in _RESNETS:
         raise NotImplementedError(f'{arch}: arch_config holds the ViT architectures; '
                                   f'use resnet_config({arch!r}) for the ResNet backbones')
+    arch, implied = resolve_arch(arch)
     if arch not in ARCHS:
         raise RuntimeError(f'Model {arch} not found; available models = {available_models()}')
-    cfg = dict(ARCHS[arch], context_length=CONTEXT_LENGTH, vocab_size=VOCAB_SIZE)
+    cfg = dict(ARCHS[arch], context_length=CONTEXT_LENGTH, vocab_size=VOCAB_SIZE, activation=implied or 'quick_gelu')
     cfg.update(override)
+    _check_activation(cfg['activation'])
     return cfg
 
 
@@ -145,6 +183,8 @@ def config_from_state_dict(sd):
     g = round((sd['visual.positional_embedding'].shape[0] - 1) ** 0.5)
     layers = len({k.split('.')[3] for k in sd if k.startswith('visual.transformer.resblocks.')})
     TW = sd['ln_final.weight'].shape[0]
+    if W % 64 or TW % 64:
+        raise NotImplementedError(f'widths {W} / {TW} are not multiples of the head dimension 64 the attention kernels are built for')
     return dict(image_size=g * P, patch=P, width=W, layers=layers,
                 embed_dim=sd['text_projection'].shape[1], text_width=TW, text_heads=TW // 64,
                 text_layers=len({k.split('.')[2] for k in sd
@@ -206,6 +246,7 @@ class CLIP(ClipBase):
                  image_precise=False, full_last_block=None, low_latency=False, ln_folded=None, q_scaled=True,
                  image_precise_blocks=None, image_precise_attn_blocks=None, image_lo_fp8=None):
         super().__init__(cfg, state_dict, dtype, chunk)
+        self.cfg['activation'] = _check_activation(self.cfg.get('activation') or 'quick_gelu')
         # split-precision (~fp32) arithmetic: on for the text tower (run once, cached by the
         # classifiers), off for the image tower (3x the GEMM work; validation only)
         self.text_precise, self.image_precise = bool(text_precise), bool(image_precise)
@@ -304,6 +345,7 @@ class CLIP(ClipBase):
         v.precise_blocks = self.image_precise_blocks
         v.precise_attn_blocks = self.image_precise_attn_blocks
         v.lo_fp8 = int(self.image_lo_fp8)
+        v.activation = _lib.activation_code(c.get('activation'))
         v.conv_w_lo = dev16_pair(conv_lo, null_if_exact=True)[1]
         vb = pk.blocks('visual.transformer', c['layers'], self.image_precise, q_scaled_all=bool(v.q_scaled),
                        ln_folded=bool(v.ln_folded), precise_first=self.image_precise_blocks, lo_fp8=self.image_lo_fp8)
@@ -350,9 +392,20 @@ class CLIP(ClipBase):
         return self.encode_patches(patches)
 
 
+def _refuse_resnet_gelu(activation):
+    if activation not in (None, 'quick_gelu'):
+        _check_activation(activation)
+        raise NotImplementedError("the ResNet towers take no activation='gelu': their convolutions use ReLU and their text tower "
+                                  'runs QuickGELU only')
+
+
 def build_random(arch, seed=0, dtype='float16', device='cuda', chunk=2560, **override):
-    """Random-weight CLIP of a named architecture (benchmarks / tests: no checkpoints ship)."""
+    """Random-weight CLIP of a named architecture (benchmarks / tests: no checkpoints ship).  activation='gelu' (or an
+    open_clip name such as 'ViT-B-32') builds the exact-GELU network."""
+    if override.get('activation', '') is None:
+        override.pop('activation')
     if arch in RESNET_ARCHS:
+        _refuse_resnet_gelu(override.pop('activation', None))
         mode = {k: override.pop(k) for k in ('precise_blocks', 'precise') if k in override}   # tolerance_mode_kwargs(arch)
         cfg = resnet_config(arch, **override)
         model = _resnet.ResNetCLIP(cfg, random_state_dict(cfg, seed), dtype=dtype, **mode)
@@ -364,14 +417,17 @@ def build_random(arch, seed=0, dtype='float16', device='cuda', chunk=2560, **ove
     return model.eval()
 
 
-def build_from_state_dict(sd, dtype='float16', device='cuda', chunk=2560, precise_blocks=0):
-    """precise_blocks: the split-precision form of a ResNet tower (tolerance_mode_kwargs); ViT checkpoints refuse it."""
+def build_from_state_dict(sd, dtype='float16', device='cuda', chunk=2560, precise_blocks=0, activation=None):
+    """precise_blocks: the split-precision form of a ResNet tower (tolerance_mode_kwargs); ViT checkpoints refuse it.
+    activation: 'quick_gelu' or 'gelu' (ACTIVATIONS above); the state dict cannot say which, so None means QuickGELU."""
     sd = {k: v for k, v in sd.items() if k not in ('input_resolution', 'context_length',
                                                    'vocab_size')}
     cfg = config_from_state_dict(sd)
     if _resnet.is_resnet_config(cfg):
+        _refuse_resnet_gelu(activation)
         model = _resnet.ResNetCLIP(cfg, sd, dtype=dtype, precise_blocks=precise_blocks)
     else:
+        cfg['activation'] = _check_activation(activation or 'quick_gelu')
         if precise_blocks:
             raise ValueError('precise_blocks is the ResNet towers\' keyword; a ViT takes CLIP(cfg, sd, '
                              '**tolerance_mode_kwargs(cfg))')
@@ -381,29 +437,139 @@ def build_from_state_dict(sd, dtype='float16', device='cuda', chunk=2560, precis
     return model.eval()
 
 
-def load(name, device='cuda', jit=False, download_root=None, dtype='float16'):
-    """``clip.load`` of the reference (test.py:26) -> (model, preprocess).
+# ------------------------------------------------------------------------------------------
+# Hugging Face (transformers.CLIPModel) layout -> OpenAI's
+# ------------------------------------------------------------------------------------------
+_HF_LAYER = (('layer_norm1', 'ln_1'), ('layer_norm2', 'ln_2'), ('self_attn.out_proj', 'attn.out_proj'), ('mlp.fc1', 'mlp.c_fc'),
+             ('mlp.fc2', 'mlp.c_proj'))
+_HF_TOP = (('vision_model.embeddings.class_embedding', 'visual.class_embedding'),
+           ('vision_model.embeddings.patch_embedding.weight', 'visual.conv1.weight'),
+           ('vision_model.embeddings.position_embedding.weight', 'visual.positional_embedding'),
+           ('vision_model.pre_layrnorm.weight', 'visual.ln_pre.weight'), ('vision_model.pre_layrnorm.bias', 'visual.ln_pre.bias'),
+           ('vision_model.post_layernorm.weight', 'visual.ln_post.weight'), ('vision_model.post_layernorm.bias', 'visual.ln_post.bias'),
+           ('text_model.embeddings.token_embedding.weight', 'token_embedding.weight'),
+           ('text_model.embeddings.position_embedding.weight', 'positional_embedding'),
+           ('text_model.final_layer_norm.weight', 'ln_final.weight'), ('text_model.final_layer_norm.bias', 'ln_final.bias'),
+           ('logit_scale', 'logit_scale'))
 
-    ``name`` is an architecture name whose checkpoint ``<name with / -> ->.pt`` sits in
-    ``download_root`` (default ``~/.cache/clip``), or a path to a checkpoint (TorchScript
-    archive or plain state dict in OpenAI's key layout).  Nothing is downloaded."""
-    path = name
-    if not os.path.isfile(path):
-        cfg = resnet_config(name) if name in RESNET_ARCHS else arch_config(name)   # raises for unknown names
-        root = download_root or os.path.expanduser('~/.cache/clip')
-        path = os.path.join(root, name.replace('/', '-') + '.pt')
-        if not os.path.isfile(path):
-            raise FileNotFoundError(
-                f'CLIP checkpoint {path} not found and this build never downloads; place the '
-                f'OpenAI checkpoint there or use eventclip_amd.clip.build_random({name!r}) '
-                f'(image {cfg["image_size"]}px) for synthetic weights')
+
+def state_dict_from_hf(hf_sd):
+    """transformers' CLIPModel state dict -> OpenAI's key layout: q / k / v_proj concatenated into
+    attn.in_proj_*, layer_norm1 / 2 -> ln_1 / 2, mlp.fc1 / fc2 -> mlp.c_fc / c_proj, the two projection matrices transposed
+    ([out, in] Linear weights -> [in, out] parameters), (transformers' spelling) pre_layrnorm -> ln_pre.  position_ids buffers
+    are dropped; any other key that has no counterpart raises."""
+    hf = {k: v for k, v in hf_sd.items() if not k.endswith('position_ids')}
+    out, used = {}, set()
+
+    def take(k):
+        if k not in hf:
+            raise KeyError(f'state_dict_from_hf: {k} is missing: not a transformers CLIPModel state dict')
+        used.add(k)
+        return hf[k]
+    for src, dst in _HF_TOP:
+        out[dst] = take(src)
+    out['visual.proj'] = take('visual_projection.weight').t().contiguous()
+    out['text_projection'] = take('text_projection.weight').t().contiguous()
+    for tower, prefix in (('vision_model', 'visual.transformer'), ('text_model', 'transformer')):
+        head = f'{tower}.encoder.layers.'
+        layers = len({k[len(head):].split('.')[0] for k in hf if k.startswith(head)})
+        for i in range(layers):
+            s, d = f'{head}{i}.', f'{prefix}.resblocks.{i}.'
+            for leaf in ('weight', 'bias'):
+                out[f'{d}attn.in_proj_{leaf}'] = torch.cat([take(f'{s}self_attn.{p}_proj.{leaf}') for p in 'qkv'], 0)
+                for a, b in _HF_LAYER:
+                    out[f'{d}{b}.{leaf}'] = take(f'{s}{a}.{leaf}')
+    extra = sorted(set(hf) - used)
+    if extra:
+        raise KeyError(f'state_dict_from_hf: no counterpart for {extra[:4]}{" ..." if len(extra) > 4 else ""}')
+    return out
+
+
+def _read_state_dict(path):
+    """A checkpoint file -> state dict on the CPU: *.safetensors, a TorchScript archive, or a torch.save'd dict."""
+    if path.endswith('.safetensors'):
+        try:
+            from safetensors.torch import load_file
+        except ImportError as e:
+            raise ImportError(f'{path}: reading *.safetensors needs the safetensors package, which is not installed; '
+                              'convert the file to a torch.save\'d state dict, or install safetensors') from e
+        return load_file(path, device='cpu')
     try:
-        sd = torch.jit.load(path, map_location='cpu').state_dict()
+        return torch.jit.load(path, map_location='cpu').state_dict()
     except RuntimeError:
         sd = torch.load(path, map_location='cpu')
         if isinstance(sd, dict) and 'state_dict' in sd:
             sd = sd['state_dict']
-    model = build_from_state_dict(sd, dtype=dtype, device=device)
+        return sd
+
+
+_HF_ACT = {'gelu': 'gelu', 'quick_gelu': 'quick_gelu'}
+
+
+def hf_activation(config):
+    """A transformers CLIP config (the dict of config.json) -> 'gelu' / 'quick_gelu'; refuses any other hidden_act, towers
+    that disagree, and attention heads that are not 64 wide."""
+    acts = []
+    for part in ('vision_config', 'text_config'):
+        c = config.get(part) or {}
+        act = c.get('hidden_act', 'quick_gelu')             # transformers' CLIP default
+        if act not in _HF_ACT:
+            raise NotImplementedError(f'{part}.hidden_act = {act!r}: the towers run {sorted(_HF_ACT)} only')
+        acts.append(_HF_ACT[act])
+        hidden, heads = c.get('hidden_size'), c.get('num_attention_heads')
+        if hidden is not None and heads is not None and hidden != 64 * heads:
+            raise NotImplementedError(f'{part}: head dimension {hidden} / {heads} = {hidden / heads:g}; the attention kernels '
+                                      'are built for 64')
+    if acts[0] != acts[1]:
+        raise NotImplementedError(f'vision_config.hidden_act {acts[0]!r} and text_config.hidden_act {acts[1]!r} differ: a model '
+                                  'has one activation here')
+    return acts[0]
+
+
+def _load_hf_directory(path, activation):
+    import json
+    with open(os.path.join(path, 'config.json')) as f:
+        act = hf_activation(json.load(f))
+    if activation is not None and _check_activation(activation) != act:
+        raise ValueError(f"activation={activation!r} contradicts {os.path.join(path, 'config.json')} (hidden_act -> {act!r})")
+    for leaf in ('model.safetensors', 'pytorch_model.bin'):
+        if os.path.isfile(os.path.join(path, leaf)):
+            return state_dict_from_hf(_read_state_dict(os.path.join(path, leaf))), act
+    raise FileNotFoundError(f'{path}: neither model.safetensors nor pytorch_model.bin beside config.json')
+
+
+def load(name, device='cuda', jit=False, download_root=None, dtype='float16', activation=None):
+    """``clip.load`` of the reference (test.py:26) -> (model, preprocess).
+
+    ``name`` is an architecture name whose checkpoint ``<name with / -> ->.pt`` sits in
+    ``download_root`` (default ``~/.cache/clip``), or a path to a checkpoint (TorchScript
+    archive, plain state dict in OpenAI's key layout -- open_clip's ``open_clip_pytorch_model.bin`` is one --
+    or ``*.safetensors`` of the same), or a directory in Hugging Face layout (``config.json`` beside
+    ``model.safetensors`` / ``pytorch_model.bin``).  Nothing is downloaded.
+
+    ``activation``: 'quick_gelu' / 'gelu'.  A checkpoint FILE cannot say which network it holds, so None means
+    QuickGELU (OpenAI's): pass 'gelu' for open_clip's models without a -quickgelu suffix.  An open_clip architecture
+    name and an HF directory's config.json say it themselves (None takes their word; a contradiction raises)."""
+    path = name
+    if os.path.isdir(path) and os.path.isfile(os.path.join(path, 'config.json')):
+        sd, activation = _load_hf_directory(path, activation)
+    else:
+        if not os.path.isfile(path):
+            cfg = resnet_config(name) if name in RESNET_ARCHS else arch_config(name)   # raises for unknown names
+            if name not in RESNET_ARCHS:
+                implied = resolve_arch(name)[1]
+                if activation is not None and implied is not None and _check_activation(activation) != implied:
+                    raise ValueError(f'activation={activation!r} contradicts the architecture name {name!r} ({implied!r})')
+                activation = activation or implied
+            root = download_root or os.path.expanduser('~/.cache/clip')
+            path = os.path.join(root, name.replace('/', '-') + '.pt')
+            if not os.path.isfile(path):
+                raise FileNotFoundError(
+                    f'CLIP checkpoint {path} not found and this build never downloads; place the '
+                    f'OpenAI checkpoint there or use eventclip_amd.clip.build_random({name!r}) '
+                    f'(image {cfg["image_size"]}px) for synthetic weights')
+        sd = _read_state_dict(path)
+    model = build_from_state_dict(sd, dtype=dtype, device=device, activation=activation)
     return model, Preprocess(model.cfg['image_size'])
 
 

@@ -149,6 +149,7 @@ class Packer:
         t.ln_final_g, t.ln_final_b = dev32(sd['ln_final.weight']), dev32(sd['ln_final.bias'])
         t.proj_w, proj_lo = self.dev16_pair(sd['text_projection'].t())
         t.precise = int(precise)
+        t.activation = _lib.activation_code(c.get('activation'))
         if precise:
             t.proj_w_lo = proj_lo
         tb = self.blocks('transformer', c['text_layers'], precise)

@@ -25,6 +25,7 @@
 //    activation row panel hit the same L2.
 #include <type_traits>
 
+#include "activation.h"
 #include "common.h"
 #include "mfma.h"
 
@@ -122,6 +123,28 @@ __device__ __forceinline__ float quick_gelu_grad(float x)
     const float sg = __builtin_amdgcn_rcpf(1.f + __expf(-1.702f * x));
     return sg * (1.f + 1.702f * x * (1.f - sg));
 }
+// ec_gemm_args.activation: which function the GELU epilogues apply.  A template parameter of the kernels (ACT) that
+// defaults to QuickGELU: the instantiations that existed before it compile to the instruction streams they had.
+enum { ACT_QUICK = 0, ACT_ERF = 1 };
+template <int ACT> __device__ __forceinline__ float act_gelu(float x)
+{
+    if constexpr (ACT == ACT_ERF) return gelu_erf(x);
+    else return quick_gelu(x);
+}
+template <int ACT> __device__ __forceinline__ f32x4 act_gelu4(f32x4 x)
+{
+    if constexpr (ACT == ACT_ERF) return gelu_erf4(x);
+    else return quick_gelu4(x);
+}
+template <int ACT> __device__ __forceinline__ float act_gelu_grad(float x)
+{
+    if constexpr (ACT == ACT_ERF) return gelu_erf_grad(x);
+    else return quick_gelu_grad(x);
+}
+constexpr bool epi_is_gelu(int e)
+{
+    return e == EC_EPI_GELU16 || e == EC_EPI_GELU16_SAVE || e == EC_EPI_GELU_BWD16 || e == EC_EPI_GELU16_LN;
+}
 constexpr bool epi_is16(int e)
 {
     return e == EC_EPI_STORE16 || e == EC_EPI_GELU16 || e == EC_EPI_GELU16_SAVE || e == EC_EPI_GELU_BWD16 ||
@@ -141,7 +164,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk)
 // buffer-addressed forms below): a 16 x 64 row group is 16 rows of 128 B (pitch 144 B); after the transpose
 // 8 consecutive lanes cover one full 128-B row and a store instruction writes 8 whole lines.
 // scratch: 2 x 16 x 144 bytes per wave.
-template <int DT, int EPI, int TM>
+template <int DT, int EPI, int TM, int ACT = ACT_QUICK>
 __device__ __forceinline__ void epilogue16_lds(const GemmArgs &g, f32x4 (&acc)[TM][4], int m_base,
                                                int n_base, int lane, unsigned char *scratch,
                                                const float *lds_rowstat = nullptr)
@@ -204,7 +227,7 @@ __device__ __forceinline__ void epilogue16_lds(const GemmArgs &g, f32x4 (&acc)[T
             for (int r = 0; r < 4; r++) {
                 float y = v[r];
                 // (the multiplies and the add as packed instructions on four values at a time: measured, no gain)
-                if constexpr (EPI == EC_EPI_GELU16 || EPI == EC_EPI_GELU16_SAVE || EPI == EC_EPI_GELU16_LN) y = quick_gelu(y);
+                if constexpr (EPI == EC_EPI_GELU16 || EPI == EC_EPI_GELU16_SAVE || EPI == EC_EPI_GELU16_LN) y = act_gelu<ACT>(y);
                 o[4 * j + r] = to16(y, elem());
             }
         }
@@ -238,13 +261,13 @@ __device__ __forceinline__ void epilogue16_lds(const GemmArgs &g, f32x4 (&acc)[T
             u32x4 v = *reinterpret_cast<const u32x4 *>(buf + row * PITCH + (lane & 7) * 16);
             const int m = m_base + i * 16 + row;
             if constexpr (EPI == EC_EPI_GELU_BWD16) {
-                // out = dg * QuickGELU'(u), u = the saved pre-activation at the same [m, n]
+                // out = dg * GELU'(u) (QuickGELU's or the exact one's: ACT), u = the saved pre-activation at the same [m, n]
                 if (m < g.M && col_ok) {
                     const v8 uu = *reinterpret_cast<const v8 *>((const elem *)g.aux + (long)m * g.ldc + col);
                     v8 dg = __builtin_bit_cast(v8, v);
 #pragma unroll
                     for (int e = 0; e < 8; e++)
-                        dg[e] = to16((float)dg[e] * quick_gelu_grad((float)uu[e]), elem());
+                        dg[e] = to16((float)dg[e] * act_gelu_grad<ACT>((float)uu[e]), elem());
                     v = __builtin_bit_cast(u32x4, dg);
                 }
             }
@@ -464,7 +487,7 @@ __device__ __forceinline__ void epilogue_hl_buf(const GemmArgs &g, f32x4 (&acc)[
 // 16-bit outputs (STORE16 / GELU16 and their folded-LayerNorm forms).  lds_rowstat: the wave row's 128 statistics
 // pairs in LDS (has_lds; always a pointer INTO the shared array, so that the reads compile to ds_read and not to
 // flat loads, whose s_waitcnt vmcnt(0) lgkmcnt(0) also waited for the next tile's first K tile), else g.rowstat
-template <int DT, int EPI, int TM, bool HAS_LDS, bool LOUT = false, bool LOUT8 = false, typename F>
+template <int DT, int EPI, int TM, bool HAS_LDS, bool LOUT = false, bool LOUT8 = false, int ACT = ACT_QUICK, typename F>
 __device__ __forceinline__ void epilogue16_buf(const GemmArgs &g, f32x4 (&acc)[TM][4], int m_base, int n_base,
                                                int lane, unsigned char *scratch, const float *lds_rowstat, F &&between)
 {
@@ -522,7 +545,7 @@ __device__ __forceinline__ void epilogue16_buf(const GemmArgs &g, f32x4 (&acc)[T
                 v = acc[i][j] * rs0[i] + (cs[j] * rs1[i] + bias[j]);
             else
                 v = acc[i][j] + bias[j];
-            if constexpr (EPI == EC_EPI_GELU16 || EPI == EC_EPI_GELU16_LN) v = quick_gelu4(v);
+            if constexpr (EPI == EC_EPI_GELU16 || EPI == EC_EPI_GELU16_LN) v = act_gelu4<ACT>(v);
 #pragma unroll
             for (int r = 0; r < 4; r++) o[4 * j + r] = to16(v[r], elem());
         }
@@ -551,7 +574,7 @@ __device__ __forceinline__ void epilogue16_buf(const GemmArgs &g, f32x4 (&acc)[T
                     v = acc[i][j] * rs0[i] + (cs[j] * rs1[i] + bias[j]);
                 else
                     v = acc[i][j] + bias[j];
-                if constexpr (EPI == EC_EPI_GELU16 || EPI == EC_EPI_GELU16_LN) v = quick_gelu4(v);
+                if constexpr (EPI == EC_EPI_GELU16 || EPI == EC_EPI_GELU16_LN) v = act_gelu4<ACT>(v);
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     float x = v[r];
@@ -725,9 +748,10 @@ __device__ __forceinline__ void raster(int id, int tiles_m, int tiles_n, int &tm
 // tile's last row).  Region 1 is requested one K tile apart from regions 0, 2, 3 and has a descriptor of its own.
 // LO: STORE16 / GELU16 also write the lo part of their output to args.aux (the split-precision launches only)
 enum { LO_NONE = 0, LO_16 = 1, LO_E4M3 = 2 };
-template <int DT, int EPI, int TL = 0, bool TN = false, int LO = LO_NONE, int SEG = 0>
+template <int DT, int EPI, int TL = 0, bool TN = false, int LO = LO_NONE, int SEG = 0, int ACT = ACT_QUICK>
 __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
 {
+    static_assert(ACT == ACT_QUICK || epi_is_gelu(EPI), "an activation goes with the GELU epilogues");
     typedef typename T16<DT>::v8 v8;
     typedef typename T16<DT>::v4 v4;
     static_assert(!TN || EPI == EC_EPI_STORE32, "transposed operands: fp32 store only");
@@ -1198,14 +1222,14 @@ __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
             epilogue32_buf<EPI, 8, TN>(ge, acc, wm0, wn0, elane, reinterpret_cast<float *>(smem + KT) + wave * (16 * 68), next_tile);
         else if constexpr (BUF_EPI) {
             if (lds_stats)
-                epilogue16_buf<DT, EPI, 8, true, LOUT, LOUT8>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144),
+                epilogue16_buf<DT, EPI, 8, true, LOUT, LOUT8, ACT>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144),
                                                  side + slot * 512 + wm * 256, next_tile);
             else
-                epilogue16_buf<DT, EPI, 8, false, LOUT, LOUT8>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144), nullptr, next_tile);
+                epilogue16_buf<DT, EPI, 8, false, LOUT, LOUT8, ACT>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144), nullptr, next_tile);
         }
         else {    // the training epilogues (second output / second input): the general form
             next_tile();
-            epilogue16_lds<DT, EPI, 8>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144), nullptr);
+            epilogue16_lds<DT, EPI, 8, ACT>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144), nullptr);
         }
         tstamp(4);
         if (more) {
@@ -1233,7 +1257,7 @@ __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
     if constexpr (TL == 2) clock_stamp(g.diag, 2);
 }
 
-template <int DT, int EPI, int TL = 0, bool TN = false, int LO = LO_NONE, int SEG = 0>
+template <int DT, int EPI, int TL = 0, bool TN = false, int LO = LO_NONE, int SEG = 0, int ACT = ACT_QUICK>
 int launch2pp(const GemmArgs &g0, hipStream_t stream)
 {
     GemmArgs g = g0;
@@ -1242,7 +1266,7 @@ int launch2pp(const GemmArgs &g0, hipStream_t stream)
     // two staging buffers + the row-statistics side area (LN epilogues) / the tail of the hi-lo epilogue's double
     // scratch (8 waves x 2 x 16 rows x 68 floats = 68 KiB from the second staging buffer on)
     constexpr int lds = 2 * 4 * 128 * 128 + (epi_is_ln(EPI) ? 2 * 2048 : 0) + (EPI == EC_EPI_RESID_HL ? 4608 : 0);
-    auto kern = gemm2pp_kernel<DT, EPI, TL, TN, LO, SEG>;
+    auto kern = gemm2pp_kernel<DT, EPI, TL, TN, LO, SEG, ACT>;
     if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds)) return rc;
     const int cus = ec::cu_count();
     EC_REQUIRE(cus > 0, "ec_gemm: cannot read the device's compute-unit count");
@@ -1360,8 +1384,16 @@ template <int DT, int EPI> int dispatch_variant(const GemmArgs &g, int variant, 
     }
 }
 
-template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipStream_t s)
+// a GELU epilogue of the default kernel with the activation the caller named (ec_gemm_args.activation)
+template <int DT, int EPI, int LO = LO_NONE, int SEG = 0> int launch_gelu(const GemmArgs &g, int act, hipStream_t s)
 {
+    static_assert(epi_is_gelu(EPI), "GELU epilogues only");
+    return act == ACT_ERF ? launch2pp<DT, EPI, 0, false, LO, SEG, ACT_ERF>(g, s) : launch2pp<DT, EPI, 0, false, LO, SEG>(g, s);
+}
+
+template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, int act, hipStream_t s)
+{
+    EC_REQUIRE(act == ACT_QUICK || variant == 0, "ec_gemm: args.activation = %d needs variant 0", act);
     if (g.nseg > 1) {
         // split-precision operands: the segmented main loop (default variant only)
         EC_REQUIRE(variant == 0, "ec_gemm: A_lo / W_lo need variant 0");
@@ -1373,9 +1405,9 @@ template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipS
                     return g.aux ? launch2pp<DT, EC_EPI_STORE16, 0, false, LO_16, 2>(g, s)
                                  : launch2pp<DT, EC_EPI_STORE16, 0, false, LO_NONE, 2>(g, s);
                 case EC_EPI_GELU16:
-                    if (g.aux && g.aux8_scale != 0.f) return launch2pp<DT, EC_EPI_GELU16, 0, false, LO_E4M3, 2>(g, s);
-                    return g.aux ? launch2pp<DT, EC_EPI_GELU16, 0, false, LO_16, 2>(g, s)
-                                 : launch2pp<DT, EC_EPI_GELU16, 0, false, LO_NONE, 2>(g, s);
+                    if (g.aux && g.aux8_scale != 0.f) return launch_gelu<DT, EC_EPI_GELU16, LO_E4M3, 2>(g, act, s);
+                    return g.aux ? launch_gelu<DT, EC_EPI_GELU16, LO_16, 2>(g, act, s)
+                                 : launch_gelu<DT, EC_EPI_GELU16, LO_NONE, 2>(g, act, s);
                 case EC_EPI_STORE32: return launch2pp<DT, EC_EPI_STORE32, 0, false, LO_NONE, 2>(g, s);
                 case EC_EPI_RESID_HL:
                     EC_REQUIRE(g.aux, "ec_gemm: EC_EPI_RESID_HL needs args.aux (the lo plane)");
@@ -1391,8 +1423,8 @@ template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipS
             return g.aux ? launch2pp<DT, EC_EPI_STORE16, 0, false, LO_16, 1>(g, s)
                          : launch2pp<DT, EC_EPI_STORE16, 0, false, LO_NONE, 1>(g, s);
         case EC_EPI_GELU16:
-            return g.aux ? launch2pp<DT, EC_EPI_GELU16, 0, false, LO_16, 1>(g, s)
-                         : launch2pp<DT, EC_EPI_GELU16, 0, false, LO_NONE, 1>(g, s);
+            return g.aux ? launch_gelu<DT, EC_EPI_GELU16, LO_16, 1>(g, act, s)
+                         : launch_gelu<DT, EC_EPI_GELU16, LO_NONE, 1>(g, act, s);
         case EC_EPI_STORE32: return launch2pp<DT, EC_EPI_STORE32, 0, false, LO_NONE, 1>(g, s);
         case EC_EPI_RESID32: return launch2pp<DT, EC_EPI_RESID32, 0, false, LO_NONE, 1>(g, s);
         case EC_EPI_RESID_HL:
@@ -1405,16 +1437,16 @@ template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipS
                "ec_gemm: STORE16 / GELU16 write their lo part (args.aux) in the launches that take A_lo / W_lo only");
     switch (epi) {
     case EC_EPI_STORE16: return dispatch_variant<DT, EC_EPI_STORE16>(g, variant, s);
-    case EC_EPI_GELU16: return dispatch_variant<DT, EC_EPI_GELU16>(g, variant, s);
+    case EC_EPI_GELU16: return act == ACT_ERF ? launch_gelu<DT, EC_EPI_GELU16>(g, act, s) : dispatch_variant<DT, EC_EPI_GELU16>(g, variant, s);
     case EC_EPI_RESID32: return dispatch_variant<DT, EC_EPI_RESID32>(g, variant, s);
     case EC_EPI_STORE32: return dispatch_variant<DT, EC_EPI_STORE32>(g, variant, s);
     // the training epilogues only exist in the default kernel
     case EC_EPI_GELU16_SAVE:
         EC_REQUIRE(variant == 0 && g.aux, "ec_gemm: EC_EPI_GELU16_SAVE needs variant 0 and args.aux");
-        return launch2pp<DT, EC_EPI_GELU16_SAVE>(g, s);
+        return launch_gelu<DT, EC_EPI_GELU16_SAVE>(g, act, s);
     case EC_EPI_GELU_BWD16:
         EC_REQUIRE(variant == 0 && g.aux, "ec_gemm: EC_EPI_GELU_BWD16 needs variant 0 and args.aux");
-        return launch2pp<DT, EC_EPI_GELU_BWD16>(g, s);
+        return launch_gelu<DT, EC_EPI_GELU_BWD16>(g, act, s);
     // LayerNorm folded into the GEMMs (default kernel only)
     case EC_EPI_RESID_HL:
 #ifdef EC_GEMM_DIAG
@@ -1433,7 +1465,7 @@ template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipS
         if ((variant == 18 || variant == 19) && g.rowstat && g.colsum) return dispatch_variant<DT, EC_EPI_GELU16_LN>(g, variant, s);
 #endif
         EC_REQUIRE(variant == 0 && g.rowstat && g.colsum, "ec_gemm: EC_EPI_GELU16_LN needs variant 0, row_stats and col_sums");
-        return launch2pp<DT, EC_EPI_GELU16_LN>(g, s);
+        return launch_gelu<DT, EC_EPI_GELU16_LN>(g, act, s);
     default: return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown epilogue %d", epi);
     }
 }
@@ -1446,7 +1478,7 @@ template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, hipS
 // and this kernel adds the partial sums up and applies the epilogue.  The fp32 summation order then depends on
 // the batch count, i.e. on M: callers that need results independent of the batch size do not pass scratch.
 // ---------------------------------------------------------------------------------------
-template <int DT>
+template <int DT, int ACT = ACT_QUICK>
 __global__ __launch_bounds__(256) void kbatch_fixup_kernel(const float *partial, int splits, int M, int N, const float *bias,
                                                            const float *resid, void *C, long ldc, void *aux, int epi)
 {
@@ -1472,11 +1504,11 @@ __global__ __launch_bounds__(256) void kbatch_fixup_kernel(const float *partial,
                 *reinterpret_cast<v4 *>((elem *)aux + o) = u;
             }
 #pragma unroll
-            for (int j = 0; j < 4; j++) out[j] = to16(quick_gelu(a[j]), elem());
+            for (int j = 0; j < 4; j++) out[j] = to16(act_gelu<ACT>(a[j]), elem());
         } else if (epi == EC_EPI_GELU_BWD16) {
             const v4 u = *reinterpret_cast<const v4 *>((const elem *)aux + o);
 #pragma unroll
-            for (int j = 0; j < 4; j++) out[j] = to16((float)to16(a[j], elem()) * quick_gelu_grad((float)u[j]), elem());
+            for (int j = 0; j < 4; j++) out[j] = to16((float)to16(a[j], elem()) * act_gelu_grad<ACT>((float)u[j]), elem());
         } else {
 #pragma unroll
             for (int j = 0; j < 4; j++) out[j] = to16(a[j], elem());
@@ -1488,7 +1520,7 @@ __global__ __launch_bounds__(256) void kbatch_fixup_kernel(const float *partial,
 // -> EC_OK after launching the K-batched form, KBATCH_NOT_APPLICABLE (a positive value: never an error code) when the
 // launch does not qualify and the caller goes on as usual, or the negative error code of a launch that failed
 constexpr int KBATCH_NOT_APPLICABLE = 1;
-template <int DT> int try_kbatched(const GemmArgs &g0, int epi, float *ws, size_t ws_bytes, hipStream_t stream)
+template <int DT> int try_kbatched(const GemmArgs &g0, int epi, int act, float *ws, size_t ws_bytes, hipStream_t stream)
 {
     const int cus = ec::cu_count();
     const int tiles = ec::ceil_div(g0.M, 256) * ec::ceil_div(g0.N, 256);
@@ -1502,8 +1534,13 @@ template <int DT> int try_kbatched(const GemmArgs &g0, int epi, float *ws, size_
     g.C = ws, g.ldc = g0.N, g.bias = nullptr, g.resid = nullptr, g.aux = nullptr;
     if (int rc = launch2pp<DT, EC_EPI_STORE32>(g, stream)) return rc;
     const long n4 = (long)g0.M * g0.N / 4;
-    hipLaunchKernelGGL(kbatch_fixup_kernel<DT>, dim3((unsigned)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048)), dim3(256),
-                       0, stream, ws, splits, g0.M, g0.N, g0.bias, g0.resid, g0.C, g0.ldc, g0.aux, epi);
+    const dim3 grid((unsigned)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048));
+    if (act == ACT_ERF)
+        hipLaunchKernelGGL((kbatch_fixup_kernel<DT, ACT_ERF>), grid, dim3(256), 0, stream, ws, splits, g0.M, g0.N, g0.bias, g0.resid,
+                           g0.C, g0.ldc, g0.aux, epi);
+    else
+        hipLaunchKernelGGL(kbatch_fixup_kernel<DT>, grid, dim3(256), 0, stream, ws, splits, g0.M, g0.N, g0.bias, g0.resid, g0.C,
+                           g0.ldc, g0.aux, epi);
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }
@@ -1584,6 +1621,10 @@ extern "C" EC_API int ec_gemm(const ec_gemm_args *a, ec_stream_t stream)
     EC_REQUIRE(!a->row_stats || a->M < (1 << 27), "ec_gemm: row_stats addresses its pairs with 32-bit byte offsets (M = %d)", a->M);
     EC_REQUIRE(((uintptr_t)a->row_sums & 7) == 0, "ec_gemm: row_sums must be 8-byte aligned");
     // an option the dispatched kernel would not read is refused, not ignored
+    EC_REQUIRE(a->activation == ACT_QUICK || a->activation == ACT_ERF, "ec_gemm: unknown args.activation %d (0 = QuickGELU, 1 = exact GELU)",
+               a->activation);
+    EC_REQUIRE(a->activation == ACT_QUICK || epi_is_gelu(a->epilogue),
+               "ec_gemm: args.activation goes with the GELU16, GELU16_LN, GELU16_SAVE and GELU_BWD16 epilogues (epilogue %d)", a->epilogue);
     const bool ln_epi = a->epilogue == EC_EPI_STORE16_LN || a->epilogue == EC_EPI_GELU16_LN;
     EC_REQUIRE(!a->aux || !(a->epilogue == EC_EPI_STORE32 || a->epilogue == EC_EPI_RESID32 || ln_epi),
                "ec_gemm: args.aux goes with the STORE16, GELU16, GELU16_SAVE, GELU_BWD16 and RESID_HL epilogues (epilogue %d)", a->epilogue);
@@ -1634,12 +1675,12 @@ extern "C" EC_API int ec_gemm(const ec_gemm_args *a, ec_stream_t stream)
                    "ec_gemm: epilogue %d needs aux", a->epilogue);
         EC_REQUIRE(a->resid == nullptr || ((uintptr_t)a->resid & 15) == 0, "ec_gemm: resid must be 16-byte aligned");
         int rc = KBATCH_NOT_APPLICABLE;
-        if (a->dtype == EC_F16) rc = try_kbatched<EC_F16>(g, a->epilogue, static_cast<float *>(a->ws), a->ws_bytes, s);
-        else if (a->dtype == EC_BF16) rc = try_kbatched<EC_BF16>(g, a->epilogue, static_cast<float *>(a->ws), a->ws_bytes, s);
+        if (a->dtype == EC_F16) rc = try_kbatched<EC_F16>(g, a->epilogue, a->activation, static_cast<float *>(a->ws), a->ws_bytes, s);
+        else if (a->dtype == EC_BF16) rc = try_kbatched<EC_BF16>(g, a->epilogue, a->activation, static_cast<float *>(a->ws), a->ws_bytes, s);
         if (rc != KBATCH_NOT_APPLICABLE) return rc;   // launched, or failed with a real error code
     }
-    if (a->dtype == EC_F16) return dispatch_epi<EC_F16>(g, a->epilogue, a->variant, s);
-    if (a->dtype == EC_BF16) return dispatch_epi<EC_BF16>(g, a->epilogue, a->variant, s);
+    if (a->dtype == EC_F16) return dispatch_epi<EC_F16>(g, a->epilogue, a->variant, a->activation, s);
+    if (a->dtype == EC_BF16) return dispatch_epi<EC_BF16>(g, a->epilogue, a->variant, a->activation, s);
     return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown dtype %d", a->dtype);
 }
 

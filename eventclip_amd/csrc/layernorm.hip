@@ -10,6 +10,7 @@
 //
 // Each lane keeps its slice of the row in registers (float4 x up to 8), two
 // shuffle reductions (mean, then centred variance), one write.
+#include "activation.h"
 #include "common.h"
 #include "mfma.h"
 #include "tower_ops.h"
@@ -206,9 +207,9 @@ __global__ __launch_bounds__(256) void row_stats_merge_kernel(const float *sums,
     }
 }
 
-// fp32 [n] -> (optionally QuickGELU) -> 16-bit hi and lo parts.  LO_F16: the lo part as fp16 whatever DT (the planes of
-// the folded chain's residual stream: EC_EPI_RESID_HL reads its lo plane as fp16)
-template <int DT, bool LO_F16 = false>
+// fp32 [n] -> (optionally QuickGELU; ERF: the exact GELU of activation.h instead) -> 16-bit hi and lo parts.  LO_F16: the
+// lo part as fp16 whatever DT (the planes of the folded chain's residual stream: EC_EPI_RESID_HL reads its lo plane as fp16)
+template <int DT, bool LO_F16 = false, bool ERF = false>
 __global__ __launch_bounds__(256) void split16_kernel(const float *x, long n, int gelu, void *hi,
                                                       void *lo)
 {
@@ -216,7 +217,9 @@ __global__ __launch_bounds__(256) void split16_kernel(const float *x, long n, in
     typedef typename T16<DT>::v4 v4;
     for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
         float4 v = *reinterpret_cast<const float4 *>(x + i);
-        if (gelu) {
+        if constexpr (ERF) {
+            v.x = ec::gelu_erf(v.x), v.y = ec::gelu_erf(v.y), v.z = ec::gelu_erf(v.z), v.w = ec::gelu_erf(v.w);
+        } else if (gelu) {
             v.x = v.x / (1.f + expf(-1.702f * v.x));
             v.y = v.y / (1.f + expf(-1.702f * v.y));
             v.z = v.z / (1.f + expf(-1.702f * v.z));
@@ -436,13 +439,18 @@ EC_API int ec_split16(const float *x, long n, int gelu, void *hi16, void *lo16, 
                       ec_stream_t stream)
 {
     EC_REQUIRE(n >= 0 && n % 4 == 0, "ec_split16: n=%ld must be a multiple of 4", n);
+    EC_REQUIRE(gelu >= 0 && gelu <= 2, "ec_split16: gelu=%d (0 = none, 1 = QuickGELU, 2 = exact GELU)", gelu);
     if (n == 0) return EC_OK;
     EC_REQUIRE(x && hi16 && lo16, "ec_split16: null buffer");
     EC_REQUIRE(aligned(x, 16) && aligned(hi16, 8) && aligned(lo16, 8), "ec_split16: misaligned buffer");
     const unsigned grid = (unsigned)((n / 4 + 255) / 256 < 65536 ? (n / 4 + 255) / 256 : 65536);
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)n * 8.0);
-    if (dtype == EC_F16)
+    if (gelu == 2 && dtype == EC_F16)
+        hipLaunchKernelGGL((split16_kernel<EC_F16, false, true>), dim3(grid), dim3(256), 0, s, x, n, gelu, hi16, lo16);
+    else if (gelu == 2 && dtype == EC_BF16)
+        hipLaunchKernelGGL((split16_kernel<EC_BF16, false, true>), dim3(grid), dim3(256), 0, s, x, n, gelu, hi16, lo16);
+    else if (dtype == EC_F16)
         hipLaunchKernelGGL(split16_kernel<EC_F16>, dim3(grid), dim3(256), 0, s, x, n, gelu, hi16, lo16);
     else if (dtype == EC_BF16)
         hipLaunchKernelGGL(split16_kernel<EC_BF16>, dim3(grid), dim3(256), 0, s, x, n, gelu, hi16,

@@ -66,6 +66,8 @@ struct Gemm {
         if (p && e4m3) g.aux_e4m3 = 1, g.aux_exp = LO8_EXP;
         return *this;
     }
+    // the GELU epilogues: QuickGELU (0) or the exact GELU (1), ec_vit_weights.activation / ec_text_weights.activation
+    Gemm &act(int activation) { return g.activation = activation, *this; }
     // EC_EPI_*_LN (folded LayerNorm): row statistics + column sums
     Gemm &ln(const float *row_stats, long stride, const float *col_sums)
     {

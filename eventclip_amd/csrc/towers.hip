@@ -63,7 +63,7 @@ int attention(const BlockBufs &b, const RowsView &v, int n_seq, int S, int W, in
 }
 
 int run_blocks(const ec_block_weights *blocks, int layers, int n_seq, int S, int W, int heads,
-               int causal, int dtype, const BlockBufs &b, ec_stream_t s, bool first_only = false,
+               int causal, int dtype, int act, const BlockBufs &b, ec_stream_t s, bool first_only = false,
                bool q_scaled = false)
 {
     const int rows = n_seq * S;
@@ -81,7 +81,7 @@ int run_blocks(const ec_block_weights *blocks, int layers, int n_seq, int S, int
         EC_TRY(attention(b, v, n_seq, S, W, heads, causal, dtype, q_scaled, s));
         EC_TRY(Gemm(v.m, W, W, dtype, EC_EPI_RESID32, b.h, w.out_w, w.out_b, b.x).ld(0, v.ldx).k_batched().run(s));
         EC_TRY(ec_layernorm(b.x, v.ldx, nullptr, w.ln2_g, w.ln2_b, v.m, W, LN_EPS, b.h, W, dtype, s));
-        EC_TRY(Gemm(v.m, 4 * W, W, dtype, EC_EPI_GELU16, b.h, w.fc1_w, w.fc1_b, b.mlp).k_batched().run(s));
+        EC_TRY(Gemm(v.m, 4 * W, W, dtype, EC_EPI_GELU16, b.h, w.fc1_w, w.fc1_b, b.mlp).act(act).k_batched().run(s));
         EC_TRY(Gemm(v.m, W, 4 * W, dtype, EC_EPI_RESID32, b.mlp, w.fc2_w, w.fc2_b, b.x).ld(0, v.ldx).k_batched().run(s));
     }
     return EC_OK;
@@ -94,7 +94,7 @@ int run_blocks(const ec_block_weights *blocks, int layers, int n_seq, int S, int
 // and the LayerNorm passes (4 + 2 bytes per element each) are gone: 16.24 -> 15.48 ms per block at the bench shape
 // (tools/bench_fold.py; 15.87 with a statistics pass over the hi plane instead of the epilogue's sums), same
 // rounding points.
-int run_blocks_folded(const ec_block_weights *blocks, int layers, int n_seq, int S, int W, int heads, int dtype,
+int run_blocks_folded(const ec_block_weights *blocks, int layers, int n_seq, int S, int W, int heads, int dtype, int act,
                       const BlockBufs &b, ec_stream_t s, bool first_only, bool q_scaled, int nsplit = 0, bool exact16 = false,
                       int nattn = 0, bool lo_fp8 = false)
 {
@@ -149,7 +149,7 @@ int run_blocks_folded(const ec_block_weights *blocks, int layers, int n_seq, int
             // rounding of QuickGELU's output in the first blocks is the next contribution behind q / k)
             void *m_lo = pa ? b.mlp_lo : nullptr;
             Gemm qkv = Gemm(rows, 3 * W, W, dtype, EC_EPI_STORE16, b.h, w.qkv_w, w.qkv_b, b.qkv).aux(pa ? qkv_lo : nullptr);
-            Gemm fc1 = Gemm(rows, 4 * W, W, dtype, EC_EPI_GELU16, b.h, w.fc1_w, w.fc1_b, b.mlp).aux(m_lo, lo_fp8);
+            Gemm fc1 = Gemm(rows, 4 * W, W, dtype, EC_EPI_GELU16, b.h, w.fc1_w, w.fc1_b, b.mlp).act(act).aux(m_lo, lo_fp8);
             Gemm fc2 = Gemm(rows, W, 4 * W, dtype, EC_EPI_RESID_HL, b.mlp, w.fc2_w, w.fc2_b, x_hi).aux(x_lo).row_sums(next_default ? b.sums : nullptr);
             if (lo_fp8) {
                 qkv.fp8({h_lo1, w.qkv_w8, h8_1, w.qkv_wlo8, w.qkv_w8_exp, w.qkv_wlo8_exp});
@@ -183,7 +183,7 @@ int run_blocks_folded(const ec_block_weights *blocks, int layers, int n_seq, int
         EC_TRY(attention(b, v, n_seq, S, W, heads, 0, dtype, q_scaled, s));
         EC_TRY(Gemm(v.m, W, W, dtype, EC_EPI_RESID_HL, b.h, w.out_w, w.out_b, x_hi).ld(0, v.ldx).aux(x_lo).row_sums(b.sums).run(s));
         EC_TRY(merge_stats(v.m));
-        EC_TRY(Gemm(v.m, 4 * W, W, dtype, EC_EPI_GELU16_LN, x_hi, w.fc1_w_ln, w.fc1_bf, b.mlp).ld(v.ldx, 0).ln(b.stats, 1, w.fc1_cs).run(s));
+        EC_TRY(Gemm(v.m, 4 * W, W, dtype, EC_EPI_GELU16_LN, x_hi, w.fc1_w_ln, w.fc1_bf, b.mlp).act(act).ld(v.ldx, 0).ln(b.stats, 1, w.fc1_cs).run(s));
         EC_TRY(Gemm(v.m, W, 4 * W, dtype, EC_EPI_RESID_HL, b.mlp, w.fc2_w, w.fc2_b, x_hi).ld(0, v.ldx).aux(x_lo)
                    .row_sums(next_default ? b.sums : nullptr).run(s));
         if (next_default) EC_TRY(merge_stats(rows));
@@ -201,7 +201,7 @@ struct PreciseBufs : RowBufs {
 };
 
 int run_blocks_precise(const ec_block_weights *blocks, int layers, int n_seq, int S, int W, int heads,
-                       int causal, int dtype, const PreciseBufs &b, ec_stream_t s, bool exact16 = false)
+                       int causal, int dtype, int act, const PreciseBufs &b, ec_stream_t s, bool exact16 = false)
 {
     const int rows = n_seq * S;
     for (int l = 0; l < layers; l++) {
@@ -225,7 +225,7 @@ int run_blocks_precise(const ec_block_weights *blocks, int layers, int n_seq, in
         EC_TRY(ec_layernorm_split(b.x, W, nullptr, w.ln2_g, w.ln2_b, rows, W, LN_EPS, b.h_hi, b.h_lo,
                                   W, dtype, s));
         EC_TRY(Gemm(rows, 4 * W, W, dtype, EC_EPI_STORE32, b.h_hi, w.fc1_w, w.fc1_b, b.wide).lo(b.h_lo, w.fc1_w_lo).run(s));
-        EC_TRY(ec_split16(b.wide, (long)rows * 4 * W, 1, b.m_hi, b.m_lo, dtype, s));
+        EC_TRY(ec_split16(b.wide, (long)rows * 4 * W, act == EC_ACT_GELU ? 2 : 1, b.m_hi, b.m_lo, dtype, s));
         EC_TRY(Gemm(rows, W, 4 * W, dtype, EC_EPI_RESID32, b.m_hi, w.fc2_w, w.fc2_b, b.x).lo(b.m_lo, w.fc2_w_lo).run(s));
     }
     return EC_OK;
@@ -317,6 +317,7 @@ EC_API int ec_vit_encode(const ec_vit_weights *w, const void *patches, int n_img
     EC_REQUIRE(w->image_size % w->patch == 0, "ec_vit_encode: image %d not a multiple of patch %d",
                w->image_size, w->patch);
     EC_REQUIRE(w->width == w->heads * 64, "ec_vit_encode: head dim must be 64");
+    EC_REQUIRE(w->activation == EC_ACT_QUICK_GELU || w->activation == EC_ACT_GELU, "ec_vit_encode: unknown activation %d", w->activation);
     EC_REQUIRE(w->kpad % 64 == 0 && w->kpad >= 6 * w->patch * w->patch, "ec_vit_encode: bad kpad %d",
                w->kpad);
     EC_REQUIRE(w->conv_w && w->proj_w && (w->weights_exact16 || (w->conv_w_lo && w->proj_w_lo)),
@@ -363,12 +364,12 @@ EC_API int ec_vit_encode(const ec_vit_weights *w, const void *patches, int n_img
         EC_TRY(patch_embed(w, p, n * G, patch_out, stream));
         if (precise) {
             EC_TRY(ec_vit_embed(patch_out, w->cls, w->pos, w->ln_pre_g, w->ln_pre_b, n, S, W, LN_EPS, pb.x, stream));
-            EC_TRY(run_blocks_precise(w->blocks, w->layers, n, S, W, w->heads, 0, dt, pb, stream, w->weights_exact16 != 0));
+            EC_TRY(run_blocks_precise(w->blocks, w->layers, n, S, W, w->heads, 0, dt, w->activation, pb, stream, w->weights_exact16 != 0));
         } else if (folded) {
             // residual stream as hi + lo planes in the fp32 stream's 4 bytes per element
             void *x_hi = b.x, *x_lo = reinterpret_cast<unsigned char *>(b.x) + (size_t)n * S * W * 2;
             EC_TRY(vit_embed_hl(patch_out, w->cls, w->pos, w->ln_pre_g, w->ln_pre_b, n, S, W, LN_EPS, x_hi, x_lo, dt, stream));
-            EC_TRY(run_blocks_folded(w->blocks, w->layers, n, S, W, w->heads, dt, b, stream, w->full_last_block == 0,
+            EC_TRY(run_blocks_folded(w->blocks, w->layers, n, S, W, w->heads, dt, w->activation, b, stream, w->full_last_block == 0,
                                      w->q_scaled != 0, pblocks, w->weights_exact16 != 0,
                                      w->precise_attn_blocks < pblocks ? w->precise_attn_blocks : pblocks, pblocks > 0 && w->lo_fp8 != 0));
             // the class rows back to fp32 (x = hi + lo) for ln_post; patch_out (the mlp buffer) is free by now
@@ -376,7 +377,7 @@ EC_API int ec_vit_encode(const ec_vit_weights *w, const void *patches, int n_img
             cls_x = patch_out, ld_cls = W;
         } else {
             EC_TRY(ec_vit_embed(patch_out, w->cls, w->pos, w->ln_pre_g, w->ln_pre_b, n, S, W, LN_EPS, b.x, stream));
-            EC_TRY(run_blocks(w->blocks, w->layers, n, S, W, w->heads, 0, dt, b, stream, w->full_last_block == 0, w->q_scaled != 0));
+            EC_TRY(run_blocks(w->blocks, w->layers, n, S, W, w->heads, 0, dt, w->activation, b, stream, w->full_last_block == 0, w->q_scaled != 0));
         }
         // ln_post on the CLS rows, then @ proj.  These n rows are the features themselves: their 16-bit rounding is
         // not averaged over anything downstream and was 45 % of the logit error budget (tools/rounding_budget.py),
@@ -397,6 +398,7 @@ EC_API int ec_text_encode(const ec_text_weights *w, const int32_t *tokens, int n
     if (n_txt == 0) return EC_OK;
     EC_REQUIRE(tokens && feats && workspace, "ec_text_encode: null buffer");
     EC_REQUIRE(w->width == w->heads * 64, "ec_text_encode: head dim must be 64");
+    EC_REQUIRE(w->activation == EC_ACT_QUICK_GELU || w->activation == EC_ACT_GELU, "ec_text_encode: unknown activation %d", w->activation);
     EC_REQUIRE(w->out_dim % 16 == 0, "ec_text_encode: out_dim %d", w->out_dim);
     const int S = w->ctx, W = w->width, dt = w->dtype;
     if (chunk > n_txt) chunk = n_txt;
@@ -413,8 +415,8 @@ EC_API int ec_text_encode(const ec_text_weights *w, const int32_t *tokens, int n
         const int32_t *tok = tokens + (size_t)i0 * S;
         float *x = precise ? pb.x : b.x, *out = feats + (size_t)i0 * w->out_dim;
         EC_TRY(ec_text_embed(tok, w->token_embedding, w->pos, n, S, W, w->vocab, x, stream));
-        EC_TRY(precise ? run_blocks_precise(w->blocks, w->layers, n, S, W, w->heads, 1, dt, pb, stream)
-                       : run_blocks(w->blocks, w->layers, n, S, W, w->heads, 1, dt, b, stream));
+        EC_TRY(precise ? run_blocks_precise(w->blocks, w->layers, n, S, W, w->heads, 1, dt, w->activation, pb, stream)
+                       : run_blocks(w->blocks, w->layers, n, S, W, w->heads, 1, dt, w->activation, b, stream));
         hipLaunchKernelGGL(eot_index_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), tok, n, S, eot.idx);
         EC_CHECK_HIP(hipGetLastError());
         // ln_final on the EOT rows, then @ text_projection: on hi + lo operands in the precise tower

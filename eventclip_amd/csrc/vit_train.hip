@@ -24,6 +24,7 @@
 //             probabilities from the saved log-sum-exp (attention_bwd.hip);
 //   gradients come out fp32 in the state dict's layouts; a NULL pointer skips the work behind it
 //   (LoRA on q k v o needs the attention weight gradients only: none of the MLP's dW GEMMs run).
+#include "activation.h"
 #include "common.h"
 #include "mfma.h"
 #include "tower_ops.h"
@@ -54,7 +55,7 @@ __device__ __forceinline__ float quick_gelu_f(float x)
 
 // ------------------------------------------------------------------------------------------
 // Transposed 16-bit copies: dst_t[n][m] = f(src[row(m)][n]) for m < M, 0 for M <= m < Mp.
-// MODE 0: 16-bit source; 1: QuickGELU of a 16-bit source; 2: fp32 source, optionally also written row-major
+// MODE 0: 16-bit source; 1: QuickGELU of a 16-bit source (3: the exact GELU, activation.h); 2: fp32 source, optionally also written row-major
 // as 16 bit (the dX GEMM's operand).  (The blocks' weight gradients no longer need these copies: weight_grad_rows.)
 // Logical row m reads source row (m / seq_out) * seq_in + seq_off + m % seq_out (seq_out = 0: row m):
 // the patch rows of the embedding gradient skip every sequence's class-token row.
@@ -89,6 +90,10 @@ __global__ __launch_bounds__(256) void transpose_kernel(const void *src, long ld
                 if (MODE == 1) {
 #pragma unroll
                     for (int j = 0; j < 8; j++) v[j] = to16(quick_gelu_f((float)v[j]), elem());
+                }
+                if (MODE == 3) {
+#pragma unroll
+                    for (int j = 0; j < 8; j++) v[j] = to16(ec::gelu_erf((float)v[j]), elem());
                 }
             }
         }
@@ -1406,7 +1411,7 @@ EC_API int ec_vit_train_forward(const ec_vit_weights *w, const void *patches, in
         EC_TRY(ec_attention_train(b.qkv[l], b.att[l], b.lse[l], n_img, S, W, w->heads, dt, stream));
         EC_TRY(Gemm(M, W, W, dt, EC_EPI_RESID32, b.att[l], p.out_w, p.out_b, b.xm[l]).resid(b.x[l]).run(stream));
         EC_TRY(ec_layernorm(b.xm[l], W, nullptr, p.ln2_g, p.ln2_b, M, W, LN_EPS, b.h2[l], W, dt, stream));
-        EC_TRY(Gemm(M, 4 * W, W, dt, EC_EPI_GELU16_SAVE, b.h2[l], p.fc1_w, p.fc1_b, b.gact[l]).aux(b.u[l]).run(stream));
+        EC_TRY(Gemm(M, 4 * W, W, dt, EC_EPI_GELU16_SAVE, b.h2[l], p.fc1_w, p.fc1_b, b.gact[l]).aux(b.u[l]).act(w->activation).run(stream));
         EC_TRY(gemm_rows32(M, W, 4 * W, dt, EC_EPI_RESID32, b.gact[l], p.fc2_w, b.x[l + 1], b.xm[l], p.fc2_b, b.part,
                            b.part_floats, stream));
     }
@@ -1471,6 +1476,8 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
                "ec_vit_train_backward: stages %d .. %d of %d", stage_begin, stage_end, w->layers + 2);
     EC_REQUIRE(n_img > 0, "ec_vit_train_backward: n_img=%d", n_img);
     EC_REQUIRE(wt && wt->blocks && wt->proj && gr && gr->blocks, "ec_vit_train_backward: null weight / gradient structs");
+    EC_REQUIRE(wt->activation == w->activation, "ec_vit_train_backward: ec_vit_train_weights.activation %d differs from "
+               "ec_vit_weights.activation %d (the forward pass ran with the latter)", wt->activation, w->activation);
     EC_REQUIRE(patches && d_feats && workspace, "ec_vit_train_backward: null buffer");
     EC_REQUIRE(!lora || (lora->blocks && lora->rank > 0 && lora->rank <= 64), "ec_vit_train_backward: LoRA rank %d (1 .. 64)",
                lora ? lora->rank : 0);
@@ -1536,7 +1543,7 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
         // (b.dx16 is the 16-bit copy of b.dx: written by the LayerNorm backward that produced it)
         if (q.fc2_b) EC_TRY(bias_grad<float>(b.dx, W, M, W, b, q.fc2_b, s));
         if (q.fc2_w) EC_TRY(weight_grad_rows(dt, b.dx16, W, b.gact[l], 4L * W, W, 4 * W, M, b, q.fc2_w, stream));
-        EC_TRY(Gemm(M, 4 * W, W, dt, EC_EPI_GELU_BWD16, b.dx16, pt.fc2_wt, nullptr, b.g16).aux(b.u[l]).run(stream));
+        EC_TRY(Gemm(M, 4 * W, W, dt, EC_EPI_GELU_BWD16, b.dx16, pt.fc2_wt, nullptr, b.g16).aux(b.u[l]).act(wt->activation).run(stream));
         if (q.fc1_b) {
             if (dt == EC_F16) EC_TRY(bias_grad<_Float16>((const _Float16 *)b.g16, 4L * W, M, 4 * W, b, q.fc1_b, s));
             else EC_TRY(bias_grad<__bf16>((const __bf16 *)b.g16, 4L * W, M, 4 * W, b, q.fc1_b, s));

@@ -174,7 +174,9 @@ class VisualTower:
         t = _lib.EcVitTrainWeights()
         t.blocks = ctypes.cast(blocks_t, ctypes.POINTER(_lib.EcBlockWeightsT))
         t.proj = m['proj'].data_ptr()
-        self._vit, self._vit_t, self._keep = v, t, (blocks, blocks_t)
+        # cfg['activation']: both passes of the training tower (GELU16_SAVE forward, GELU_BWD16 backward)
+        v.activation = t.activation = _lib.activation_code(c.get('activation'))
+        self._vit,self._vit_t, self._keep = v, t, (blocks, blocks_t)
 
     def matrix_names(self):
         out = ['conv1.weight', 'proj']

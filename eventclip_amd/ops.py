@@ -31,7 +31,7 @@ def _gemm_args(A, W, out, M, N, K, epilogue, splits):
 
 def gemm(A, W, bias=None, epilogue='store16', out=None, variant=0, diag=None, resid=None, aux=None,
          splits=1, K=None, ws=None, row_stats=None, col_sums=None, row_stats_stride=0, row_sums=None,
-         A_lo=None, W_lo=None, A_lo8=None, W8=None, A8=None, W_lo8=None, aux8=None):
+         A_lo=None, W_lo=None, A_lo8=None, W8=None, A8=None, W_lo8=None, aux8=None, activation=None):
     """out = epi(A[M,K] @ W[N,K]^T + bias).  epilogue: store16 | gelu16 | resid32 | store32 |
     gelu16_save (aux receives the pre-activation) | gelu_bwd16 (out = acc * QuickGELU'(aux)).
     resid32 accumulates into ``out`` (fp32) in place, or computes out = resid + ... when ``resid`` is given.
@@ -42,7 +42,9 @@ def gemm(A, W, bias=None, epilogue='store16', out=None, variant=0, diag=None, re
     Split-precision operands in one launch: ``A_lo`` / ``W_lo`` (the lo parts, same shapes and strides):
     out = epi(A_lo W^T + A W_lo^T + A W^T + bias); with them store16 / gelu16 take ``aux`` as the output's lo part.
     Lo products on the FP8 matrix path: ``A_lo8`` + ``W8`` in place of A_lo W^T, ``A8`` + ``W_lo8`` in place of A W_lo^T, each
-    a pair (uint8 tensor [rows, 2 K] whose first K bytes per row are e4m3, exponent) as quantize_e4m3 returns them."""
+    a pair (uint8 tensor [rows, 2 K] whose first K bytes per row are e4m3, exponent) as quantize_e4m3 returns them.
+    ``activation``: None / 'quick_gelu' or 'gelu' (exact, x Phi(x)), or the raw ec_gemm_args.activation value as an int: what
+    the gelu* epilogues apply; ec_gemm refuses it with any other epilogue."""
     import torch
     _lib.require_gpu()
     epi = {'store16': _lib.EC_EPI_STORE16, 'gelu16': _lib.EC_EPI_GELU16,
@@ -67,6 +69,7 @@ def gemm(A, W, bias=None, epilogue='store16', out=None, variant=0, diag=None, re
         f'{epilogue} writes a {want} {shape} tensor, got {out.dtype} {tuple(out.shape)}'
     a = _gemm_args(A, W, out, M, N, K, epi, splits)
     a.variant = variant
+    a.activation = activation if isinstance(activation, int) else _lib.activation_code(activation)
     a.bias = bias.data_ptr() if bias is not None else None
     a.diag = diag.data_ptr() if diag is not None else None    # EC_GEMM_DIAG builds only
     if resid is not None:

@@ -58,12 +58,15 @@ EC_API const char *ec_last_error(void);
  *   606  ec_adapter_weights + post_norm, ec_adapter_train_params + post_norm (the post-LN encoder layout; 0 = pre-LN, what
  *        every zero-initialised struct of an older caller meant); ec_adapter_forward takes 8 layers; the fused training
  *        steps take EC_AGG_MAX
+ *   607  + activation at the end of ec_vit_weights, ec_text_weights and ec_vit_train_weights and, in ec_gemm_args, in the four
+ *        bytes of alignment padding behind `splits` (offsets and size unchanged) (0 = QuickGELU, what every zero-initialised
+ *        struct of an older caller meant; 1 = exact GELU, x Phi(x)); ec_split16's gelu argument takes 2
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does, with its ctypes mirrors.) */
-#define EC_ABI_VERSION 606
+#define EC_ABI_VERSION 607
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);
@@ -266,7 +269,7 @@ EC_API int ec_randaugment(const uint8_t *frames_in, uint8_t *frames_out, int F, 
  * ------------------------------------------------------------------------ */
 enum {
     EC_EPI_STORE16 = 0, /* C16 = acc + bias */
-    EC_EPI_GELU16 = 1,  /* C16 = QuickGELU(acc + bias), x * sigmoid(1.702 x) */
+    EC_EPI_GELU16 = 1,  /* C16 = QuickGELU(acc + bias), x * sigmoid(1.702 x); with args.activation = 1 here and in the GELU epilogues below: the exact GELU, x Phi(x) */
     EC_EPI_RESID32 = 2, /* C32 += acc + bias   (fp32 residual stream, in place) */
     EC_EPI_STORE32 = 3, /* C32 = acc + bias */
     /* training (ec_vit_train_*; default variant only): */
@@ -308,6 +311,15 @@ typedef struct {
     int splits;        /* > 1: that many independent products over consecutive K-column ranges of A and W
                           (batch s reads columns s*K .. (s+1)*K - 1 and writes C + s * split_stride elements):
                           the partial sums of a weight gradient whose reduction dimension is the batch */
+    int activation;    /* (ABI 607) what the GELU epilogues apply: EC_ACT_QUICK_GELU (0) = x sigmoid(1.702 x), OpenAI's checkpoints;
+                          EC_ACT_GELU (1) = x Phi(x), torch.nn.GELU(): open_clip's models without a -quickgelu suffix, Hugging Face
+                          hidden_act "gelu".  Read by EC_EPI_GELU16, GELU16_LN, GELU16_SAVE (C = GELU(u)), GELU_BWD16 (C = dg GELU'(aux)
+                          = dg (Phi + u phi)) and the K-batched form of those (ws), variant 0.  Nonzero with any other epilogue, or a
+                          value other than 0 / 1: EC_ERR_INVALID (refused, not ignored).  |result - x Phi(x)| <= 2^-21 |x| and
+                          |derivative error| <= 2^-20 before the 16-bit rounding.
+                          LAYOUT: these are the four bytes that were alignment padding between `splits` and the 8-byte
+                          `split_stride`: no field moved and sizeof(ec_gemm_args) is what it was (248), so the struct did not have to
+                          grow; a zero-initialised struct of an older caller ({} / memset / calloc) carries 0 = QuickGELU here. */
     long split_stride;
     void *ws;          /* optional fp32 scratch (ws_bytes).  When given and the launch would leave most CUs idle
                           (tiles x 2 <= CUs: a few frames), the product is cut into K-batches whose partial sums a
@@ -361,6 +373,7 @@ typedef struct {
                                  element in the first N bytes of rows of 2 . ldc bytes -- the A_lo8 operand of the GEMM that follows */
     int aux_exp;
 } ec_gemm_args;
+enum { EC_ACT_QUICK_GELU = 0, EC_ACT_GELU = 1 };
 
 EC_API int ec_gemm(const ec_gemm_args *args, ec_stream_t stream);
 
@@ -395,7 +408,7 @@ EC_API int ec_layernorm_split(const float *x, long ldx, const int32_t *row_idx, 
  * stride ldx) into hi / lo parts at row stride ldo: the LayerNorm of the split-operand blocks (precise_blocks). */
 EC_API int ec_layernorm_hl(const void *x_hi, const void *x_lo, long ldx, const float *gamma, const float *beta, int rows,
                            int width, float eps, void *out16, void *out16_lo, long ldo, int dtype, ec_stream_t stream);
-/* fp32 [n] -> (QuickGELU if gelu) -> hi / lo 16-bit parts */
+/* fp32 [n] -> (gelu: 0 = nothing, 1 = QuickGELU, 2 = exact GELU x Phi(x); anything else: EC_ERR_INVALID) -> hi / lo 16-bit parts */
 /* ... with the lo part as the e4m3 operand of ec_gemm_args.A_lo8 (round 6): out_lo8 = round_e4m3((LN(x) - out16) . 2^lo_exp) and,
  * when out_hi8 is given, out_hi8 = round_e4m3(out16 . 2^hi_exp) (ec_gemm_args.A8), one byte per element in the first `width`
  * bytes of rows of 2 . ldo bytes (the byte row pitch of out16); values beyond +-448 . 2^-exp saturate.  f16 planes. */
@@ -588,6 +601,10 @@ typedef struct {
                                    product measures 0.51 - 0.52 of the f16 one.  The lo part is ~2^-11 of its hi part, so e4m3's 2^-4
                                    still removes ~95 % of the 16-bit operand-rounding error (profiles/r6_fp8_model_8_5.txt, r6_parity_seeds.txt).
                                    out_proj (the attention output's lo part) stays 16-bit.  Needs the *_w8 fields of every split-operand block. */
+    int activation;             /* (ABI 607, appended) EC_ACT_QUICK_GELU (0, OpenAI's checkpoints) or EC_ACT_GELU (1, open_clip without
+                                   -quickgelu / Hugging Face hidden_act "gelu"): the MLP activation of every block, in every chain
+                                   (plain, folded, split-operand with or without lo_fp8, precise, low_latency) and in
+                                   ec_vit_train_forward.  Nothing in a state dict names it: the caller has to know. */
 } ec_vit_weights;
 
 typedef struct {
@@ -600,6 +617,7 @@ typedef struct {
     const ec_block_weights *blocks; /* host array [layers] */
     int precise;                    /* != 0: split-precision arithmetic (text features are cached) */
     const void *proj_w_lo;
+    int activation;                 /* (ABI 607, appended) as ec_vit_weights.activation, both chains of the text tower */
 } ec_text_weights;
 
 /* bytes of scratch needed to push `chunk` images (or texts) through at once */
@@ -856,6 +874,8 @@ typedef struct {
 typedef struct {
     const ec_block_weights_t *blocks; /* host array [layers] */
     const float *proj;                /* visual.proj [W, out_dim] fp32 */
+    int activation;                   /* (ABI 607, appended) the activation whose derivative the backward pass applies; must equal
+                                         ec_vit_weights.activation of the same call (the forward pass ran with that one) */
 } ec_vit_train_weights;
 
 /* Gradient outputs, fp32, overwritten (not accumulated), state-dict layouts.  NULL = not wanted: the work
