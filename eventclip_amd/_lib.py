@@ -331,6 +331,14 @@ SIGNATURES = {
                                            c_int, c_void_p, ctypes.POINTER(EcVitGrads), ctypes.POINTER(EcVitLora), c_void_p,
                                            ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p]),
     'ec_vit_train_layout': (c_int, [ctypes.POINTER(EcVitWeights), c_int, c_void_p, c_int]),
+    'ec_vit_train_backward_image_scratch_bytes': (ctypes.c_size_t, [ctypes.POINTER(EcVitWeights), c_int]),
+    'ec_vit_train_backward_image': (c_int, [ctypes.POINTER(EcVitWeights), ctypes.POINTER(EcVitTrainWeights), c_void_p,
+                                            c_int, c_void_p, ctypes.POINTER(EcVitGrads), ctypes.POINTER(EcVitLora), c_void_p,
+                                            c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t,
+                                            c_void_p]),
+    'ec_patch_embed_backward': (c_int, [ctypes.POINTER(EcVitWeights), c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_void_p, c_void_p]),
+    'ec_unpatchify': (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'ec_pack_weight16_batched': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'ec_fingerprint_batched': (c_int, [c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p]),
     'ec_layernorm_backward_partials': (ctypes.c_size_t, [c_int, c_int]),
@@ -371,7 +379,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 607      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
+ABI_VERSION = 608      # EC_ABI_VERSION of include/eventclip_hip.h these bindings mirror
 
 
 class HipLibraryError(RuntimeError):

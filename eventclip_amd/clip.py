@@ -376,9 +376,43 @@ class CLIP(ClipBase):
         assert patches.dtype == self.compute_dtype and patches.is_contiguous()
         return torch.ops.eventclip_hip.vit_encode(patches, torch_ops.handle_of(self))
 
+    def encode_image(self, image, differentiable=False):
+        """image: float tensor [N, 3, R, R] as CLIP's preprocess produces -> fp32 [N, D].
+
+        differentiable=True: the features stay attached to the autograd graph of ``image`` (saliency, adversarial probes, a
+        learnable front end): they come from a frozen training-form tower (``ft.VisualTower``, built on first use, its
+        operand copies re-packed when the weights were written) through ``eventclip_hip::vit_image_fwd``, whose backward
+        is ``ec_vit_train_backward_image`` with no weight gradient asked for.  The parameters receive no gradient.  The
+        training form is the plain chain (plain q, LayerNorm not folded into the GEMMs), so its features differ from the
+        default call's in the last bits (below 1e-3 max-normalised in float16).  The split-precision tower has no training form.
+        Costs: the cached tower holds its own 16-bit operand copies of the vision weights beside the serving ones (twice the
+        memory), and building or re-packing it marks the serving copies stale, so the first default call after it re-packs
+        them (the same bits).  ``.cuda()`` / ``.to()`` drop the cached tower; a graph built before stays valid -- it keeps
+        the tower it ran through alive and differentiates the weights as they were."""
+        if differentiable:
+            return self._encode_image_differentiable(image)
+        return self._encode_image(image)
+
+    def _apply(self, fn, *a, **k):
+        self._diff_tower = None          # built over the parameters where they were
+        return super()._apply(fn, *a, **k)
+
+    def _encode_image_differentiable(self, image):
+        from . import ft, torch_ops
+        c = self.cfg
+        R = c['image_size']
+        if image.dim() != 4 or image.shape[1] != 3 or image.shape[2] != R or image.shape[3] != R:
+            raise ValueError(f'encode_image expects [N, 3, {R}, {R}], got {tuple(image.shape)}')
+        t = getattr(self, '_diff_tower', None)
+        if t is None:
+            t = self._diff_tower = ft.VisualTower(self)     # refuses image_precise: no training form
+        img = image.to(t.dev, torch.float32)
+        # a frozen tower: parameters that require grad elsewhere go in detached
+        params = [t.param[n].detach() for n in t.trainable()] + ([p.detach() for p in t.lora.params.values()] if t.lora else [])
+        return torch.ops.eventclip_hip.vit_image_fwd(img, params, torch_ops.handle_of(t))[0]
+
     @torch.no_grad()
-    def encode_image(self, image):
-        """image: float tensor [N, 3, R, R] as CLIP's preprocess produces -> fp32 [N, D]."""
+    def _encode_image(self, image):
         pk = self._pack()
         c = self.cfg
         R, P = c['image_size'], c['patch']

@@ -139,15 +139,24 @@ class FTCLIPClassifier(FSCLIPClassifier):
     def _forward_train(self, data_dict):
         """clip_cls_ft.py:196-243 with autograd: the valid views as patch rows under ``no_grad`` (``ec_patchify``), the
         tower through ``vit_train_fwd`` with its trainable tensors as inputs, ``text_feats = F.normalize(parameter)``
-        in torch, then ``classify`` with the live text (its ``row_idx`` is the identity adapter's zero scatter)."""
+        in torch, then ``classify`` with the live text (its ``row_idx`` is the identity adapter's zero scatter).
+        When ``data_dict['img']`` requires grad the valid views go through ``vit_image_fwd`` as fp32 images instead, and
+        ``loss.backward()`` fills ``img.grad`` (padded views: exact zeros, the gradient of the indexing)."""
         if not self.autograd:
             return super()._forward_train(data_dict)
         from . import torch_ops
         t = self._operand_tower()
-        with torch.no_grad():
-            patches, valid_masks, row_idx = ft.valid_patches(t, data_dict)
         params = [t.param[n] for n in t.trainable()] + (list(t.lora.params.values()) if t.lora else [])
-        feats, _ = torch.ops.eventclip_hip.vit_train_fwd(patches, params, torch_ops.handle_of(t))
+        img = data_dict.get('img')
+        if 'patches' not in data_dict and torch.is_tensor(img) and img.requires_grad:
+            valid_masks = data_dict['valid_mask'].to(t.dev)
+            row_idx = ft.compact_row_idx(valid_masks)
+            x = img[valid_masks.to(img.device)].to(t.dev, torch.float32)
+            feats, _ = torch.ops.eventclip_hip.vit_image_fwd(x, params, torch_ops.handle_of(t))
+        else:
+            with torch.no_grad():
+                patches, valid_masks, row_idx = ft.valid_patches(t, data_dict)
+            feats, _ = torch.ops.eventclip_hip.vit_train_fwd(patches, params, torch_ops.handle_of(t))
         text_t = self.get_text_feats().float().t().contiguous()          # [C, K], differentiable under prompt tuning
         full_logits, logits, probs = self._classify(feats, row_idx.to(torch.int32).contiguous(), normalize=True,
                                                     text_t=text_t)

@@ -23,7 +23,9 @@
 //             backward recomputes its statistics from the saved input, attention backward recomputes the
 //             probabilities from the saved log-sum-exp (attention_bwd.hip);
 //   gradients come out fp32 in the state dict's layouts; a NULL pointer skips the work behind it
-//   (LoRA on q k v o needs the attention weight gradients only: none of the MLP's dW GEMMs run).
+//   (LoRA on q k v o needs the attention weight gradients only: none of the MLP's dW GEMMs run);
+//   the image's gradient (ec_vit_train_backward_image) runs the chain down to the embedding whatever weight gradients
+//   are asked for: d image = unpatchify(d pre . conv1.weight), one more dX product and a permutation.
 #include "activation.h"
 #include "common.h"
 #include "mfma.h"
@@ -377,6 +379,25 @@ __global__ __launch_bounds__(256) void pos_grad_kernel(const float *de, int n_im
         }
         if (dpos) *reinterpret_cast<float4 *>(dpos + (long)s * W + c) = a;
         if (dcls && s == 0) *reinterpret_cast<float4 *>(dcls + c) = a;
+    }
+}
+
+// The adjoint of ec_patchify's layout: d_image[img][c][y][x] = the (c, y % p, x % p) column of the row of patch
+// (y / p, x / p) of image img.  Patches do not overlap: a permutation, every output element written once, by the
+// thread that owns it (consecutive threads walk an image row: coalesced stores, reads in runs of p floats).
+__global__ __launch_bounds__(256) void unpatchify_kernel(const float *rows, long ld, int seq, int row_off, long total, int R,
+                                                         int p, float *d_image)
+{
+    const int g = R / p;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int x = (int)(i % R);
+        long t = i / R;
+        const int y = (int)(t % R);
+        t /= R;
+        const int c = (int)(t % 3);
+        const long img = t / 3;
+        const long row = img * seq + row_off + (long)(y / p) * g + x / p;
+        d_image[i] = rows[row * ld + (long)(c * p + y % p) * p + x % p];
     }
 }
 
@@ -1347,6 +1368,28 @@ int gemm_rows32(int M, int N, int K, int dtype, int epi, const void *A, const vo
     return EC_OK;
 }
 
+// conv1's weight rows as the [N, K] operand of its data gradient: 3 p^2 rows of W columns, padded to ec_gemm's N
+inline int conv_t_rows(const ec_vit_weights *w) { return (3 * w->patch * w->patch + 15) / 16 * 16; }
+
+// d image = unpatchify(d_tok . conv1.weight): the data gradient of the patch embedding.  d_tok16 is the 16-bit copy of
+// d loss / d pre [n_img S, W] (class rows included: the product computes them, unpatchify skips them); conv1.weight^T
+// comes as hi + lo parts (ec_gemm_args.W_lo), so the weight's rounding does not enter; fp32 accumulation and output.
+// The product runs over conv1.weight's 3 p^2 true columns -- a patch row's hi and lo groups both carry the pixel,
+// whose gradient is formed once.
+int embed_data_grad(const ec_vit_weights *w, const void *conv_wt, const void *conv_wt_lo, const void *d_tok16, int n_img,
+                    float *d_pix, float *d_image, ec_stream_t stream)
+{
+    const int g = w->image_size / w->patch, S = g * g + 1, kt = conv_t_rows(w);
+    EC_TRY(Gemm(n_img * S, kt, w->width, w->dtype, EC_EPI_STORE32, d_tok16, conv_wt, nullptr, d_pix).lo(nullptr, conv_wt_lo).run(stream));
+    return ec_unpatchify(d_pix, kt, S, 1, n_img, w->image_size, w->patch, d_image, stream);
+}
+
+// what a backward pass that differentiates the image is handed on top of the weight-gradient form
+struct ImageGrad {
+    const void *conv_wt, *conv_wt_lo;   // conv1.weight^T [conv_t_rows, W] as hi / lo (lo NULL: the weight is its 16-bit value)
+    float *d_image;                     // fp32 [n_img, 3, R, R] out
+};
+
 }  // namespace
 
 extern "C" {
@@ -1434,7 +1477,7 @@ EC_API int ec_vit_train_backward(const ec_vit_weights *w, const ec_vit_train_wei
 static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches, int n_img,
                            const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora, int stage_begin,
                            int stage_end, void *workspace, size_t workspace_bytes, void *scratch, size_t scratch_bytes,
-                           ec_stream_t stream);
+                           ec_stream_t stream, const ImageGrad *image = nullptr);
 
 EC_API int ec_vit_train_backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
                                         int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
@@ -1466,10 +1509,64 @@ EC_API int ec_vit_train_backward_over(const ec_vit_weights *w, const ec_vit_trai
                            tape_bytes, scratch, scratch_bytes, stream);
 }
 
+EC_API size_t ec_vit_train_backward_image_scratch_bytes(const ec_vit_weights *w, int n_img)
+{
+    if (!w || n_img <= 0 || w->patch <= 0 || w->layers < 1 || w->layers > 64) return 0;
+    Scratch tape{nullptr, 0, 0}, own{nullptr, 0, 0};
+    TrainBufs b;
+    carve_train(tape, w, n_img, b, &own);
+    const int g = w->image_size / w->patch;
+    own.take((size_t)n_img * (g * g + 1) * conv_t_rows(w) * 4);
+    return own.off;
+}
+
+// ec_vit_train_backward_over that also differentiates the image: the chain runs down to the embedding whatever weight
+// gradients are asked for (none at all is legal: a frozen tower launches no weight-gradient kernel).
+EC_API int ec_vit_train_backward_image(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
+                                       int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
+                                       const void *conv_wt, const void *conv_wt_lo, float *d_image, const void *tape,
+                                       size_t tape_bytes, void *scratch, size_t scratch_bytes, ec_stream_t stream)
+{
+    EC_REQUIRE(scratch && conv_wt && d_image, "ec_vit_train_backward_image: null scratch / conv1 operand / d_image");
+    EC_REQUIRE((((uintptr_t)conv_wt | (uintptr_t)conv_wt_lo) & 15) == 0, "ec_vit_train_backward_image: conv1 operands must be 16-byte aligned");
+    const ImageGrad image = {conv_wt, conv_wt_lo, d_image};
+    return backward_stages(w, wt, patches, n_img, d_feats, gr, lora, 0, w ? w->layers + 2 : 0, const_cast<void *>(tape),
+                           tape_bytes, scratch, scratch_bytes, stream, &image);
+}
+
+EC_API int ec_patch_embed_backward(const ec_vit_weights *w, const void *conv_wt, const void *conv_wt_lo, const void *d_tok16,
+                                   int n_img, float *d_pix, float *d_image, ec_stream_t stream)
+{
+    EC_TRY(check_geometry(w, "ec_patch_embed_backward"));
+    EC_REQUIRE(n_img > 0, "ec_patch_embed_backward: n_img=%d", n_img);
+    EC_REQUIRE(conv_wt && d_tok16 && d_pix && d_image, "ec_patch_embed_backward: null buffer");
+    return embed_data_grad(w, conv_wt, conv_wt_lo, d_tok16, n_img, d_pix, d_image, stream);
+}
+
+EC_API int ec_unpatchify(const float *rows, long ld, int seq, int row_off, int n_img, int n_px, int patch, float *d_image,
+                         ec_stream_t stream)
+{
+    EC_REQUIRE(n_img >= 0 && patch > 0 && n_px > 0 && n_px % patch == 0, "ec_unpatchify: bad geometry (n_px %d, patch %d)", n_px,
+               patch);
+    const int G = (n_px / patch) * (n_px / patch);
+    EC_REQUIRE(row_off >= 0 && seq >= row_off + G && ld >= 3L * patch * patch,
+               "ec_unpatchify: %d rows per image from row %d for %d patches, row stride %ld for %d columns", seq, row_off, G, ld,
+               3 * patch * patch);
+    if (n_img == 0) return EC_OK;
+    EC_REQUIRE(rows && d_image, "ec_unpatchify: null buffer");
+    const long total = (long)n_img * 3 * n_px * n_px;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ec::ProfScope prof(ec::PROF_UNPATCHIFY, s, 0, 8.0 * total);
+    hipLaunchKernelGGL(unpatchify_kernel, dim3((unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384)), dim3(256),
+                       0, s, rows, ld, seq, row_off, total, n_px, patch, d_image);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
 static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches, int n_img,
                            const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora, int stage_begin,
                            int stage_end, void *workspace, size_t workspace_bytes, void *scratch, size_t scratch_bytes,
-                           ec_stream_t stream)
+                           ec_stream_t stream, const ImageGrad *image)
 {
     EC_TRY(check_geometry(w, "ec_vit_train_backward"));
     EC_REQUIRE(stage_begin >= 0 && stage_begin <= stage_end && stage_end <= w->layers + 2,
@@ -1488,6 +1585,7 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
     Scratch own{(unsigned char *)scratch, 0, scratch_bytes};
     TrainBufs b;
     const size_t need = carve_train(sc, w, n_img, b, scratch ? &own : nullptr);
+    float *d_pix = image ? (float *)own.take((size_t)n_img * S * conv_t_rows(w) * 4) : nullptr;
     if (need > workspace_bytes)
         return ec::fail(EC_ERR_WORKSPACE, "ec_vit_train_backward: workspace %zu < %zu bytes", workspace_bytes, need);
     if (scratch && own.off > scratch_bytes)
@@ -1496,9 +1594,9 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
     const int Mp = b.Mp;
 
     // how far down the gradient has to travel: the lowest block with a gradient asked for, or the
-    // embedding (-1); nothing below that is computed
+    // embedding (-1: one of its gradients, or the image's); nothing below that is computed
     int lowest = L;
-    if (gr->conv_w || gr->cls || gr->pos || gr->ln_pre_g || gr->ln_pre_b) lowest = -1;
+    if (image || gr->conv_w || gr->cls || gr->pos || gr->ln_pre_g || gr->ln_pre_b) lowest = -1;
     else
         for (int l = 0; l < L; l++) {
             const ec_block_grads &q = gr->blocks[l];
@@ -1595,8 +1693,9 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
     if (lowest >= 0 || stage_end <= L + 1) return EC_OK;
 
     // ---- embedding: x[0] = ln_pre([cls; patches . conv1^T] + pos) ----
+    // (the image's gradient: d pre also as 16 bit, the operand of its dX product)
     EC_TRY(ln_backward(b.pre, W, b.dx, W, w->ln_pre_g, M, W, b.dh32, W, 0, gr->ln_pre_g, gr->ln_pre_b, b.lnpart, b.ln_wgs,
-                       s));
+                       s, image ? b.dx16 : nullptr, dt));
     if (gr->pos || gr->cls) {
         hipLaunchKernelGGL(pos_grad_kernel, dim3((unsigned)S), dim3(256), 0, s, b.dh32, n_img, S, W, gr->pos, gr->cls);
         EC_CHECK_HIP(hipGetLastError());
@@ -1607,6 +1706,7 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
         EC_TRY(transpose<0>(dt, patches, w->kpad, R, w->kpad, Mp, 0, 0, 0, b.tb, nullptr, s));
         EC_TRY(weight_grad(dt, b.ta, b.tb, W, w->kpad, b, gr->conv_w, 3 * w->patch * w->patch, stream));
     }
+    if (image) EC_TRY(embed_data_grad(w, image->conv_wt, image->conv_wt_lo, b.dx16, n_img, d_pix, image->d_image, stream));
     return EC_OK;
 }
 

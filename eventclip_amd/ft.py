@@ -128,10 +128,12 @@ class VisualTower:
         self.effective = {}
         k = 3 * self.P * self.P
         self.k, self.kpad, self.klo = k, ((2 * k + 63) // 64) * 64, ((k + 63) // 64) * 64
+        self.kt = ((k + 15) // 16) * 16       # rows of conv1.weight^T as ec_gemm's [N, K] operand (the image's gradient)
         W, D = self.W, self.D
         z16 = lambda *shape: torch.zeros(shape, dtype=self.cd, device=dev)      # noqa: E731
         self.packed = dict(conv=z16(W, self.kpad), conv_lo=z16(W, self.klo), conv_hi_tmp=z16(W, k),
                            conv_lo_tmp=z16(W, k), proj_lo_tmp=z16(W, D), proj_pair=z16(2, D, W))
+        self._conv_t_stale = True             # conv_t / conv_lo_t: built when an image gradient first asks (conv_operands)
         self.packed['proj_t'], self.packed['proj_lo_t'] = self.packed['proj_pair'][0], self.packed['proj_pair'][1]
         shapes = dict(qkv_w=(3 * W, W), out_w=(W, W), fc1_w=(4 * W, W), fc2_w=(W, 4 * W))
         for i in range(self.L):
@@ -211,9 +213,25 @@ class VisualTower:
             pk['conv'][:, :self.k] = pk['conv_hi_tmp']                          # [w_hi | w_hi | 0]
             pk['conv'][:, self.k:2 * self.k] = pk['conv_hi_tmp']
             pk['conv_lo'][:, :self.k] = pk['conv_lo_tmp']                       # [w_lo | 0]
+            self._conv_t_stale = True                                           # (the transposed copies: conv_operands)
         if 'proj' in todo:
             pk['proj_lo_t'].copy_(pk['proj_lo_tmp'].t())
         self.clip._packed = None       # the inference copies of clip.py are stale once a master moved
+
+    def conv_operands(self):
+        """conv1.weight TRANSPOSED as hi / lo 16-bit [kt, W] (rows past 3 p^2 zero): the [N, K] operand of the image
+        gradient's product (``ec_vit_train_backward_image``).  Only that pass reads them, so they are built from the
+        packed hi / lo parts when it first asks and again after ``pack`` re-packed conv1.weight -- the trainers and the
+        weight-gradient paths launch nothing for them."""
+        pk = self.packed
+        if self._conv_t_stale:
+            if 'conv_t' not in pk:
+                pk['conv_t'] = torch.zeros((self.kt, self.W), dtype=self.cd, device=self.dev)
+                pk['conv_lo_t'] = torch.zeros((self.kt, self.W), dtype=self.cd, device=self.dev)
+            pk['conv_t'][:self.k].copy_(pk['conv_hi_tmp'].t())
+            pk['conv_lo_t'][:self.k].copy_(pk['conv_lo_tmp'].t())
+            self._conv_t_stale = False
+        return pk['conv_t'], pk['conv_lo_t']
 
     def _fingerprints(self):
         """One 64-bit fingerprint per master, then per LoRA factor (``ec_fingerprint_batched``: one launch; the

@@ -18,12 +18,14 @@ mirrors of the reference's interface (vis / preprocess / clip / adapter / clip_c
     torch.ops.eventclip_hip.resnet_encode      ec_resnet_encode                models/clip_cls.py:101 (ResNet backbones)
     torch.ops.eventclip_hip.vit_train_fwd      ec_vit_train_forward            models/clip_cls_ft.py:196-243, the tower with a tape
     torch.ops.eventclip_hip.vit_train_bwd      ec_vit_train_backward_over      its backward, over the forward's tape
+    torch.ops.eventclip_hip.vit_image_fwd      ec_patchify + ec_vit_train_forward   the same tower from the fp32 image
+    torch.ops.eventclip_hip.vit_image_bwd      ec_vit_train_backward_image     its backward: d image and the parameter gradients
 
 Weights live in packed C structs owned by the Python modules; an op receives them as an integer
 handle into a registry of live modules (tensors-only signatures keep the ops traceable, and the
 registered fake kernels give their output shapes without touching the device).
 
-``classify``, ``adapter_train_fwd`` and ``vit_train_fwd`` carry autograd formulas (``torch.library.register_autograd``)
+``classify``, ``adapter_train_fwd``, ``vit_train_fwd`` and ``vit_image_fwd`` carry autograd formulas (``torch.library.register_autograd``)
 whose backward passes are the ``*_bwd`` ops, so ``loss.backward()`` reaches ``text_feats``, the adapter's parameters and
 the vision tower's, which ``adapter_train_fwd`` / ``vit_train_fwd`` take as real tensor inputs.  The ``*_bwd`` ops have no formula of their own: there is no double
 backward, and asking for one raises.
@@ -462,7 +464,8 @@ def vit_train_fwd(patches: torch.Tensor, params: List[torch.Tensor],
     (``_tower_params``) -> (feats fp32 [N, D]; tape uint8 [ec_vit_train_workspace_bytes]: the saved activations
     ``vit_train_bwd`` reads, followed by the scratch of both passes).  The tape is this call's own, so several forwards
     may be alive at once.  Operand copies of masters or factors written since they were packed are rebuilt first
-    (``VisualTower.refresh``)."""
+    (``VisualTower.refresh``).  ``patches`` is not differentiable: a gradient in its 16 bits would underflow, and a patch
+    row carries every pixel twice (hi | lo).  The gradient with respect to the image is ``vit_image_fwd``'s, in fp32."""
     t = _resolve(tower_handle, 'vit_train_fwd')
     _tower_params(t, params, 'vit_train_fwd')
     t.refresh()
@@ -545,5 +548,118 @@ def _vit_backward(ctx, d_feats, d_tape):
 vit_train_fwd.register_autograd(_vit_backward, setup_context=_vit_setup)
 
 
+# ---- the same tower from the fp32 image, differentiable with respect to it ----
+def _image_tape(t, n):
+    """-> (bytes of the training workspace rounded to 256, bytes of the tape: the workspace, then the patch rows)"""
+    ws = (t.workspace_bytes(n) + 255) // 256 * 256
+    return ws, ws + n * t.G * t.kpad * 2
+
+
+@custom_op(f'{NAMESPACE}::vit_image_fwd', mutates_args=(), device_types='cuda')
+def vit_image_fwd(image: torch.Tensor, params: List[torch.Tensor], tower_handle: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """image fp32 [N, 3, R, R] (what ``ec_patchify`` takes), params as ``vit_train_fwd`` takes them -> (feats fp32 [N, D];
+    tape uint8: the training workspace of ``vit_train_fwd`` followed by the 16-bit patch rows, which conv1's weight
+    gradient reads).  The same launches as ``vit_train_fwd`` on ``patchify(image)``: the same bits.  The autograd formula
+    returns d image (``vit_image_bwd``) next to the parameter gradients."""
+    t = _resolve(tower_handle, 'vit_image_fwd')
+    _tower_params(t, params, 'vit_image_fwd')
+    t.refresh()
+    n, R = int(image.shape[0]), t.cfg['image_size']
+    if image.dtype != torch.float32 or tuple(image.shape) != (n, 3, R, R) or n == 0:
+        raise RuntimeError(f'{NAMESPACE}::vit_image_fwd: image {tuple(image.shape)} {image.dtype}, '
+                           f'[N > 0, 3, {R}, {R}] torch.float32 expected')
+    image = image.contiguous()
+    ws, total = _image_tape(t, n)
+    feats = torch.empty((n, t.D), dtype=torch.float32, device=image.device)
+    tape = _lib.scratch(total, image.device).zero_()
+    patches = tape[ws:total]
+    _lib.launch('ec_patchify', image, n, R, t.P, t.kpad, patches, t.code)
+    _lib.launch('ec_vit_train_forward', t._vit, patches, n, feats, tape, ws)
+    return feats, tape
+
+
+@vit_image_fwd.register_fake
+def _(image, params, tower_handle):
+    t = _resolve(tower_handle, 'vit_image_fwd')
+    n = image.shape[0]
+    return (image.new_empty((n, t.D), dtype=torch.float32),
+            image.new_empty((max(_image_tape(t, n)[1], 256),), dtype=torch.uint8))
+
+
+@custom_op(f'{NAMESPACE}::vit_image_bwd', mutates_args=(), device_types='cuda')
+def vit_image_bwd(params: List[torch.Tensor], tape: torch.Tensor, d_feats: torch.Tensor, tower_handle: int,
+                  need_image: bool, need: List[bool]) -> List[torch.Tensor]:
+    """The backward of ``vit_image_fwd`` over its tape: 1 + len(params) tensors -- d image fp32 [N, 3, R, R] where
+    need_image, then the gradient of params[i] where need[i]; an empty tensor for what is not needed.  With need_image the
+    chain runs down to the embedding whatever ``need`` says (``ec_vit_train_backward_image``); weight-, bias- and
+    LoRA-gradient kernels run only for what ``need`` names, none at all for a frozen tower.  Without it this is
+    ``vit_train_bwd`` on the tape's patch rows.  The tape is only read."""
+    t = _resolve(tower_handle, 'vit_image_bwd')
+    names, keys = _tower_params(t, params, 'vit_image_bwd')
+    if len(need) != len(params):
+        raise RuntimeError(f'{NAMESPACE}::vit_image_bwd: need has {len(need)} entries for {len(params)} parameters')
+    n, R = int(d_feats.shape[0]), t.cfg['image_size']
+    ws, total = _image_tape(t, max(n, 1))
+    if n == 0 or tuple(d_feats.shape) != (n, t.D) or tape.numel() < total:
+        raise RuntimeError(f'{NAMESPACE}::vit_image_bwd: d_feats {tuple(d_feats.shape)} / tape of {tape.numel()} bytes do '
+                           f'not belong to a forward over {n} images')
+    d_feats = _f32c(d_feats)
+    patches = tape[ws:total]
+    grads = [torch.empty_like(p) if b else None for p, b in zip(params, need)]
+    tower_grads = {k: g for k, g in zip(names, grads) if g is not None}
+    factor_grads = {k: g for k, g in zip(keys, grads[len(names):]) if g is not None}
+    spare = []                       # the partner of a factor whose own gradient is not asked for: written, dropped
+    if factor_grads:
+        for _, _, kd, ku in t.lora.projections():
+            for a, b in ((kd, ku), (ku, kd)):
+                if a in factor_grads and b not in factor_grads:
+                    spare.append(b)
+                    factor_grads[b] = torch.empty_like(t.lora.params[b])
+    g, keep_g = t.grads_over(tower_grads)                                   # noqa: F841 (the struct's block array)
+    lora, keep_l = t.lora.struct_for(factor_grads) if factor_grads else (None, None)   # noqa: F841
+    d_image = None
+    if need_image:
+        d_image = torch.empty((n, 3, R, R), dtype=torch.float32, device=d_feats.device)
+        scr = _lib.scratch(_lib.lib().ec_vit_train_backward_image_scratch_bytes(ctypes.byref(t._vit), n), d_feats.device)
+        conv_t, conv_lo_t = t.conv_operands()
+        _lib.launch('ec_vit_train_backward_image', t._vit, t._vit_t, patches, n, d_feats, g, lora, conv_t, conv_lo_t,
+                    d_image, tape, ws, scr, scr.numel())
+    elif tower_grads or factor_grads:
+        scr = _lib.scratch(_lib.lib().ec_vit_train_backward_scratch_bytes(ctypes.byref(t._vit), n), d_feats.device)
+        _lib.launch('ec_vit_train_backward_over', t._vit, t._vit_t, patches, n, d_feats, g, lora, tape, ws, scr, scr.numel())
+    return [d_feats.new_empty((0,), dtype=torch.float32) if x is None else x for x in [d_image] + grads]
+
+
+@vit_image_bwd.register_fake
+def _(params, tape, d_feats, tower_handle, need_image, need):
+    t = _resolve(tower_handle, 'vit_image_bwd')
+    n, R = d_feats.shape[0], t.cfg['image_size']
+    return ([d_feats.new_empty((n, 3, R, R) if need_image else (0,), dtype=torch.float32)] +
+            [p.new_empty(tuple(p.shape) if b else (0,), dtype=torch.float32) for p, b in zip(params, need)])
+
+
+def _vit_image_setup(ctx, inputs, output):
+    image, params, tower_handle = inputs
+    ctx.save_for_backward(output[1], *params)
+    ctx.tower_handle = tower_handle
+    # the graph keeps its tower alive (handles are weak): an owner that drops or rebuilds its cached tower -- CLIP.cuda() /
+    # .to() after encode_image(differentiable=True) -- leaves a live graph able to run its backward
+    ctx.tower = _resolve(tower_handle, 'vit_image_fwd')
+    ctx.mark_non_differentiable(output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _vit_image_backward(ctx, d_feats, d_tape):
+    tape, *params = ctx.saved_tensors
+    need_image, need = bool(ctx.needs_input_grad[0]), list(ctx.needs_input_grad[1])
+    if d_feats is None or not (need_image or any(need)):
+        return None, [None] * len(params), None
+    got = torch.ops.eventclip_hip.vit_image_bwd(params, tape, d_feats, ctx.tower_handle, need_image, need)
+    return got[0] if need_image else None, [g if b else None for g, b in zip(got[1:], need)], None
+
+
+vit_image_fwd.register_autograd(_vit_image_backward, setup_context=_vit_image_setup)
+
+
 OPS = ('events_to_frames', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode',
-       'classify_bwd', 'adapter_train_fwd', 'adapter_train_bwd', 'vit_train_fwd', 'vit_train_bwd')
+       'classify_bwd', 'adapter_train_fwd', 'adapter_train_bwd', 'vit_train_fwd', 'vit_train_bwd', 'vit_image_fwd', 'vit_image_bwd')

@@ -61,12 +61,14 @@ EC_API const char *ec_last_error(void);
  *   607  + activation at the end of ec_vit_weights, ec_text_weights and ec_vit_train_weights and, in ec_gemm_args, in the four
  *        bytes of alignment padding behind `splits` (offsets and size unchanged) (0 = QuickGELU, what every zero-initialised
  *        struct of an older caller meant; 1 = exact GELU, x Phi(x)); ec_split16's gelu argument takes 2
+ *   608  + ec_vit_train_backward_image / _image_scratch_bytes, ec_patch_embed_backward, ec_unpatchify: the vision tower
+ *        differentiated with respect to its input image (additive: no struct or argument list changed)
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does, with its ctypes mirrors.) */
-#define EC_ABI_VERSION 607
+#define EC_ABI_VERSION 608
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);
@@ -963,6 +965,36 @@ EC_API int ec_vit_train_backward_over(const ec_vit_weights *w, const ec_vit_trai
                                       const void *tape, size_t tape_bytes, void *scratch, size_t scratch_bytes,
                                       ec_stream_t stream);
 EC_API int ec_vit_train_layout(const ec_vit_weights *w, int n_img, int64_t *offsets, int n_offsets);
+
+/* ---- the gradient with respect to the input image (ABI 608) ----
+ * ec_vit_train_backward_over that also writes d_image fp32 [n_img, 3, R, R] = d loss / d (the fp32 image ec_patchify took).
+ * The chain runs down to the embedding whatever weight gradients are asked for; weight-, bias- and LoRA-gradient launches
+ * run only where `grads` / `lora` name an output, as in every other form, and a `grads` with no output at all (a frozen
+ * tower) is legal: no weight-gradient kernel is launched.  Below ln_pre:
+ *   d_pix[n S, 3 p^2] = d_tok . conv1.weight    one more dX product of ec_gemm: the 16-bit copy of d loss / d pre as A, and
+ *                                               conv1.weight TRANSPOSED as the [N, K] operand in hi + lo parts (W_lo), so the
+ *                                               weight's rounding does not enter; fp32 accumulation, fp32 out;
+ *   d_image = unpatchify(d_pix)                 the adjoint of ec_patchify's layout (ec_unpatchify).
+ * A patch row carries each pixel twice (its hi and lo column groups); the gradient with respect to the PIXEL is formed
+ * once, over conv1.weight's 3 p^2 true columns.  conv_wt / conv_wt_lo: 16-bit [ceil16(3 p^2), W], row c = column c of
+ * conv1.weight viewed [W, 3 p^2] ((channel, i, j) order), rows past 3 p^2 zero; conv_wt_lo NULL = the weight IS its 16-bit
+ * value.  scratch: ec_vit_train_backward_image_scratch_bytes (the _over scratch + d_pix); the tape is only read.  The
+ * 16-bit patch tensor itself has no gradient: 16 bits would underflow. */
+EC_API size_t ec_vit_train_backward_image_scratch_bytes(const ec_vit_weights *w, int n_img);
+EC_API int ec_vit_train_backward_image(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
+                                       int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
+                                       const void *conv_wt, const void *conv_wt_lo, float *d_image, const void *tape,
+                                       size_t tape_bytes, void *scratch, size_t scratch_bytes, ec_stream_t stream);
+/* The embedding's data gradient alone: d_tok16 16-bit [n_img S, W] (S = patches + 1 rows per image; the class rows are
+ * computed and skipped), d_pix fp32 [n_img S, ceil16(3 p^2)] scratch, d_image fp32 [n_img, 3, R, R] out.  Of `w` the
+ * geometry and dtype are read. */
+EC_API int ec_patch_embed_backward(const ec_vit_weights *w, const void *conv_wt, const void *conv_wt_lo, const void *d_tok16,
+                                   int n_img, float *d_pix, float *d_image, ec_stream_t stream);
+/* d_image[img][c][y][x] = rows[(img seq + row_off + (y / p) (R / p) + x / p) ld + (c p + y % p) p + x % p]: fp32 rows in
+ * conv1.weight's (c, i, j) column order, `seq` rows per image of which the patches start at row_off (1 skips a class row),
+ * back to fp32 [n_img, 3, R, R].  A permutation: every element written exactly once, no atomics, deterministic. */
+EC_API int ec_unpatchify(const float *rows, long ld, int seq, int row_off, int n_img, int n_px, int patch, float *d_image,
+                         ec_stream_t stream);
 
 /* fp32 [rows, cols] -> any of: hi = round16(w) [rows, cols]; lo = round16(w - hi); hi_t = hi transposed
  * [cols, rows] (NULL outputs are skipped), for a list of same-shape matrices in one launch (`items`: DEVICE array):

@@ -3,7 +3,7 @@ configs/ftclip/ft_text_fsclip_nin_params*.py -- ViT-L/14, N-ImageNet geometry, 1
 2 views per GPU, K = 1000, Adam, `lora='qkvo-16'` or every visual parameter).
 
     python tools/bench_ft.py [--arch ViT-L/14] [--samples 32] [--views 2] [--classes 1000] [--steps 5]
-                             [--modes lora,full,bias] [--dtype float16] [--graph | --autograd]
+                             [--modes lora,full,bias] [--dtype float16] [--graph | --autograd | --input-grad]
 
 Prints one JSON line per mode: ms per step, frames/s, the split forward / loss / backward / update, the
 algorithmic flops (3 x the forward's 2 M N K for a full step; LoRA skips the MLP's weight gradients) and the
@@ -16,7 +16,14 @@ touched.
 launches, `FTTrainer(graph=True)`, and the reference's loop on `FTCLIPClassifier(clip_dict=dict(..., autograd=True))`
 (`clf(data)`, `calc_train_loss`, `torch.amp.GradScaler`, `loss.backward()`, `torch.optim.Adam` over the two parameter
 groups of method.py:165-180): ms per step (the median of `--rounds` rounds of `--steps` steps) and the host's share of
-it (until the last step is queued)."""
+it (until the last step is queued).
+
+`--input-grad` prints one line: a FROZEN tower differentiated with respect to its input image (`CLIP.encode_image(image,
+differentiable=True)`, `eventclip_hip::vit_image_fwd` / `vit_image_bwd`: forward + backward to `image.grad`) beside the
+`--autograd` full step (every visual parameter trainable), interleaved round by round in one process on the same number
+of frames (`--samples` x `--views`, default 64): ms of forward + backward and of the backward alone for both (device
+time between events, medians over the rounds), and the kernels the frozen backward launched -- which must hold no
+weight-gradient, bias-gradient or LoRA launch (checked: the tool fails otherwise)."""
 import argparse
 import json
 import os
@@ -122,6 +129,94 @@ def autograd_rows(a):
         torch.cuda.empty_cache()
 
 
+# every weight-, bias- and LayerNorm-gradient ends in a partial-sum reduction, conv1's starts with transposed copies
+# (K-batched GEMMs are no sign of one: the dX products' last row tiles run in K-batches too, gemm_rows32)
+WEIGHT_GRAD_KERNELS = ('transpose_kernel', 'colsum_kernel + reduce_kernel')
+
+
+def input_grad_row(a):
+    """A frozen tower's forward + backward to the image beside the full autograd step, interleaved."""
+    import statistics
+    from eventclip_amd import _lib, clip as eclip
+    from eventclip_amd.clip_cls_ft import FTCLIPClassifier
+    dev = _lib.require_gpu()
+    B, T, K = a.samples, a.views, a.classes
+    n = B * T
+    frozen = eclip.build_random(a.arch, seed=0, dtype=a.dtype)
+    R = frozen.cfg['image_size']
+    torch.manual_seed(0)
+    image = (torch.randn(n, 3, R, R, device=dev) * 0.5).requires_grad_(True)
+    d_feats = torch.randn(n, frozen.cfg['embed_dim'], device=dev)
+    model = eclip.build_random(a.arch, seed=0, dtype=a.dtype)
+    cd = dict(clip_model=model, prompt='a point cloud image of a {}', class_names=[f'c{i}' for i in range(K)],
+              agg_func='mean', class_tokens=eclip.synthetic_tokens(K), only_conv1=False, only_bias=False, only_ln=False,
+              lora=-1, autograd=True)
+    clf = FTCLIPClassifier(adapter_dict=dict(adapter_type='text-identity', residual=0.95), clip_dict=cd,
+                           loss_dict=dict(use_logits_loss=True, use_probs_loss=False)).cuda().train()
+    named = [(k, p) for k, p in clf.named_parameters() if p.requires_grad]
+    opt = torch.optim.Adam([{'params': [p for k, p in named if 'model.visual' not in k], 'lr': 2e-5},
+                            {'params': [p for k, p in named if 'model.visual' in k], 'lr': 2e-5}])
+    scaler = torch.amp.GradScaler('cuda', init_scale=4096.0)
+    data = _batch(clf._operand_tower(), B, T, K, dev)
+    ev = lambda: torch.cuda.Event(enable_timing=True)      # noqa: E731
+
+    def frozen_pass():
+        image.grad = None
+        e0, e1, e2 = ev(), ev(), ev()
+        e0.record()
+        feats = frozen.encode_image(image, differentiable=True)
+        e1.record()
+        feats.backward(d_feats)
+        e2.record()
+        return e0, e1, e2
+
+    def full_step():
+        opt.zero_grad(set_to_none=True)
+        e0, e1, e2 = ev(), ev(), ev()
+        e0.record()
+        loss = clf.calc_train_loss(data, clf(data))['ce_loss']
+        e1.record()
+        scaler.scale(loss).backward()
+        e2.record()
+        scaler.step(opt)
+        scaler.update()
+        return e0, e1, e2
+    passes = {'frozen_image': frozen_pass, 'full_step': full_step}
+    for fn in passes.values():
+        for _ in range(max(a.warmup, 3)):
+            fn()
+    torch.cuda.synchronize()
+    both, bwd = {k: [] for k in passes}, {k: [] for k in passes}
+    for _ in range(a.rounds):
+        for k, fn in passes.items():
+            marks = [fn() for _ in range(a.steps)]
+            torch.cuda.synchronize()
+            both[k].append(statistics.median(e0.elapsed_time(e2) for e0, _, e2 in marks))
+            bwd[k].append(statistics.median(e1.elapsed_time(e2) for _, e1, e2 in marks))
+    # the structural condition: what the frozen backward launches
+    image.grad = None
+    feats = frozen.encode_image(image, differentiable=True)
+    torch.cuda.synchronize()
+    _lib.profile_begin()
+    feats.backward(d_feats)
+    torch.cuda.synchronize()
+    entries = [p for p in _lib.profile_end() if p['launches']]
+    prof = {p['name']: p['launches'] for p in entries}
+    # counted: the launches of the weight-gradient classes, and ec_sgemm's beyond the head's one (the LoRA products)
+    weight_grad = sum(prof.get(k, 0) for k in WEIGHT_GRAD_KERNELS) + max(prof.get('sgemm_kernel', 0) - 1, 0)
+    un = [p for p in entries if p['name'] == 'unpatchify_kernel']
+    print(json.dumps(dict(mode='input_grad', arch=a.arch, frames=n, dtype=a.dtype, steps=a.steps, rounds=a.rounds,
+                          fwd_bwd_ms={k: round(statistics.median(v), 2) for k, v in both.items()},
+                          bwd_ms={k: round(statistics.median(v), 2) for k, v in bwd.items()},
+                          bwd_ms_rounds={k: [round(x, 2) for x in v] for k, v in bwd.items()},
+                          full_step_trainable_tensors=len(named), frozen_backward_launches=prof,
+                          frozen_backward_kernel_ms={p['name']: round(p['total_ms'], 3) for p in entries},
+                          unpatchify_gb_per_s=round(un[0]['bytes'] / un[0]['total_ms'] / 1e6, 1) if un else None,
+                          frozen_weight_grad_launches=weight_grad)), flush=True)
+    assert weight_grad == 0, f'the frozen backward launched weight-gradient kernels: {prof}'
+    assert image.grad is not None and bool(torch.isfinite(image.grad).all())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--arch', default='ViT-L/14')
@@ -136,8 +231,12 @@ def main():
     ap.add_argument('--graph', action='store_true', help='replay the step from a hipGraph (recorded after 2 eager steps)')
     ap.add_argument('--autograd', action='store_true',
                     help='the step through torch autograd beside FTTrainer eager and graph=True, interleaved')
-    ap.add_argument('--rounds', type=int, default=3, help='--autograd: rounds of --steps steps per path')
+    ap.add_argument('--input-grad', action='store_true',
+                    help='a frozen tower forward + backward to the image beside the --autograd full step, interleaved')
+    ap.add_argument('--rounds', type=int, default=3, help='--autograd / --input-grad: rounds of --steps steps per path')
     a = ap.parse_args()
+    if a.input_grad:
+        return input_grad_row(a)
     if a.autograd:
         return autograd_rows(a)
     from eventclip_amd import _lib, clip as eclip, ft
