@@ -13,7 +13,9 @@
 //             -> through the row normalisation: dT = (dU - u (u . dU)) / |t|;
 //   update    torch.optim.Adam (`optimizer = 'Adam'` in the configs).
 // The encoder is frozen, so its features are an input (cached once per epoch); everything here is a
-// few MFLOP per sample and latency / launch bound: five small kernels on one stream.
+// few MFLOP per sample and latency / launch bound: six small launches on one stream (head_launches).
+// The same head serves 'text-trans' behind the adapter (ec_fs_trans_loss_grad) and fine-tuning, where the features'
+// own gradient goes back into the vision tower (ec_ft_loss_grad, models/clip_cls_ft.py:196-256).
 #include "common.h"
 #include "mfma.h"
 
@@ -506,12 +508,15 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float *f, long n, f
 // row_idx (optional): mixed / dmixed are compact rows, view r lives in row row_idx[r]; only the rows that a valid view
 // names are written (the caller clears dmixed first).  valid == nullptr: valid iff row_idx names one of the n_rows rows.
 // normalize == 0: the forward only gathered and masked, dm = valid ? dfn * scale : 0.
+// scalars (optional): the device step_scalars array, scalars[EC_STEP_GRAD_SCALE] replaces scale.
 __global__ __launch_bounds__(256) void normalize_bwd_kernel(const float *mixed, const float *fn, const float *dfn,
                                                             const unsigned char *valid, const int *row_idx, int n_rows,
-                                                            int normalize, int R, int D, float scale, float *dmixed)
+                                                            int normalize, int R, int D, float scale,
+                                                            const float *scalars, float *dmixed)
 {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (r >= R) return;
+    if (scalars) scale = scalars[EC_STEP_GRAD_SCALE];
     const int ri = row_idx ? row_idx[r] : r;
     const bool ok = valid ? valid[r] != 0 : (ri >= 0 && ri < n_rows);
     if (row_idx && !ok) return;
@@ -592,14 +597,66 @@ __global__ __launch_bounds__(TR_THREADS) void classify_dz_kernel(const float *fu
 
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
+// Hands out the fp32 buffers of a workspace in call order, each 256-byte aligned; on a null base it only counts bytes.
+struct Carve {
+    unsigned char *p;
+    size_t off;
+    float *f(size_t n)
+    {
+        float *r = p ? reinterpret_cast<float *>(p + off) : nullptr;
+        off += align256(n * 4);
+        return r;
+    }
+};
+
+// The loss head's buffers: carve_head puts them at the front of every fused step's workspace.
+struct HeadBufs {
+    float *Fn, *dL, *u, *dU, *inv_norm, *loss_b;
+};
+void carve_head(Carve &c, int B, int T, int D, int K, HeadBufs &h)
+{
+    const size_t R = (size_t)B * T;
+    h.Fn = c.f(R * D), h.dL = c.f(R * K), h.u = c.f((size_t)K * D), h.dU = c.f((size_t)K * D);
+    h.inv_norm = c.f(K), h.loss_b = c.f(B);
+}
+
+// The loss head on feats [B * T, D]: loss, grad_text, agg_logits (optional); h.Fn (normalised views), h.dL (per-view
+// logit gradients) and h.u (normalised text) stay behind for the caller's own backward.
+// row_idx (optional, int32 [B, T]): feats holds only the valid views, row_idx[b, v] = the row of view (b, v)
+int head_launches(hipStream_t s, const char *who, const float *feats, const int *row_idx, const unsigned char *valid,
+                  const int *labels, const float *text_param, int B, int T, int D, int K, float logit_scale, int agg,
+                  int use_probs_loss, const HeadBufs &h, float *loss, float *grad_text, float *agg_logits)
+{
+    const size_t lds = ((size_t)T * K + TR_WAVES + 3 * (size_t)T) * 4;
+    EC_REQUIRE(lds <= 160 * 1024, "%s: T * K = %d floats exceed the LDS", who, T * K);
+    if (lds > 64 * 1024)
+        if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(fs_loss_grad_kernel), 160 * 1024)) return rc;
+    const int R = B * T;
+    hipLaunchKernelGGL(text_norm_kernel, dim3(K), dim3(64), 0, s, text_param, D, h.u, h.inv_norm);
+    hipLaunchKernelGGL(fs_normalize_kernel, dim3((unsigned)((R + TR_WAVES - 1) / TR_WAVES)), dim3(TR_THREADS), 0, s, feats, valid,
+                       row_idx, 0, 1, R, D, h.Fn);
+    // full_logits [R, K] = logit_scale * Fn u^T, into the dL rows
+    hipLaunchKernelGGL(sgemm_kernel<false>, dim3((K + 63) / 64, (unsigned)((R + 63) / 64)), dim3(256), 0, s, h.Fn, (long)D, 1L, h.u,
+                       1L, (long)D, R, K, D, logit_scale, 0.f, static_cast<const float *>(nullptr), h.dL, (long)K);
+    hipLaunchKernelGGL(fs_loss_grad_kernel, dim3(B), dim3(TR_THREADS), lds, s, valid, labels, B, T, K, agg, use_probs_loss, h.dL,
+                       h.loss_b, agg_logits);
+    // dU[K, D] = logit_scale * dL^T Fn: the reduction runs over the R view rows
+    hipLaunchKernelGGL(sgemm_kernel<false>, dim3((D + 63) / 64, (K + 63) / 64), dim3(256), 0, s, h.dL, 1L, (long)K, h.Fn, (long)D,
+                       1L, K, D, R, logit_scale, 0.f, static_cast<const float *>(nullptr), h.dU, (long)D);
+    hipLaunchKernelGGL(text_grad_finish_kernel, dim3(K), dim3(64), 0, s, h.u, h.dU, h.inv_norm, D, h.loss_b, B,
+                       grad_text, loss);
+    return EC_OK;
+}
+
 }  // namespace
 
 extern "C" EC_API size_t ec_fs_text_train_workspace_bytes(int B, int T, int D, int K)
 {
     if (B <= 0 || T <= 0 || D <= 0 || K <= 0) return 0;
-    const size_t R = (size_t)B * T;
-    return align256(R * D * 4) + align256(R * K * 4) + 2 * align256((size_t)K * D * 4) + align256((size_t)K * 4) +
-           align256((size_t)B * 4);
+    Carve c{nullptr, 0};
+    HeadBufs h;
+    carve_head(c, B, T, D, K, h);
+    return c.off;
 }
 
 extern "C" EC_API int ec_fs_text_loss_grad(const float *img_feats, const uint8_t *valid, const int32_t *labels,
@@ -608,57 +665,47 @@ extern "C" EC_API int ec_fs_text_loss_grad(const float *img_feats, const uint8_t
                                            float *grad_text, float *agg_logits, void *workspace,
                                            size_t workspace_bytes, ec_stream_t stream)
 {
-    return ec::fs_text_loss_grad(img_feats, nullptr, valid, labels, text_param, B, T, D, K, logit_scale, agg,
-                                 use_probs_loss, loss, grad_text, agg_logits, workspace, workspace_bytes, stream);
-}
-
-// row_idx (optional, int32 [B, T]): img_feats holds only the valid views, row_idx[b, v] = the row of view (b, v)
-int ec::fs_text_loss_grad(const float *img_feats, const int32_t *row_idx, const uint8_t *valid, const int32_t *labels,
-                          const float *text_param, int B, int T, int D, int K, float logit_scale, int agg,
-                          int use_probs_loss, float *loss, float *grad_text, float *agg_logits, void *workspace,
-                          size_t workspace_bytes, ec_stream_t stream)
-{
     EC_REQUIRE(B > 0 && T > 0 && D > 0 && K > 0, "ec_fs_text_loss_grad: bad shape");
     EC_REQUIRE(agg == EC_AGG_SUM || agg == EC_AGG_MEAN || agg == EC_AGG_MAX, "ec_fs_text_loss_grad: unknown agg %d", agg);
     EC_REQUIRE(img_feats && valid && labels && text_param && loss && grad_text && workspace,
                "ec_fs_text_loss_grad: null buffer");
-    EC_REQUIRE(workspace_bytes >= ec_fs_text_train_workspace_bytes(B, T, D, K),
-               "ec_fs_text_loss_grad: workspace too small");
-    const size_t lds = ((size_t)T * K + TR_WAVES + 3 * (size_t)T) * 4;
-    EC_REQUIRE(lds <= 160 * 1024, "ec_fs_text_loss_grad: T * K = %d floats exceed the LDS", T * K);
-    unsigned char *w = static_cast<unsigned char *>(workspace);
-    const size_t R = (size_t)B * T;
-    float *Fn = (float *)w;
-    w += align256(R * D * 4);
-    float *dL = (float *)w;
-    w += align256(R * K * 4);
-    float *u = (float *)w;
-    w += align256((size_t)K * D * 4);
-    float *dU = (float *)w;
-    w += align256((size_t)K * D * 4);
-    float *inv_norm = (float *)w;
-    w += align256((size_t)K * 4);
-    float *loss_b = (float *)w;
+    Carve c{static_cast<unsigned char *>(workspace), 0};
+    HeadBufs h;
+    carve_head(c, B, T, D, K, h);
+    EC_REQUIRE(workspace_bytes >= c.off, "ec_fs_text_loss_grad: workspace too small");
+    if (int rc = head_launches(static_cast<hipStream_t>(stream), "ec_fs_text_loss_grad", img_feats, nullptr, valid, labels,
+                               text_param, B, T, D, K, logit_scale, agg, use_probs_loss, h, loss, grad_text, agg_logits))
+        return rc;
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
+// The fine-tuning head (models/clip_cls_ft.py:196-256): ec_fs_text_loss_grad on features that may be compact over the
+// valid views, plus grad_img = grad_scale * d loss / d img_feats in the features' own layout.  dFn lives behind the
+// head's buffers; with a null grad_text the unused text gradient is written there first.
+extern "C" EC_API int ec_ft_loss_grad(const float *img_feats, const int32_t *row_idx, const uint8_t *valid,
+                                      const int32_t *labels, const float *text_param, int B, int T, int D, int K,
+                                      float logit_scale, int agg, int use_probs_loss, float grad_scale,
+                                      const float *step_scalars, float *loss, float *grad_text, float *grad_img,
+                                      float *agg_logits, void *workspace, size_t workspace_bytes, ec_stream_t stream)
+{
+    EC_REQUIRE(B > 0 && T > 0 && D > 0 && K > 0, "ec_ft_loss_grad: bad shape");
+    EC_REQUIRE(agg == EC_AGG_SUM || agg == EC_AGG_MEAN || agg == EC_AGG_MAX, "ec_ft_loss_grad: unknown agg %d", agg);
+    EC_REQUIRE(img_feats && valid && labels && text_param && loss && grad_img && workspace, "ec_ft_loss_grad: null buffer");
+    Carve c{static_cast<unsigned char *>(workspace), 0};
+    HeadBufs h;
+    carve_head(c, B, T, D, K, h);
+    const size_t R = (size_t)B * T, n_dfn = (R > (size_t)K ? R : (size_t)K) * D;
+    EC_REQUIRE(workspace_bytes >= c.off + n_dfn * 4, "ec_ft_loss_grad: workspace too small");
+    float *dfn = c.f(n_dfn);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    static size_t attr_lds = 0;
-    if (lds > 64 * 1024 && lds > attr_lds) {
-        EC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fs_loss_grad_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
-    hipLaunchKernelGGL(text_norm_kernel, dim3(K), dim3(64), 0, s, text_param, D, u, inv_norm);
-    hipLaunchKernelGGL(fs_normalize_kernel, dim3((unsigned)((R + TR_WAVES - 1) / TR_WAVES)), dim3(TR_THREADS), 0, s, img_feats, valid,
-                       row_idx, 0, 1, (int)R, D, Fn);
-    // full_logits [R, K] = logit_scale * Fn u^T, into the dL rows
-    hipLaunchKernelGGL(sgemm_kernel<false>, dim3((K + 63) / 64, (unsigned)((R + 63) / 64)), dim3(256), 0, s, Fn, (long)D, 1L, u, 1L,
-                       (long)D, (int)R, K, D, logit_scale, 0.f, static_cast<const float *>(nullptr), dL, (long)K);
-    hipLaunchKernelGGL(fs_loss_grad_kernel, dim3(B), dim3(TR_THREADS), lds, s, valid, labels, B, T, K, agg, use_probs_loss, dL,
-                       loss_b, agg_logits);
-    // dU[K, D] = logit_scale * dL^T Fn: the reduction runs over the R view rows
-    hipLaunchKernelGGL(sgemm_kernel<false>, dim3((D + 63) / 64, (K + 63) / 64), dim3(256), 0, s, dL, 1L, (long)K, Fn, (long)D, 1L,
-                       K, D, (int)R, logit_scale, 0.f, static_cast<const float *>(nullptr), dU, (long)D);
-    hipLaunchKernelGGL(text_grad_finish_kernel, dim3(K), dim3(64), 0, s, u, dU, inv_norm, D, loss_b, B,
-                       grad_text, loss);
+    if (int rc = head_launches(s, "ec_ft_loss_grad", img_feats, row_idx, valid, labels, text_param, B, T, D, K, logit_scale,
+                               agg, use_probs_loss, h, loss, grad_text ? grad_text : dfn, agg_logits))
+        return rc;
+    // dFn[R, D] = logit_scale * dL[R, K] . u[K, D]
+    if (int rc = ec_sgemm(h.dL, K, 1, h.u, D, 1, (int)R, D, K, logit_scale, 0.f, dfn, D, stream)) return rc;
+    hipLaunchKernelGGL(normalize_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, img_feats, h.Fn, dfn, valid,
+                       row_idx, 0, 1, (int)R, D, grad_scale, step_scalars, grad_img);
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }
@@ -693,17 +740,6 @@ extern "C" EC_API int ec_adam_step(float *param, const float *grad, float *exp_a
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-struct Carve {
-    unsigned char *p;
-    size_t off;
-    float *f(size_t n)
-    {
-        float *r = p ? reinterpret_cast<float *>(p + off) : nullptr;
-        off += align256(n * 4);
-        return r;
-    }
-};
-
 struct LayerBufs {
     float *xhat1, *rstd1, *a, *qkv, *P, *o, *h1, *xhat2, *rstd2, *bn, *f;
 };
@@ -723,8 +759,7 @@ struct TransBufs {
     float *mixed, *dfn;
     AdapterTape tape;
     AdapterScratch bw;
-    // shared with the text-identity path
-    float *Fn, *dL, *u, *dU, *inv_norm, *loss_b;
+    HeadBufs head;
 };
 
 void carve_tape(Carve &c, int B, int T, int D, int d, int ffn, int heads, int layers, AdapterTape &t)
@@ -748,8 +783,7 @@ void carve_scratch(Carve &c, int B, int T, int D, int d, int ffn, AdapterScratch
 size_t carve_trans(Carve &c, int B, int T, int D, int K, int d, int ffn, int heads, int layers, TransBufs &t)
 {
     const size_t R = (size_t)B * T;
-    t.Fn = c.f(R * D), t.dL = c.f(R * K), t.u = c.f((size_t)K * D), t.dU = c.f((size_t)K * D);
-    t.inv_norm = c.f(K), t.loss_b = c.f(B);
+    carve_head(c, B, T, D, K, t.head);
     t.mixed = c.f(R * D), t.dfn = c.f(R * D);
     carve_tape(c, B, T, D, d, ffn, heads, layers, t.tape);
     carve_scratch(c, B, T, D, d, ffn, t.bw);
@@ -808,6 +842,57 @@ bool adapter_geometry_ok(const ec_adapter_train_params *w, int T)
 // ReLU, linear1, d a = d f W1 + d s2, norm1, out_proj, attention, and in_proj_weight's gradient against the layer's INPUT
 // (h0, or the previous layer's bn), d h = d qkv Wqkv + d s1.
 
+// What every launch of one adapter pass shares.
+struct AdapterRun {
+    hipStream_t s;
+    int B, T, R, d, ffn, heads;
+    float dp;
+    unsigned long long seed;
+};
+
+void copy(hipStream_t s, const float *x, long n, float *out)
+{
+    hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for(n)), dim3(256), 0, s, x, (const float *)nullptr, n, 1.f, 0.f, out);
+}
+// out = base + dropout(x) at dropout site `site` (base may be null)
+void dropout_add(const AdapterRun &a, unsigned site, const float *base, const float *x, long n, float *out)
+{
+    hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for(n)), dim3(256), 0, a.s, base, x, n, a.dp, a.seed, site, out);
+}
+void layer_norm_fwd(const AdapterRun &a, const float *x, const float *g, const float *b, float *y, float *xhat, float *rstd)
+{
+    hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((a.R + 3) / 4)), dim3(256), 0, a.s, x, g, b, a.R, a.d, y, xhat, rstd);
+}
+// dst = base + dropout(linear(x)): through ftmp with dropout, else a copy of base and the linear accumulating onto it
+void residual_linear_fwd(const AdapterRun &a, unsigned site, const float *x, const float *W, const float *bias, int in,
+                         const float *base, float *ftmp, float *dst)
+{
+    if (a.dp > 0.f) {
+        linear_fwd(a.s, x, W, bias, a.R, in, a.d, ftmp);
+        dropout_add(a, site, base, ftmp, (long)a.R * a.d, dst);
+    } else {
+        copy(a.s, base, (long)a.R * a.d, dst);
+        linear_fwd(a.s, x, W, bias, a.R, in, a.d, dst, 1.f);
+    }
+}
+// b.h1 = base + dropout1(out_proj(attn(in_proj(x))))
+void attn_branch_fwd(const AdapterRun &a, int l, const ec_adapter_train_layer &p, const LayerBufs &b,
+                     const unsigned char *valid, const float *x, const float *base, float *ftmp)
+{
+    linear_fwd(a.s, x, p.qkv_w, p.qkv_b, a.R, a.d, 3 * a.d, b.qkv);
+    hipLaunchKernelGGL(adapter_attn_fwd_kernel, dim3(a.B * a.heads), dim3(64), 0, a.s, b.qkv, valid, a.T, a.d, a.heads, b.P,
+                       b.o, a.dp, a.seed, (unsigned)(4 * l));
+    residual_linear_fwd(a, 4 * l + 1, b.o, p.o_w, p.o_b, a.d, base, ftmp, b.h1);
+}
+// dst = base + dropout2(linear2(dropout(relu(linear1(x))))), the dropped post-activation kept in b.f
+void mlp_branch_fwd(const AdapterRun &a, int l, const ec_adapter_train_layer &p, const LayerBufs &b, const float *x,
+                    const float *base, float *ftmp, float *dst)
+{
+    linear_fwd(a.s, x, p.w1, p.b1, a.R, a.d, a.ffn, b.f, 0.f, true);
+    if (a.dp > 0.f) dropout_add(a, 4 * l + 2, nullptr, b.f, (long)a.R * a.ffn, b.f);
+    residual_linear_fwd(a, 4 * l + 3, b.f, p.w2, p.b2, a.ffn, base, ftmp, dst);
+}
+
 // The adapter's forward (adapter.py:82-105) over all R = B * T view rows, saving what the backward reads:
 // mixed [R, D] = r img_feats + (1 - r) out_proj(encoder(in_proj(img_feats))).  The one launch sequence behind
 // ec_fs_trans_loss_grad and ec_adapter_train_forward.
@@ -815,88 +900,77 @@ void adapter_train_fwd_launches(hipStream_t s, const float *img_feats, const uns
                                 const ec_adapter_train_params *w, float dp, unsigned long long seed, AdapterTape &t,
                                 float *mixed)
 {
-    const int D = w->in_dim, d = w->d_model, ffn = w->ffn_dim, heads = w->heads, layers = w->layers, R = B * T;
+    const AdapterRun a{s, B, T, B * T, w->d_model, w->ffn_dim, w->heads, dp, seed};
+    const int D = w->in_dim, d = a.d, R = a.R;
     const float r = w->residual;
-    const unsigned ln_grid = (unsigned)((R + 3) / 4);
     linear_fwd(s, img_feats, w->in_w, w->in_b, R, D, d, t.h0);
     const float *h = t.h0;
-    for (int l = 0; l < layers && w->post_norm; l++) {
-        // post-LN: s1 = h + dropout1(out_proj(attn(in_proj(h)))), a = norm1(s1),
-        //          s2 = a + dropout2(linear2(dropout(relu(linear1(a))))), bn = norm2(s2) -- the next layer's input
+    for (int l = 0; l < w->layers; l++) {
         const ec_adapter_train_layer &p = w->blocks[l];
-        LayerBufs &b = t.L[l];
-        linear_fwd(s, h, p.qkv_w, p.qkv_b, R, d, 3 * d, b.qkv);
-        hipLaunchKernelGGL(adapter_attn_fwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, valid, T, d, heads, b.P, b.o,
-                           dp, seed, (unsigned)(4 * l));
-        if (dp > 0.f) {
-            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, t.ftmp);
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, t.ftmp,
-                               (long)R * d, dp, seed, (unsigned)(4 * l + 1), b.h1);
+        const LayerBufs &b = t.L[l];
+        if (w->post_norm) {
+            attn_branch_fwd(a, l, p, b, valid, h, h, t.ftmp);
+            layer_norm_fwd(a, b.h1, p.ln1_g, p.ln1_b, b.a, b.xhat1, b.rstd1);
+            mlp_branch_fwd(a, l, p, b, b.a, b.a, t.ftmp, t.hfin);      // s2 lives in hfin until norm2 has read it
+            layer_norm_fwd(a, t.hfin, p.ln2_g, p.ln2_b, b.bn, b.xhat2, b.rstd2);
+            h = b.bn;
+            if (l == w->layers - 1) {   // out_proj (and its backward) read the encoder's output from hfin, as pre-LN
+                copy(s, b.bn, (long)R * d, t.hfin);
+                h = t.hfin;
+            }
         } else {
-            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, (const float *)nullptr,
-                               (long)R * d, 1.f, 0.f, b.h1);
-            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, b.h1, 1.f);
+            layer_norm_fwd(a, h, p.ln1_g, p.ln1_b, b.a, b.xhat1, b.rstd1);
+            attn_branch_fwd(a, l, p, b, valid, b.a, h, t.ftmp);
+            layer_norm_fwd(a, b.h1, p.ln2_g, p.ln2_b, b.bn, b.xhat2, b.rstd2);
+            mlp_branch_fwd(a, l, p, b, b.bn, b.h1, t.ftmp, t.hfin);
+            h = t.hfin;      // this layer's input is dead (ln_1 consumed it, h1 took its copy): reuse its slot
         }
-        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, b.h1, p.ln1_g, p.ln1_b, R, d, b.a, b.xhat1,
-                           b.rstd1);
-        linear_fwd(s, b.a, p.w1, p.b1, R, d, ffn, b.f, 0.f, true);
-        if (dp > 0.f)
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s,
-                               (const float *)nullptr, b.f, (long)R * ffn, dp, seed, (unsigned)(4 * l + 2), b.f);
-        if (dp > 0.f) {                 // s2 lives in hfin until norm2 has read it: it is not kept
-            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.ftmp);
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.a, t.ftmp,
-                               (long)R * d, dp, seed, (unsigned)(4 * l + 3), t.hfin);
-        } else {
-            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.a, (const float *)nullptr,
-                               (long)R * d, 1.f, 0.f, t.hfin);
-            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.hfin, 1.f);
-        }
-        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, t.hfin, p.ln2_g, p.ln2_b, R, d, b.bn, b.xhat2,
-                           b.rstd2);
-        h = b.bn;
-        if (l == layers - 1) {          // out_proj (and its backward) read the encoder's output from hfin, as pre-LN
-            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.bn, (const float *)nullptr,
-                               (long)R * d, 1.f, 0.f, t.hfin);
-            h = t.hfin;
-        }
-    }
-    for (int l = 0; l < layers && !w->post_norm; l++) {
-        const ec_adapter_train_layer &p = w->blocks[l];
-        LayerBufs &b = t.L[l];
-        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, h, p.ln1_g, p.ln1_b, R, d, b.a, b.xhat1, b.rstd1);
-        linear_fwd(s, b.a, p.qkv_w, p.qkv_b, R, d, 3 * d, b.qkv);
-        hipLaunchKernelGGL(adapter_attn_fwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, valid, T, d, heads, b.P, b.o,
-                           dp, seed, (unsigned)(4 * l));
-        if (dp > 0.f) {
-            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, t.ftmp);
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, t.ftmp,
-                               (long)R * d, dp, seed, (unsigned)(4 * l + 1), b.h1);   // h1 = h + dropout1(out_proj(o))
-        } else {
-            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, h, (const float *)nullptr,
-                               (long)R * d, 1.f, 0.f, b.h1);
-            linear_fwd(s, b.o, p.o_w, p.o_b, R, d, d, b.h1, 1.f);                   // h1 = h + out_proj(o)
-        }
-        hipLaunchKernelGGL(ln_fwd_kernel, dim3(ln_grid), dim3(256), 0, s, b.h1, p.ln2_g, p.ln2_b, R, d, b.bn, b.xhat2,
-                           b.rstd2);
-        linear_fwd(s, b.bn, p.w1, p.b1, R, d, ffn, b.f, 0.f, true);                   // relu(linear1)
-        if (dp > 0.f)
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s,
-                               (const float *)nullptr, b.f, (long)R * ffn, dp, seed, (unsigned)(4 * l + 2), b.f);
-        if (dp > 0.f) {
-            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.ftmp);
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.h1, t.ftmp,
-                               (long)R * d, dp, seed, (unsigned)(4 * l + 3), t.hfin);  // h = h1 + dropout2(linear2(f))
-        } else {
-            hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, b.h1, (const float *)nullptr,
-                               (long)R * d, 1.f, 0.f, t.hfin);
-            linear_fwd(s, b.f, p.w2, p.b2, R, ffn, d, t.hfin, 1.f);                   // h = h1 + linear2(f)
-        }
-        h = t.hfin;      // this layer's input is dead (ln_1 consumed it, h1 took its copy): reuse its slot
     }
     linear_fwd(s, h, w->out_w, w->out_b, R, d, D, t.y);
     hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * D)), dim3(256), 0, s, img_feats, t.y, (long)R * D, r,
                        1.f - r, mixed);                                             // Adapter.residual_add
+}
+
+// The gradient below a residual branch's dropout: dsum itself without dropout, else masked and rescaled into tmp.
+const float *dropout_bwd(const AdapterRun &a, unsigned site, const float *dsum, float *tmp)
+{
+    if (a.dp <= 0.f) return dsum;
+    dropout_add(a, site, nullptr, dsum, (long)a.R * a.d, tmp);
+    return tmp;
+}
+// Backward of mlp_branch_fwd's branch from dsum = d loss / d its residual sum: linear2, ReLU, linear1 with x the
+// tape slot linear1 read; dx = dx_beta * dx + d f W1.
+void mlp_branch_bwd(const AdapterRun &a, int l, const ec_adapter_train_layer &p, const ec_adapter_train_layer &q,
+                    const LayerBufs &b, const AdapterScratch &x, const float *dsum, const float *lin1_in, float *dx,
+                    float dx_beta)
+{
+    const float *dlin2 = dropout_bwd(a, 4 * l + 3, dsum, x.dtmp_d);
+    linear_bwd(a.s, b.f, p.w2, dlin2, a.R, a.ffn, a.d, x.df, 0.f, q.w2, q.b2);
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(blocks_for((long)a.R * a.ffn)), dim3(256), 0, a.s, b.f, (long)a.R * a.ffn,
+                       1.f / (1.f - a.dp), x.df);
+    linear_bwd(a.s, lin1_in, p.w1, x.df, a.R, a.d, a.ffn, dx, dx_beta, q.w1, q.b1);
+}
+// Backward of attn_branch_fwd's branch from dsum = d loss / d its residual sum (its dropout undone into `undo`):
+// out_proj, attention, in_proj with qkv_in the slot in_proj read; dx = dx_beta * dx + d qkv Wqkv.
+void attn_branch_bwd(const AdapterRun &a, int l, const ec_adapter_train_layer &p, const ec_adapter_train_layer &q,
+                     const LayerBufs &b, const AdapterScratch &x, const float *dsum, float *undo, const float *qkv_in,
+                     float *dx, float dx_beta)
+{
+    const float *dlin_o = dropout_bwd(a, 4 * l + 1, dsum, undo);
+    linear_bwd(a.s, b.o, p.o_w, dlin_o, a.R, a.d, a.d, x.dtmp_d, 0.f, q.o_w, q.o_b);
+    hipLaunchKernelGGL(adapter_attn_bwd_kernel, dim3(a.B * a.heads), dim3(64), 0, a.s, b.qkv, b.P, x.dtmp_d, a.T, a.d,
+                       a.heads, x.dqkv, a.dp, a.seed, (unsigned)(4 * l));
+    linear_bwd(a.s, qkv_in, p.qkv_w, x.dqkv, a.R, a.d, 3 * a.d, dx, dx_beta, q.qkv_w, q.qkv_b);
+}
+// LayerNorm's backward from dy: its parameter gradients, then dx = (skip, the gradient of a residual around the
+// norm, copied in first) + the norm's input gradient.
+void layer_norm_bwd(const AdapterRun &a, const float *dy, const float *xhat, const float *rstd, const float *g, float *dg,
+                    float *db, const float *skip, float *dx)
+{
+    ln_param_bwd(a.s, dy, xhat, a.R, a.d, dg, db);
+    if (skip) copy(a.s, skip, (long)a.R * a.d, dx);
+    hipLaunchKernelGGL(ln_bwd_kernel, dim3((unsigned)((a.R + 3) / 4)), dim3(256), 0, a.s, dy, xhat, rstd, g, a.R, a.d, dx,
+                       skip ? 1 : 0);
 }
 
 // The adapter's backward from x.dy = d loss / d out_proj's output: every non-null gradient of g, and (d_img non-null)
@@ -906,80 +980,28 @@ void adapter_train_bwd_launches(hipStream_t s, const float *img_feats, int B, in
                                 const ec_adapter_train_params *g, float dp, unsigned long long seed,
                                 const AdapterTape &t, const AdapterScratch &x, float *d_img, float d_img_beta)
 {
-    const int D = w->in_dim, d = w->d_model, ffn = w->ffn_dim, heads = w->heads, layers = w->layers, R = B * T;
-    const unsigned ln_grid = (unsigned)((R + 3) / 4);
-    const float keep_scale = 1.f / (1.f - dp);
+    const AdapterRun a{s, B, T, B * T, w->d_model, w->ffn_dim, w->heads, dp, seed};
+    const int D = w->in_dim, d = a.d, R = a.R;
     linear_bwd(s, t.hfin, w->out_w, x.dy, R, d, D, x.dh, 0.f, g->out_w, g->out_b);
-    for (int l = layers - 1; l >= 0 && w->post_norm; l--) {
-        // post-LN; x.dh = d loss / d bn (the layer's output) on entry, d loss / d the layer's input on exit
+    for (int l = w->layers - 1; l >= 0; l--) {
+        // x.dh = d loss / d the layer's output on entry, d loss / d the layer's input on exit
         const ec_adapter_train_layer &p = w->blocks[l];
         const ec_adapter_train_layer &q = g->blocks[l];
         const LayerBufs &b = t.L[l];
-        const float *hin = l ? t.L[l - 1].bn : t.h0;
-        // bn = norm2(s2): nothing skips norm2, so its input gradient is d s2 alone
-        ln_param_bwd(s, x.dh, b.xhat2, R, d, q.ln2_g, q.ln2_b);
-        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, x.dh, b.xhat2, b.rstd2, p.ln2_g, R, d, x.dh1, 0);
-        // s2 = a + dropout2(linear2(dropout(relu(linear1(a)))))
-        const float *dlin2 = x.dh1;
-        if (dp > 0.f) {
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
-                               (const float *)nullptr, x.dh1, (long)R * d, dp, seed, (unsigned)(4 * l + 3), x.dtmp_d);
-            dlin2 = x.dtmp_d;
+        if (w->post_norm) {
+            // bn = norm2(s2): nothing skips norm2, so its input gradient is d s2 alone
+            layer_norm_bwd(a, x.dh, b.xhat2, b.rstd2, p.ln2_g, q.ln2_g, q.ln2_b, nullptr, x.dh1);
+            mlp_branch_bwd(a, l, p, q, b, x, x.dh1, b.a, x.dh1, 1.f);                  // d a = d f W1 + d s2
+            layer_norm_bwd(a, x.dh1, b.xhat1, b.rstd1, p.ln1_g, q.ln1_g, q.ln1_b, nullptr, x.dh);
+            // x.dh = d s1, the residual's share of d h; d a is consumed, dh1 takes the undone dropout
+            attn_branch_bwd(a, l, p, q, b, x, x.dh, x.dh1, l ? t.L[l - 1].bn : t.h0, x.dh, 1.f);   // d h = d qkv Wqkv + d s1
+        } else {
+            mlp_branch_bwd(a, l, p, q, b, x, x.dh, b.bn, x.dtmp_d, 0.f);
+            layer_norm_bwd(a, x.dtmp_d, b.xhat2, b.rstd2, p.ln2_g, q.ln2_g, q.ln2_b, x.dh, x.dh1);
+            // dh takes the undone dropout: it is rebuilt from dh1 below
+            attn_branch_bwd(a, l, p, q, b, x, x.dh1, x.dh, b.a, x.dtmp_d, 0.f);
+            layer_norm_bwd(a, x.dtmp_d, b.xhat1, b.rstd1, p.ln1_g, q.ln1_g, q.ln1_b, x.dh1, x.dh);
         }
-        linear_bwd(s, b.f, p.w2, dlin2, R, ffn, d, x.df, 0.f, q.w2, q.b2);
-        hipLaunchKernelGGL(relu_bwd_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s, b.f, (long)R * ffn,
-                           keep_scale, x.df);
-        linear_bwd(s, b.a, p.w1, x.df, R, d, ffn, x.dh1, 1.f, q.w1, q.b1);          // d a = d f W1 + d s2
-        // a = norm1(s1)
-        ln_param_bwd(s, x.dh1, b.xhat1, R, d, q.ln1_g, q.ln1_b);
-        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, x.dh1, b.xhat1, b.rstd1, p.ln1_g, R, d, x.dh, 0);
-        // s1 = h + dropout1(out_proj(attn(in_proj(h)))); x.dh = d s1, the residual's share of d h
-        const float *dlin_o = x.dh;
-        if (dp > 0.f) {
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
-                               (const float *)nullptr, x.dh, (long)R * d, dp, seed, (unsigned)(4 * l + 1), x.dh1);
-            dlin_o = x.dh1;       // d a is consumed
-        }
-        linear_bwd(s, b.o, p.o_w, dlin_o, R, d, d, x.dtmp_d, 0.f, q.o_w, q.o_b);
-        hipLaunchKernelGGL(adapter_attn_bwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, b.P, x.dtmp_d, T, d, heads,
-                           x.dqkv, dp, seed, (unsigned)(4 * l));
-        linear_bwd(s, hin, p.qkv_w, x.dqkv, R, d, 3 * d, x.dh, 1.f, q.qkv_w, q.qkv_b);   // d h = d qkv Wqkv + d s1
-    }
-    for (int l = layers - 1; l >= 0 && !w->post_norm; l--) {
-        const ec_adapter_train_layer &p = w->blocks[l];
-        const ec_adapter_train_layer &q = g->blocks[l];
-        const LayerBufs &b = t.L[l];
-        // h = h1 + dropout2(linear2(dropout(relu(linear1(ln2(h1))))))
-        const float *dlin2 = x.dh;
-        if (dp > 0.f) {
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
-                               (const float *)nullptr, x.dh, (long)R * d, dp, seed, (unsigned)(4 * l + 3), x.dtmp_d);
-            dlin2 = x.dtmp_d;
-        }
-        linear_bwd(s, b.f, p.w2, dlin2, R, ffn, d, x.df, 0.f, q.w2, q.b2);
-        hipLaunchKernelGGL(relu_bwd_kernel, dim3(blocks_for((long)R * ffn)), dim3(256), 0, s, b.f, (long)R * ffn,
-                           keep_scale, x.df);
-        linear_bwd(s, b.bn, p.w1, x.df, R, d, ffn, x.dtmp_d, 0.f, q.w1, q.b1);
-        ln_param_bwd(s, x.dtmp_d, b.xhat2, R, d, q.ln2_g, q.ln2_b);
-        hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, x.dh, (const float *)nullptr,
-                           (long)R * d, 1.f, 0.f, x.dh1);
-        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, x.dtmp_d, b.xhat2, b.rstd2, p.ln2_g, R, d, x.dh1,
-                           1);
-        // h1 = h + dropout1(out_proj(attn(in_proj(ln1(h)))))
-        const float *dlin_o = x.dh1;
-        if (dp > 0.f) {
-            hipLaunchKernelGGL(dropout_add_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s,
-                               (const float *)nullptr, x.dh1, (long)R * d, dp, seed, (unsigned)(4 * l + 1), x.dh);
-            dlin_o = x.dh;        // dh is rebuilt from dh1 below
-        }
-        linear_bwd(s, b.o, p.o_w, dlin_o, R, d, d, x.dtmp_d, 0.f, q.o_w, q.o_b);
-        hipLaunchKernelGGL(adapter_attn_bwd_kernel, dim3(B * heads), dim3(64), 0, s, b.qkv, b.P, x.dtmp_d, T, d, heads,
-                           x.dqkv, dp, seed, (unsigned)(4 * l));
-        linear_bwd(s, b.a, p.qkv_w, x.dqkv, R, d, 3 * d, x.dtmp_d, 0.f, q.qkv_w, q.qkv_b);
-        ln_param_bwd(s, x.dtmp_d, b.xhat1, R, d, q.ln1_g, q.ln1_b);
-        hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for((long)R * d)), dim3(256), 0, s, x.dh1, (const float *)nullptr,
-                           (long)R * d, 1.f, 0.f, x.dh);
-        hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(256), 0, s, x.dtmp_d, b.xhat1, b.rstd1, p.ln1_g, R, d, x.dh, 1);
     }
     linear_bwd(s, img_feats, w->in_w, x.dh, R, D, d, d_img, d_img_beta, g->in_w, g->in_b);
 }
@@ -1017,37 +1039,19 @@ extern "C" EC_API int ec_fs_trans_loss_grad(const float *img_feats, const uint8_
     const size_t need = carve_trans(c, B, T, D, K, d, ffn, heads, layers, t);
     if (need > workspace_bytes)
         return ec::fail(EC_ERR_WORKSPACE, "ec_fs_trans_loss_grad: workspace %zu < %zu bytes", workspace_bytes, need);
-    const size_t lds = ((size_t)T * K + TR_WAVES + 3 * (size_t)T) * 4;
-    EC_REQUIRE(lds <= 160 * 1024, "ec_fs_trans_loss_grad: T * K = %d floats exceed the LDS", T * K);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    static size_t attr_lds = 0;
-    if (lds > 64 * 1024 && lds > attr_lds) {
-        EC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fs_loss_grad_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
     const int R = B * T;
     const float r = w->residual;
 
     adapter_train_fwd_launches(s, img_feats, valid, B, T, w, dropout_p, dropout_seed, t.tape, t.mixed);
-
-    // ---------------- loss, dL, text gradient (shared with 'text-identity') ----------------
-    hipLaunchKernelGGL(text_norm_kernel, dim3(K), dim3(64), 0, s, text_param, D, t.u, t.inv_norm);
-    hipLaunchKernelGGL(fs_normalize_kernel, dim3((unsigned)((R + TR_WAVES - 1) / TR_WAVES)), dim3(TR_THREADS), 0, s, t.mixed, valid,
-                       (const int *)nullptr, 0, 1, R, D, t.Fn);
-    hipLaunchKernelGGL(sgemm_kernel<false>, dim3((K + 63) / 64, (unsigned)((R + 63) / 64)), dim3(256), 0, s, t.Fn, (long)D, 1L, t.u,
-                       1L, (long)D, R, K, D, logit_scale, 0.f, static_cast<const float *>(nullptr), t.dL, (long)K);
-    hipLaunchKernelGGL(fs_loss_grad_kernel, dim3(B), dim3(TR_THREADS), lds, s, valid, labels, B, T, K, agg, use_probs_loss, t.dL,
-                       t.loss_b, agg_logits);
-    hipLaunchKernelGGL(sgemm_kernel<false>, dim3((D + 63) / 64, (K + 63) / 64), dim3(256), 0, s, t.dL, 1L, (long)K, t.Fn, (long)D,
-                       1L, K, D, R, logit_scale, 0.f, static_cast<const float *>(nullptr), t.dU, (long)D);
-    hipLaunchKernelGGL(text_grad_finish_kernel, dim3(K), dim3(64), 0, s, t.u, t.dU, t.inv_norm, D, t.loss_b, B,
-                       grad_text, loss);
+    if (int rc = head_launches(s, "ec_fs_trans_loss_grad", t.mixed, nullptr, valid, labels, text_param, B, T, D, K,
+                               logit_scale, agg, use_probs_loss, t.head, loss, grad_text, agg_logits))
+        return rc;
 
     // ---------------- backward into the adapter ----------------
-    gemm(s, false, t.dL, K, 1, t.u, D, 1, R, D, K, logit_scale, 0.f, nullptr, t.dfn);   // dFn = s dL u
-    hipLaunchKernelGGL(normalize_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, t.mixed, t.Fn, t.dfn, valid,
-                       (const int *)nullptr, 0, 1, R, D, 1.f - r, t.bw.dy);            // dY = (1 - r) dMixed
+    gemm(s, false, t.head.dL, K, 1, t.head.u, D, 1, R, D, K, logit_scale, 0.f, nullptr, t.dfn);   // dFn = s dL u
+    hipLaunchKernelGGL(normalize_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, t.mixed, t.head.Fn, t.dfn, valid,
+                       (const int *)nullptr, 0, 1, R, D, 1.f - r, (const float *)nullptr, t.bw.dy);   // dY = (1 - r) dMixed
     adapter_train_bwd_launches(s, img_feats, B, T, w, g, dropout_p, dropout_seed, t.tape, t.bw, nullptr, 0.f);
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
@@ -1210,7 +1214,8 @@ extern "C" EC_API int ec_classify_backward(const float *feats, int n_rows, const
     if (d_feats) {
         gemm(s, false, dZ, K, 1, text_t, 1, K, R, C, K, logit_scale, 0.f, nullptr, dFn);   // dFn = scale dZ text
         hipLaunchKernelGGL(normalize_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, feats, Fn, dFn,
-                           (const unsigned char *)nullptr, row_idx, n_rows, normalize, R, C, 1.f, d_feats);
+                           (const unsigned char *)nullptr, row_idx, n_rows, normalize, R, C, 1.f, (const float *)nullptr,
+                           d_feats);
     }
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;

@@ -930,28 +930,6 @@ __global__ __launch_bounds__(256) void unscale_check_kernel(float *g, long n, fl
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(found_inf, 1);
 }
 
-// through F.normalize + the validity mask (clip_cls_ft.py:214-217): d f = valid ? (dfn - fn (fn . dfn)) / |f| : 0
-// (row_idx: feats / dfeats hold the valid views only, view r lives in row row_idx[r]; invalid views have no row)
-__global__ __launch_bounds__(256) void feat_grad_kernel(const float *feats, const float *fn, const float *dfn,
-                                                        const unsigned char *valid, const int *row_idx, int R, int D,
-                                                        float scale, float *dfeats, const float *scalars)
-{
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= R) return;
-    if (scalars) scale = scalars[EC_STEP_GRAD_SCALE];
-    if (row_idx && !valid[r]) return;
-    const long row = row_idx ? row_idx[r] : r;
-    float s = 0.f, dot = 0.f;
-    for (int j = lane; j < D; j += 64) {
-        const float m = feats[row * D + j];
-        s += m * m, dot += fn[(long)r * D + j] * dfn[(long)r * D + j];
-    }
-    const float inv = valid[r] ? scale / fmaxf(__builtin_sqrtf(wave_sum(s)), 1e-12f) : 0.f;
-    dot = wave_sum(dot);
-    for (int j = lane; j < D; j += 64)
-        dfeats[row * D + j] = (dfn[(long)r * D + j] - fn[(long)r * D + j] * dot) * inv;
-}
-
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -1835,36 +1813,6 @@ EC_API int ec_grad_unscale_check(float *grad, int64_t n, float inv_scale, int32_
     ec::ProfScope prof(ec::PROF_OPTIMIZER, static_cast<hipStream_t>(stream), 0, 8.0 * n);
     hipLaunchKernelGGL(unscale_check_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), grad, (long)n, inv_scale, found_inf, step_scalars);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
-}
-
-EC_API int ec_ft_loss_grad(const float *img_feats, const int32_t *row_idx, const uint8_t *valid, const int32_t *labels,
-                           const float *text_param, int B, int T, int D, int K, float logit_scale, int agg,
-                           int use_probs_loss, float grad_scale, const float *step_scalars,
-                           float *loss, float *grad_text, float *grad_img, float *agg_logits, void *workspace,
-                           size_t workspace_bytes, ec_stream_t stream)
-{
-    EC_REQUIRE(B > 0 && T > 0 && D > 0 && K > 0, "ec_ft_loss_grad: bad shape");
-    EC_REQUIRE(img_feats && valid && labels && text_param && loss && grad_img && workspace, "ec_ft_loss_grad: null buffer");
-    const size_t base = ec_fs_text_train_workspace_bytes(B, T, D, K);
-    const size_t R = (size_t)B * T;
-    EC_REQUIRE(workspace_bytes >= base + (R > (size_t)K ? R : (size_t)K) * D * 4, "ec_ft_loss_grad: workspace too small");
-    // the few-shot head leaves Fn (normalised views), dL (per-view logit gradients) and u (normalised text) at
-    // the front of its workspace, in this order (train.hip: ec_fs_text_loss_grad)
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    float *gt = grad_text ? grad_text : reinterpret_cast<float *>(ws + base);   // unused text gradient: scratch
-    EC_TRY(ec::fs_text_loss_grad(img_feats, row_idx, valid, labels, text_param, B, T, D, K, logit_scale, agg, use_probs_loss,
-                                 loss, gt, agg_logits, workspace, base, stream));
-    auto a256 = [](size_t x) { return (x + 255) / 256 * 256; };
-    const float *Fn = reinterpret_cast<const float *>(ws);
-    const float *dL = reinterpret_cast<const float *>(ws + a256(R * D * 4));
-    const float *u = reinterpret_cast<const float *>(ws + a256(R * D * 4) + a256(R * K * 4));
-    float *dfn = reinterpret_cast<float *>(ws + base);
-    // dFn[R, D] = logit_scale * dL[R, K] . u[K, D]
-    EC_TRY(ec_sgemm(dL, K, 1, u, D, 1, (int)R, D, K, logit_scale, 0.f, dfn, D, stream));
-    hipLaunchKernelGGL(feat_grad_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       img_feats, Fn, dfn, valid, row_idx, (int)R, D, grad_scale, grad_img, step_scalars);
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }

@@ -46,6 +46,7 @@ C = {
     'attn_bwd': 1.15,    # Measured: 0.96
     'elementwise': 2.2,  # a x + b y: three roundings.  Measured: 1.83
     'head': 1.75,        # loss, aggregated logits and d text of head_cases and the saturated sample.  Measured: 1.47
+    'head_dfeats': 0.5,  # d feats of the same cases, scaled by GRAD_SCALE.  Measured: 0.43
     'dz': 2.7,           # Measured: 2.27
     'adam': 1.5,         # p, m and v of adam_cases.  Measured: 1.28
     'chain1': 4.5,       # gradients end to end through 1 layer at R = 1040 (the two-trip dropout case).  Measured: 3.79
@@ -488,8 +489,9 @@ def normalize_bwd_S(m, fn, dfn, ok, scale=1.0, edfn=None):
 # ---------------------------------------------------------------------------------------------------------------
 # the text-identity head: normalise, logits, loss, dL, d text (clip_cls.py forward, calc_train_loss, autograd)
 # ---------------------------------------------------------------------------------------------------------------
-def text_head(ar, feats, valid, labels, text, scale, agg, probs, mean_over_T=False, with_S=False):
-    """feats [B, T, D], valid bool [B, T], labels int64 [B], text [K, D] -> dict(loss, agg_logits [B, K], grad_text [K, D]).
+def text_head(ar, feats, valid, labels, text, scale, agg, probs, mean_over_T=False, with_S=False, grad_scale=1.0):
+    """feats [B, T, D], valid bool [B, T], labels int64 [B], text [K, D] -> dict(loss, agg_logits [B, K], grad_text [K, D],
+    d_feats [B, T, D] = grad_scale d loss / d feats: the fine-tuning head's feature gradient).
     with_S (float64 only): also the first-order propagation of one unit roundoff per step ('S_*') and of TRANS per
     __expf / __logf ('E_*') through the chain."""
     B, T, D = feats.shape
@@ -562,8 +564,17 @@ def text_head(ar, feats, valid, labels, text, scale, agg, probs, mean_over_T=Fal
     dU = sc * ar.mm(dL.reshape(B * T, K).T, Fn.reshape(B * T, D))
     dot = ar.sum(u * dU)
     grad = (dU - u * dot[:, None]) * inv[:, None]
-    out.update(loss=ar.sum(loss_b, 0) / B, agg_logits=agg_logits, grad_text=grad)
+    dfn = (sc * ar.mm(dL.reshape(B * T, K), u)).reshape(B, T, D)
+    out.update(loss=ar.sum(loss_b, 0) / B, agg_logits=agg_logits, grad_text=grad,
+               d_feats=normalize_bwd(ar, feats, Fn, dfn, valid, grad_scale))
     if with_S:
+        # d Fn = scale dL u carries S_dL and E_dL through |u| as d U does through |Fn|; the row normalisation's backward
+        # propagates both as input errors (its edfn) on top of its own roundoff
+        S_dfn = (float(sc) * ((S_dL + 2 * dL.abs()).reshape(B * T, K) @ u.abs())).reshape(B, T, D)
+        E_dfn = (float(sc) * (E_dL.reshape(B * T, K) @ u.abs())).reshape(B, T, D)
+        out['S_d_feats'] = normalize_bwd_S(feats, Fn, dfn, valid, grad_scale)[0] + \
+            normalize_bwd_S(feats, Fn, dfn, valid, grad_scale, S_dfn)[1]
+        out['E_d_feats'] = normalize_bwd_S(feats, Fn, dfn, valid, grad_scale, E_dfn)[1]
         fa = Fn.abs().reshape(B * T, D)
         S_dU = float(sc) * ((S_dL + 2 * dL.abs()).reshape(B * T, K).T @ fa)
         E_dU = float(sc) * (E_dL.reshape(B * T, K).T @ fa)
@@ -613,19 +624,27 @@ def head_inputs(B, T, D, K, last_label, seed=0, saturated=False):
     return feats.float().contiguous(), valid, labels, text
 
 
-def check_head(impl, case, what, poison=None, scale=100.0, saturated=False):
+GRAD_SCALE = 1536.0          # a gradient scaler's value that is no power of two: the product with it rounds
+
+
+def check_head(impl, case, what, poison=None, scale=100.0, saturated=False, grad_scale=None):
     """impl(feats, valid, labels, text, scale, agg, probs) -> (loss [1], grad_text, agg_logits) as CPU tensors.  -> the worst
-    error / bound.  poison: invalid views are filled with it first (any value there must change nothing)."""
+    error / bound.  poison: invalid views are filled with it first (any value there must change nothing).  grad_scale:
+    impl takes it as one more argument and returns d_feats [B, T, D] as a fourth tensor."""
     B, T, D, K, agg, probs, last = case
     feats, valid, labels, text = head_inputs(B, T, D, K, last, saturated=saturated)
     if poison is not None:
         feats = torch.where(valid[..., None], feats, torch.full_like(feats, poison))
-    r = text_head(A64, feats.double(), valid, labels, text.double(), scale, agg, probs, with_S=True)
-    loss, grad, logits = impl(feats, valid, labels, text, scale, agg, probs)
+    r = text_head(A64, feats.double(), valid, labels, text.double(), scale, agg, probs, with_S=True,
+                  grad_scale=grad_scale or 1.0)
+    loss, grad, logits, *d_feats = impl(feats, valid, labels, text, scale, agg, probs, *([grad_scale] if grad_scale else []))
+    assert len(d_feats) == (1 if grad_scale else 0)
     worst = 0.0
     for name, got in (('loss', loss.reshape(())), ('agg_logits', logits), ('grad_text', grad)):
         key = 'agg' if name == 'agg_logits' else name
         worst = max(worst, within(got, r[name], 'head', r['S_' + key], r['E_' + key], f'{what} {case}: {name}'))
+    for got in d_feats:
+        worst = max(worst, within(got, r['d_feats'], 'head_dfeats', r['S_d_feats'], r['E_d_feats'], f'{what} {case}: d_feats'))
     return worst
 
 

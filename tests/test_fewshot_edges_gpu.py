@@ -187,6 +187,68 @@ def test_text_head_lds_opt_in_and_limit(hip):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# (d') ec_ft_loss_grad: the same head plus the feature gradient, dense or compact over the valid views
+# ---------------------------------------------------------------------------------------------------------------
+def _ft_head_raw(feats, valid, labels, text, scale, agg, probs, grad_scale, compact=False, scalars=False):
+    """-> (loss [1], grad_text, agg_logits, grad_img) as CPU tensors.  compact: the valid views' rows alone, in REVERSED view
+    order, with row_idx; grad_img comes back in that layout.  scalars: grad_scale travels in a device step_scalars array
+    (every other entry NaN) and the by-value argument holds another value."""
+    B, T, D = feats.shape
+    K = text.shape[0]
+    L = _L()
+    lib = L.lib()
+    need = int(lib.ec_fs_text_train_workspace_bytes(B, T, D, K)) + max(B * T, K) * D * 4
+    ws = torch.empty(need + 256, dtype=torch.uint8, device='cuda')
+    f, row_idx = feats, None
+    if compact:
+        okf = valid.reshape(-1)
+        n = int(okf.sum())
+        row_idx = torch.where(okf, n - torch.cumsum(okf.int(), 0), torch.full((B * T,), -1)).to(torch.int32).cuda()
+        f = feats.reshape(B * T, D)[okf].flip(0)
+    step = None
+    if scalars:
+        step = torch.full((L.EC_STEP_COUNT,), float('nan'))
+        step[L.EC_STEP_GRAD_SCALE] = grad_scale
+        step = step.cuda()
+    rows = f.numel() // D
+    loss, grad, logits, gimg = _pattern((1,)), _pattern((K, D)), _pattern((B, K)), _pattern((rows + 1, D))
+    f, v8, lab, t = f.contiguous().cuda(), valid.to(torch.uint8).cuda(), labels.to(torch.int32).cuda(), text.cuda()
+    rc = lib.ec_ft_loss_grad(f.data_ptr(), row_idx.data_ptr() if compact else None, v8.data_ptr(), lab.data_ptr(), t.data_ptr(),
+                             B, T, D, K, float(scale), fr.AGG[agg], int(probs), -7.0 if scalars else float(grad_scale),
+                             step.data_ptr() if scalars else None, loss.data_ptr(), grad.data_ptr(), gimg.data_ptr(),
+                             logits.data_ptr(), ws.data_ptr(), need, L.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0, lib.ec_last_error()
+    assert bool((_bits(gimg[rows]) == -0x12345679).all()), 'ec_ft_loss_grad wrote past the last feature row'
+    return loss.cpu(), grad.cpu(), logits.cpu(), gimg[:rows].cpu()
+
+
+@pytest.mark.parametrize('group', range(6))
+def test_ft_head_edges(group, hip):
+    """The head's K, T, B and D edges through ec_ft_loss_grad: loss, aggregated logits, d text and the feature gradient per
+    element on dense features, invalid views exactly zero; compact rows with row_idx give the bits of the dense result
+    gathered; grad_scale read from step_scalars gives the bits of the same value passed by value."""
+    worst = 0.0
+    for c in _head_groups()[group]:
+        dense = []
+
+        def impl(*a):
+            out = _ft_head_raw(*a)
+            dense.append((a, out))
+            return out[:3] + (out[3].reshape(a[0].shape),)
+        worst = max(worst, fr.check_head(impl, c, 'ec_ft_loss_grad', grad_scale=fr.GRAD_SCALE))
+        (a, want), = dense
+        valid, d_dense = a[1], want[3].reshape(a[0].shape)
+        assert bool((d_dense[~valid] == 0).all()), f'{c}: gradient on an invalid view'
+        gathered = want[:3] + (d_dense[valid].flip(0),)
+        for scalars in (False, True):
+            got = _ft_head_raw(*a, compact=True, scalars=scalars)
+            for name, g, w in zip(('loss', 'grad_text', 'agg_logits', 'grad_img'), got, gathered):
+                assert torch.equal(_bits(g), _bits(w)), f'{c}: compact {name} differs from the dense one (step_scalars {scalars})'
+    _report(f'ft head group {group}', worst)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # (e) ec_classify_backward, directed: dZ read back exactly through d_feats (text_t the identity, no normalisation, scale 1)
 # ---------------------------------------------------------------------------------------------------------------
 def _classify_dz(full, ok, agg, d_full, d_logits, d_probs, want_text=False):

@@ -20,9 +20,9 @@ E2E = fr.E2E_CASES
 # the F32 models behind the checks' interfaces, with their planted faults
 # ---------------------------------------------------------------------------------------------------------------
 def head_model(mean_over_T=False):
-    def impl(feats, valid, labels, text, scale, agg, probs):
-        r = fr.text_head(A32, feats, valid, labels, text, scale, agg, probs, mean_over_T=mean_over_T)
-        return r['loss'], r['grad_text'], r['agg_logits']
+    def impl(feats, valid, labels, text, scale, agg, probs, grad_scale=None):
+        r = fr.text_head(A32, feats, valid, labels, text, scale, agg, probs, mean_over_T=mean_over_T, grad_scale=grad_scale or 1.0)
+        return (r['loss'], r['grad_text'], r['agg_logits']) + ((r['d_feats'],) if grad_scale else ())
     return impl
 
 
@@ -86,9 +86,9 @@ def run_all_checks():
     for c in fr.gemm_cases():
         fr.check_gemm(gm, fr.gemm_case(*c), f'gemm {c}')
     for c in fr.head_cases():
-        fr.check_head(head_model(), c, 'head')
-    fr.check_head(head_model(), (3, 2, 64, 5, 'mean', True, 0), 'head saturated', saturated=True)
-    fr.check_head(head_model(), (3, 2, 64, 5, 'sum', False, 1), 'head saturated', saturated=True)
+        fr.check_head(head_model(), c, 'head', grad_scale=fr.GRAD_SCALE)
+    fr.check_head(head_model(), (3, 2, 64, 5, 'mean', True, 0), 'head saturated', saturated=True, grad_scale=fr.GRAD_SCALE)
+    fr.check_head(head_model(), (3, 2, 64, 5, 'sum', False, 1), 'head saturated', saturated=True, grad_scale=fr.GRAD_SCALE)
     for c in fr.adam_cases():
         fr.check_adam(adam_model(), c, 'adam')
     for K in fr.DZ_K:
@@ -260,7 +260,8 @@ def test_head_yardstick_is_torch(agg, probs):
     B, T, D, K = 5, 4, 33, 7
     feats, valid, labels, text = fr.head_inputs(B, T, D, K, 1)
     t = text.double().requires_grad_(True)
-    Fn = torch.nn.functional.normalize(feats.double(), dim=-1) * valid[..., None]
+    f = feats.double().requires_grad_(True)
+    Fn = torch.nn.functional.normalize(f, dim=-1) * valid[..., None]
     L = 100.0 * Fn @ torch.nn.functional.normalize(t, dim=-1).T
     nv = valid.sum(1, keepdim=True).double()
     logits = L.sum(1) / (nv if agg == 'mean' else 1.0)
@@ -270,10 +271,12 @@ def test_head_yardstick_is_torch(agg, probs):
     else:
         loss = torch.nn.functional.cross_entropy(logits, labels)
     loss.backward()
-    r = fr.text_head(A64, feats.double(), valid, labels, text.double(), 100.0, agg, probs)
+    r = fr.text_head(A64, feats.double(), valid, labels, text.double(), 100.0, agg, probs, grad_scale=fr.GRAD_SCALE)
     close(r['loss'], loss.detach(), 'loss')
     close(r['agg_logits'], logits.detach(), 'logits')
     close(r['grad_text'], t.grad, 'grad_text')
+    assert not bool(valid.all()) and float(f.grad.abs().max()) > 0
+    close(r['d_feats'], fr.GRAD_SCALE * f.grad, 'd_feats')
 
 
 @pytest.mark.parametrize('agg', list(fr.AGG))
