@@ -28,7 +28,7 @@ import torch
 
 from . import _lib
 from . import resnet as _resnet
-from .clip_base import ATTN_Q_SCALE, ClipBase, Packer, _assign, _block_keys   # noqa: F401 (re-exported)
+from .clip_base import ATTN_Q_SCALE, ClipBase, Packer, _assign, _block_keys, patch_row_widths   # noqa: F401 (re-exported)
 from .preprocess import Preprocess
 from .resnet import RESNET_ARCHS, resnet_config
 
@@ -313,11 +313,7 @@ class CLIP(ClipBase):
         dev32, dev16, dev16_pair = pk.dev32, pk.dev16, pk.dev16_pair
         c = self.cfg
         P, W = c['patch'], c['width']
-        # a patch row carries every pixel value as hi + lo 16-bit parts, [hi | lo | 0] (kpad wide);
-        # conv1.weight is packed as [w_hi | w_hi | 0] and [w_lo | 0] (ec_vit_encode, patch_embed)
-        k = 3 * P * P
-        kpad = ((2 * k + 63) // 64) * 64
-        klo = ((k + 63) // 64) * 64
+        k, kpad, klo = patch_row_widths(P)
         cw = sd['visual.conv1.weight'].reshape(W, k).float().cpu()
         conv = torch.zeros(W, kpad)
         conv[:, :k] = cw
@@ -408,7 +404,7 @@ class CLIP(ClipBase):
             t = self._diff_tower = ft.VisualTower(self)     # refuses image_precise: no training form
         img = image.to(t.dev, torch.float32)
         # a frozen tower: parameters that require grad elsewhere go in detached
-        params = [t.param[n].detach() for n in t.trainable()] + ([p.detach() for p in t.lora.params.values()] if t.lora else [])
+        params = [p.detach() for p in t.op_params()]
         return torch.ops.eventclip_hip.vit_image_fwd(img, params, torch_ops.handle_of(t))[0]
 
     @torch.no_grad()

@@ -17,6 +17,14 @@ def _block_keys(prefix, i):
                             'mlp.c_proj.bias')]
 
 
+def patch_row_widths(patch):
+    """-> (k, kpad, klo) of a patch size: the 3 p^2 values of a patch; the width of a patch row, which carries every pixel
+    as hi + lo 16-bit parts [hi | lo | 0], and of conv1.weight packed against it as [w_hi | w_hi | 0]; the width of
+    conv1.weight's lo part [w_lo | 0] (ec_vit_encode, patch_embed)."""
+    k = 3 * patch * patch
+    return k, (2 * k + 63) // 64 * 64, (k + 63) // 64 * 64
+
+
 # log2(e) / sqrt(head dim 64): what ec_attention_scaled_q expects in the q columns (include/eventclip_hip.h)
 ATTN_Q_SCALE = 0.125 * 1.4426950408889634
 

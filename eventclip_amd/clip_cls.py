@@ -23,11 +23,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
 from . import clip as eclip
 from .adapter import IdentityAdapter, TransformerAdapter, compact_row_idx, dense_row_idx
-
-_AGG = {'sum': _lib.EC_AGG_SUM, 'mean': _lib.EC_AGG_MEAN, 'max': _lib.EC_AGG_MAX}
+from .train import _AGG
 
 
 def _l2_normalize(x):

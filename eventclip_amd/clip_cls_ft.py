@@ -146,7 +146,7 @@ class FTCLIPClassifier(FSCLIPClassifier):
             return super()._forward_train(data_dict)
         from . import torch_ops
         t = self._operand_tower()
-        params = [t.param[n] for n in t.trainable()] + (list(t.lora.params.values()) if t.lora else [])
+        params = t.op_params()
         img = data_dict.get('img')
         if 'patches' not in data_dict and torch.is_tensor(img) and img.requires_grad:
             valid_masks = data_dict['valid_mask'].to(t.dev)
@@ -173,11 +173,7 @@ class FTCLIPClassifier(FSCLIPClassifier):
         t = self._operand_tower()
         if t is None:
             return super().get_img_feats(imgs)
-        from . import _lib
-        x = imgs.to(t.dev, torch.float32).contiguous()
-        patches = torch.empty((x.shape[0], t.G, t.kpad), dtype=t.cd, device=t.dev)
-        _lib.launch('ec_patchify', x, x.shape[0], t.cfg['image_size'], t.P, t.kpad, patches, t.code)
-        return self._adjust_dtype(t.encode_patches(patches))
+        return self._adjust_dtype(t.encode_patches(t.patchify(imgs)))
 
     # ---- checkpoints: model.visual.* travels with the classifier (clip_cls_ft.py:313-333) ----
     def state_dict(self, *args, **kwargs):

@@ -1368,13 +1368,19 @@ struct ImageGrad {
     float *d_image;                     // fp32 [n_img, 3, R, R] out
 };
 
+// the geometry every training entry point sizes its buffers from (TrainBufs holds at most 64 blocks)
+inline bool train_geometry_ok(const ec_vit_weights *w, int n_img)
+{
+    return w && n_img > 0 && w->patch > 0 && w->layers >= 1 && w->layers <= 64;
+}
+
 }  // namespace
 
 extern "C" {
 
 EC_API size_t ec_vit_train_workspace_bytes(const ec_vit_weights *w, int n_img)
 {
-    if (!w || n_img <= 0 || w->patch <= 0 || w->layers < 1 || w->layers > 64) return 0;
+    if (!train_geometry_ok(w, n_img)) return 0;
     Scratch sc{nullptr, 0, 0};
     TrainBufs b;
     return carve_train(sc, w, n_img, b);
@@ -1384,7 +1390,7 @@ EC_API size_t ec_vit_train_workspace_bytes(const ec_vit_weights *w, int n_img)
 // hand out null pointers): the two cannot drift apart.
 EC_API int ec_vit_train_layout(const ec_vit_weights *w, int n_img, int64_t *offsets, int n_offsets)
 {
-    EC_REQUIRE(w && n_img > 0 && w->patch > 0 && w->layers >= 1 && w->layers <= 64,
+    EC_REQUIRE(train_geometry_ok(w, n_img),
                "ec_vit_train_layout: bad geometry (n_img %d)", n_img);
     const int L = w->layers, need = EC_VT_BLOCK0 + EC_VT_PER_BLOCK * L;
     if (!offsets) return need;
@@ -1441,110 +1447,13 @@ EC_API int ec_vit_train_forward(const ec_vit_weights *w, const void *patches, in
     return Gemm(n_img, w->out_dim, W, dt, EC_EPI_STORE32, b.cls_hi, w->proj_w, nullptr, feats).lo(b.cls_lo, w->proj_w_lo).run(stream);
 }
 
-EC_API int ec_vit_train_backward(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches, int n_img,
-                                 const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora, void *workspace,
-                                 size_t workspace_bytes, ec_stream_t stream)
-{
-    return ec_vit_train_backward_stages(w, wt, patches, n_img, d_feats, gr, lora, 0, w ? w->layers + 2 : 0, workspace,
-                                        workspace_bytes, stream);
-}
-
 // Stages: 0 = the head (ln_post, proj), 1 .. L = blocks L - 1 .. 0, L + 1 = the embedding.  The state between
 // stages (the residual-stream gradient and its 16-bit copy) lives in the workspace, so a caller can run a few
 // blocks, hand their finished gradients to a collective on another stream, and carry on.
 static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches, int n_img,
                            const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora, int stage_begin,
                            int stage_end, void *workspace, size_t workspace_bytes, void *scratch, size_t scratch_bytes,
-                           ec_stream_t stream, const ImageGrad *image = nullptr);
-
-EC_API int ec_vit_train_backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
-                                        int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
-                                        int stage_begin, int stage_end, void *workspace, size_t workspace_bytes,
-                                        ec_stream_t stream)
-{
-    return backward_stages(w, wt, patches, n_img, d_feats, gr, lora, stage_begin, stage_end, workspace, workspace_bytes,
-                           nullptr, 0, stream);
-}
-
-EC_API size_t ec_vit_train_backward_scratch_bytes(const ec_vit_weights *w, int n_img)
-{
-    if (!w || n_img <= 0 || w->patch <= 0 || w->layers < 1 || w->layers > 64) return 0;
-    Scratch tape{nullptr, 0, 0}, own{nullptr, 0, 0};
-    TrainBufs b;
-    carve_train(tape, w, n_img, b, &own);
-    return own.off;
-}
-
-// The whole pass with the tape only read: the scratch that ec_vit_train_backward keeps behind the tape in the same
-// buffer comes from the caller (ec_vit_train_backward_scratch_bytes), so the tape's buffer is not written at all.
-EC_API int ec_vit_train_backward_over(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
-                                      int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
-                                      const void *tape, size_t tape_bytes, void *scratch, size_t scratch_bytes,
-                                      ec_stream_t stream)
-{
-    EC_REQUIRE(scratch, "ec_vit_train_backward_over: null scratch");
-    return backward_stages(w, wt, patches, n_img, d_feats, gr, lora, 0, w ? w->layers + 2 : 0, const_cast<void *>(tape),
-                           tape_bytes, scratch, scratch_bytes, stream);
-}
-
-EC_API size_t ec_vit_train_backward_image_scratch_bytes(const ec_vit_weights *w, int n_img)
-{
-    if (!w || n_img <= 0 || w->patch <= 0 || w->layers < 1 || w->layers > 64) return 0;
-    Scratch tape{nullptr, 0, 0}, own{nullptr, 0, 0};
-    TrainBufs b;
-    carve_train(tape, w, n_img, b, &own);
-    const int g = w->image_size / w->patch;
-    own.take((size_t)n_img * (g * g + 1) * conv_t_rows(w) * 4);
-    return own.off;
-}
-
-// ec_vit_train_backward_over that also differentiates the image: the chain runs down to the embedding whatever weight
-// gradients are asked for (none at all is legal: a frozen tower launches no weight-gradient kernel).
-EC_API int ec_vit_train_backward_image(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
-                                       int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
-                                       const void *conv_wt, const void *conv_wt_lo, float *d_image, const void *tape,
-                                       size_t tape_bytes, void *scratch, size_t scratch_bytes, ec_stream_t stream)
-{
-    EC_REQUIRE(scratch && conv_wt && d_image, "ec_vit_train_backward_image: null scratch / conv1 operand / d_image");
-    EC_REQUIRE((((uintptr_t)conv_wt | (uintptr_t)conv_wt_lo) & 15) == 0, "ec_vit_train_backward_image: conv1 operands must be 16-byte aligned");
-    const ImageGrad image = {conv_wt, conv_wt_lo, d_image};
-    return backward_stages(w, wt, patches, n_img, d_feats, gr, lora, 0, w ? w->layers + 2 : 0, const_cast<void *>(tape),
-                           tape_bytes, scratch, scratch_bytes, stream, &image);
-}
-
-EC_API int ec_patch_embed_backward(const ec_vit_weights *w, const void *conv_wt, const void *conv_wt_lo, const void *d_tok16,
-                                   int n_img, float *d_pix, float *d_image, ec_stream_t stream)
-{
-    EC_TRY(check_geometry(w, "ec_patch_embed_backward"));
-    EC_REQUIRE(n_img > 0, "ec_patch_embed_backward: n_img=%d", n_img);
-    EC_REQUIRE(conv_wt && d_tok16 && d_pix && d_image, "ec_patch_embed_backward: null buffer");
-    return embed_data_grad(w, conv_wt, conv_wt_lo, d_tok16, n_img, d_pix, d_image, stream);
-}
-
-EC_API int ec_unpatchify(const float *rows, long ld, int seq, int row_off, int n_img, int n_px, int patch, float *d_image,
-                         ec_stream_t stream)
-{
-    EC_REQUIRE(n_img >= 0 && patch > 0 && n_px > 0 && n_px % patch == 0, "ec_unpatchify: bad geometry (n_px %d, patch %d)", n_px,
-               patch);
-    const int G = (n_px / patch) * (n_px / patch);
-    EC_REQUIRE(row_off >= 0 && seq >= row_off + G && ld >= 3L * patch * patch,
-               "ec_unpatchify: %d rows per image from row %d for %d patches, row stride %ld for %d columns", seq, row_off, G, ld,
-               3 * patch * patch);
-    if (n_img == 0) return EC_OK;
-    EC_REQUIRE(rows && d_image, "ec_unpatchify: null buffer");
-    const long total = (long)n_img * 3 * n_px * n_px;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    ec::ProfScope prof(ec::PROF_UNPATCHIFY, s, 0, 8.0 * total);
-    hipLaunchKernelGGL(unpatchify_kernel, dim3((unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384)), dim3(256),
-                       0, s, rows, ld, seq, row_off, total, n_px, patch, d_image);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
-}
-
-static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches, int n_img,
-                           const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora, int stage_begin,
-                           int stage_end, void *workspace, size_t workspace_bytes, void *scratch, size_t scratch_bytes,
-                           ec_stream_t stream, const ImageGrad *image)
+                           ec_stream_t stream, const ImageGrad *image = nullptr)
 {
     EC_TRY(check_geometry(w, "ec_vit_train_backward"));
     EC_REQUIRE(stage_begin >= 0 && stage_begin <= stage_end && stage_end <= w->layers + 2,
@@ -1685,6 +1594,98 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
         EC_TRY(weight_grad(dt, b.ta, b.tb, W, w->kpad, b, gr->conv_w, 3 * w->patch * w->patch, stream));
     }
     if (image) EC_TRY(embed_data_grad(w, image->conv_wt, image->conv_wt_lo, b.dx16, n_img, d_pix, image->d_image, stream));
+    return EC_OK;
+}
+
+EC_API int ec_vit_train_backward(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches, int n_img,
+                                 const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora, void *workspace,
+                                 size_t workspace_bytes, ec_stream_t stream)
+{
+    return ec_vit_train_backward_stages(w, wt, patches, n_img, d_feats, gr, lora, 0, w ? w->layers + 2 : 0, workspace,
+                                        workspace_bytes, stream);
+}
+
+EC_API int ec_vit_train_backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
+                                        int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
+                                        int stage_begin, int stage_end, void *workspace, size_t workspace_bytes,
+                                        ec_stream_t stream)
+{
+    return backward_stages(w, wt, patches, n_img, d_feats, gr, lora, stage_begin, stage_end, workspace, workspace_bytes,
+                           nullptr, 0, stream);
+}
+
+EC_API size_t ec_vit_train_backward_scratch_bytes(const ec_vit_weights *w, int n_img)
+{
+    if (!train_geometry_ok(w, n_img)) return 0;
+    Scratch tape{nullptr, 0, 0}, own{nullptr, 0, 0};
+    TrainBufs b;
+    carve_train(tape, w, n_img, b, &own);
+    return own.off;
+}
+
+// The whole pass with the tape only read: the scratch that ec_vit_train_backward keeps behind the tape in the same
+// buffer comes from the caller (ec_vit_train_backward_scratch_bytes), so the tape's buffer is not written at all.
+EC_API int ec_vit_train_backward_over(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
+                                      int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
+                                      const void *tape, size_t tape_bytes, void *scratch, size_t scratch_bytes,
+                                      ec_stream_t stream)
+{
+    EC_REQUIRE(scratch, "ec_vit_train_backward_over: null scratch");
+    return backward_stages(w, wt, patches, n_img, d_feats, gr, lora, 0, w ? w->layers + 2 : 0, const_cast<void *>(tape),
+                           tape_bytes, scratch, scratch_bytes, stream);
+}
+
+EC_API size_t ec_vit_train_backward_image_scratch_bytes(const ec_vit_weights *w, int n_img)
+{
+    if (!train_geometry_ok(w, n_img)) return 0;
+    Scratch tape{nullptr, 0, 0}, own{nullptr, 0, 0};
+    TrainBufs b;
+    carve_train(tape, w, n_img, b, &own);
+    const int g = w->image_size / w->patch;
+    own.take((size_t)n_img * (g * g + 1) * conv_t_rows(w) * 4);
+    return own.off;
+}
+
+// ec_vit_train_backward_over that also differentiates the image: the chain runs down to the embedding whatever weight
+// gradients are asked for (none at all is legal: a frozen tower launches no weight-gradient kernel).
+EC_API int ec_vit_train_backward_image(const ec_vit_weights *w, const ec_vit_train_weights *wt, const void *patches,
+                                       int n_img, const float *d_feats, const ec_vit_grads *gr, const ec_vit_lora *lora,
+                                       const void *conv_wt, const void *conv_wt_lo, float *d_image, const void *tape,
+                                       size_t tape_bytes, void *scratch, size_t scratch_bytes, ec_stream_t stream)
+{
+    EC_REQUIRE(scratch && conv_wt && d_image, "ec_vit_train_backward_image: null scratch / conv1 operand / d_image");
+    EC_REQUIRE((((uintptr_t)conv_wt | (uintptr_t)conv_wt_lo) & 15) == 0, "ec_vit_train_backward_image: conv1 operands must be 16-byte aligned");
+    const ImageGrad image = {conv_wt, conv_wt_lo, d_image};
+    return backward_stages(w, wt, patches, n_img, d_feats, gr, lora, 0, w ? w->layers + 2 : 0, const_cast<void *>(tape),
+                           tape_bytes, scratch, scratch_bytes, stream, &image);
+}
+
+EC_API int ec_patch_embed_backward(const ec_vit_weights *w, const void *conv_wt, const void *conv_wt_lo, const void *d_tok16,
+                                   int n_img, float *d_pix, float *d_image, ec_stream_t stream)
+{
+    EC_TRY(check_geometry(w, "ec_patch_embed_backward"));
+    EC_REQUIRE(n_img > 0, "ec_patch_embed_backward: n_img=%d", n_img);
+    EC_REQUIRE(conv_wt && d_tok16 && d_pix && d_image, "ec_patch_embed_backward: null buffer");
+    return embed_data_grad(w, conv_wt, conv_wt_lo, d_tok16, n_img, d_pix, d_image, stream);
+}
+
+EC_API int ec_unpatchify(const float *rows, long ld, int seq, int row_off, int n_img, int n_px, int patch, float *d_image,
+                         ec_stream_t stream)
+{
+    EC_REQUIRE(n_img >= 0 && patch > 0 && n_px > 0 && n_px % patch == 0, "ec_unpatchify: bad geometry (n_px %d, patch %d)", n_px,
+               patch);
+    const int G = (n_px / patch) * (n_px / patch);
+    EC_REQUIRE(row_off >= 0 && seq >= row_off + G && ld >= 3L * patch * patch,
+               "ec_unpatchify: %d rows per image from row %d for %d patches, row stride %ld for %d columns", seq, row_off, G, ld,
+               3 * patch * patch);
+    if (n_img == 0) return EC_OK;
+    EC_REQUIRE(rows && d_image, "ec_unpatchify: null buffer");
+    const long total = (long)n_img * 3 * n_px * n_px;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ec::ProfScope prof(ec::PROF_UNPATCHIFY, s, 0, 8.0 * total);
+    hipLaunchKernelGGL(unpatchify_kernel, dim3((unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384)), dim3(256),
+                       0, s, rows, ld, seq, row_off, total, n_px, patch, d_image);
+    EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }
 

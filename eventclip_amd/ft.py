@@ -8,7 +8,7 @@ train.py:121) -- is here three layers over the C ABI:
 
 ``VisualTower``   fp32 master weights of ``clip.visual`` + the 16-bit operand copies the kernels read
                   (``ec_pack_weight16``), ``forward`` (``ec_vit_train_forward``) and ``backward``
-                  (``ec_vit_train_backward``) returning gradients by state-dict name;
+                  (``ec_vit_train_backward_stages``) returning gradients by state-dict name;
 ``LoraFactors``   the low-rank factors with the reference's key names, the merged weights they act through
                   (lora.py:138-150, :50-52); their gradients come straight from the activations inside the backward pass;
 ``FTTrainer``     one optimisation step: loss and feature gradients (``ec_ft_loss_grad``), the gradient scaler
@@ -28,7 +28,8 @@ import torch.distributed as dist
 from . import _lib
 from ._lib import device_table
 from .adapter import compact_row_idx
-from .train import _AGG, adam_table, cosine_warmup_lr
+from .clip_base import patch_row_widths
+from .train import _AGG, adam_table, cosine_warmup_lr, world_size
 
 _BLOCK = (('ln1_g', 'ln_1.weight'), ('ln1_b', 'ln_1.bias'), ('qkv_w', 'attn.in_proj_weight'),
           ('qkv_b', 'attn.in_proj_bias'), ('out_w', 'attn.out_proj.weight'), ('out_b', 'attn.out_proj.bias'),
@@ -38,14 +39,54 @@ _TOP = (('conv_w', 'conv1.weight'), ('cls', 'class_embedding'), ('pos', 'positio
         ('ln_pre_g', 'ln_pre.weight'), ('ln_pre_b', 'ln_pre.bias'), ('ln_post_g', 'ln_post.weight'),
         ('ln_post_b', 'ln_post.bias'), ('proj', 'proj'))
 _MATRICES = ('qkv_w', 'out_w', 'fc1_w', 'fc2_w')
+_HEAD = frozenset(leaf for _, leaf in _TOP[5:])        # _TOP: the embedding's five tensors, then the head's three
+_TOP_FIELD = {leaf: field for field, leaf in _TOP}
+_BLOCK_FIELD = {leaf: field for field, leaf in _BLOCK}
+_FIELD_RANK = {field: i for i, (field, _) in enumerate(_TOP + _BLOCK)}
+_BLOCK_NAME = re.compile(r'^transformer\.resblocks\.(\d+)\.(.+)$')
 
 
 def _block_name(i, leaf):
     return f'transformer.resblocks.{i}.{leaf}'
 
 
+def visual_name_parts(name):
+    """A master's state-dict name -> (its block, or None for the embedding and the head; its field in ``EcVitGrads`` /
+    ``EcBlockGrads``, which is its field in the weight structs too)."""
+    if name in _TOP_FIELD:
+        return None, _TOP_FIELD[name]
+    m = _BLOCK_NAME.match(name)
+    if not m or m.group(2) not in _BLOCK_FIELD:
+        raise KeyError(f'{name!r} is not a parameter of the vision tower')
+    return int(m.group(1)), _BLOCK_FIELD[m.group(2)]
+
+
+def canonical_order(names):
+    """The names in gradient-buffer order: embedding | blocks 0 .. L-1 | head, so that the part of the buffer a
+    stretch of the backward pass completes is one contiguous slice."""
+    def rank(n):
+        block, field = visual_name_parts(n)
+        return (1 if block is not None else 2 * (n in _HEAD), block or 0, _FIELD_RANK[field])
+    return sorted(names, key=rank)
+
+
+def lora_checkpoint_keys(spec, layers):
+    """{master name: its key under ``model.visual.`` in a checkpoint of the reference's LoRA-injected modules
+    (``inject_lora_modules``)} for the masters the injection renames: in_proj_weight in every block, out_proj's weight
+    and bias with 'o' in the spec.  Every other master keeps its name."""
+    _, _, lora_o = parse_lora(spec)
+    out = {}
+    for i in range(layers):
+        pre = _block_name(i, 'attn')
+        out[pre + '.in_proj_weight'] = pre + '.in_proj_weight.merged_proj'
+        if lora_o:
+            out[pre + '.out_proj.weight'] = pre + '.out_proj.linear.weight'
+            out[pre + '.out_proj.bias'] = pre + '.out_proj.linear.bias'
+    return out
+
+
 def plain_visual_name(name):
-    """A name under ``model.visual`` as the reference's LoRA-injected modules spell it (``inject_lora_modules``) ->
+    """The inverse of ``lora_checkpoint_keys``: a name under ``model.visual`` as the LoRA-injected modules spell it ->
     the plain state-dict name of that master; None for a LoRA factor."""
     if '.lora_' in name:
         return None
@@ -126,8 +167,8 @@ class VisualTower:
         self._seen = self._fp = None      # the fingerprints ``refresh`` last packed; its item table
         self._train_flags = self._train_names = None
         self.effective = {}
-        k = 3 * self.P * self.P
-        self.k, self.kpad, self.klo = k, ((2 * k + 63) // 64) * 64, ((k + 63) // 64) * 64
+        self.k, self.kpad, self.klo = patch_row_widths(self.P)
+        k = self.k
         self.kt = ((k + 15) // 16) * 16       # rows of conv1.weight^T as ec_gemm's [N, K] operand (the image's gradient)
         W, D = self.W, self.D
         z16 = lambda *shape: torch.zeros(shape, dtype=self.cd, device=dev)      # noqa: E731
@@ -284,7 +325,21 @@ class VisualTower:
             self._train_flags = flags
         return self._train_names
 
+    def op_params(self):
+        """The tensors the ``eventclip_hip::vit_train_*`` / ``vit_image_*`` ops take as ``params``: the Parameters of
+        the trainable masters in ``canonical()`` order, then the LoRA factors."""
+        return [self.param[n] for n in self.trainable()] + (list(self.lora.params.values()) if self.lora else [])
+
     # ---- passes ----
+    def patchify(self, images, out=None):
+        """images [N, 3, R, R] -> their patch rows, 16-bit [N, G, kpad] (one ``ec_patchify`` launch); written into
+        ``out``, any buffer of that many bytes, when given."""
+        x = images.to(self.dev, torch.float32).contiguous()
+        if out is None:
+            out = torch.empty((x.shape[0], self.G, self.kpad), dtype=self.cd, device=self.dev)
+        _lib.launch('ec_patchify', x, x.shape[0], self.cfg['image_size'], self.P, self.kpad, out, self.code)
+        return out
+
     def workspace_bytes(self, n):
         """Bytes of the training workspace (tape + both passes' scratch) for n images."""
         return int(_lib.lib().ec_vit_train_workspace_bytes(ctypes.byref(self._vit), n))
@@ -360,16 +415,9 @@ class VisualTower:
         the caller keeps both, and the tensors, alive over the launch)."""
         bg = (_lib.EcBlockGrads * self.L)()
         g = _lib.EcVitGrads()
-        top = {leaf: f for f, leaf in _TOP}
-        blk = {leaf: f for f, leaf in _BLOCK}
         for name, t in tensors.items():
-            if name in top:
-                setattr(g, top[name], t.data_ptr())
-            else:
-                m = re.match(r'^transformer\.resblocks\.(\d+)\.(.+)$', name)
-                if not m or m.group(2) not in blk:
-                    raise KeyError(f'{name!r} is not a parameter of the vision tower')
-                setattr(bg[int(m.group(1))], blk[m.group(2)], t.data_ptr())
+            block, field = visual_name_parts(name)
+            setattr(g if block is None else bg[block], field, t.data_ptr())
         g.blocks = ctypes.cast(bg, ctypes.POINTER(_lib.EcBlockGrads))
         return g, bg
 
@@ -401,22 +449,8 @@ class VisualTower:
         return views, flat
 
     def canonical(self, names):
-        """The names in gradient-buffer order: embedding | blocks 0 .. L-1 | head, so that the part of the buffer a
-        stretch of the backward pass completes is one contiguous slice."""
-        emb = ('conv1.weight', 'class_embedding', 'positional_embedding', 'ln_pre.weight', 'ln_pre.bias')
-        head = ('ln_post.weight', 'ln_post.bias', 'proj')
-        leaf = {lf: i for i, (_, lf) in enumerate(_BLOCK)}
-
-        def rank(n):
-            if n in emb:
-                return (0, 0, emb.index(n))
-            if n in head:
-                return (2, 0, head.index(n))
-            m = re.match(r'^transformer\.resblocks\.(\d+)\.(.+)$', n)
-            if not m or m.group(2) not in leaf:
-                raise KeyError(f'{n!r} is not a parameter of the vision tower')
-            return (1, int(m.group(1)), leaf[m.group(2)])
-        return sorted(names, key=rank)
+        """``canonical_order``: embedding | blocks 0 .. L-1 | head."""
+        return canonical_order(names)
 
     def bucket_plan(self, want, blocks_per_bucket=4):
         """[(stage_begin, stage_end, flat_lo, flat_hi)]: the backward pass cut into the head, groups of
@@ -429,17 +463,15 @@ class VisualTower:
             hit = [spans[n] for n in want if pred(n)]
             return (min(o for o, _ in hit), max(o + c for o, c in hit)) if hit else (0, 0)
 
-        def block_of(n):
-            m = re.match(r'^transformer\.resblocks\.(\d+)\.', n)
-            return int(m.group(1)) if m else None
+        block_of = {n: visual_name_parts(n)[0] for n in want}
         L, plan = self.L, []
-        plan.append((0, 1) + span(lambda n: n in ('ln_post.weight', 'ln_post.bias', 'proj')))
+        plan.append((0, 1) + span(lambda n: n in _HEAD))
         hi = L - 1
         while hi >= 0:
             lo = max(hi - blocks_per_bucket + 1, 0)
-            plan.append((L - hi, L - lo + 1) + span(lambda n, lo=lo, hi=hi: block_of(n) is not None and lo <= block_of(n) <= hi))
+            plan.append((L - hi, L - lo + 1) + span(lambda n, lo=lo, hi=hi: block_of[n] is not None and lo <= block_of[n] <= hi))
             hi = lo - 1
-        plan.append((L + 1, L + 2) + span(lambda n: block_of(n) is None and n not in ('ln_post.weight', 'ln_post.bias', 'proj')))
+        plan.append((L + 1, L + 2) + span(lambda n: block_of[n] is None and n not in _HEAD))
         return plan
 
 
@@ -502,6 +534,7 @@ class LoraFactors:
         self.tower = tower
         tower.lora = self
         self.r, self.lora_k, self.lora_o = parse_lora(spec)
+        self.checkpoint_keys = lora_checkpoint_keys(spec, tower.L)
         W, dev = tower.W, tower.dev
         shapes = lora_factor_shapes(spec, tower.L, W)
         if params is None:
@@ -601,13 +634,7 @@ class LoraFactors:
 
     def state_dict_entries(self):
         """The tower's attention entries as the reference's LoRA-injected modules name them."""
-        t, out = self.tower, {}
-        for i in range(t.L):
-            pre = _block_name(i, 'attn')
-            out[pre + '.in_proj_weight.merged_proj'] = t.master[pre + '.in_proj_weight']
-            if self.lora_o:
-                out[pre + '.out_proj.linear.weight'] = t.master[pre + '.out_proj.weight']
-                out[pre + '.out_proj.linear.bias'] = t.master[pre + '.out_proj.bias']
+        out = {key: self.tower.master[name] for name, key in self.checkpoint_keys.items()}
         out.update(self.params)
         return out
 
@@ -620,10 +647,7 @@ def valid_patches(tower, data_dict):
     if 'patches' in data_dict:
         return data_dict['patches'], valid, data_dict['row_idx']
     row_idx = compact_row_idx(valid)
-    x = data_dict['img'][valid].to(t.dev, torch.float32).contiguous()
-    patches = torch.empty((x.shape[0], t.G, t.kpad), dtype=t.cd, device=t.dev)
-    _lib.launch('ec_patchify', x, x.shape[0], t.cfg['image_size'], t.P, t.kpad, patches, t.code)
-    return patches, valid, row_idx
+    return t.patchify(data_dict['img'][valid]), valid, row_idx
 
 
 class GradScaler:
@@ -766,7 +790,7 @@ class FTTrainer:
         data augmentation -- averaging gradients over replicas that started apart lets them drift apart for good.
         Masters that do not train are broadcast too (a rank may have built them differently); the 16-bit operand
         copies are rebuilt from what arrived."""
-        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        if world_size() == 1:
             return
         seen = set()
         for t in list(self.tensors.values()) + list(self.tower.master.values()):
@@ -808,15 +832,8 @@ class FTTrainer:
         self.resolve()
         t = self.tower
         vis = dict(vis)
-        src_of = {name: name for name in t.master}          # checkpoint key of every master
-        if self.lora:
-            for i in range(t.L):
-                pre = _block_name(i, 'attn')
-                src_of[pre + '.in_proj_weight'] = pre + '.in_proj_weight.merged_proj'
-                if self.lora.lora_o:
-                    src_of[pre + '.out_proj.weight'] = pre + '.out_proj.linear.weight'
-                    src_of[pre + '.out_proj.bias'] = pre + '.out_proj.linear.bias'
-        targets = [(m, src_of[name]) for name, m in t.master.items()]
+        renamed = self.lora.checkpoint_keys if self.lora else {}
+        targets = [(m, renamed.get(name, name)) for name, m in t.master.items()]
         if self.lora:
             targets += [(p, k) for k, p in self.lora.params.items()]
         for dst, key in targets:
@@ -824,11 +841,8 @@ class FTTrainer:
                 dst.copy_(torch.as_tensor(vis[key]).to(dst.device, dst.dtype))      # in place: addresses are baked in
             elif strict:
                 raise KeyError(f'checkpoint lacks model.visual.{key}')
-        if self.lora and not self.lora.lora_k:    # the k rows carry no factors: their merged rows are the base rows
-            W = t.W
-            for i in range(t.L):
-                n = _block_name(i, 'attn.in_proj_weight')
-                t.effective[n][W:2 * W].copy_(t.master[n][W:2 * W])
+        if self.lora:
+            self.lora.copy_plain_rows()
         t.pack()
         if self.lora:
             self.lora.merge()
@@ -926,8 +940,8 @@ class FTTrainer:
         clf, t = self.clf, self.tower
         patches, valid, row_idx = self._patches(data_dict)
         labels = data_dict['label'].to(t.dev)
-        ddp = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        world = dist.get_world_size() if ddp else 1
+        world = world_size()
+        ddp = world > 1
         if not clf.prompt_tuning:
             self._fixed_text = clf.get_text_feats().float()
         self.resolve()                                # the previous step's verdict: this step's scale
@@ -965,14 +979,8 @@ class FTTrainer:
 
     def visual_state_dict(self):
         """``model.visual.*`` as the reference's checkpoint holds it (LoRA keys when LoRA is on)."""
-        t = self.tower
-        out = dict(t.master)
+        renamed = self.lora.checkpoint_keys if self.lora else {}
+        out = {name: m for name, m in self.tower.master.items() if name not in renamed}
         if self.lora:
-            for i in range(t.L):
-                pre = _block_name(i, 'attn')
-                out.pop(pre + '.in_proj_weight')
-                if self.lora.lora_o:
-                    out.pop(pre + '.out_proj.weight')
-                    out.pop(pre + '.out_proj.bias')
             out.update(self.lora.state_dict_entries())
         return {'model.visual.' + k: v for k, v in out.items()}

@@ -446,7 +446,7 @@ def _tower_params(t, params, what):
     autograd routes their gradients; the kernels read them where the tower bound them (and their operand copies)."""
     names = t.trainable()
     keys = list(t.lora.params) if t.lora is not None else []
-    own = [t.master[n] for n in names] + [t.lora.params[k] for k in keys]
+    own = t.op_params()
     if len(params) != len(own):
         raise RuntimeError(f'{NAMESPACE}::{what}: {len(params)} parameters, {len(own)} expected (the trainable masters '
                            'in canonical() order, then the LoRA factors)')
@@ -455,6 +455,31 @@ def _tower_params(t, params, what):
             raise RuntimeError(f'{NAMESPACE}::{what}: params[{i}] {tuple(p.shape)} is not the tower\'s '
                                f'{(names + keys)[i]} {tuple(o.shape)}')
     return names, keys
+
+
+def _image_tape(t, n):
+    """``vit_image_fwd``'s tape -> (bytes of the training workspace rounded to 256, bytes of the tape: the workspace, then
+    the patch rows)"""
+    ws = (t.workspace_bytes(n) + 255) // 256 * 256
+    return ws, ws + n * t.G * t.kpad * 2
+
+
+def _forward_begin(what, x, params, tower_handle, image):
+    """The common start of ``vit_train_fwd`` (x: the patch rows) and ``vit_image_fwd`` (image: x is the fp32 image): the
+    tower behind the handle with its operand copies up to date (``VisualTower.refresh``), x checked, this call's outputs.
+    -> (tower, N, x contiguous, feats fp32 [N, D], the tape -- zeroed, its alignment gaps and scratch too: an output --,
+    (bytes of the training workspace at its head, bytes in all: ``_image_tape``))"""
+    t = _resolve(tower_handle, what)
+    _tower_params(t, params, what)
+    t.refresh()
+    n, R = int(x.shape[0]), t.cfg['image_size']
+    noun, dtype, row = ('image', torch.float32, (3, R, R)) if image else ('patches', t.cd, (t.G, t.kpad))
+    if x.dtype != dtype or tuple(x.shape) != (n,) + row or n == 0:
+        raise RuntimeError(f'{NAMESPACE}::{what}: {noun} {tuple(x.shape)} {x.dtype}, '
+                           f'[N > 0, {", ".join(map(str, row))}] {dtype} expected')
+    ws, total = _image_tape(t, n) if image else (t.workspace_bytes(n),) * 2
+    feats = torch.empty((n, t.D), dtype=torch.float32, device=x.device)
+    return t, n, x.contiguous(), feats, _lib.scratch(total, x.device).zero_(), (ws, total)
 
 
 @custom_op(f'{NAMESPACE}::vit_train_fwd', mutates_args=(), device_types='cuda')
@@ -466,16 +491,7 @@ def vit_train_fwd(patches: torch.Tensor, params: List[torch.Tensor],
     may be alive at once.  Operand copies of masters or factors written since they were packed are rebuilt first
     (``VisualTower.refresh``).  ``patches`` is not differentiable: a gradient in its 16 bits would underflow, and a patch
     row carries every pixel twice (hi | lo).  The gradient with respect to the image is ``vit_image_fwd``'s, in fp32."""
-    t = _resolve(tower_handle, 'vit_train_fwd')
-    _tower_params(t, params, 'vit_train_fwd')
-    t.refresh()
-    n = int(patches.shape[0])
-    if patches.dtype != t.cd or tuple(patches.shape) != (n, t.G, t.kpad) or n == 0:
-        raise RuntimeError(f'{NAMESPACE}::vit_train_fwd: patches {tuple(patches.shape)} {patches.dtype}, '
-                           f'[N > 0, {t.G}, {t.kpad}] {t.cd} expected')
-    patches = patches.contiguous()
-    feats = torch.empty((n, t.D), dtype=torch.float32, device=patches.device)
-    tape = _lib.scratch(t.workspace_bytes(n), patches.device).zero_()     # its alignment gaps and scratch too: an output
+    t, n, patches, feats, tape, _ = _forward_begin('vit_train_fwd', patches, params, tower_handle, image=False)
     _lib.launch('ec_vit_train_forward', t._vit, patches, n, feats, tape, tape.numel())
     return feats, tape
 
@@ -488,6 +504,45 @@ def _(patches, params, tower_handle):
             patches.new_empty((max(t.workspace_bytes(n), 256),), dtype=torch.uint8))
 
 
+def _tower_backward(t, what, params, need, patches, n, d_feats, tape, tape_bytes, need_image):
+    """The backward pass behind ``vit_train_bwd`` and ``vit_image_bwd`` over the first ``tape_bytes`` of a forward's tape
+    and its patch rows: ``ec_vit_train_backward_image`` with need_image, ``ec_vit_train_backward_over`` when only a
+    parameter gradient is needed, no launch when nothing is.  -> [d image, the gradient of params[0], params[1], ...],
+    every one a fresh allocation, an empty tensor for what is not needed."""
+    names, keys = _tower_params(t, params, what)
+    if len(need) != len(params):
+        raise RuntimeError(f'{NAMESPACE}::{what}: need has {len(need)} entries for {len(params)} parameters')
+    if n == 0 or tuple(d_feats.shape) != (n, t.D) or tape_bytes < t.workspace_bytes(n) or \
+            patches.numel() * patches.element_size() < n * t.G * t.kpad * 2:
+        raise RuntimeError(f'{NAMESPACE}::{what}: d_feats {tuple(d_feats.shape)} / tape of {tape.numel()} bytes do '
+                           f'not belong to a forward over {n} images')
+    d_feats, dev = _f32c(d_feats), d_feats.device
+    grads = [torch.empty_like(p) if b else None for p, b in zip(params, need)]
+    tower_grads = {k: g for k, g in zip(names, grads) if g is not None}
+    factor_grads = {k: g for k, g in zip(keys, grads[len(names):]) if g is not None}
+    # the kernels write both factors of a projection: the partner of a factor whose own gradient is not asked for gets a
+    # buffer that is dropped
+    for _, _, kd, ku in t.lora.projections() if factor_grads else ():
+        for a, b in ((kd, ku), (ku, kd)):
+            if a in factor_grads and b not in factor_grads:
+                factor_grads[b] = torch.empty_like(t.lora.params[b])
+    g, keep_g = t.grads_over(tower_grads)                                   # noqa: F841 (the struct's block array)
+    lora, keep_l = t.lora.struct_for(factor_grads) if factor_grads else (None, None)   # noqa: F841
+    d_image = None
+    if need_image:
+        R = t.cfg['image_size']
+        d_image = torch.empty((n, 3, R, R), dtype=torch.float32, device=dev)
+        scr = _lib.scratch(_lib.lib().ec_vit_train_backward_image_scratch_bytes(ctypes.byref(t._vit), n), dev)
+        conv_t, conv_lo_t = t.conv_operands()
+        _lib.launch('ec_vit_train_backward_image', t._vit, t._vit_t, patches, n, d_feats, g, lora, conv_t, conv_lo_t,
+                    d_image, tape, tape_bytes, scr, scr.numel())
+    elif tower_grads or factor_grads:
+        scr = _lib.scratch(_lib.lib().ec_vit_train_backward_scratch_bytes(ctypes.byref(t._vit), n), dev)
+        _lib.launch('ec_vit_train_backward_over', t._vit, t._vit_t, patches, n, d_feats, g, lora, tape, tape_bytes, scr,
+                    scr.numel())
+    return [d_feats.new_empty((0,), dtype=torch.float32) if x is None else x for x in [d_image] + grads]
+
+
 @custom_op(f'{NAMESPACE}::vit_train_bwd', mutates_args=(), device_types='cuda')
 def vit_train_bwd(patches: torch.Tensor, params: List[torch.Tensor], tape: torch.Tensor, d_feats: torch.Tensor,
                   tower_handle: int, need: List[bool]) -> List[torch.Tensor]:
@@ -496,31 +551,8 @@ def vit_train_bwd(patches: torch.Tensor, params: List[torch.Tensor], tape: torch
     allocation the caller owns.  The tape is only read (``ec_vit_train_backward_over``: the pass's scratch is this
     call's own), so a second call gives the same bits."""
     t = _resolve(tower_handle, 'vit_train_bwd')
-    names, keys = _tower_params(t, params, 'vit_train_bwd')
-    if len(need) != len(params):
-        raise RuntimeError(f'{NAMESPACE}::vit_train_bwd: need has {len(need)} entries for {len(params)} parameters')
     n = int(patches.shape[0])
-    if tuple(d_feats.shape) != (n, t.D) or tape.numel() < t.workspace_bytes(n):
-        raise RuntimeError(f'{NAMESPACE}::vit_train_bwd: d_feats {tuple(d_feats.shape)} / tape of {tape.numel()} bytes do '
-                           f'not belong to a forward over {n} images')
-    patches, d_feats = patches.contiguous(), _f32c(d_feats)
-    grads = [torch.empty_like(p) if b else None for p, b in zip(params, need)]
-    tower_grads = {k: g for k, g in zip(names, grads) if g is not None}
-    factor_grads = {k: g for k, g in zip(keys, grads[len(names):]) if g is not None}
-    spare = []                       # the partner of a factor whose own gradient is not asked for: written, dropped
-    if factor_grads:
-        for _, _, kd, ku in t.lora.projections():
-            for a, b in ((kd, ku), (ku, kd)):
-                if a in factor_grads and b not in factor_grads:
-                    spare.append(b)
-                    factor_grads[b] = torch.empty_like(t.lora.params[b])
-    g, keep_g = t.grads_over(tower_grads)                                   # noqa: F841 (the struct's block array)
-    lora, keep_l = t.lora.struct_for(factor_grads) if factor_grads else (None, None)   # noqa: F841
-    if tower_grads or factor_grads:
-        ws = _lib.scratch(_lib.lib().ec_vit_train_backward_scratch_bytes(ctypes.byref(t._vit), n), patches.device)
-        _lib.launch('ec_vit_train_backward_over', t._vit, t._vit_t, patches, n, d_feats, g, lora, tape, tape.numel(), ws,
-                    ws.numel())
-    return [patches.new_empty((0,), dtype=torch.float32) if x is None else x for x in grads]
+    return _tower_backward(t, 'vit_train_bwd', params, need, patches.contiguous(), n, d_feats, tape, tape.numel(), False)[1:]
 
 
 @vit_train_bwd.register_fake
@@ -528,16 +560,20 @@ def _(patches, params, tape, d_feats, tower_handle, need):
     return [p.new_empty(tuple(p.shape) if b else (0,), dtype=torch.float32) for p, b in zip(params, need)]
 
 
-def _vit_setup(ctx, inputs, output):
-    patches, params, tower_handle = inputs
-    ctx.save_for_backward(patches, output[1], *params)
+def _tower_setup(ctx, tower_handle, tape, *saved):
+    ctx.save_for_backward(tape, *saved)
     ctx.tower_handle = tower_handle
-    ctx.mark_non_differentiable(output[1])
+    ctx.mark_non_differentiable(tape)
     ctx.set_materialize_grads(False)
 
 
+def _vit_setup(ctx, inputs, output):
+    patches, params, tower_handle = inputs
+    _tower_setup(ctx, tower_handle, output[1], patches, *params)
+
+
 def _vit_backward(ctx, d_feats, d_tape):
-    patches, tape, *params = ctx.saved_tensors
+    tape, patches, *params = ctx.saved_tensors
     need = list(ctx.needs_input_grad[1])
     if d_feats is None or not any(need):
         return None, [None] * len(params), None
@@ -549,31 +585,14 @@ vit_train_fwd.register_autograd(_vit_backward, setup_context=_vit_setup)
 
 
 # ---- the same tower from the fp32 image, differentiable with respect to it ----
-def _image_tape(t, n):
-    """-> (bytes of the training workspace rounded to 256, bytes of the tape: the workspace, then the patch rows)"""
-    ws = (t.workspace_bytes(n) + 255) // 256 * 256
-    return ws, ws + n * t.G * t.kpad * 2
-
-
 @custom_op(f'{NAMESPACE}::vit_image_fwd', mutates_args=(), device_types='cuda')
 def vit_image_fwd(image: torch.Tensor, params: List[torch.Tensor], tower_handle: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """image fp32 [N, 3, R, R] (what ``ec_patchify`` takes), params as ``vit_train_fwd`` takes them -> (feats fp32 [N, D];
     tape uint8: the training workspace of ``vit_train_fwd`` followed by the 16-bit patch rows, which conv1's weight
     gradient reads).  The same launches as ``vit_train_fwd`` on ``patchify(image)``: the same bits.  The autograd formula
     returns d image (``vit_image_bwd``) next to the parameter gradients."""
-    t = _resolve(tower_handle, 'vit_image_fwd')
-    _tower_params(t, params, 'vit_image_fwd')
-    t.refresh()
-    n, R = int(image.shape[0]), t.cfg['image_size']
-    if image.dtype != torch.float32 or tuple(image.shape) != (n, 3, R, R) or n == 0:
-        raise RuntimeError(f'{NAMESPACE}::vit_image_fwd: image {tuple(image.shape)} {image.dtype}, '
-                           f'[N > 0, 3, {R}, {R}] torch.float32 expected')
-    image = image.contiguous()
-    ws, total = _image_tape(t, n)
-    feats = torch.empty((n, t.D), dtype=torch.float32, device=image.device)
-    tape = _lib.scratch(total, image.device).zero_()
-    patches = tape[ws:total]
-    _lib.launch('ec_patchify', image, n, R, t.P, t.kpad, patches, t.code)
+    t, n, image, feats, tape, (ws, total) = _forward_begin('vit_image_fwd', image, params, tower_handle, image=True)
+    patches = t.patchify(image, out=tape[ws:total])
     _lib.launch('ec_vit_train_forward', t._vit, patches, n, feats, tape, ws)
     return feats, tape
 
@@ -595,39 +614,9 @@ def vit_image_bwd(params: List[torch.Tensor], tape: torch.Tensor, d_feats: torch
     LoRA-gradient kernels run only for what ``need`` names, none at all for a frozen tower.  Without it this is
     ``vit_train_bwd`` on the tape's patch rows.  The tape is only read."""
     t = _resolve(tower_handle, 'vit_image_bwd')
-    names, keys = _tower_params(t, params, 'vit_image_bwd')
-    if len(need) != len(params):
-        raise RuntimeError(f'{NAMESPACE}::vit_image_bwd: need has {len(need)} entries for {len(params)} parameters')
-    n, R = int(d_feats.shape[0]), t.cfg['image_size']
-    ws, total = _image_tape(t, max(n, 1))
-    if n == 0 or tuple(d_feats.shape) != (n, t.D) or tape.numel() < total:
-        raise RuntimeError(f'{NAMESPACE}::vit_image_bwd: d_feats {tuple(d_feats.shape)} / tape of {tape.numel()} bytes do '
-                           f'not belong to a forward over {n} images')
-    d_feats = _f32c(d_feats)
-    patches = tape[ws:total]
-    grads = [torch.empty_like(p) if b else None for p, b in zip(params, need)]
-    tower_grads = {k: g for k, g in zip(names, grads) if g is not None}
-    factor_grads = {k: g for k, g in zip(keys, grads[len(names):]) if g is not None}
-    spare = []                       # the partner of a factor whose own gradient is not asked for: written, dropped
-    if factor_grads:
-        for _, _, kd, ku in t.lora.projections():
-            for a, b in ((kd, ku), (ku, kd)):
-                if a in factor_grads and b not in factor_grads:
-                    spare.append(b)
-                    factor_grads[b] = torch.empty_like(t.lora.params[b])
-    g, keep_g = t.grads_over(tower_grads)                                   # noqa: F841 (the struct's block array)
-    lora, keep_l = t.lora.struct_for(factor_grads) if factor_grads else (None, None)   # noqa: F841
-    d_image = None
-    if need_image:
-        d_image = torch.empty((n, 3, R, R), dtype=torch.float32, device=d_feats.device)
-        scr = _lib.scratch(_lib.lib().ec_vit_train_backward_image_scratch_bytes(ctypes.byref(t._vit), n), d_feats.device)
-        conv_t, conv_lo_t = t.conv_operands()
-        _lib.launch('ec_vit_train_backward_image', t._vit, t._vit_t, patches, n, d_feats, g, lora, conv_t, conv_lo_t,
-                    d_image, tape, ws, scr, scr.numel())
-    elif tower_grads or factor_grads:
-        scr = _lib.scratch(_lib.lib().ec_vit_train_backward_scratch_bytes(ctypes.byref(t._vit), n), d_feats.device)
-        _lib.launch('ec_vit_train_backward_over', t._vit, t._vit_t, patches, n, d_feats, g, lora, tape, ws, scr, scr.numel())
-    return [d_feats.new_empty((0,), dtype=torch.float32) if x is None else x for x in [d_image] + grads]
+    n = int(d_feats.shape[0])
+    ws, total = _image_tape(t, n)
+    return _tower_backward(t, 'vit_image_bwd', params, need, tape[ws:total], n, d_feats, tape, ws, need_image)
 
 
 @vit_image_bwd.register_fake
@@ -639,14 +628,11 @@ def _(params, tape, d_feats, tower_handle, need_image, need):
 
 
 def _vit_image_setup(ctx, inputs, output):
-    image, params, tower_handle = inputs
-    ctx.save_for_backward(output[1], *params)
-    ctx.tower_handle = tower_handle
+    _, params, tower_handle = inputs
+    _tower_setup(ctx, tower_handle, output[1], *params)
     # the graph keeps its tower alive (handles are weak): an owner that drops or rebuilds its cached tower -- CLIP.cuda() /
     # .to() after encode_image(differentiable=True) -- leaves a live graph able to run its backward
     ctx.tower = _resolve(tower_handle, 'vit_image_fwd')
-    ctx.mark_non_differentiable(output[1])
-    ctx.set_materialize_grads(False)
 
 
 def _vit_image_backward(ctx, d_feats, d_tape):

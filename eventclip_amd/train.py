@@ -21,6 +21,11 @@ _AGG = {'sum': _lib.EC_AGG_SUM, 'mean': _lib.EC_AGG_MEAN, 'max': _lib.EC_AGG_MAX
 _scratch = collections.defaultdict(_lib.Scratch)      # device index -> the loss kernels' workspace
 
 
+def world_size():
+    """Ranks of torch.distributed's default process group; 1 without one."""
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
 def fs_text_loss_grad(img_feats, valid, labels, text_param, logit_scale, agg='sum', use_probs_loss=False,
                       return_logits=False):
     """img_feats fp32 CUDA [B, T, D] (raw encoder outputs), valid bool [B, T], labels int [B],
@@ -144,9 +149,9 @@ class TextFeatTrainer:
         clf = self.clf
         loss, grad = fs_text_loss_grad(img_feats, valid, labels, clf.text_feats.data, clf.logit_scale,
                                        clf.agg_func, clf.use_probs_loss)
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if world_size() > 1:
             dist.all_reduce(grad)                                        # DDP: mean of the rank gradients
-            grad /= dist.get_world_size()
+            grad /= world_size()
         lr = cosine_warmup_lr(self.steps, self.total_steps, self.lr, self.lr / 100., self.warmup_steps)
         self.steps += 1
         adam_step(clf.text_feats.data, grad, self.exp_avg, self.exp_avg_sq, self.steps, lr, self.betas,
@@ -188,9 +193,9 @@ class AdapterTrainer:
         loss, _ = fs_trans_loss_grad(img_feats, valid, labels, text, clf.logit_scale, clf.adapter,
                                      clf.agg_func, clf.use_probs_loss, dropout_p=self.dropout,
                                      seed=self.seed * 1000003 + self.steps, out=self._grads)
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if world_size() > 1:
             dist.all_reduce(self._flat)
-            self._flat /= dist.get_world_size()
+            self._flat /= world_size()
         lr = cosine_warmup_lr(self.steps, self.total_steps, self.lr, self.lr / 100., self.warmup_steps)
         self.steps += 1
         _lib.launch('ec_adam_step_multi', self._items, len(self.tensors), self._max_n, float(lr), float(lr),

@@ -41,6 +41,50 @@ def test_lora_spec_parsing():
         ft.parse_lora('kv-4')                                    # lora.py:353: q and v are mandatory
 
 
+def test_visual_names_parse_to_block_and_struct_field():
+    for field, leaf in ft._TOP:
+        assert ft.visual_name_parts(leaf) == (None, field)
+    for block in (0, 11):
+        for field, leaf in ft._BLOCK:
+            assert ft.visual_name_parts(ft._block_name(block, leaf)) == (block, field)
+    for bad in ('transformer.resblocks.0.attn.bogus', 'visual.proj'):
+        with pytest.raises(KeyError, match='is not a parameter of the vision tower'):
+            ft.visual_name_parts(bad)
+        with pytest.raises(KeyError):
+            ft.canonical_order(['proj', bad])
+
+
+def test_canonical_order_is_embedding_blocks_head():
+    import random
+    ns = names(2)
+    block = lambda i: [ft._block_name(i, leaf) for _, leaf in ft._BLOCK]      # noqa: E731
+    want = ['conv1.weight', 'class_embedding', 'positional_embedding', 'ln_pre.weight', 'ln_pre.bias'] + block(0) + \
+        block(1) + ['ln_post.weight', 'ln_post.bias', 'proj']
+    assert sorted(want) == sorted(ns)
+    for seed in range(3):
+        shuffled = list(ns)
+        random.Random(seed).shuffle(shuffled)
+        assert ft.canonical_order(shuffled) == want
+    assert ft.canonical_order(['proj', ft._block_name(1, 'ln_1.bias'), 'ln_pre.bias']) == \
+        ['ln_pre.bias', ft._block_name(1, 'ln_1.bias'), 'proj']            # a subset keeps the rule
+
+
+@pytest.mark.parametrize('spec', ['qv-2', 'qkv-2', 'qkvo-2'])
+def test_lora_checkpoint_keys_and_plain_names_are_inverses(spec):
+    keys = ft.lora_checkpoint_keys(spec, 2)
+    masters = set(names(2))
+    assert set(keys) <= masters
+    for master, key in keys.items():
+        assert key != master and ft.plain_visual_name(key) == master
+    for master in masters - set(keys):                   # every other master keeps its name in the checkpoint
+        assert ft.plain_visual_name(master) == master
+    factors = ft.lora_factor_shapes(spec, 2, 64)
+    assert factors and all(ft.plain_visual_name(k) is None for k in factors)
+    out_proj = {ft._block_name(i, 'attn.out_proj.' + leaf) for i in range(2) for leaf in ('weight', 'bias')}
+    in_proj = {ft._block_name(i, 'attn.in_proj_weight') for i in range(2)}
+    assert set(keys) == (in_proj | out_proj if spec == 'qkvo-2' else in_proj)
+
+
 def test_grad_scaler_policy_is_torchs():
     s = ft.GradScaler(init_scale=1024.0, growth_interval=3)
     for found in (False, False, True, False, False, False, False):

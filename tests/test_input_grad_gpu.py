@@ -310,6 +310,49 @@ def test_frozen_tower_gives_the_same_image_gradient_and_launches_no_weight_gradi
     assert got[0].numel() == 0 and all(torch.equal(a, b) for a, b in zip(got[1:], ref))
 
 
+@pytest.mark.parametrize('spec', [None, 'qv-2'])
+def test_without_the_image_the_two_backward_ops_are_one_pass(hip, monkeypatch, spec):
+    """``vit_image_bwd(need_image=False, need)`` returns the bits of ``vit_train_bwd(patches, need)``: with every master
+    needed (spec None); under 'qv-2' with every factor needed and with exactly one factor of a down / up pair needed --
+    the kernels write both, so the op has to find the partner a buffer, and the wanted gradient is the one the full call
+    gives.  With nothing needed neither op launches."""
+    from eventclip_amd import torch_ops
+    ops = torch.ops.eventclip_hip
+    tower, params, names, cfg, n, _ = A.tower_with_params('tiny', spec=spec)
+    torch.manual_seed(8)
+    imgs = torch.randn(n, 3, cfg['image_size'], cfg['image_size'], device='cuda')
+    d_feats = torch.randn(n, cfg['embed_dim'], device='cuda')
+    h = torch_ops.handle_of(tower)
+    plain = [p.detach() for p in params]
+    patches = T._patchify(tower, imgs)
+    _, tape0 = ops.vit_train_fwd(patches, plain, h)
+    _, tape = ops.vit_image_fwd(imgs, plain, h)
+    needs = [[True] * len(plain)]
+    if spec is not None:
+        _, _, kd, ku = tower.lora.projections()[-1]             # v of the last block: the pass stops there
+        needs += [[k == kd for k in names], [k == ku for k in names]]
+        assert all(sum(need) == 1 for need in needs[1:])
+    launches = A.count_launches(monkeypatch)
+    full = None
+    for need in needs:
+        got = ops.vit_image_bwd(plain, tape, d_feats, h, False, need)
+        ref = ops.vit_train_bwd(patches, plain, tape0, d_feats, h, need)
+        full = full or ref
+        assert len(got) == 1 + len(ref) == 1 + len(plain) and got[0].numel() == 0
+        for k, b, p, a, r, f in zip(names, need, plain, got[1:], ref, full):
+            if b:
+                assert a.shape == p.shape and bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0, k
+                assert torch.equal(a, r) and torch.equal(a, f), k
+            else:
+                assert a.numel() == 0 and r.numel() == 0, k
+    assert [nm for nm, _ in launches] == ['ec_vit_train_backward_over'] * (2 * len(needs))
+    del launches[:]
+    none = [False] * len(plain)
+    assert all(t.numel() == 0 for t in ops.vit_image_bwd(plain, tape, d_feats, h, False, none))
+    assert all(t.numel() == 0 for t in ops.vit_train_bwd(patches, plain, tape0, d_feats, h, none))
+    assert not launches
+
+
 # ------------------------------------------------------------------------------------------------
 # 5. the classifier
 # ------------------------------------------------------------------------------------------------

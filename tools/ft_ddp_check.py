@@ -73,16 +73,12 @@ def main():
     out = None
     if rank == 0:
         import eventclip_amd.ft as ftmod
-        saved = ftmod.dist
-        class _NoDist:                         # the single-process reference run must not see the process group
-            @staticmethod
-            def is_available():
-                return False
-        ftmod.dist = _NoDist
+        saved = ftmod.world_size
+        ftmod.world_size = lambda: 1           # the single-process reference run must not see the process group
         clf1, tr1 = build(mode)
         whole = tr1.step({'img': imgs.cuda(), 'valid_mask': valid.cuda(), 'label': labels.cuda()})
         tr1.resolve()
-        ftmod.dist = saved
+        ftmod.world_size = saved
         worst = 0.0
         for k, v in tr1.last['grads'].items():
             if k.endswith('attn.in_proj_bias'):
