@@ -23,11 +23,17 @@
 //  * blockIdx -> tile mapping is XCD-aware: the 8 XCDs each get a contiguous
 //    range of tiles ordered N-fastest, so the N/BN tiles that share an
 //    activation row panel hit the same L2.
+//
+// Host side, each said once: epi_traits (what an epilogue is: the kernel and launch2pp read it), check_args
+// (ec_gemm_args -> GemmArgs + Launch, or the refusal), launch_table (every legal (epilogue, segments, lo output) ->
+// its launch2pp instantiation; launch_row adds the activation and the diagnostic variants), try_kbatched (the
+// low-latency form; its split rule is tower_ops.h's kbatch_splits).  ec_gemm = check, try the K-batched form, dispatch.
 #include <type_traits>
 
 #include "activation.h"
 #include "common.h"
 #include "mfma.h"
+#include "tower_ops.h"
 
 namespace {
 
@@ -141,16 +147,40 @@ template <int ACT> __device__ __forceinline__ float act_gelu_grad(float x)
     if constexpr (ACT == ACT_ERF) return gelu_erf_grad(x);
     else return quick_gelu_grad(x);
 }
-constexpr bool epi_is_gelu(int e)
+// The lo output of STORE16 / GELU16 (args.aux in the launches that take A_lo / W_lo): none, 16-bit, or e4m3 bytes
+enum { LO_NONE = 0, LO_16 = 1, LO_E4M3 = 2 };
+
+// What an epilogue IS, said once: the kernel, launch2pp and ec_gemm's checks all read it from here.
+struct EpiTraits {
+    bool out16;        // runs the 16-bit epilogue forms and C has 2-byte elements (RESID_HL: the fp32 forms' tile scratch)
+    bool gelu;         // applies ec_gemm_args.activation
+    bool ln;           // LayerNorm folded in: reads row_stats / col_sums
+    bool buf;          // buffer-addressed epilogue; false: the general LDS form (the training epilogues)
+    int tail;          // hand-over wait: the epilogue's last `tail` memory operations need not have completed (0: all must)
+    int lds_extra;     // LDS bytes behind the two staging buffers: the statistics' side area / the tail of the hi-lo scratch
+    int prof;          // profiler class
+    double out_bytes;  // bytes written (and read) per output element, for the profiler's byte count
+};
+constexpr EpiTraits epi_traits(int e, int lo = LO_NONE)
 {
-    return e == EC_EPI_GELU16 || e == EC_EPI_GELU16_SAVE || e == EC_EPI_GELU_BWD16 || e == EC_EPI_GELU16_LN;
+    const int t16 = lo != LO_NONE ? 32 : 16;             // a lo output doubles the stores and the bytes
+    const double b16 = lo != LO_NONE ? 4.0 : 2.0;
+    switch (e) {                       // out16  gelu   ln     buf    tail lds_extra prof                    out_bytes
+    case EC_EPI_STORE16:     return {true,  false, false, true,  t16, 0,        ec::PROF_GEMM_STORE16, b16};
+    case EC_EPI_GELU16:      return {true,  true,  false, true,  t16, 0,        ec::PROF_GEMM_GELU16,  b16};
+    case EC_EPI_RESID32:     return {false, false, false, true,  48,  0,        ec::PROF_GEMM_RESID32, 8.0};
+    case EC_EPI_STORE32:     return {false, false, false, true,  32,  0,        ec::PROF_GEMM_STORE32, 4.0};
+    case EC_EPI_GELU16_SAVE: return {true,  true,  false, false, 0,   0,        ec::PROF_GEMM_GELU16,  4.0};
+    case EC_EPI_GELU_BWD16:  return {true,  true,  false, false, 0,   0,        ec::PROF_GEMM_STORE16, 4.0};
+    case EC_EPI_RESID_HL:    return {false, false, false, true,  48,  4608,     ec::PROF_GEMM_RESID32, 8.0};
+    case EC_EPI_STORE16_LN:  return {true,  false, true,  true,  t16, 2 * 2048, ec::PROF_GEMM_STORE16, b16};
+    case EC_EPI_GELU16_LN:   return {true,  true,  true,  true,  t16, 2 * 2048, ec::PROF_GEMM_GELU16,  b16};
+    default:                 return {false, false, false, false, 0,   0,        ec::PROF_GEMM_STORE32, 4.0};   // no epilogue
+    }
 }
-constexpr bool epi_is16(int e)
-{
-    return e == EC_EPI_STORE16 || e == EC_EPI_GELU16 || e == EC_EPI_GELU16_SAVE || e == EC_EPI_GELU_BWD16 ||
-           e == EC_EPI_STORE16_LN || e == EC_EPI_GELU16_LN;
-}
-constexpr bool epi_is_ln(int e) { return e == EC_EPI_STORE16_LN || e == EC_EPI_GELU16_LN; }
+constexpr bool epi_is_gelu(int e) { return epi_traits(e).gelu; }
+constexpr bool epi_is16(int e) { return epi_traits(e).out16; }
+constexpr bool epi_is_ln(int e) { return epi_traits(e).ln; }
 
 // bijective XCD remap (blocks b and b+8 share an XCD): XCD x gets a contiguous id range
 __device__ __forceinline__ int xcd_remap(int bid, int nblk)
@@ -747,11 +777,11 @@ __device__ __forceinline__ void raster(int id, int tiles_m, int tiles_n, int &tm
 // check on gfx950 -- offset + soffset >= num_records reads zeros -- so a range that covers it no longer ends at the
 // tile's last row).  Region 1 is requested one K tile apart from regions 0, 2, 3 and has a descriptor of its own.
 // LO: STORE16 / GELU16 also write the lo part of their output to args.aux (the split-precision launches only)
-enum { LO_NONE = 0, LO_16 = 1, LO_E4M3 = 2 };
 template <int DT, int EPI, int TL = 0, bool TN = false, int LO = LO_NONE, int SEG = 0, int ACT = ACT_QUICK>
 __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
 {
-    static_assert(ACT == ACT_QUICK || epi_is_gelu(EPI), "an activation goes with the GELU epilogues");
+    constexpr EpiTraits ET = epi_traits(EPI, LO);
+    static_assert(ACT == ACT_QUICK || ET.gelu, "an activation goes with the GELU epilogues");
     typedef typename T16<DT>::v8 v8;
     typedef typename T16<DT>::v4 v4;
     static_assert(!TN || EPI == EC_EPI_STORE32, "transposed operands: fp32 store only");
@@ -1181,7 +1211,7 @@ __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
 
         const int cm0 = m0, cn0 = n0;
         if (g.splits > 1)
-            ge.C = static_cast<unsigned char *>(g.C) + (long)sp0 * g.split_stride * (epi_is16(EPI) ? 2 : 4);
+            ge.C = static_cast<unsigned char *>(g.C) + (long)sp0 * g.split_stride * (ET.out16 ? 2 : 4);
         const int next = id + gridDim.x;
         const bool more = next < ntiles;
         tstamp(3);
@@ -1210,17 +1240,15 @@ __global__ __launch_bounds__(512) void gemm2pp_kernel(const GemmArgs g)
         // tile (their stores are never predicated: the range check drops what does not exist).  The asm form is the
         // scheduling fence; the builtin right behind it costs nothing (it is satisfied already) and tells hipcc's
         // wait-count pass what has completed.
-        constexpr bool BUF_EPI = EPI == EC_EPI_RESID_HL || EPI == EC_EPI_STORE16 || EPI == EC_EPI_GELU16 || epi_is_ln(EPI) ||
-                                 EPI == EC_EPI_STORE32 || EPI == EC_EPI_RESID32;
         constexpr bool LOUT = LO != LO_NONE;       // 16-bit output as hi + lo parts (args.aux)
         constexpr bool LOUT8 = LO == LO_E4M3;      // ... the lo part as e4m3 bytes
-        constexpr int TAIL = !BUF_EPI ? 0 : EPI == EC_EPI_RESID_HL ? 48 : EPI == EC_EPI_STORE32 ? 32 : EPI == EC_EPI_RESID32 ? 48 : LOUT ? 32 : 16;
+        constexpr int TAIL = ET.tail;
         constexpr int enc_tail = (TAIL & 15) | (7 << 4) | (15 << 8) | ((TAIL >> 4) << 14);
         if constexpr (EPI == EC_EPI_RESID_HL)
             epilogue_hl_buf<DT, 8>(ge, acc, wm0, wn0, elane, reinterpret_cast<float *>(smem + KT) + wave * (2 * 16 * 68), next_tile);
-        else if constexpr (!epi_is16(EPI))
+        else if constexpr (!ET.out16)
             epilogue32_buf<EPI, 8, TN>(ge, acc, wm0, wn0, elane, reinterpret_cast<float *>(smem + KT) + wave * (16 * 68), next_tile);
-        else if constexpr (BUF_EPI) {
+        else if constexpr (ET.buf) {
             if (lds_stats)
                 epilogue16_buf<DT, EPI, 8, true, LOUT, LOUT8, ACT>(ge, acc, wm0, wn0, elane, smem + KT + wave * (2 * 16 * 144),
                                                  side + slot * 512 + wm * 256, next_tile);
@@ -1263,27 +1291,22 @@ int launch2pp(const GemmArgs &g0, hipStream_t stream)
     GemmArgs g = g0;
     g.tiles_m = ec::ceil_div(g.M, 256);
     g.tiles_n = ec::ceil_div(g.N, 256);
+    constexpr EpiTraits ET = epi_traits(EPI, LO);
     // two staging buffers + the row-statistics side area (LN epilogues) / the tail of the hi-lo epilogue's double
     // scratch (8 waves x 2 x 16 rows x 68 floats = 68 KiB from the second staging buffer on)
-    constexpr int lds = 2 * 4 * 128 * 128 + (epi_is_ln(EPI) ? 2 * 2048 : 0) + (EPI == EC_EPI_RESID_HL ? 4608 : 0);
+    constexpr int lds = 2 * 4 * 128 * 128 + ET.lds_extra;
     auto kern = gemm2pp_kernel<DT, EPI, TL, TN, LO, SEG, ACT>;
     if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds)) return rc;
     const int cus = ec::cu_count();
     EC_REQUIRE(cus > 0, "ec_gemm: cannot read the device's compute-unit count");
-    constexpr int cls = (EPI == EC_EPI_STORE16 || EPI == EC_EPI_GELU_BWD16 || EPI == EC_EPI_STORE16_LN) ? ec::PROF_GEMM_STORE16
-                        : (EPI == EC_EPI_GELU16 || EPI == EC_EPI_GELU16_SAVE || EPI == EC_EPI_GELU16_LN) ? ec::PROF_GEMM_GELU16
-                        : (EPI == EC_EPI_RESID32 || EPI == EC_EPI_RESID_HL) ? ec::PROF_GEMM_RESID32 : ec::PROF_GEMM_STORE32;
-    constexpr double out_b = (EPI == EC_EPI_STORE16 || EPI == EC_EPI_GELU16 || epi_is_ln(EPI)) ? (LO != LO_NONE ? 4.0 : 2.0)
-                             : (EPI == EC_EPI_GELU16_SAVE || EPI == EC_EPI_GELU_BWD16) ? 4.0
-                             : ((EPI == EC_EPI_RESID32 || EPI == EC_EPI_RESID_HL) ? 8.0 : 4.0);
     // segments: every product's flops; the bytes of the parts that exist (a part shared by two segments counts once)
     const int nseg = SEG ? g.nseg : 1;
     const unsigned full = (1u << nseg) - 1, ma = g.seg_mask & full, mw = (g.seg_mask >> 4) & full;
     const int parts_a = SEG && ma != 0 && ma != full ? 2 : 1, parts_w = SEG && mw != 0 && mw != full ? 2 : 1;
     const int nf8 = SEG == 2 ? g.nf8 : 0;    // (an e4m3 product: the same flops, half the operand bytes)
-    ec::ProfScope prof(g.splits > 1 ? (int)ec::PROF_GEMM_DW : cls, stream, 2.0 * g.M * g.N * g.K * g.splits * nseg,
+    ec::ProfScope prof(g.splits > 1 ? (int)ec::PROF_GEMM_DW : ET.prof, stream, 2.0 * g.M * g.N * g.K * g.splits * nseg,
                        (2.0 * g.M * g.K * parts_a + 2.0 * g.N * g.K * parts_w + nf8 * (1.0 * g.M * g.K + 1.0 * g.N * g.K) +
-                        out_b * g.M * g.N) * g.splits);
+                        ET.out_bytes * g.M * g.N) * g.splits);
     const int tiles = g.tiles_m * g.tiles_n * g.splits;
     hipLaunchKernelGGL(kern, dim3(tiles < cus ? tiles : cus), dim3(512), lds, stream, g);
     EC_CHECK_HIP(hipGetLastError());
@@ -1366,108 +1389,102 @@ __global__ __launch_bounds__(256, 1) void mfma_probe_kernel(const unsigned char 
 #endif
 
 
+// What check_args makes of an ec_gemm_args beside the GemmArgs: which kernel of the table below runs
+struct Launch {
+    int dtype, epi;
+    int seg;          // 0: plain operands; 1: 16-bit A_lo / W_lo segments; 2: e4m3 lo products in front of them
+    int lo;           // LO_*: the lo output of STORE16 / GELU16
+    int act, variant; // ACT_*; ec_gemm_args.variant
+    bool tn;          // transposed operands
+    float *ws;        // non-null: a candidate for the K-batched form with this scratch (try_kbatched decides)
+    size_t ws_bytes;
+};
+
 // Variant 0, the default kernel, is the only one that ships.  The diagnostic build (-DEC_GEMM_DIAG: python -m
 // eventclip_amd.build --diag, which tools/ load explicitly) adds the same kernel with s_memtime records through
 // args.diag: 18 = per-tile timeline records, 19 = clock stamps at the workgroup's start and end.  The product
 // library rejects those variant numbers.
-template <int DT, int EPI> int dispatch_variant(const GemmArgs &g, int variant, hipStream_t s)
-{
-    switch (variant) {
-    case 0: return launch2pp<DT, EPI>(g, s);                     // default: persistent staggered 2-phase
 #ifdef EC_GEMM_DIAG
-    case 18: return launch2pp<DT, EPI, 1>(g, s);     // timeline records -> args.diag
-    case 19: return launch2pp<DT, EPI, 2>(g, s);     // clock stamps at the workgroup's start and end -> args.diag
+constexpr bool DIAG_BUILD = true;
+#else
+constexpr bool DIAG_BUILD = false;
 #endif
-    default:
-        return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown variant %d (diagnostic variants need an "
-                        "EC_GEMM_DIAG build)", variant);
+constexpr bool diag_variant(int v) { return DIAG_BUILD && (v == 18 || v == 19); }
+
+// One row of the table: the kernel of (EPI, SEG, LO) with the activation the caller named and, for the rows that exist
+// with records (DIAG: the plain inference epilogues), the diagnostic build's variants.
+template <int DT, int EPI, int SEG = 0, int LO = LO_NONE, bool DIAG = false> int launch_row(const GemmArgs &g, const Launch &l, hipStream_t s)
+{
+    if constexpr (SEG == 2 && DT != EC_F16) {
+        return ec::fail(EC_ERR_INVALID, "ec_gemm: e4m3 lo products need dtype EC_F16");
+    } else {
+        if constexpr (DIAG && DIAG_BUILD) {
+            if (l.variant == 18) return launch2pp<DT, EPI, 1>(g, s);     // timeline records -> args.diag
+            if (l.variant == 19) return launch2pp<DT, EPI, 2>(g, s);     // clock stamps at the workgroup's start and end -> args.diag
+        }
+        if (l.variant != 0) return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown variant %d (diagnostic variants need an EC_GEMM_DIAG build)", l.variant);
+        if constexpr (epi_is_gelu(EPI))
+            if (l.act == ACT_ERF) return launch2pp<DT, EPI, 0, false, LO, SEG, ACT_ERF>(g, s);
+        return launch2pp<DT, EPI, 0, false, LO, SEG>(g, s);                // default: persistent staggered 2-phase
     }
 }
 
-// a GELU epilogue of the default kernel with the activation the caller named (ec_gemm_args.activation)
-template <int DT, int EPI, int LO = LO_NONE, int SEG = 0> int launch_gelu(const GemmArgs &g, int act, hipStream_t s)
+// THE TABLE of legal launches: every (epilogue, segments, lo output) that has a kernel, once.  What has no row is refused.
+constexpr long row(int epi, int seg, int lo) { return (long)epi * 16 + seg * 4 + lo; }
+template <int DT> int launch_table(const GemmArgs &g, const Launch &l, hipStream_t s)
 {
-    static_assert(epi_is_gelu(EPI), "GELU epilogues only");
-    return act == ACT_ERF ? launch2pp<DT, EPI, 0, false, LO, SEG, ACT_ERF>(g, s) : launch2pp<DT, EPI, 0, false, LO, SEG>(g, s);
-}
-
-template <int DT> int dispatch_epi(const GemmArgs &g, int epi, int variant, int act, hipStream_t s)
-{
-    EC_REQUIRE(act == ACT_QUICK || variant == 0, "ec_gemm: args.activation = %d needs variant 0", act);
-    if (g.nseg > 1) {
-        // split-precision operands: the segmented main loop (default variant only)
-        EC_REQUIRE(variant == 0, "ec_gemm: A_lo / W_lo need variant 0");
-        if (g.nf8 > 0) {
-            // ... with e4m3 lo products in front (f16 only; the epilogues the tolerance mode's blocks use)
-            if constexpr (DT == EC_F16) {
-                switch (epi) {
-                case EC_EPI_STORE16:
-                    return g.aux ? launch2pp<DT, EC_EPI_STORE16, 0, false, LO_16, 2>(g, s)
-                                 : launch2pp<DT, EC_EPI_STORE16, 0, false, LO_NONE, 2>(g, s);
-                case EC_EPI_GELU16:
-                    if (g.aux && g.aux8_scale != 0.f) return launch_gelu<DT, EC_EPI_GELU16, LO_E4M3, 2>(g, act, s);
-                    return g.aux ? launch_gelu<DT, EC_EPI_GELU16, LO_16, 2>(g, act, s)
-                                 : launch_gelu<DT, EC_EPI_GELU16, LO_NONE, 2>(g, act, s);
-                case EC_EPI_STORE32: return launch2pp<DT, EC_EPI_STORE32, 0, false, LO_NONE, 2>(g, s);
-                case EC_EPI_RESID_HL:
-                    EC_REQUIRE(g.aux, "ec_gemm: EC_EPI_RESID_HL needs args.aux (the lo plane)");
-                    return launch2pp<DT, EC_EPI_RESID_HL, 0, false, LO_NONE, 2>(g, s);
-                default: return ec::fail(EC_ERR_INVALID, "ec_gemm: e4m3 lo products go with the STORE16, GELU16, STORE32 and RESID_HL epilogues (got %d)", epi);
-                }
-            } else {
-                return ec::fail(EC_ERR_INVALID, "ec_gemm: e4m3 lo products need dtype EC_F16");
-            }
-        }
-        switch (epi) {
-        case EC_EPI_STORE16:
-            return g.aux ? launch2pp<DT, EC_EPI_STORE16, 0, false, LO_16, 1>(g, s)
-                         : launch2pp<DT, EC_EPI_STORE16, 0, false, LO_NONE, 1>(g, s);
-        case EC_EPI_GELU16:
-            return g.aux ? launch_gelu<DT, EC_EPI_GELU16, LO_16, 1>(g, act, s)
-                         : launch_gelu<DT, EC_EPI_GELU16, LO_NONE, 1>(g, act, s);
-        case EC_EPI_STORE32: return launch2pp<DT, EC_EPI_STORE32, 0, false, LO_NONE, 1>(g, s);
-        case EC_EPI_RESID32: return launch2pp<DT, EC_EPI_RESID32, 0, false, LO_NONE, 1>(g, s);
-        case EC_EPI_RESID_HL:
-            EC_REQUIRE(g.aux, "ec_gemm: EC_EPI_RESID_HL needs args.aux (the lo plane)");
-            return launch2pp<DT, EC_EPI_RESID_HL, 0, false, LO_NONE, 1>(g, s);
-        default: return ec::fail(EC_ERR_INVALID, "ec_gemm: A_lo / W_lo go with the STORE16, GELU16, STORE32, RESID32 and RESID_HL epilogues (got %d)", epi);
-        }
-    }
-    EC_REQUIRE(!((epi == EC_EPI_STORE16 || epi == EC_EPI_GELU16) && g.aux),
-               "ec_gemm: STORE16 / GELU16 write their lo part (args.aux) in the launches that take A_lo / W_lo only");
-    switch (epi) {
-    case EC_EPI_STORE16: return dispatch_variant<DT, EC_EPI_STORE16>(g, variant, s);
-    case EC_EPI_GELU16: return act == ACT_ERF ? launch_gelu<DT, EC_EPI_GELU16>(g, act, s) : dispatch_variant<DT, EC_EPI_GELU16>(g, variant, s);
-    case EC_EPI_RESID32: return dispatch_variant<DT, EC_EPI_RESID32>(g, variant, s);
-    case EC_EPI_STORE32: return dispatch_variant<DT, EC_EPI_STORE32>(g, variant, s);
+    EC_REQUIRE(l.act == ACT_QUICK || l.variant == 0, "ec_gemm: args.activation = %d needs variant 0", l.act);
+    const bool v0 = l.variant == 0 || diag_variant(l.variant);     // the default kernel or (diagnostic build) its records
+    switch (row(l.epi, l.seg, l.lo)) {
+    // ---- plain operands
+    case row(EC_EPI_STORE16, 0, LO_NONE): return launch_row<DT, EC_EPI_STORE16, 0, LO_NONE, true>(g, l, s);
+    case row(EC_EPI_GELU16, 0, LO_NONE): return launch_row<DT, EC_EPI_GELU16, 0, LO_NONE, true>(g, l, s);
+    case row(EC_EPI_RESID32, 0, LO_NONE): return launch_row<DT, EC_EPI_RESID32, 0, LO_NONE, true>(g, l, s);
+    case row(EC_EPI_STORE32, 0, LO_NONE):
+        return l.tn ? launch2pp<DT, EC_EPI_STORE32, 0, true>(g, s) : launch_row<DT, EC_EPI_STORE32, 0, LO_NONE, true>(g, l, s);
     // the training epilogues only exist in the default kernel
-    case EC_EPI_GELU16_SAVE:
-        EC_REQUIRE(variant == 0 && g.aux, "ec_gemm: EC_EPI_GELU16_SAVE needs variant 0 and args.aux");
-        return launch_gelu<DT, EC_EPI_GELU16_SAVE>(g, act, s);
-    case EC_EPI_GELU_BWD16:
-        EC_REQUIRE(variant == 0 && g.aux, "ec_gemm: EC_EPI_GELU_BWD16 needs variant 0 and args.aux");
-        return launch_gelu<DT, EC_EPI_GELU_BWD16>(g, act, s);
-    // LayerNorm folded into the GEMMs (default kernel only)
-    case EC_EPI_RESID_HL:
-#ifdef EC_GEMM_DIAG
-        if ((variant == 18 || variant == 19) && g.aux) return dispatch_variant<DT, EC_EPI_RESID_HL>(g, variant, s);
-#endif
-        EC_REQUIRE(variant == 0 && g.aux, "ec_gemm: EC_EPI_RESID_HL needs variant 0 and args.aux (the lo plane)");
-        return launch2pp<DT, EC_EPI_RESID_HL>(g, s);
-    case EC_EPI_STORE16_LN:
-#ifdef EC_GEMM_DIAG
-        if ((variant == 18 || variant == 19) && g.rowstat && g.colsum) return dispatch_variant<DT, EC_EPI_STORE16_LN>(g, variant, s);
-#endif
-        EC_REQUIRE(variant == 0 && g.rowstat && g.colsum, "ec_gemm: EC_EPI_STORE16_LN needs variant 0, row_stats and col_sums");
-        return launch2pp<DT, EC_EPI_STORE16_LN>(g, s);
-    case EC_EPI_GELU16_LN:
-#ifdef EC_GEMM_DIAG
-        if ((variant == 18 || variant == 19) && g.rowstat && g.colsum) return dispatch_variant<DT, EC_EPI_GELU16_LN>(g, variant, s);
-#endif
-        EC_REQUIRE(variant == 0 && g.rowstat && g.colsum, "ec_gemm: EC_EPI_GELU16_LN needs variant 0, row_stats and col_sums");
-        return launch_gelu<DT, EC_EPI_GELU16_LN>(g, act, s);
-    default: return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown epilogue %d", epi);
+    case row(EC_EPI_GELU16_SAVE, 0, LO_NONE):
+        EC_REQUIRE(l.variant == 0 && g.aux, "ec_gemm: EC_EPI_GELU16_SAVE needs variant 0 and args.aux");
+        return launch_row<DT, EC_EPI_GELU16_SAVE>(g, l, s);
+    case row(EC_EPI_GELU_BWD16, 0, LO_NONE):
+        EC_REQUIRE(l.variant == 0 && g.aux, "ec_gemm: EC_EPI_GELU_BWD16 needs variant 0 and args.aux");
+        return launch_row<DT, EC_EPI_GELU_BWD16>(g, l, s);
+    // LayerNorm folded into the GEMMs
+    case row(EC_EPI_RESID_HL, 0, LO_NONE):
+        EC_REQUIRE(v0 && g.aux, "ec_gemm: EC_EPI_RESID_HL needs variant 0 and args.aux (the lo plane)");
+        return launch_row<DT, EC_EPI_RESID_HL, 0, LO_NONE, true>(g, l, s);
+    case row(EC_EPI_STORE16_LN, 0, LO_NONE):
+        EC_REQUIRE(v0 && g.rowstat && g.colsum, "ec_gemm: EC_EPI_STORE16_LN needs variant 0, row_stats and col_sums");
+        return launch_row<DT, EC_EPI_STORE16_LN, 0, LO_NONE, true>(g, l, s);
+    case row(EC_EPI_GELU16_LN, 0, LO_NONE):
+        EC_REQUIRE(v0 && g.rowstat && g.colsum, "ec_gemm: EC_EPI_GELU16_LN needs variant 0, row_stats and col_sums");
+        return launch_row<DT, EC_EPI_GELU16_LN, 0, LO_NONE, true>(g, l, s);
+    // ---- split-precision operands: the segmented main loop (variant 0: check_args)
+    case row(EC_EPI_STORE16, 1, LO_NONE): return launch_row<DT, EC_EPI_STORE16, 1, LO_NONE>(g, l, s);
+    case row(EC_EPI_STORE16, 1, LO_16): return launch_row<DT, EC_EPI_STORE16, 1, LO_16>(g, l, s);
+    case row(EC_EPI_GELU16, 1, LO_NONE): return launch_row<DT, EC_EPI_GELU16, 1, LO_NONE>(g, l, s);
+    case row(EC_EPI_GELU16, 1, LO_16): return launch_row<DT, EC_EPI_GELU16, 1, LO_16>(g, l, s);
+    case row(EC_EPI_STORE32, 1, LO_NONE): return launch_row<DT, EC_EPI_STORE32, 1>(g, l, s);
+    case row(EC_EPI_RESID32, 1, LO_NONE): return launch_row<DT, EC_EPI_RESID32, 1>(g, l, s);
+    case row(EC_EPI_RESID_HL, 1, LO_NONE):
+        EC_REQUIRE(g.aux, "ec_gemm: EC_EPI_RESID_HL needs args.aux (the lo plane)");
+        return launch_row<DT, EC_EPI_RESID_HL, 1>(g, l, s);
+    // ---- ... with e4m3 lo products in front (f16 only; the epilogues the tolerance mode's blocks use)
+    case row(EC_EPI_STORE16, 2, LO_NONE): return launch_row<DT, EC_EPI_STORE16, 2, LO_NONE>(g, l, s);
+    case row(EC_EPI_STORE16, 2, LO_16): return launch_row<DT, EC_EPI_STORE16, 2, LO_16>(g, l, s);
+    case row(EC_EPI_GELU16, 2, LO_NONE): return launch_row<DT, EC_EPI_GELU16, 2, LO_NONE>(g, l, s);
+    case row(EC_EPI_GELU16, 2, LO_16): return launch_row<DT, EC_EPI_GELU16, 2, LO_16>(g, l, s);
+    case row(EC_EPI_GELU16, 2, LO_E4M3): return launch_row<DT, EC_EPI_GELU16, 2, LO_E4M3>(g, l, s);
+    case row(EC_EPI_STORE32, 2, LO_NONE): return launch_row<DT, EC_EPI_STORE32, 2>(g, l, s);
+    case row(EC_EPI_RESID_HL, 2, LO_NONE):
+        EC_REQUIRE(g.aux, "ec_gemm: EC_EPI_RESID_HL needs args.aux (the lo plane)");
+        return launch_row<DT, EC_EPI_RESID_HL, 2>(g, l, s);
     }
+    if (l.seg)
+        return ec::fail(EC_ERR_INVALID, l.seg == 2 ? "ec_gemm: e4m3 lo products go with the STORE16, GELU16, STORE32 and RESID_HL epilogues (got %d)"
+                        : "ec_gemm: A_lo / W_lo go with the STORE16, GELU16, STORE32, RESID32 and RESID_HL epilogues (got %d)", l.epi);
+    EC_REQUIRE(l.lo == LO_NONE, "ec_gemm: STORE16 / GELU16 write their lo part (args.aux) in the launches that take A_lo / W_lo only");
+    return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown epilogue %d", l.epi);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1520,37 +1537,33 @@ __global__ __launch_bounds__(256) void kbatch_fixup_kernel(const float *partial,
 // -> EC_OK after launching the K-batched form, KBATCH_NOT_APPLICABLE (a positive value: never an error code) when the
 // launch does not qualify and the caller goes on as usual, or the negative error code of a launch that failed
 constexpr int KBATCH_NOT_APPLICABLE = 1;
-template <int DT> int try_kbatched(const GemmArgs &g0, int epi, int act, float *ws, size_t ws_bytes, hipStream_t stream)
+template <int DT> int try_kbatched(const GemmArgs &g0, const Launch &l, hipStream_t stream)
 {
     const int cus = ec::cu_count();
-    const int tiles = ec::ceil_div(g0.M, 256) * ec::ceil_div(g0.N, 256);
-    if (cus <= 0 || tiles * 2 > cus || g0.N % 4 != 0) return KBATCH_NOT_APPLICABLE;
-    const int nk = g0.K / BK;
-    int splits = 1;
-    while (splits < 16 && tiles * splits * 2 <= cus && nk % (splits * 2) == 0 && nk / (splits * 2) >= 2) splits *= 2;
-    if (splits < 2 || (size_t)splits * g0.M * g0.N * 4 > ws_bytes) return KBATCH_NOT_APPLICABLE;
+    if (cus <= 0 || g0.N % 4 != 0) return KBATCH_NOT_APPLICABLE;
+    const int splits = ec_tower::kbatch_splits(ec::ceil_div(g0.M, 256) * ec::ceil_div(g0.N, 256), g0.K / BK, cus, 16, 2);
+    if (splits < 2 || (size_t)splits * g0.M * g0.N * 4 > l.ws_bytes) return KBATCH_NOT_APPLICABLE;
     GemmArgs g = g0;
     g.K = g0.K / splits, g.splits = splits, g.split_stride = (long)g0.M * g0.N;
-    g.C = ws, g.ldc = g0.N, g.bias = nullptr, g.resid = nullptr, g.aux = nullptr;
+    g.C = l.ws, g.ldc = g0.N, g.bias = nullptr, g.resid = nullptr, g.aux = nullptr;
     if (int rc = launch2pp<DT, EC_EPI_STORE32>(g, stream)) return rc;
     const long n4 = (long)g0.M * g0.N / 4;
     const dim3 grid((unsigned)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048));
-    if (act == ACT_ERF)
-        hipLaunchKernelGGL((kbatch_fixup_kernel<DT, ACT_ERF>), grid, dim3(256), 0, stream, ws, splits, g0.M, g0.N, g0.bias, g0.resid,
-                           g0.C, g0.ldc, g0.aux, epi);
-    else
-        hipLaunchKernelGGL(kbatch_fixup_kernel<DT>, grid, dim3(256), 0, stream, ws, splits, g0.M, g0.N, g0.bias, g0.resid, g0.C,
-                           g0.ldc, g0.aux, epi);
+    auto fixup = l.act == ACT_ERF ? kbatch_fixup_kernel<DT, ACT_ERF> : kbatch_fixup_kernel<DT>;
+    hipLaunchKernelGGL(fixup, grid, dim3(256), 0, stream, l.ws, splits, g0.M, g0.N, g0.bias, g0.resid, g0.C, g0.ldc, g0.aux, l.epi);
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }
 
-}  // namespace
-
-extern "C" EC_API int ec_gemm(const ec_gemm_args *a, ec_stream_t stream)
+// ec_gemm_args -> GemmArgs and Launch, or the refusal: every condition once, grouped by what it is about.  Where two fire
+// for one call the earlier one is reported (tests/test_gemm_edges_gpu.py pins which).  g.M == 0: nothing to launch.
+int check_args(const ec_gemm_args *a, GemmArgs &g, Launch &l)
 {
+    // ---- shape and alignment
     EC_REQUIRE(a != nullptr, "ec_gemm: args is null");
     EC_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0, "ec_gemm: bad shape %d x %d x %d", a->M, a->N, a->K);
+    g = GemmArgs{};
+    g.M = a->M, g.N = a->N, g.K = a->K;
     if (a->M == 0) return EC_OK;
     EC_REQUIRE(a->K % BK == 0, "ec_gemm: K=%d must be a multiple of %d", a->K, BK);
     EC_REQUIRE(a->N % 16 == 0, "ec_gemm: N=%d must be a multiple of 16", a->N);
@@ -1559,33 +1572,28 @@ extern "C" EC_API int ec_gemm(const ec_gemm_args *a, ec_stream_t stream)
     EC_REQUIRE(lda % 8 == 0 && ldc % 8 == 0, "ec_gemm: lda/ldc must be multiples of 8 elements");
     // a tile's rows are addressed with 32-bit byte offsets from the tile's origin (256 rows x stride x 4 bytes)
     EC_REQUIRE(lda < (1L << 21) && ldc < (1L << 21) && a->ldw < (1L << 21), "ec_gemm: row strides must be below 2^21 elements");
-    EC_REQUIRE((((uintptr_t)a->A | (uintptr_t)a->W | (uintptr_t)a->C) & 15) == 0,
-               "ec_gemm: buffers must be 16-byte aligned");
-    GemmArgs g;
-    g.M = a->M, g.N = a->N, g.K = a->K;
-    g.A = a->A, g.lda = lda, g.W = a->W, g.bias = a->bias, g.C = a->C, g.ldc = ldc;
-    g.tiles_m = g.tiles_n = 0;
-    g.diag = static_cast<unsigned long long *>(a->diag);
-    g.ldw = a->ldw ? a->ldw : a->K, g.resid = a->resid, g.aux = a->aux;
+    EC_REQUIRE((((uintptr_t)a->A | (uintptr_t)a->W | (uintptr_t)a->C) & 15) == 0, "ec_gemm: buffers must be 16-byte aligned");
+    const int epi = a->epilogue;
+    const bool tn = a->transposed != 0;      // A [rows, M], W [rows, N]: the row strides default to M and N
+    g.A = a->A, g.lda = tn && !a->lda ? a->M : lda, g.W = a->W, g.ldw = a->ldw ? a->ldw : tn ? a->N : a->K;
+    g.bias = a->bias, g.C = a->C, g.ldc = ldc, g.resid = a->resid, g.aux = a->aux, g.diag = static_cast<unsigned long long *>(a->diag);
     g.splits = a->splits > 1 ? a->splits : 1, g.split_stride = a->split_stride;
-    g.tn = a->transposed ? 1 : 0, g.k_valid = a->k_rows;
+    g.tn = tn, g.k_valid = a->k_rows;
     g.rowstat = a->row_stats, g.rowstat_stride = a->row_stats_stride > 0 ? a->row_stats_stride : 1, g.colsum = a->col_sums;
-    g.stat_out = nullptr, g.stat_groups = 0;
-    g.nseg = 1;
-    g.seg_da = g.seg_dw = g.seg_mask = 0;
-    g.nf8 = 0;
-    g.f8_oa[0] = g.f8_oa[1] = g.f8_ow[0] = g.f8_ow[1] = 0, g.f8_scale[0] = g.f8_scale[1] = 0x7f7f7f7f;
-    g.aux8_scale = 0.f;
+    g.nseg = 1, g.f8_scale[0] = g.f8_scale[1] = 0x7f7f7f7f;
+    l = Launch{a->dtype, epi, 0, LO_NONE, a->activation, a->variant, tn, nullptr, 0};
+
+    // ---- split-precision operands
     if (a->aux_e4m3) {
-        EC_REQUIRE(a->epilogue == EC_EPI_GELU16 && a->aux && a->A_lo8 && a->dtype == EC_F16 && a->aux_exp >= -60 && a->aux_exp <= 60,
+        EC_REQUIRE(epi == EC_EPI_GELU16 && a->aux && a->A_lo8 && a->dtype == EC_F16 && a->aux_exp >= -60 && a->aux_exp <= 60,
                    "ec_gemm: aux_e4m3 goes with EC_EPI_GELU16, an aux buffer, e4m3 lo products (A_lo8) and -60 <= aux_exp <= 60");
         g.aux8_scale = ldexpf(1.f, a->aux_exp);
     }
     const bool l8 = a->A_lo8 != nullptr, w8 = a->W_lo8 != nullptr;
     if (a->A_lo || a->W_lo || l8 || w8) {
-        // split-precision operands: up to three products into the same accumulators, the small ones first
+        // up to three products into the same accumulators, the small ones first
         // (a_lo . w + a . w_lo + a . w; a_lo . w_lo, ~2^-22 of the result, is left out)
-        EC_REQUIRE(!a->transposed && a->splits <= 1 && !a->ws && !a->resid && a->variant == 0,
+        EC_REQUIRE(!tn && a->splits <= 1 && !a->ws && !a->resid && a->variant == 0,
                    "ec_gemm: A_lo / W_lo take no transposed operands, splits, ws or resid, and variant 0");
         EC_REQUIRE((((uintptr_t)a->A_lo | (uintptr_t)a->W_lo) & 15) == 0, "ec_gemm: A_lo / W_lo must be 16-byte aligned");
         g.seg_da = a->A_lo ? (long)((intptr_t)a->A_lo - (intptr_t)a->A) : 0;
@@ -1612,76 +1620,81 @@ extern "C" EC_API int ec_gemm(const ec_gemm_args *a, ec_stream_t stream)
         }
         if (a->A_lo) g.seg_mask |= 1u << n, n++;             // a_lo . w
         if (a->W_lo) g.seg_mask |= 1u << (4 + n), n++;       // a . w_lo
-        n++;                                                 // a . w
-        g.nseg = n;
+        g.nseg = n + 1;                                      // a . w
+        l.seg = g.nf8 > 0 ? 2 : 1;
     }
+    // STORE16 / GELU16 write the lo part of their output where they are given aux (every other epilogue's aux is an operand)
+    if ((epi == EC_EPI_STORE16 || epi == EC_EPI_GELU16) && a->aux) l.lo = g.aux8_scale != 0.f ? LO_E4M3 : LO_16;
+
+    // ---- options against the epilogue: one the kernel would not read is refused, not ignored
     // what the epilogues read these with: row_stats by 16-byte LDS-DMA (two pairs at a time at stride 1, through a
     // descriptor whose range ends at pair M - 1: nothing past the array is read), col_sums as float4, row_sums written as float2
     EC_REQUIRE((((uintptr_t)a->row_stats | (uintptr_t)a->col_sums) & 15) == 0, "ec_gemm: row_stats / col_sums must be 16-byte aligned");
     EC_REQUIRE(!a->row_stats || a->M < (1 << 27), "ec_gemm: row_stats addresses its pairs with 32-bit byte offsets (M = %d)", a->M);
     EC_REQUIRE(((uintptr_t)a->row_sums & 7) == 0, "ec_gemm: row_sums must be 8-byte aligned");
-    // an option the dispatched kernel would not read is refused, not ignored
-    EC_REQUIRE(a->activation == ACT_QUICK || a->activation == ACT_ERF, "ec_gemm: unknown args.activation %d (0 = QuickGELU, 1 = exact GELU)",
-               a->activation);
-    EC_REQUIRE(a->activation == ACT_QUICK || epi_is_gelu(a->epilogue),
-               "ec_gemm: args.activation goes with the GELU16, GELU16_LN, GELU16_SAVE and GELU_BWD16 epilogues (epilogue %d)", a->epilogue);
-    const bool ln_epi = a->epilogue == EC_EPI_STORE16_LN || a->epilogue == EC_EPI_GELU16_LN;
-    EC_REQUIRE(!a->aux || !(a->epilogue == EC_EPI_STORE32 || a->epilogue == EC_EPI_RESID32 || ln_epi),
-               "ec_gemm: args.aux goes with the STORE16, GELU16, GELU16_SAVE, GELU_BWD16 and RESID_HL epilogues (epilogue %d)", a->epilogue);
-    EC_REQUIRE(!a->row_sums || a->epilogue == EC_EPI_RESID_HL, "ec_gemm: args.row_sums goes with EC_EPI_RESID_HL (epilogue %d)", a->epilogue);
-    EC_REQUIRE((!a->row_stats && !a->col_sums) || ln_epi,
-               "ec_gemm: args.row_stats / col_sums go with EC_EPI_STORE16_LN / EC_EPI_GELU16_LN (epilogue %d)", a->epilogue);
-    if (a->epilogue == EC_EPI_RESID_HL && a->row_sums) {
-        EC_REQUIRE(a->N % 64 == 0, "ec_gemm: row_sums needs N %% 64 == 0 (N = %d)", a->N);
-        g.stat_out = a->row_sums, g.stat_groups = a->N / 64;
-    }
-    if (g.tn) {
-        g.lda = a->lda ? a->lda : a->M, g.ldw = a->ldw ? a->ldw : a->N;
-        EC_REQUIRE(a->epilogue == EC_EPI_STORE32 && a->variant == 0 && !a->bias && !a->ws,
+    EC_REQUIRE(l.act == ACT_QUICK || l.act == ACT_ERF, "ec_gemm: unknown args.activation %d (0 = QuickGELU, 1 = exact GELU)", l.act);
+    EC_REQUIRE(l.act == ACT_QUICK || epi_is_gelu(epi),
+               "ec_gemm: args.activation goes with the GELU16, GELU16_LN, GELU16_SAVE and GELU_BWD16 epilogues (epilogue %d)", epi);
+    EC_REQUIRE(!a->aux || !(epi == EC_EPI_STORE32 || epi == EC_EPI_RESID32 || epi_is_ln(epi)),
+               "ec_gemm: args.aux goes with the STORE16, GELU16, GELU16_SAVE, GELU_BWD16 and RESID_HL epilogues (epilogue %d)", epi);
+    EC_REQUIRE(!a->row_sums || epi == EC_EPI_RESID_HL, "ec_gemm: args.row_sums goes with EC_EPI_RESID_HL (epilogue %d)", epi);
+    EC_REQUIRE((!a->row_stats && !a->col_sums) || epi_is_ln(epi),
+               "ec_gemm: args.row_stats / col_sums go with EC_EPI_STORE16_LN / EC_EPI_GELU16_LN (epilogue %d)", epi);
+    EC_REQUIRE(!a->row_sums || a->N % 64 == 0, "ec_gemm: row_sums needs N %% 64 == 0 (N = %d)", a->N);
+    g.stat_out = a->row_sums, g.stat_groups = a->row_sums ? a->N / 64 : 0;
+
+    if (tn) {
+        // ---- transposed operands
+        EC_REQUIRE(epi == EC_EPI_STORE32 && a->variant == 0 && !a->bias && !a->ws,
                    "ec_gemm: transposed operands go with EC_EPI_STORE32, variant 0, no bias, no ws");
         EC_REQUIRE(g.M % 8 == 0 && g.M >= 8 && g.lda % 8 == 0 && g.ldw % 8 == 0 && g.lda >= g.M && g.ldw >= g.N,
                    "ec_gemm: transposed operands need M %% 8 == 0 and row strides (multiples of 8) covering M and N");
         EC_REQUIRE(g.k_valid > 0 && (long)g.k_valid <= (long)g.K * g.splits,
                    "ec_gemm: k_rows=%d outside (0, splits * K = %ld]", g.k_valid, (long)g.K * g.splits);
-        EC_REQUIRE(g.splits == 1 || (g.split_stride >= (long)(g.M - 1) * ldc + g.N && g.split_stride % 8 == 0),
-                   "ec_gemm: split_stride %ld too small for an %d x %d output", g.split_stride, g.M, g.N);
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        if (a->dtype == EC_F16) return launch2pp<EC_F16, EC_EPI_STORE32, false, true>(g, st);
-        if (a->dtype == EC_BF16) return launch2pp<EC_BF16, EC_EPI_STORE32, false, true>(g, st);
-        return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown dtype %d", a->dtype);
+    } else {
+        // ---- splits / ldw / resid
+        EC_REQUIRE(g.ldw % 8 == 0 && g.ldw >= (long)g.K * g.splits && lda >= (long)g.K * g.splits,
+                   "ec_gemm: lda / ldw must cover splits * K columns and be multiples of 8 elements");
+        EC_REQUIRE((((uintptr_t)a->resid | (uintptr_t)a->aux) & 15) == 0, "ec_gemm: resid / aux must be 16-byte aligned");
+        EC_REQUIRE(!a->resid || epi == EC_EPI_RESID32, "ec_gemm: args.resid goes with EC_EPI_RESID32");
+        EC_REQUIRE((g.ldw == g.K && g.splits == 1 && !g.resid) || a->variant == 0, "ec_gemm: ldw / splits / resid need variant 0");
     }
-    EC_REQUIRE(g.ldw % 8 == 0 && g.ldw >= (long)g.K * g.splits && lda >= (long)g.K * g.splits,
-               "ec_gemm: lda / ldw must cover splits * K columns and be multiples of 8 elements");
-    EC_REQUIRE((((uintptr_t)a->resid | (uintptr_t)a->aux) & 15) == 0, "ec_gemm: resid / aux must be 16-byte aligned");
-    EC_REQUIRE(!a->resid || a->epilogue == EC_EPI_RESID32, "ec_gemm: args.resid goes with EC_EPI_RESID32");
-    if (g.ldw != g.K || g.splits > 1 || g.resid) {
-        EC_REQUIRE(a->variant == 0, "ec_gemm: ldw / splits / resid need variant 0");
-        EC_REQUIRE(g.splits == 1 || (g.split_stride >= (long)(g.M - 1) * ldc + g.N && g.split_stride % 8 == 0),
-                   "ec_gemm: split_stride %ld too small for an %d x %d output", g.split_stride, g.M, g.N);
-    }
-#ifdef EC_GEMM_DIAG
-    {
-        const int v = a->variant;
-        EC_REQUIRE(!(v == 18 || v == 19) || a->diag, "ec_gemm: variant %d needs args.diag", v);
-    }
-#endif
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    EC_REQUIRE(a->epilogue < EC_EPI_RESID_HL || (g.splits == 1 && !a->ws && !a->resid),
+    EC_REQUIRE(g.splits == 1 || (g.split_stride >= (long)(g.M - 1) * ldc + g.N && g.split_stride % 8 == 0),
+               "ec_gemm: split_stride %ld too small for an %d x %d output", g.split_stride, g.M, g.N);
+    EC_REQUIRE(!diag_variant(a->variant) || a->diag, "ec_gemm: variant %d needs args.diag", a->variant);
+    EC_REQUIRE(epi < EC_EPI_RESID_HL || (g.splits == 1 && !a->ws && !a->resid),
                "ec_gemm: the folded-LayerNorm epilogues take no splits / ws / resid");
-    if (a->ws && a->variant == 0 && g.splits == 1 && a->epilogue >= EC_EPI_STORE16 && a->epilogue <= EC_EPI_GELU_BWD16) {
+
+    // ---- K-batch scratch: the low-latency form of an under-filled launch (try_kbatched decides whether it is one)
+    if (a->ws && a->variant == 0 && g.splits == 1 && epi >= EC_EPI_STORE16 && epi <= EC_EPI_GELU_BWD16) {
         EC_REQUIRE(((uintptr_t)a->ws & 15) == 0, "ec_gemm: ws must be 16-byte aligned");
-        // what dispatch_epi would check: the fixup kernel reads / writes through these on the device
-        EC_REQUIRE(!(a->epilogue == EC_EPI_GELU16_SAVE || a->epilogue == EC_EPI_GELU_BWD16) || a->aux != nullptr,
-                   "ec_gemm: epilogue %d needs aux", a->epilogue);
-        EC_REQUIRE(a->resid == nullptr || ((uintptr_t)a->resid & 15) == 0, "ec_gemm: resid must be 16-byte aligned");
-        int rc = KBATCH_NOT_APPLICABLE;
-        if (a->dtype == EC_F16) rc = try_kbatched<EC_F16>(g, a->epilogue, a->activation, static_cast<float *>(a->ws), a->ws_bytes, s);
-        else if (a->dtype == EC_BF16) rc = try_kbatched<EC_BF16>(g, a->epilogue, a->activation, static_cast<float *>(a->ws), a->ws_bytes, s);
-        if (rc != KBATCH_NOT_APPLICABLE) return rc;   // launched, or failed with a real error code
+        // the fixup kernel reads / writes the pre-activation through aux on the device
+        EC_REQUIRE(!(epi == EC_EPI_GELU16_SAVE || epi == EC_EPI_GELU_BWD16) || a->aux != nullptr, "ec_gemm: epilogue %d needs aux", epi);
+        l.ws = static_cast<float *>(a->ws), l.ws_bytes = a->ws_bytes;
     }
-    if (a->dtype == EC_F16) return dispatch_epi<EC_F16>(g, a->epilogue, a->variant, a->activation, s);
-    if (a->dtype == EC_BF16) return dispatch_epi<EC_BF16>(g, a->epilogue, a->variant, a->activation, s);
-    return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown dtype %d", a->dtype);
+    return EC_OK;
+}
+
+}  // namespace
+
+// check, try the K-batched form, dispatch
+extern "C" EC_API int ec_gemm(const ec_gemm_args *a, ec_stream_t stream)
+{
+    GemmArgs g;
+    Launch l;
+    if (int rc = check_args(a, g, l)) return rc;
+    if (g.M == 0) return EC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto run = [&](auto dt) {      // the one place the runtime dtype becomes the kernels' template argument
+        if (l.ws) {
+            const int rc = try_kbatched<decltype(dt)::value>(g, l, s);
+            if (rc != KBATCH_NOT_APPLICABLE) return rc;   // launched, or failed with a real error code
+        }
+        return launch_table<decltype(dt)::value>(g, l, s);
+    };
+    if (l.dtype == EC_F16) return run(std::integral_constant<int, EC_F16>());
+    if (l.dtype == EC_BF16) return run(std::integral_constant<int, EC_BF16>());
+    return ec::fail(EC_ERR_INVALID, "ec_gemm: unknown dtype %d", l.dtype);
 }
 
 #ifdef EC_GEMM_DIAG

@@ -33,6 +33,17 @@ inline LatencyScratch &latency_scratch()
 }
 constexpr size_t LATENCY_WS_BYTES = (size_t)80 << 20;   // 256 workgroups x one 256 x 256 fp32 tile, with slack
 
+// The K-batch split rule, for ec_gemm's low-latency form (gemm.hip: try_kbatched, cap 16, 2 K tiles) and the short last
+// row of tiles of the training GEMMs (vit_train.hip: gemm_rows32, cap 8, 4 K tiles): into how many K-batches `tiles`
+// under-filling output tiles of `nk` K tiles (of 64) are cut on `cus` compute units -- doubled while the workgroups
+// still fit twice, the batches stay equal, and each keeps at least `min_nk` K tiles; at most `cap`.  1: no cut.
+inline int kbatch_splits(int tiles, int nk, int cus, int cap, int min_nk)
+{
+    int splits = 1;
+    while (splits < cap && tiles * splits * 2 <= cus && nk % (splits * 2) == 0 && nk / (splits * 2) >= min_nk) splits *= 2;
+    return splits;
+}
+
 constexpr int LO8_EXP = 12;    // lo parts of activations as e4m3 of lo . 2^12: saturates where the activation exceeds 256
 constexpr int HI8_EXP = 0;     // e4m3 copies of hi parts at scale 1: saturates beyond 448
 // the lo products on the FP8 matrix path (ec_vit_weights.lo_fp8): A_lo8 = the e4m3 lo part of A (ec_layernorm_hl8 / the

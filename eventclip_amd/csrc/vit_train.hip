@@ -52,7 +52,9 @@ __device__ __forceinline__ int units(int width, int lane)
 }
 __device__ __forceinline__ float quick_gelu_f(float x)
 {
-    return x * __builtin_amdgcn_rcpf(1.f + __expf(-1.702f * x));   // as the GEMM epilogue computes it
+    // x * sigmoid(1.702 x) with the exponential as __expf(-1.702 x): two multiplies in front of v_exp_f32.  NOT the GEMM
+    // epilogue's sequence (gemm.hip: quick_gelu folds -1.702 log2 e into one multiply): the two can differ in the last bit
+    return x * __builtin_amdgcn_rcpf(1.f + __expf(-1.702f * x));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1326,9 +1328,7 @@ int gemm_rows32(int M, int N, int K, int dtype, int epi, const void *A, const vo
     const long tiles_main = (long)(full / 256) * tiles_n;
     const bool extra_round = cus > 0 && full > 0 && rem > 0 && rem <= 128 &&
                              (tiles_main + cus - 1) / cus < (tiles_main + tiles_n + cus - 1) / cus;
-    int splits = 1;
-    if (extra_round && K >= 2048)
-        while (splits < 8 && tiles_n * splits * 2 <= cus && (K / 64) % (splits * 2) == 0 && K / (splits * 2) >= 256) splits *= 2;
+    const int splits = extra_round && K >= 2048 ? kbatch_splits(tiles_n, K / 64, cus, 8, 4) : 1;
     if (splits < 2 || (size_t)splits * rem * N > partial_floats || (epi != EC_EPI_STORE32 && epi != EC_EPI_RESID32))
         return Gemm(M, N, K, dtype, epi, A, W, bias, C).resid(resid).run(stream);
     const size_t esz = 2;

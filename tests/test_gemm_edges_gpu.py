@@ -467,3 +467,378 @@ def test_refusals(hip):
     for epi in ('store16', 'store32', 'resid_hl'):
         kw = dict(out=o16.clone(), aux=torch.zeros_like(o16)) if epi == 'resid_hl' else {}
         _refused('args.row_stats / col_sums go with', lambda: ops.gemm(A, W, bias, epi, **ln, **kw))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 10. the table of refused calls: every message ec_gemm, its dispatch and its K-batched form can give in the product build,
+#     and, where two checks fire for one call, which of them is reported
+# ---------------------------------------------------------------------------------------------------------------
+EPI = dict(store16=0, gelu16=1, resid32=2, store32=3, gelu16_save=4, gelu_bwd16=5, resid_hl=6, store16_ln=7, gelu16_ln=8)
+OUT16 = ('store16', 'gelu16', 'gelu16_save', 'gelu_bwd16', 'resid_hl', 'store16_ln', 'gelu16_ln')
+
+
+class _Pool:
+    """The device tensors every pointer of every refused call points into, each large enough for the largest launch of the
+    table (M = 256, N = 64, two batches of 192 columns, fp32): a call that is wrongly accepted runs inside allocated memory.
+    A misaligned pointer is a view that starts 8 bytes into one of them."""
+
+    def __init__(self):
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device='cuda')  # noqa: E731
+        self.op = {(n, dt): z((264, 392), dt) for n in ('A', 'W', 'A_lo', 'W_lo') for dt in (F16, BF16)}
+        self.op8 = {n: z((264, 784), torch.uint8) for n in ('A_lo8', 'W8', 'A8', 'W_lo8')}
+        self.out = {dt: z((2, 264, 72), dt) for dt in (F16, BF16, F32)}
+        self.aux = {dt: z((264, 72), dt) for dt in (F16, BF16)}
+        self.aux8 = z((264, 144), torch.uint8)
+        self.resid, self.bias = z((264, 72), F32), z((72,), F32)
+        self.stats, self.colsum, self.sums = z((2 * 264 + 8,), F32), z((72,), F32), z((264 * 2 * 2 + 8,), F32)
+        self.ws = z((1 << 20,), torch.uint8)
+        # by the name _pr's ('name', offset) fields use
+        self.A, self.W, self.A_lo, self.W_lo = (self.op[n, F16] for n in ('A', 'W', 'A_lo', 'W_lo'))
+        self.A_lo8, self.W8, self.A8, self.W_lo8 = (self.op8[n] for n in ('A_lo8', 'W8', 'A8', 'W_lo8'))
+        self.aux16 = self.aux[F16]
+
+
+@pytest.fixture(scope='module')
+def pool(hip):
+    return _Pool()
+
+
+def _from(t, v, shape, stride):
+    """the pool tensor ``t`` (v is True) or ``t`` from v bytes in, as a view of that shape and those strides"""
+    flat = t.view(-1)
+    return flat[(0 if v is True else v // t.element_size()):].as_strided(shape, stride)
+
+
+def _pg(p, epi='store16', M=16, N=64, K=128, dt=F16, splits=1, off=0, tight=False, **kw):
+    """ops.gemm on the pool's tensors.  Keywords name what the call passes: True = the pool's tensor for it, 8 = that tensor
+    from 8 bytes in (for an e4m3 operand a pair with its exponent, for ``ln`` a pair (row_stats, col_sums)); every other
+    keyword goes to ops.gemm as it is.  ``off``: A from that many elements in; ``tight``: ldw = K, what the variants other
+    than 0 require."""
+    KA = K * splits
+    ldw = KA if tight else 392
+    A, W = p.op['A', dt][:M, off:off + KA], _from(p.op['W', dt], True, (N, KA), (ldw, 1))
+    o = p.out[dt if epi in OUT16 else F32]
+    out = o[:splits, :M, :N] if splits > 1 else o[0, :M, :N]
+    for k, like in (('A_lo', A), ('W_lo', W)):
+        if k in kw:
+            kw[k] = _from(p.op[k, dt], kw[k], like.shape, like.stride())
+    for k, rows, ld in (('A_lo8', M, 392), ('W8', N, ldw), ('A8', M, 392), ('W_lo8', N, ldw)):
+        if k in kw:
+            v, e = kw[k] if isinstance(kw[k], tuple) else (kw[k], 0)
+            kw[k] = (_from(p.op8[k], v, (rows, 2 * K), (2 * ld, 1)), e)
+    if 'aux' in kw:
+        kw['aux'] = _from(p.aux[F16 if epi == 'resid_hl' else dt], kw['aux'], (M, N), (72, 1))
+    if 'aux8' in kw:
+        kw['aux8'] = (_from(p.aux8, True, (M, 2 * N), (144, 1)), kw['aux8'])
+    if 'resid' in kw:
+        kw['resid'] = _from(p.resid, kw['resid'], (M, N), (72, 1))
+    if 'ln' in kw:
+        v = kw.pop('ln')
+        s, c = v if isinstance(v, tuple) else (v, True)
+        kw['row_stats'], kw['col_sums'] = _from(p.stats, s, (2 * M,), (1,)), _from(p.colsum, c, (N,), (1,))
+    if 'row_sums' in kw:
+        kw['row_sums'] = _from(p.sums, kw['row_sums'], (M * (N // 64) * 2,), (1,))
+    if 'ws' in kw:
+        kw['ws'] = p.ws[(0 if kw['ws'] is True else kw['ws']):]
+    _ops().gemm(A, W, p.bias[:N], epi, out=out, splits=splits, **kw)
+
+
+def _pr(p, epi='store16', M=16, N=64, K=128, dt=F16, splits=1, transposed=False, over=None, **fields):
+    """ec_gemm called with an argument block filled by hand, for what ops.gemm's own assertions would stop: the block of
+    _pg's call (the pool's A, W, bias and output; rows of operands as ops.gemm_rows passes them when transposed), then
+    ``fields`` and ``over`` (the fields named like a parameter here) set as given -- a tensor stands for its address,
+    ('name', 8) for the pool's tensor ``name`` from 8 bytes in."""
+    from eventclip_amd import _lib
+    o = p.out[dt if epi in OUT16 else F32]
+    out = o[:splits, :M, :N] if splits > 1 else o[0, :M, :N]
+    if transposed:
+        A, W = p.op['A', dt][:K * splits, :M], p.op['W', dt][:K * splits, :N]
+    else:
+        A, W = p.op['A', dt][:M, :K * splits], p.op['W', dt][:N, :K * splits]
+    a = _ops()._gemm_args(A, W, out, M, N, K, EPI[epi], splits)
+    if transposed:
+        a.transposed, a.k_rows = 1, K * splits
+    else:
+        a.bias = p.bias.data_ptr()
+    for k, v in dict(fields, **(over or {})).items():
+        if isinstance(v, torch.Tensor):
+            v = v.data_ptr()
+        elif isinstance(v, tuple):
+            v = getattr(p, v[0]).data_ptr() + v[1]
+        setattr(a, k, v)
+    _lib.launch('ec_gemm', a)
+
+
+def _null_args(p):
+    from eventclip_amd import _lib
+    _lib.launch('ec_gemm', None)
+
+
+def _row_stats_2_27(p):
+    """M = 2^27 is the smallest row count the check refuses; the buffers the launch describes are allocated (not touched)."""
+    M, N, K = 1 << 27, 16, 64
+    A = torch.empty((M, K), dtype=F16, device='cuda')
+    out = torch.empty((M, N), dtype=F16, device='cuda')
+    stats = torch.empty((2 * M,), dtype=F32, device='cuda')
+    try:
+        _ops().gemm(A, p.op['W', F16][:N, :K], p.bias[:N], 'store16_ln', out=out, row_stats=stats, col_sums=p.colsum[:N])
+    finally:
+        del A, out, stats
+        torch.cuda.empty_cache()
+
+
+def _stride_2_21(p):
+    """lda = 2^21 at M = 8: A spans 7 x 2^21 + 64 elements."""
+    A = torch.empty((7 * (1 << 21) + 64,), dtype=F16, device='cuda')
+    try:
+        _pr(p, 'store16', M=8, N=16, K=64, A=A, lda=1 << 21)
+    finally:
+        del A
+        torch.cuda.empty_cache()
+
+
+LN1 = 'ec_gemm: the folded-LayerNorm epilogues take no splits / ws / resid'
+SEG_NO = 'ec_gemm: A_lo / W_lo take no transposed operands, splits, ws or resid, and variant 0'
+TN_GOES = 'ec_gemm: transposed operands go with EC_EPI_STORE32, variant 0, no bias, no ws'
+AUX_GOES = 'ec_gemm: args.aux goes with the STORE16, GELU16, GELU16_SAVE, GELU_BWD16 and RESID_HL epilogues (epilogue '
+RESID_GOES = 'ec_gemm: args.resid goes with EC_EPI_RESID32'
+E4M3_AUX = ('ec_gemm: aux_e4m3 goes with EC_EPI_GELU16, an aux buffer, e4m3 lo products (A_lo8) and -60 <= aux_exp <= 60')
+UNKNOWN_VARIANT = 'ec_gemm: unknown variant %d (diagnostic variants need an EC_GEMM_DIAG build)'
+HL_AUX = 'ec_gemm: EC_EPI_RESID_HL needs args.aux (the lo plane)'
+SEG8 = dict(A_lo8=True, W8=True)
+
+# (id, the message, the call).  In the order of the checks in csrc/gemm.hip's check_args, launch_table and launch_row.
+REFUSED = [
+    # ---- shape and alignment
+    ('null-args', 'ec_gemm: args is null', _null_args),
+    ('shape-N0', 'ec_gemm: bad shape 16 x 0 x 128', lambda p: _pr(p, over=dict(N=0))),
+    ('shape-K0', 'ec_gemm: bad shape 16 x 64 x 0', lambda p: _pr(p, over=dict(K=0))),
+    ('shape-M<0', 'ec_gemm: bad shape -1 x 64 x 128', lambda p: _pr(p, over=dict(M=-1))),
+    ('K%64', 'ec_gemm: K=96 must be a multiple of 64', lambda p: _pg(p, K=96)),
+    ('N%16', 'ec_gemm: N=24 must be a multiple of 16', lambda p: _pg(p, N=24)),
+    ('null-A', 'ec_gemm: null buffer', lambda p: _pr(p, A=None)),
+    ('null-W', 'ec_gemm: null buffer', lambda p: _pr(p, W=None)),
+    ('null-C', 'ec_gemm: null buffer', lambda p: _pr(p, C=None)),
+    ('lda%8', 'ec_gemm: lda/ldc must be multiples of 8 elements', lambda p: _pr(p, lda=132)),
+    ('ldc%8', 'ec_gemm: lda/ldc must be multiples of 8 elements', lambda p: _pr(p, ldc=68)),
+    ('lda>=2^21', 'ec_gemm: row strides must be below 2^21 elements', _stride_2_21),
+    ('A-misaligned', 'ec_gemm: buffers must be 16-byte aligned', lambda p: _pg(p, off=4)),
+    ('C-misaligned', 'ec_gemm: buffers must be 16-byte aligned', lambda p: _pr(p, C=('resid', 8), epi='store32')),
+    # ---- split-precision operands
+    ('aux_e4m3-store16', E4M3_AUX, lambda p: _pg(p, 'store16', aux8=0, **SEG8)),
+    ('aux_e4m3-no-A_lo8', E4M3_AUX, lambda p: _pg(p, 'gelu16', aux8=0, A8=True, W_lo8=True)),
+    ('aux_e4m3-bf16', E4M3_AUX, lambda p: _pg(p, 'gelu16', dt=BF16, aux8=0, **SEG8)),
+    ('aux_e4m3-exp', E4M3_AUX, lambda p: _pg(p, 'gelu16', aux8=61, **SEG8)),
+    ('seg-ws', SEG_NO, lambda p: _pg(p, 'store32', A_lo=True, ws=True)),
+    ('seg-splits', SEG_NO, lambda p: _pg(p, 'store32', K=64, splits=2, W_lo=True)),
+    ('seg-resid', SEG_NO, lambda p: _pg(p, 'resid32', A_lo=True, resid=True)),
+    ('seg-variant', SEG_NO, lambda p: _pg(p, 'store16', A_lo=True, variant=18)),
+    ('seg-transposed', SEG_NO, lambda p: _pr(p, 'store32', transposed=True, A_lo=('A_lo', 0))),
+    ('seg8-ws', SEG_NO, lambda p: _pg(p, 'store16', ws=True, **SEG8)),
+    ('A_lo-misaligned', 'ec_gemm: A_lo / W_lo must be 16-byte aligned', lambda p: _pg(p, A_lo=8)),
+    ('W_lo-misaligned', 'ec_gemm: A_lo / W_lo must be 16-byte aligned', lambda p: _pg(p, W_lo=8)),
+    ('seg8-bf16', 'ec_gemm: e4m3 lo products need dtype EC_F16 and K % 128 == 0 (K = 128)', lambda p: _pg(p, dt=BF16, **SEG8)),
+    ('seg8-K192', 'ec_gemm: e4m3 lo products need dtype EC_F16 and K % 128 == 0 (K = 192)', lambda p: _pg(p, K=192, **SEG8)),
+    ('seg8-and-16', 'ec_gemm: a lo product is given as 16-bit (A_lo / W_lo) OR as e4m3 (A_lo8 / W_lo8), not both',
+     lambda p: _pg(p, A_lo=True, **SEG8)),
+    ('seg8-and-16-W', 'ec_gemm: a lo product is given as 16-bit (A_lo / W_lo) OR as e4m3 (A_lo8 / W_lo8), not both',
+     lambda p: _pg(p, W_lo=True, A8=True, W_lo8=True)),
+    ('A_lo8-no-W8', 'ec_gemm: A_lo8 needs W8 (the e4m3 copy of W), W_lo8 needs A8 (the e4m3 copy of A)', lambda p: _pg(p, A_lo8=True)),
+    ('W_lo8-no-A8', 'ec_gemm: A_lo8 needs W8 (the e4m3 copy of W), W_lo8 needs A8 (the e4m3 copy of A)', lambda p: _pg(p, W_lo8=True)),
+    ('e4m3-misaligned', 'ec_gemm: e4m3 operands must be 16-byte aligned', lambda p: _pg(p, A_lo8=True, W8=8)),
+    ('a_lo8-exp', 'ec_gemm: a_lo8_exp + w8_exp = 127 outside -127 .. 126', lambda p: _pg(p, A_lo8=(True, 100), W8=(True, 27))),
+    ('w_lo8-exp', 'ec_gemm: a8_exp + w_lo8_exp = -128 outside -127 .. 126', lambda p: _pg(p, A8=(True, -100), W_lo8=(True, -28))),
+    # ---- options against the epilogue
+    ('row_stats-misaligned', 'ec_gemm: row_stats / col_sums must be 16-byte aligned', lambda p: _pg(p, 'store16_ln', ln=8)),
+    ('col_sums-misaligned', 'ec_gemm: row_stats / col_sums must be 16-byte aligned', lambda p: _pg(p, 'gelu16_ln', ln=(True, 8))),
+    ('row_stats-M-2^27', 'ec_gemm: row_stats addresses its pairs with 32-bit byte offsets (M = 134217728)', _row_stats_2_27),
+    ('row_sums-misaligned', 'ec_gemm: row_sums must be 8-byte aligned', lambda p: _pg(p, 'resid_hl', aux=True, row_sums=4)),
+    ('activation-unknown', 'ec_gemm: unknown args.activation 2 (0 = QuickGELU, 1 = exact GELU)', lambda p: _pg(p, 'gelu16', activation=2)),
+    ('activation-negative', 'ec_gemm: unknown args.activation -1 (0 = QuickGELU, 1 = exact GELU)', lambda p: _pg(p, 'gelu16', activation=-1)),
+    ('activation-store16', 'ec_gemm: args.activation goes with the GELU16, GELU16_LN, GELU16_SAVE and GELU_BWD16 epilogues (epilogue 0)',
+     lambda p: _pg(p, 'store16', activation=1)),
+    ('activation-resid_hl', 'ec_gemm: args.activation goes with the GELU16, GELU16_LN, GELU16_SAVE and GELU_BWD16 epilogues (epilogue 6)',
+     lambda p: _pg(p, 'resid_hl', aux=True, activation=1)),
+    ('aux-store32', AUX_GOES + '3)', lambda p: _pg(p, 'store32', aux=True)),
+    ('aux-resid32', AUX_GOES + '2)', lambda p: _pg(p, 'resid32', aux=True)),
+    ('aux-store16_ln', AUX_GOES + '7)', lambda p: _pg(p, 'store16_ln', aux=True, ln=True)),
+    ('aux-gelu16_ln', AUX_GOES + '8)', lambda p: _pg(p, 'gelu16_ln', aux=True, ln=True)),
+    ('row_sums-store16', 'ec_gemm: args.row_sums goes with EC_EPI_RESID_HL (epilogue 0)', lambda p: _pg(p, 'store16', row_sums=True)),
+    ('row_sums-gelu16_ln', 'ec_gemm: args.row_sums goes with EC_EPI_RESID_HL (epilogue 8)', lambda p: _pg(p, 'gelu16_ln', ln=True, row_sums=True)),
+    ('stats-store16', 'ec_gemm: args.row_stats / col_sums go with EC_EPI_STORE16_LN / EC_EPI_GELU16_LN (epilogue 0)',
+     lambda p: _pg(p, 'store16', ln=True)),
+    ('col_sums-resid_hl', 'ec_gemm: args.row_stats / col_sums go with EC_EPI_STORE16_LN / EC_EPI_GELU16_LN (epilogue 6)',
+     lambda p: _pr(p, 'resid_hl', aux=('aux16', 0), col_sums=('colsum', 0))),
+    ('row_sums-N16', 'ec_gemm: row_sums needs N % 64 == 0 (N = 16)', lambda p: _pr(p, 'resid_hl', N=16, aux=('aux16', 0), row_sums=('sums', 0))),
+    # ---- transposed operands
+    ('tn-bias', TN_GOES, lambda p: _pr(p, 'store32', transposed=True, bias=('bias', 0))),
+    ('tn-ws', TN_GOES, lambda p: _pr(p, 'store32', transposed=True, ws=('ws', 0), ws_bytes=1 << 20)),
+    ('tn-variant', TN_GOES, lambda p: _pr(p, 'store32', transposed=True, variant=18)),
+    ('tn-store16', TN_GOES, lambda p: _pr(p, 'store16', transposed=True)),
+    ('tn-M%8', 'ec_gemm: transposed operands need M % 8 == 0 and row strides (multiples of 8) covering M and N',
+     lambda p: _pr(p, 'store32', transposed=True, over=dict(M=12))),
+    ('tn-lda<M', 'ec_gemm: transposed operands need M % 8 == 0 and row strides (multiples of 8) covering M and N',
+     lambda p: _pr(p, 'store32', transposed=True, lda=8)),
+    ('tn-ldw<N', 'ec_gemm: transposed operands need M % 8 == 0 and row strides (multiples of 8) covering M and N',
+     lambda p: _pr(p, 'store32', transposed=True, ldw=56)),
+    ('tn-k_rows0', 'ec_gemm: k_rows=0 outside (0, splits * K = 128]', lambda p: _pr(p, 'store32', transposed=True, k_rows=0)),
+    ('tn-k_rows>', 'ec_gemm: k_rows=129 outside (0, splits * K = 128]', lambda p: _pr(p, 'store32', K=64, splits=2, transposed=True, k_rows=129)),
+    ('tn-split_stride', 'ec_gemm: split_stride 1136 too small for an 16 x 64 output',
+     lambda p: _pr(p, 'store32', K=64, splits=2, transposed=True, split_stride=1136)),
+    ('tn-split_stride%8', 'ec_gemm: split_stride 19012 too small for an 16 x 64 output',
+     lambda p: _pr(p, 'store32', K=64, splits=2, transposed=True, split_stride=19012)),
+    ('tn-dtype', 'ec_gemm: unknown dtype 7', lambda p: _pr(p, 'store32', transposed=True, dtype=7)),
+    # ---- splits / ldw / resid
+    ('ldw<K', 'ec_gemm: lda / ldw must cover splits * K columns and be multiples of 8 elements', lambda p: _pr(p, ldw=64)),
+    ('ldw%8', 'ec_gemm: lda / ldw must cover splits * K columns and be multiples of 8 elements', lambda p: _pr(p, ldw=132)),
+    ('lda<splits*K', 'ec_gemm: lda / ldw must cover splits * K columns and be multiples of 8 elements',
+     lambda p: _pr(p, 'store32', K=64, splits=2, lda=64)),
+    ('resid-misaligned', 'ec_gemm: resid / aux must be 16-byte aligned', lambda p: _pg(p, 'resid32', resid=8)),
+    ('aux-misaligned', 'ec_gemm: resid / aux must be 16-byte aligned', lambda p: _pg(p, 'gelu16_save', aux=8)),
+    ('resid-store32', RESID_GOES, lambda p: _pg(p, 'store32', resid=True)),
+    ('resid-resid_hl', RESID_GOES, lambda p: _pg(p, 'resid_hl', aux=True, resid=True)),
+    ('splits-variant', 'ec_gemm: ldw / splits / resid need variant 0', lambda p: _pg(p, 'store32', K=64, splits=2, variant=18)),
+    ('ldw-variant', 'ec_gemm: ldw / splits / resid need variant 0', lambda p: _pr(p, 'store32', K=64, variant=19)),
+    ('resid-variant', 'ec_gemm: ldw / splits / resid need variant 0', lambda p: _pg(p, 'resid32', resid=True, variant=1, tight=True)),
+    ('split_stride', 'ec_gemm: split_stride 1136 too small for an 16 x 64 output', lambda p: _pr(p, 'store32', K=64, splits=2, split_stride=1136)),
+    ('split_stride%8', 'ec_gemm: split_stride 19012 too small for an 16 x 64 output',
+     lambda p: _pr(p, 'store32', K=64, splits=2, split_stride=19012)),
+    ('ln-ws', LN1, lambda p: _pg(p, 'store16_ln', ln=True, ws=True)),
+    ('ln-splits', LN1, lambda p: _pg(p, 'gelu16_ln', K=64, splits=2, ln=True)),
+    ('hl-ws', LN1, lambda p: _pg(p, 'resid_hl', aux=True, ws=True)),
+    ('epi9-ws', LN1, lambda p: _pr(p, ws=('ws', 0), ws_bytes=1 << 20, epilogue=9)),
+    # ---- K-batch scratch
+    ('ws-misaligned', 'ec_gemm: ws must be 16-byte aligned', lambda p: _pg(p, 'store16', ws=8)),
+    ('ws-gelu16_save-no-aux', 'ec_gemm: epilogue 4 needs aux', lambda p: _pg(p, 'gelu16_save', ws=True)),
+    ('ws-gelu_bwd16-no-aux', 'ec_gemm: epilogue 5 needs aux', lambda p: _pg(p, 'gelu_bwd16', ws=True)),
+    ('dtype', 'ec_gemm: unknown dtype 2', lambda p: _pr(p, dtype=2)),
+    ('dtype-ws', 'ec_gemm: unknown dtype -1', lambda p: _pr(p, dtype=-1, ws=('ws', 0), ws_bytes=1 << 20)),
+    # ---- the table of launches
+    ('erf-variant', 'ec_gemm: args.activation = 1 needs variant 0', lambda p: _pg(p, 'gelu16', activation=1, variant=18, tight=True)),
+    ('seg8-resid_hl-no-aux', HL_AUX, lambda p: _pr(p, 'resid_hl', A_lo8=('A_lo8', 0), W8=('W8', 0))),
+    ('seg8-resid32', 'ec_gemm: e4m3 lo products go with the STORE16, GELU16, STORE32 and RESID_HL epilogues (got 2)',
+     lambda p: _pg(p, 'resid32', **SEG8)),
+    ('seg8-gelu16_save', 'ec_gemm: e4m3 lo products go with the STORE16, GELU16, STORE32 and RESID_HL epilogues (got 4)',
+     lambda p: _pg(p, 'gelu16_save', aux=True, A8=True, W_lo8=True)),
+    ('seg-resid_hl-no-aux', HL_AUX, lambda p: _pr(p, 'resid_hl', A_lo=('A_lo', 0))),
+    ('seg-gelu_bwd16', 'ec_gemm: A_lo / W_lo go with the STORE16, GELU16, STORE32, RESID32 and RESID_HL epilogues (got 5)',
+     lambda p: _pg(p, 'gelu_bwd16', aux=True, W_lo=True)),
+    ('seg-store16_ln', 'ec_gemm: A_lo / W_lo go with the STORE16, GELU16, STORE32, RESID32 and RESID_HL epilogues (got 7)',
+     lambda p: _pg(p, 'store16_ln', ln=True, A_lo=True)),
+    ('seg-epi9', 'ec_gemm: A_lo / W_lo go with the STORE16, GELU16, STORE32, RESID32 and RESID_HL epilogues (got 9)',
+     lambda p: _pr(p, A_lo=('A_lo', 0), epilogue=9)),
+    ('lo-out-store16', 'ec_gemm: STORE16 / GELU16 write their lo part (args.aux) in the launches that take A_lo / W_lo only',
+     lambda p: _pg(p, 'store16', aux=True)),
+    ('lo-out-gelu16', 'ec_gemm: STORE16 / GELU16 write their lo part (args.aux) in the launches that take A_lo / W_lo only',
+     lambda p: _pg(p, 'gelu16', dt=BF16, aux=True)),
+    ('gelu16_save-no-aux', 'ec_gemm: EC_EPI_GELU16_SAVE needs variant 0 and args.aux', lambda p: _pg(p, 'gelu16_save')),
+    ('gelu16_save-variant', 'ec_gemm: EC_EPI_GELU16_SAVE needs variant 0 and args.aux', lambda p: _pg(p, 'gelu16_save', aux=True, variant=18, tight=True)),
+    ('gelu_bwd16-no-aux', 'ec_gemm: EC_EPI_GELU_BWD16 needs variant 0 and args.aux', lambda p: _pg(p, 'gelu_bwd16')),
+    ('gelu_bwd16-variant', 'ec_gemm: EC_EPI_GELU_BWD16 needs variant 0 and args.aux', lambda p: _pg(p, 'gelu_bwd16', aux=True, variant=19, tight=True)),
+    ('resid_hl-no-aux', 'ec_gemm: EC_EPI_RESID_HL needs variant 0 and args.aux (the lo plane)', lambda p: _pr(p, 'resid_hl')),
+    ('resid_hl-variant', 'ec_gemm: EC_EPI_RESID_HL needs variant 0 and args.aux (the lo plane)', lambda p: _pg(p, 'resid_hl', aux=True, variant=18, tight=True)),
+    ('store16_ln-no-stats', 'ec_gemm: EC_EPI_STORE16_LN needs variant 0, row_stats and col_sums', lambda p: _pr(p, 'store16_ln')),
+    ('store16_ln-no-col_sums', 'ec_gemm: EC_EPI_STORE16_LN needs variant 0, row_stats and col_sums',
+     lambda p: _pr(p, 'store16_ln', row_stats=('stats', 0))),
+    ('store16_ln-variant', 'ec_gemm: EC_EPI_STORE16_LN needs variant 0, row_stats and col_sums', lambda p: _pg(p, 'store16_ln', ln=True, variant=19, tight=True)),
+    ('gelu16_ln-no-stats', 'ec_gemm: EC_EPI_GELU16_LN needs variant 0, row_stats and col_sums', lambda p: _pr(p, 'gelu16_ln')),
+    ('gelu16_ln-variant', 'ec_gemm: EC_EPI_GELU16_LN needs variant 0, row_stats and col_sums', lambda p: _pg(p, 'gelu16_ln', ln=True, variant=18, tight=True)),
+    ('epilogue-9', 'ec_gemm: unknown epilogue 9', lambda p: _pr(p, epilogue=9)),
+    ('epilogue-negative', 'ec_gemm: unknown epilogue -1', lambda p: _pr(p, epilogue=-1)),
+    ('epilogue-negative-ws', 'ec_gemm: unknown epilogue -1', lambda p: _pr(p, epilogue=-1, ws=('ws', 0), ws_bytes=1 << 20)),
+] + [
+    (f'variant-{v}-{e}-{d}', UNKNOWN_VARIANT % v, lambda p, e=e, v=v, d=d: _pg(p, e, dt=DT[d], variant=v, tight=True))
+    for e in ('store16', 'gelu16', 'resid32', 'store32') for v, d in ((18, 'float16'), (19, 'bfloat16'), (1, 'float16'))
+] + [
+    # a scratch that qualifies for the K-batched form (one tile, 8 K tiles) does not hide the variant from the dispatch
+    ('variant-ws', UNKNOWN_VARIANT % 18, lambda p: _pg(p, 'store16', M=256, K=384, ws=True, variant=18, tight=True)),
+]
+
+# Two checks fire for one call: which is reported.  (id, the message reported, the call)
+REFUSED_FIRST = [
+    ('shape>K%64', 'ec_gemm: bad shape 16 x 0 x 96', lambda p: _pr(p, over=dict(N=0, K=96))),
+    ('K%64>N%16', 'ec_gemm: K=96 must be a multiple of 64', lambda p: _pg(p, N=24, K=96)),
+    ('N%16>null', 'ec_gemm: N=24 must be a multiple of 16', lambda p: _pr(p, N=24, A=None)),
+    ('null>lda%8', 'ec_gemm: null buffer', lambda p: _pr(p, W=None, lda=132)),
+    ('ld%8>aligned', 'ec_gemm: lda/ldc must be multiples of 8 elements', lambda p: _pr(p, lda=132, A=('A', 8))),
+    ('aligned>aux_e4m3', 'ec_gemm: buffers must be 16-byte aligned', lambda p: _pr(p, A=('A', 8), aux_e4m3=1)),
+    ('aux_e4m3>seg', E4M3_AUX, lambda p: _pg(p, 'store16', aux8=0, ws=True, **SEG8)),
+    ('seg>seg-misaligned', SEG_NO, lambda p: _pg(p, 'store32', A_lo=8, ws=True)),
+    ('seg+resid', SEG_NO, lambda p: _pg(p, 'store16', A_lo=True, resid=True)),
+    ('seg+resid-misaligned', SEG_NO, lambda p: _pg(p, 'resid32', W_lo=True, resid=8)),
+    ('seg+transposed+bias', SEG_NO, lambda p: _pr(p, 'store32', transposed=True, bias=('bias', 0), W_lo=('W_lo', 0))),
+    ('seg+activation', SEG_NO, lambda p: _pg(p, 'store16', A_lo=True, ws=True, activation=2)),
+    ('seg+ln+ws', SEG_NO, lambda p: _pg(p, 'store16_ln', ln=True, A_lo=True, ws=True)),
+    ('seg-misaligned>seg8', 'ec_gemm: A_lo / W_lo must be 16-byte aligned', lambda p: _pg(p, K=192, W_lo=8, **SEG8)),
+    ('seg8-K>both', 'ec_gemm: e4m3 lo products need dtype EC_F16 and K % 128 == 0 (K = 192)', lambda p: _pg(p, K=192, A_lo=True, **SEG8)),
+    ('both>needs', 'ec_gemm: a lo product is given as 16-bit (A_lo / W_lo) OR as e4m3 (A_lo8 / W_lo8), not both',
+     lambda p: _pg(p, A_lo=True, A_lo8=True)),
+    ('needs>e4m3-misaligned', 'ec_gemm: A_lo8 needs W8 (the e4m3 copy of W), W_lo8 needs A8 (the e4m3 copy of A)', lambda p: _pg(p, A_lo8=8)),
+    ('e4m3-misaligned>exp', 'ec_gemm: e4m3 operands must be 16-byte aligned', lambda p: _pg(p, A_lo8=(8, 100), W8=(True, 100))),
+    ('a_lo8-exp>w_lo8-exp', 'ec_gemm: a_lo8_exp + w8_exp = 200 outside -127 .. 126',
+     lambda p: _pg(p, A_lo8=(True, 100), W8=(True, 100), A8=(True, 100), W_lo8=(True, 100))),
+    ('seg8-exp>stats-misaligned', 'ec_gemm: a8_exp + w_lo8_exp = 200 outside -127 .. 126',
+     lambda p: _pg(p, 'store16_ln', ln=8, A8=(True, 100), W_lo8=(True, 100))),
+    ('seg-misaligned>activation', 'ec_gemm: A_lo / W_lo must be 16-byte aligned', lambda p: _pg(p, 'store16', A_lo=8, activation=1)),
+    ('seg8-bf16>aux', 'ec_gemm: e4m3 lo products need dtype EC_F16 and K % 128 == 0 (K = 128)', lambda p: _pg(p, 'store32', dt=BF16, aux=True, **SEG8)),
+    ('stats-misaligned>row_sums-misaligned', 'ec_gemm: row_stats / col_sums must be 16-byte aligned', lambda p: _pg(p, 'store16', ln=(True, 8), row_sums=4)),
+    ('row_sums-misaligned>activation', 'ec_gemm: row_sums must be 8-byte aligned', lambda p: _pg(p, 'store16', row_sums=4, activation=2)),
+    ('activation-unknown>goes', 'ec_gemm: unknown args.activation 2 (0 = QuickGELU, 1 = exact GELU)', lambda p: _pg(p, 'store16', activation=2)),
+    ('activation>aux', 'ec_gemm: args.activation goes with the GELU16, GELU16_LN, GELU16_SAVE and GELU_BWD16 epilogues (epilogue 3)',
+     lambda p: _pg(p, 'store32', activation=1, aux=True)),
+    ('aux>row_sums', AUX_GOES + '3)', lambda p: _pg(p, 'store32', aux=True, row_sums=True)),
+    ('row_sums>stats', 'ec_gemm: args.row_sums goes with EC_EPI_RESID_HL (epilogue 0)', lambda p: _pg(p, 'store16', row_sums=True, ln=True)),
+    ('stats>N%64', 'ec_gemm: args.row_stats / col_sums go with EC_EPI_STORE16_LN / EC_EPI_GELU16_LN (epilogue 6)',
+     lambda p: _pr(p, 'resid_hl', N=16, aux=('aux16', 0), row_sums=('sums', 0), row_stats=('stats', 0))),
+    ('N%64>resid', 'ec_gemm: row_sums needs N % 64 == 0 (N = 16)',
+     lambda p: _pr(p, 'resid_hl', N=16, aux=('aux16', 0), row_sums=('sums', 0), resid=('resid', 0))),
+    ('aux>tn', AUX_GOES + '3)', lambda p: _pr(p, 'store32', transposed=True, bias=('bias', 0), aux=('aux16', 0))),
+    ('activation>tn', 'ec_gemm: args.activation goes with the GELU16, GELU16_LN, GELU16_SAVE and GELU_BWD16 epilogues (epilogue 3)',
+     lambda p: _pr(p, 'store32', transposed=True, bias=('bias', 0), activation=1)),
+    ('tn+bias+ws', TN_GOES, lambda p: _pr(p, 'store32', transposed=True, bias=('bias', 0), ws=('ws', 8), ws_bytes=1 << 19)),
+    ('tn-goes>strides', TN_GOES, lambda p: _pr(p, 'resid32', transposed=True, lda=8)),
+    ('tn-goes>resid', TN_GOES, lambda p: _pr(p, 'store16_ln', transposed=True, resid=('resid', 8))),
+    ('tn-strides>k_rows', 'ec_gemm: transposed operands need M % 8 == 0 and row strides (multiples of 8) covering M and N',
+     lambda p: _pr(p, 'store32', transposed=True, ldw=56, k_rows=0)),
+    ('tn-k_rows>split_stride', 'ec_gemm: k_rows=0 outside (0, splits * K = 128]',
+     lambda p: _pr(p, 'store32', K=64, splits=2, transposed=True, k_rows=0, split_stride=8)),
+    ('tn-split_stride>dtype', 'ec_gemm: split_stride 8 too small for an 16 x 64 output',
+     lambda p: _pr(p, 'store32', K=64, splits=2, transposed=True, split_stride=8, dtype=7)),
+    ('ldw>resid-misaligned', 'ec_gemm: lda / ldw must cover splits * K columns and be multiples of 8 elements',
+     lambda p: _pr(p, 'resid32', ldw=64, resid=('resid', 8))),
+    ('misaligned>resid-goes', 'ec_gemm: resid / aux must be 16-byte aligned', lambda p: _pg(p, 'store32', resid=8)),
+    ('resid-goes>variant', RESID_GOES, lambda p: _pg(p, 'store16', resid=True, variant=18)),
+    ('ln+ws+resid', RESID_GOES, lambda p: _pg(p, 'store16_ln', ln=True, ws=True, resid=True)),
+    ('hl+resid+splits', RESID_GOES, lambda p: _pg(p, 'resid_hl', K=64, splits=2, aux=True, resid=True)),
+    ('variant>split_stride', 'ec_gemm: ldw / splits / resid need variant 0',
+     lambda p: _pr(p, 'store32', K=64, splits=2, split_stride=8, variant=18)),
+    ('split_stride>ln', 'ec_gemm: split_stride 8 too small for an 16 x 64 output',
+     lambda p: _pr(p, 'gelu16_ln', K=64, splits=2, split_stride=8, row_stats=('stats', 0), col_sums=('colsum', 0))),
+    ('ln-splits>no-stats', LN1, lambda p: _pr(p, 'store16_ln', K=64, splits=2, split_stride=19008)),
+    ('ln-ws>ws-misaligned', LN1, lambda p: _pg(p, 'gelu16_ln', ln=True, ws=8)),
+    ('ln-ws>dtype', LN1, lambda p: _pr(p, 'resid_hl', aux=('aux16', 0), ws=('ws', 0), ws_bytes=1 << 20, dtype=7)),
+    ('ws-misaligned>needs-aux', 'ec_gemm: ws must be 16-byte aligned', lambda p: _pg(p, 'gelu16_save', ws=8)),
+    ('ws-needs-aux>dtype', 'ec_gemm: epilogue 5 needs aux', lambda p: _pr(p, 'gelu_bwd16', ws=('ws', 0), ws_bytes=1 << 20, dtype=7)),
+    ('ws-misaligned>dtype', 'ec_gemm: ws must be 16-byte aligned', lambda p: _pr(p, 'store32', ws=('ws', 8), ws_bytes=1 << 19, dtype=7)),
+    ('variant-skips-ws-check', UNKNOWN_VARIANT % 18, lambda p: _pg(p, 'store16', ws=8, variant=18, tight=True)),
+    ('splits-skip-ws-check', 'ec_gemm: unknown dtype 7', lambda p: _pr(p, 'store32', K=64, splits=2, ws=('ws', 8), ws_bytes=1 << 19, dtype=7)),
+    ('dtype>epilogue', 'ec_gemm: unknown dtype 7', lambda p: _pr(p, epilogue=9, dtype=7)),
+    ('dtype>erf-variant', 'ec_gemm: unknown dtype 7', lambda p: _pr(p, 'gelu16', activation=1, variant=18, dtype=7, ldw=0)),
+    ('erf-variant>needs-aux', 'ec_gemm: args.activation = 1 needs variant 0', lambda p: _pg(p, 'gelu16_save', activation=1, variant=18, tight=True)),
+    ('erf-variant>lo-out', 'ec_gemm: args.activation = 1 needs variant 0', lambda p: _pg(p, 'gelu16', aux=True, activation=1, variant=18, tight=True)),
+    ('seg8-gelu_bwd16-no-aux', 'ec_gemm: e4m3 lo products go with the STORE16, GELU16, STORE32 and RESID_HL epilogues (got 5)',
+     lambda p: _pr(p, 'gelu_bwd16', A_lo8=('A_lo8', 0), W8=('W8', 0))),
+    ('lo-out>variant', 'ec_gemm: STORE16 / GELU16 write their lo part (args.aux) in the launches that take A_lo / W_lo only',
+     lambda p: _pg(p, 'store16', aux=True, variant=18, tight=True)),
+    ('needs-aux>variant', 'ec_gemm: EC_EPI_GELU16_SAVE needs variant 0 and args.aux', lambda p: _pg(p, 'gelu16_save', variant=18, tight=True)),
+]
+
+
+@pytest.mark.parametrize('case', REFUSED + REFUSED_FIRST, ids=lambda c: c[0])
+def test_refused_calls(case, pool):
+    """Each refusal by its whole message.  The sites of csrc/gemm.hip that no call reaches in the product build have no case:
+    `variant %d needs args.diag` (diagnostic build), `cannot read the device's compute-unit count`, and launch_row's
+    `e4m3 lo products need dtype EC_F16`, which keeps the e4m3 kernels from being built for bf16 and which check_args' own
+    dtype check for e4m3 operands shadows."""
+    _, message, call = case
+    _refused(message, lambda: call(pool))
