@@ -22,6 +22,7 @@ extern "C" {
 #endif
 
 #define EC_API __attribute__((visibility("default")))
+#define EC_DEVICE /* on a pointer parameter: an array of header structs in DEVICE memory (a binding passes its address) */
 
 typedef void *ec_stream_t; /* hipStream_t */
 
@@ -67,7 +68,8 @@ EC_API const char *ec_last_error(void);
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
- * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does, with its ctypes mirrors.) */
+ * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does; its ctypes bindings are
+ * derived from this header when it is imported, so THIS file is the only statement of the ABI.) */
 #define EC_ABI_VERSION 608
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
@@ -153,7 +155,7 @@ EC_API size_t ec_events_sort_workspace_bytes(const ec_events_params *prm);
  */
 EC_API int ec_events_to_frames(const float *events, const int64_t *frame_range, int F,
                                const ec_events_params *prm, uint8_t *frames, int32_t *raw_counts,
-                               int32_t *kept_counts, ec_frame_stats *stats, ec_stream_t stream);
+                               int32_t *kept_counts, EC_DEVICE ec_frame_stats *stats, ec_stream_t stream);
 
 /* center_events (datasets/utils.py:38-57, applied to every N-Caltech / N-ImageNet sample at
  * caltech.py:176), in place: t -= min t, x -= ((x_max + x_min + 1) - W) // 2, y likewise.
@@ -195,7 +197,7 @@ EC_API int ec_pack_events(const float *events, int64_t n, uint64_t *packed,
 EC_API int ec_events_to_frames_packed(const uint64_t *events, const int64_t *frame_range, int F,
                                       const ec_events_params *prm, uint8_t *frames,
                                       int32_t *raw_counts, int32_t *kept_counts,
-                                      ec_frame_stats *stats, ec_stream_t stream);
+                                      EC_DEVICE ec_frame_stats *stats, ec_stream_t stream);
 
 /* ec_center_events on packed events (integer form of utils.py:53-54; t relative to the sample's
  * first event).  A coordinate shifted below 0 wraps above 32767 and is dropped by the binning. */
@@ -258,7 +260,7 @@ EC_API size_t ec_randaugment_workspace_bytes(int F, int H, int W, int num_ops);
 /* frames_in / frames_out: uint8 [F, H, W, 3] (distinct buffers); ops: DEVICE array [F, num_ops]
  * (frames of one sample carry the same descriptors); fill: the RandAugment fill colour, host. */
 EC_API int ec_randaugment(const uint8_t *frames_in, uint8_t *frames_out, int F, int H, int W,
-                          const ec_aug_op *ops, int num_ops, const uint8_t fill[3], void *workspace,
+                          EC_DEVICE const ec_aug_op *ops, int num_ops, const uint8_t fill[3], void *workspace,
                           size_t workspace_bytes, ec_stream_t stream);
 
 /* ------------------------------------------------------------------------
@@ -1003,7 +1005,7 @@ typedef struct {
     const float *w;
     void *hi, *lo, *hi_t;
 } ec_pack_item;
-EC_API int ec_pack_weight16_batched(const ec_pack_item *items, int n_items, int rows, int cols, int dtype,
+EC_API int ec_pack_weight16_batched(EC_DEVICE const ec_pack_item *items, int n_items, int rows, int cols, int dtype,
                                     ec_stream_t stream);
 
 /* Has anybody written these tensors since their operand copies were packed?  out[i] = a 64-bit fingerprint of the n
@@ -1016,7 +1018,8 @@ typedef struct {
     const void *ptr;
     int64_t n;
 } ec_span_item;
-EC_API int ec_fingerprint_batched(const ec_span_item *items, int n_items, int64_t max_n, uint64_t *out, ec_stream_t stream);
+EC_API int ec_fingerprint_batched(EC_DEVICE const ec_span_item *items, int n_items, int64_t max_n, uint64_t *out,
+                                  ec_stream_t stream);
 
 /* LayerNorm backward (fp32): x rows at stride ldx (the forward input), dy rows at stride ldy.
  * dx rows at stride ldo: dx = (accumulate ? dx : 0) + dLN; d_gamma / d_beta [width] (NULL = skip; they need
@@ -1052,9 +1055,10 @@ typedef struct {
     const float *dW;
     float *d_up, *d_down;
 } ec_lora_item;
-EC_API int ec_lora_merge_batched(const ec_lora_item *items, int n_items, int rows, int cols, int r, ec_stream_t stream);
+EC_API int ec_lora_merge_batched(EC_DEVICE const ec_lora_item *items, int n_items, int rows, int cols, int r,
+                                 ec_stream_t stream);
 EC_API size_t ec_lora_grad_scratch_floats(int n_items, int rows, int cols, int r);
-EC_API int ec_lora_grad_batched(const ec_lora_item *items, int n_items, int rows, int cols, int r, float *scratch,
+EC_API int ec_lora_grad_batched(EC_DEVICE const ec_lora_item *items, int n_items, int rows, int cols, int r, float *scratch,
                                 ec_stream_t stream);
 
 /* ec_adam_step over a list of tensors in one launch (`items`: DEVICE array; group selects lr0 / lr1: the
@@ -1068,8 +1072,8 @@ typedef struct {
     int64_t n;
     int group;
 } ec_adam_item;
-EC_API int ec_adam_step_multi(const ec_adam_item *items, int n_items, int64_t max_n, float lr0, float lr1, float beta1,
-                              float beta2, float eps, float weight_decay, int step, const int32_t *skip_flag,
+EC_API int ec_adam_step_multi(EC_DEVICE const ec_adam_item *items, int n_items, int64_t max_n, float lr0, float lr1,
+                              float beta1, float beta2, float eps, float weight_decay, int step, const int32_t *skip_flag,
                               const float *step_scalars /* NULL, or lr0 / lr1 / 1 - beta1^t / sqrt(1 - beta2^t) */,
                               ec_stream_t stream);
 

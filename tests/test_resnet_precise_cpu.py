@@ -101,33 +101,14 @@ def test_new_symbols_exported_and_bound():
     assert _lib.ABI_VERSION >= 602 and _lib.lib().ec_version() == _lib.ABI_VERSION
 
 
-def _cc():
-    return shutil.which(os.environ.get('CC', 'cc'))
-
-
-def test_struct_sizes_match_header(tmp_path):
-    """The ctypes mirrors against the header: sizes and the offsets of the new fields from a C program compiled
-    against include/eventclip_hip.h, and the library's own check of ec_resnet_weights.struct_bytes."""
+def test_struct_sizes_match_header():
+    """The library's own check of ec_resnet_weights.struct_bytes.  (The sizes and offsets of these structs, like every
+    other's, against a C program compiled from the header: tests/test_capi_symbols.py.)"""
     lib = _lib.lib()
     w = _lib.EcResnetWeights()
     w.struct_bytes = ctypes.sizeof(_lib.EcResnetWeights) - 8          # the struct of ABI 601
     assert lib.ec_resnet_workspace_bytes(ctypes.byref(w), 4) == 0
     assert b'struct_bytes' in lib.ec_last_error()
-    cc = _cc()
-    if cc is None:
-        pytest.skip('no C compiler')
-    src = tmp_path / 'sizes.c'
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "eventclip_hip.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu\\n", sizeof(ec_resnet_conv_w), sizeof(ec_resnet_block), '
-                   'sizeof(ec_resnet_weights), offsetof(ec_resnet_conv_w, w_lo), '
-                   'offsetof(ec_resnet_weights, precise_blocks)); return 0; }\n')
-    exe = tmp_path / 'sizes'
-    r = subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
-    assert got == [ctypes.sizeof(_lib.EcResnetConvW), ctypes.sizeof(_lib.EcResnetBlock),
-                   ctypes.sizeof(_lib.EcResnetWeights), _lib.EcResnetConvW.w_lo.offset,
-                   _lib.EcResnetWeights.precise_blocks.offset]
 
 
 def _fake_weights(precise_blocks, dtype=_lib.EC_F16, lo=True):
