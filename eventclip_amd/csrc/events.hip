@@ -22,6 +22,8 @@
 // The float stage is the float64 sequence numpy >= 2 executes for
 // vis.py:27-39, including the fused multiply-add of the dgemm behind
 // `hist @ cmap`, with FP contraction disabled everywhere else.
+#include <algorithm>
+#include <climits>
 #include <cstdlib>
 
 #include "common.h"
@@ -1517,23 +1519,25 @@ __global__ __launch_bounds__(256) void pack_events_kernel(const float4 *events, 
     }
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------
+// Host side.  events_plan() is the one statement of which kernels a launch runs, how each of them carves its LDS and
+// how the caller's workspace is laid out: launch_events() marshals it into EvArgs and walks its chunks,
+// ec_events_sort_workspace_bytes() answers with its worth_bytes.  Neither decides anything about the geometry itself.
+// ---------------------------------------------------------------------------------------------
 
-extern "C" EC_API int ec_center_events(float *events, const int64_t *sample_range, int B, int H, int W,
-                                       ec_stream_t stream)
+template <typename EV, void (*KERNEL)(EV *, const long long *, int, int)>
+int center_events(const char *name, void *events, const int64_t *sample_range, int B, int H, int W, ec_stream_t stream)
 {
-    EC_REQUIRE(B >= 0 && H > 0 && W > 0, "ec_center_events: bad arguments");
+    EC_REQUIRE(B >= 0 && H > 0 && W > 0, "%s: bad arguments", name);
     if (B == 0) return EC_OK;
-    EC_REQUIRE(events && sample_range, "ec_center_events: null buffer");
-    EC_REQUIRE(((uintptr_t)events & 15) == 0, "ec_center_events: events must be 16-byte aligned");
-    hipLaunchKernelGGL(center_events_kernel, dim3(B), dim3(1024), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<float4 *>(events),
+    EC_REQUIRE(events && sample_range, "%s: null buffer", name);
+    EC_REQUIRE(((uintptr_t)events & (sizeof(EV) - 1)) == 0, "%s: events must be %d-byte aligned", name, (int)sizeof(EV));
+    hipLaunchKernelGGL(KERNEL, dim3(B), dim3(1024), 0, static_cast<hipStream_t>(stream), static_cast<EV *>(events),
                        reinterpret_cast<const long long *>(sample_range), H, W);
     EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }
 
-namespace {
 // EC_EVENTS_NO_BAND10 / EC_EVENTS_NO_PACK10 (fall back to the 32-bit band kernel: A/B timing) are read by the diagnostic build
 // only; the product library's kernel choice never depends on the process environment
 #ifdef EC_EVENTS_DIAG
@@ -1542,18 +1546,24 @@ bool events_env_off(const char *name) { return getenv(name) != nullptr; }
 constexpr bool events_env_off(const char *) { return false; }
 #endif
 
+constexpr int EV_LDS_TOTAL = 160 * 1024;     // a CU's LDS; the 32-bit kernel always asks for all of it (one workgroup per CU)
+constexpr long EV_FLAG_BYTES = 65536;        // per-frame redo flags of the 10-bit kernels: the most frames of one chunk
+
+// compute units of the current device; 256 where there is none to ask (a size queried before a device exists)
+inline int events_cus() { const int n = ec::cu_count(); return n > 0 ? n : 256; }
+// EvArgs.band_magic for bands of `rows` rows
+inline unsigned band_magic_of(int rows) { return (unsigned)((0x100000000ull + (unsigned)rows - 1) / (unsigned)rows); }
 
 // LDS bytes of the whole-frame 10-bit histogram, and whether that path applies: the frame fits as packed
 // counts next to the reduction scratch and the LUT.  (Also for sensors whose 32-bit histogram would fit:
 // the packed kernel takes its statistics from the binning and keeps the next frame's events in flight,
 // and two of its workgroups share a CU when the histogram is small, N-Cars: 32 KB.)
 inline long pack10_bytes(int H, int W) { return (((long)H * W * 2 + 2) / 3 * 4 + 15) / 16 * 16; }
-inline bool pack10_fits(int H, int W) { return pack10_bytes(H, W) + EV_SCRATCH_BYTES <= 160 * 1024; }
+inline bool pack10_fits(int H, int W) { return pack10_bytes(H, W) + EV_SCRATCH_BYTES <= EV_LDS_TOTAL; }
 
 // Row bands of 10-bit counts for sensors whose whole histogram does not fit (events_band10_kernel): rows per band a
 // multiple of 12 / gcd(W, 12) so that every band is whole groups of 12 pixels, as many as fit the LDS next to the
 // side arrays, then evened out over the bands.
-constexpr long B10_FLAG_BYTES = 65536;
 struct B10Plan {
     bool ok;
     int rows, bands, cap;
@@ -1567,7 +1577,7 @@ inline B10Plan b10_plan(int H, int W, int max_frame_events)
     int gcd = W % 12, t = 12;
     while (gcd) { const int r = t % gcd; t = gcd; gcd = r; }          // t = gcd(W, 12)
     const int unit = 12 / t;
-    const long budget_fields = ((long)160 * 1024 - B10_SIDE_BYTES) / 16 * 16 / 4 * 3;
+    const long budget_fields = ((long)EV_LDS_TOTAL - B10_SIDE_BYTES) / 16 * 16 / 4 * 3;
     int rows = (int)(budget_fields / ((long)W * 2)) / unit * unit;
     if (rows < unit) return p;
     const int bands = ec::ceil_div(H, rows);
@@ -1577,7 +1587,81 @@ inline B10Plan b10_plan(int H, int W, int max_frame_events)
     p.bin_bytes = (((long)rows * W * 2 + 2) / 3 * 4 + 15) / 16 * 16;
     p.cap = 64 * ec::ceil_div(max_frame_events, EV_THREADS);
     p.region_bytes = (size_t)p.bands * EV_WAVES * p.cap * 4;
-    p.ok = p.bin_bytes + B10_SIDE_BYTES <= (long)160 * 1024;
+    p.ok = p.bin_bytes + B10_SIDE_BYTES <= (long)EV_LDS_TOTAL;
+    return p;
+}
+
+struct EvPlan {
+    // the 32-bit kernel alone, or behind a 10-bit kernel (whole frame / row bands) that flags the frames it leaves to it
+    enum Path { ONLY32, WHOLE10, BAND10 } path;
+    // events_to_frames_kernel, EV_LDS_TOTAL bytes: [histogram band | reduction scratch | event cache or sort counters].
+    // With the per-frame event count bounded (max_frame_events, known to the caller from split_event_count's N) the
+    // cache takes 4 B per event and the band gets what is left.  Frames too long for that are bucketed by band in the
+    // workspace (sorts: one slot of sort_cap indices per workgroup, which then walks several frames); without a
+    // workspace, or for frames longer than the bound, every band pass re-reads the events from L2.
+    int cache_events, bin_bytes, rows_per_band, bands;
+    unsigned band_magic;
+    bool sorts;
+    int sort_cap;
+    int grid_cap;            // its grid is min(frames of the chunk, grid_cap)
+    // the 10-bit kernel in front: dynamic LDS, bytes of its histogram, most workgroups; BAND10: b10.rows / bands / cap
+    int front_lds, front_bin_bytes, front_wgs;
+    unsigned front_magic;    // BAND10: band_magic_of(b10.rows)
+    B10Plan b10;
+    // workspace: [redo flags, a byte per frame of a chunk | BAND10: b10.region_bytes per workgroup of the banded kernel].
+    // The words behind the flags (ONLY32: all of it) are the sort slots of the 32-bit kernel, which runs after the regions' use
+    long chunk_frames;       // frames per pair of launches
+    size_t words_offset;     // flag bytes in front of the regions / slots
+    size_t worth_bytes;      // all that this geometry can put to use on `cus` compute units
+};
+
+// ws_bytes: of the caller's workspace, 0 without one; counts: raw / kept counts are asked for
+inline EvPlan events_plan(int H, int W, int max_frame_events, size_t ws_bytes, bool counts, int cus)
+{
+    EvPlan p = {};
+    p.grid_cap = INT_MAX, p.chunk_frames = LONG_MAX;
+    const long row_bytes = (long)W * 2 * 4;
+    if (H <= 0 || W <= 0 || row_bytes > EV_BIN_BYTES) return p;      // no launch takes it
+    const bool fits = pack10_fits(H, W);
+    p.b10 = b10_plan(H, W, max_frame_events);                         // (ok only where the whole frame does not fit)
+    if (p.b10.ok && !counts && ws_bytes >= (size_t)EV_FLAG_BYTES + p.b10.region_bytes && !events_env_off("EC_EVENTS_NO_BAND10")) {
+        p.path = EvPlan::BAND10;
+        p.front_bin_bytes = (int)p.b10.bin_bytes, p.front_lds = p.front_bin_bytes + B10_SIDE_BYTES;
+        p.front_magic = band_magic_of(p.b10.rows);
+        p.chunk_frames = EV_FLAG_BYTES, p.words_offset = (size_t)EV_FLAG_BYTES;
+        const size_t wgs_fit = (ws_bytes - p.words_offset) / p.b10.region_bytes;
+        p.front_wgs = wgs_fit < (size_t)cus ? (int)wgs_fit : cus;
+    } else if (fits && ws_bytes >= 256 && !events_env_off("EC_EVENTS_NO_PACK10")) {
+        p.path = EvPlan::WHOLE10;       // the workspace is the flag array, however long: no sort slots here
+        p.front_bin_bytes = (int)pack10_bytes(H, W), p.front_lds = p.front_bin_bytes + EV_SCRATCH_BYTES;
+        p.chunk_frames = (long)ws_bytes;
+        // one persistent workgroup per CU for the 10-bit kernel (it writes every frame's flag), two where two fit its LDS
+        // (1024 threads each: at most two fit a CU); the 32-bit kernel behind it walks the flags with one per CU
+        p.front_wgs = cus * (2 * p.front_lds <= EV_LDS_TOTAL ? 2 : 1);
+        p.grid_cap = cus;
+    }
+    int bin_budget = EV_BIN_BYTES;
+    if (max_frame_events > 0) {
+        const long left = (long)EV_BIN_BYTES - ((long)max_frame_events * 4 + 15) / 16 * 16;
+        // worth it when the whole frame then needs at most 8 bands
+        if (left >= row_bytes && ec::ceil_div(H, (int)(left / row_bytes)) <= 8) p.cache_events = max_frame_events, bin_budget = (int)left;
+    }
+    const int sort_budget = std::min((EV_LDS_TOTAL - EV_SCRATCH_BYTES - EV_SORT_BYTES) / 16 * 16, EV_BIN_BYTES);
+    const int sort_rows = (int)(sort_budget / row_bytes);
+    const bool sortable = p.cache_events == 0 && max_frame_events > 0 && sort_rows >= 1 && ec::ceil_div(H, sort_rows) > 1 &&
+                          ec::ceil_div(H, sort_rows) <= EV_SORT_MAX_BANDS;
+    const size_t slots = sortable && p.path != EvPlan::WHOLE10 ? (ws_bytes - p.words_offset) / ((size_t)max_frame_events * 4) : 0;
+    if (slots >= 1) {
+        p.sorts = true, p.sort_cap = max_frame_events, bin_budget = sort_budget;
+        p.grid_cap = slots < (size_t)cus ? (int)slots : cus;
+    }
+    p.bands = ec::ceil_div(H, (int)(bin_budget / row_bytes));
+    p.rows_per_band = ec::ceil_div(H, p.bands);
+    p.bin_bytes = (int)((p.rows_per_band * row_bytes + 15) / 16 * 16);
+    p.band_magic = band_magic_of(p.rows_per_band);
+    p.worth_bytes = fits ? (size_t)EV_FLAG_BYTES
+                  : p.b10.ok ? (size_t)EV_FLAG_BYTES + (size_t)cus * p.b10.region_bytes
+                  : sortable ? (size_t)cus * (size_t)max_frame_events * 4 : 0;
     return p;
 }
 
@@ -1593,11 +1677,15 @@ int launch_events(const void *events, const int64_t *frame_range, int F, const e
     EC_REQUIRE(prm->H > 0 && prm->W > 0, "ec_events_to_frames: bad shape (%d,%d)", prm->H, prm->W);
     EC_REQUIRE(((uintptr_t)events & (sizeof(EV) - 1)) == 0,
                "ec_events_to_frames: events must be %d-byte aligned", (int)sizeof(EV));
-    const int row_bytes = prm->W * 2 * 4;
-    EC_REQUIRE(row_bytes <= EV_BIN_BYTES, "ec_events_to_frames: W=%d too wide for one LDS row band",
-               prm->W);
+    EC_REQUIRE((long)prm->W * 2 * 4 <= EV_BIN_BYTES, "ec_events_to_frames: W=%d too wide for one LDS row band", prm->W);
 
-    EvArgs a;
+    const EvPlan plan = events_plan(prm->H, prm->W, prm->max_frame_events, prm->sort_workspace ? prm->sort_workspace_bytes : 0,
+                                    raw_counts || kept_counts, events_cus());
+    unsigned char *ws = static_cast<unsigned char *>(prm->sort_workspace);
+    const bool words = plan.sorts || plan.path == EvPlan::BAND10;       // the workspace holds 32-bit words, not only flags
+    EC_REQUIRE(!words || ((uintptr_t)ws & 3) == 0, "ec_events_to_frames: sort workspace alignment");
+
+    EvArgs a = {};
     a.events = events;
     a.range = reinterpret_cast<const long long *>(frame_range);
     a.H = prm->H;
@@ -1615,65 +1703,24 @@ int launch_events(const void *events, const int64_t *frame_range, int F, const e
     a.raw = raw_counts;
     a.kept = kept_counts;
     a.stats = stats;
-    // LDS plan: [histogram band | reduction scratch | event cache or sort counters].  With the
-    // per-frame event count bounded (max_frame_events, known to the caller from
-    // split_event_count's N) the cache takes 4 B per event and the band gets what is left.  Frames
-    // too long for that are bucketed by band in the caller's sort workspace (one slot of
-    // max_frame_events indices per resident workgroup, which then walks several frames); without
-    // a workspace, or for frames longer than the bound, every band pass re-reads the events from L2.
-    constexpr int LDS_TOTAL = 160 * 1024;
-    int cache_events = 0, bin_budget = EV_BIN_BYTES;
-    if (prm->max_frame_events > 0) {
-        const long cache_bytes = ((long)prm->max_frame_events * 4 + 15) / 16 * 16;
-        const long left = (long)EV_BIN_BYTES - cache_bytes;
-        // worth it when the whole frame then needs at most 8 bands
-        if (left >= row_bytes && ec::ceil_div(prm->H, (int)(left / row_bytes)) <= 8) {
-            cache_events = prm->max_frame_events;
-            bin_budget = (int)left;
-        }
+    a.rows_per_band = plan.rows_per_band, a.bands = plan.bands;
+    a.bin_bytes = plan.bin_bytes;
+    a.cache_events = plan.cache_events;
+    a.band_magic = plan.band_magic;
+    a.sort_ws = plan.sorts ? reinterpret_cast<unsigned *>(ws + plan.words_offset) : nullptr;
+    a.sort_cap = plan.sort_cap;
+    if (plan.path != EvPlan::ONLY32) a.redo = ws;
+    if (plan.path == EvPlan::BAND10) {
+        a.b10_ws = reinterpret_cast<unsigned *>(ws + plan.words_offset);
+        a.b10_rows = plan.b10.rows, a.b10_bands = plan.b10.bands, a.b10_cap = plan.b10.cap, a.b10_events = prm->max_frame_events;
     }
-    int grid = F;
-    a.sort_ws = nullptr;
-    a.sort_cap = 0;
-    // banded 10-bit path (events_band10_kernel): the workspace is [frame flags | code regions, one per CU]; what the
-    // 32-bit kernel behind it uses as sort slots for the frames it is left with is the region area
-    const B10Plan b10 = b10_plan(prm->H, prm->W, prm->max_frame_events);
-    const int cus_now = ec::cu_count() > 0 ? ec::cu_count() : 256;
-    const bool use_b10 = b10.ok && !raw_counts && !kept_counts && prm->sort_workspace &&
-                         prm->sort_workspace_bytes >= (size_t)B10_FLAG_BYTES + b10.region_bytes && !events_env_off("EC_EVENTS_NO_BAND10");
-    unsigned char *sort_base = static_cast<unsigned char *>(prm->sort_workspace) + (use_b10 ? B10_FLAG_BYTES : 0);
-    const size_t sort_bytes = prm->sort_workspace ? prm->sort_workspace_bytes - (use_b10 ? B10_FLAG_BYTES : 0) : 0;
-    if (cache_events == 0 && prm->max_frame_events > 0 && prm->sort_workspace) {
-        const int sort_budget = (LDS_TOTAL - EV_SCRATCH_BYTES - EV_SORT_BYTES) / 16 * 16;
-        const int budget = sort_budget < EV_BIN_BYTES ? sort_budget : EV_BIN_BYTES;
-        const int rows = budget / row_bytes;
-        const size_t slot = (size_t)prm->max_frame_events * 4;
-        const size_t slots = sort_bytes / slot;
-        if (rows >= 1 && ec::ceil_div(prm->H, rows) > 1 && ec::ceil_div(prm->H, rows) <= EV_SORT_MAX_BANDS &&
-            slots >= 1) {
-            EC_REQUIRE(((uintptr_t)prm->sort_workspace & 3) == 0, "ec_events_to_frames: sort workspace alignment");
-            bin_budget = budget;
-            a.sort_ws = reinterpret_cast<unsigned *>(sort_base);
-            a.sort_cap = prm->max_frame_events;
-            int cus = 256;
-            int dev = 0;
-            if (hipGetDevice(&dev) == hipSuccess)
-                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            grid = F < cus ? F : cus;
-            if ((size_t)grid > slots) grid = (int)slots;
-        }
-    }
-    const int max_rows = bin_budget / row_bytes;
-    a.bands = ec::ceil_div(prm->H, max_rows);
-    a.rows_per_band = ec::ceil_div(prm->H, a.bands);
-    a.bin_bytes = (a.rows_per_band * row_bytes + 15) / 16 * 16;
-    a.cache_events = cache_events;
-    a.F = F;
-    a.band_magic = (unsigned)((0x100000000ull + (unsigned)a.rows_per_band - 1) / (unsigned)a.rows_per_band);
 
-    const int lds = LDS_TOTAL;   // always the full carve: one attribute call, one workgroup per CU
-    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(events_to_frames_kernel<EV>), lds))
-        return rc;
+    void (*const front)(const EvArgs) = plan.path == EvPlan::WHOLE10 ? events_pack10_kernel<EV>
+                                        : plan.path == EvPlan::BAND10 ? events_band10_kernel<EV> : nullptr;
+    // (the full LDS as every kernel's limit: one attribute call each)
+    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(events_to_frames_kernel<EV>), EV_LDS_TOTAL)) return rc;
+    if (front)
+        if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(front), EV_LDS_TOTAL)) return rc;
     hipStream_t hs = static_cast<hipStream_t>(stream);
     // algorithmic bytes: 16 B (packed: 8 B) per event in + 3*H*W out.  The frame
     // ranges live on the device; the caller states their total length in prm->total_events (0 =
@@ -1681,75 +1728,25 @@ int launch_events(const void *events, const int64_t *frame_range, int F, const e
     ec::ProfScope prof(ec::PROF_EVENTS, hs, 0,
                        (double)F * prm->H * prm->W * 3.0 +
                            (double)(prm->total_events > 0 ? prm->total_events : 0) * sizeof(EV));
-    a.redo = nullptr;
-    if (use_b10) {
-        // banded 10-bit path first, then the 32-bit kernel for the frames it flagged (none, for ordinary data)
-        const int b10_lds = (int)b10.bin_bytes + B10_SIDE_BYTES;
-        if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(events_band10_kernel<EV>), lds)) return rc;
-        uint8_t *flags = static_cast<uint8_t *>(prm->sort_workspace);
-        size_t wgs_fit = (prm->sort_workspace_bytes - B10_FLAG_BYTES) / b10.region_bytes;
-        if (wgs_fit > (size_t)cus_now) wgs_fit = (size_t)cus_now;
-        for (long f0 = 0; f0 < F; f0 += B10_FLAG_BYTES) {
-            const int fc = (int)(F - f0 < B10_FLAG_BYTES ? F - f0 : B10_FLAG_BYTES);
-            EvArgs g = a;
-            g.range = a.range + 2 * f0;
-            g.frames = a.frames + f0 * prm->H * prm->W * 3;
-            g.stats = a.stats ? a.stats + f0 : nullptr;
-            g.F = fc;
-            g.redo = flags;
+    // per chunk of frames: the 10-bit kernel, if any, then the 32-bit kernel for the frames it flagged (none, for ordinary
+    // data: its workgroups return at once).  Without a front kernel the one chunk is all F frames
+    const long M = (long)prm->H * prm->W;
+    for (long f0 = 0; f0 < F; f0 += plan.chunk_frames) {
+        EvArgs g = a;
+        g.F = (int)std::min<long>(F - f0, plan.chunk_frames);
+        g.range += 2 * f0;
+        g.frames += f0 * M * 3;
+        if (g.raw) g.raw += f0 * M * 2;
+        if (g.kept) g.kept += f0 * M * 2;
+        if (g.stats) g.stats += f0;
+        if (front) {
             EvArgs p = g;
-            p.bin_bytes = (int)b10.bin_bytes;
-            p.b10_ws = reinterpret_cast<unsigned *>(sort_base);
-            p.b10_rows = b10.rows, p.b10_bands = b10.bands, p.b10_cap = b10.cap, p.b10_events = prm->max_frame_events;
-            p.band_magic = (unsigned)((0x100000000ull + (unsigned)b10.rows - 1) / (unsigned)b10.rows);
-            const int wgs = fc < (int)wgs_fit ? fc : (int)wgs_fit;
-            hipLaunchKernelGGL(events_band10_kernel<EV>, dim3(wgs), dim3(EV_THREADS), b10_lds, hs, p);
-            hipLaunchKernelGGL(events_to_frames_kernel<EV>, dim3(fc < grid ? fc : grid), dim3(EV_THREADS), lds, hs, g);
-            EC_CHECK_HIP(hipGetLastError());
+            p.bin_bytes = plan.front_bin_bytes, p.band_magic = plan.front_magic;
+            hipLaunchKernelGGL(front, dim3(std::min(g.F, plan.front_wgs)), dim3(EV_THREADS), plan.front_lds, hs, p);
         }
-        return EC_OK;
+        hipLaunchKernelGGL(events_to_frames_kernel<EV>, dim3(std::min(g.F, plan.grid_cap)), dim3(EV_THREADS), EV_LDS_TOTAL, hs, g);
+        EC_CHECK_HIP(hipGetLastError());
     }
-    if (pack10_fits(prm->H, prm->W) && prm->sort_workspace && prm->sort_workspace_bytes >= 256 &&
-        !events_env_off("EC_EVENTS_NO_PACK10")) {
-        // whole-frame 10-bit path first, then the 32-bit kernel for the frames it flagged (none, for
-        // ordinary data: its workgroups return at once).  The caller's workspace holds the flags.
-        if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(events_pack10_kernel<EV>), lds))
-            return rc;
-        const int p10_lds = (int)pack10_bytes(prm->H, prm->W) + EV_SCRATCH_BYTES;
-        const int p10_per_cu = 2 * p10_lds <= LDS_TOTAL ? 2 : 1;     // 1024 threads each: at most two fit a CU
-        uint8_t *flags = static_cast<uint8_t *>(prm->sort_workspace);
-        const long cap = (long)prm->sort_workspace_bytes;
-        const long M2 = (long)prm->H * prm->W * 2;
-        if (a.sort_ws) {            // the workspace is the flag array here, not sort slots
-            a.sort_ws = nullptr;
-            a.sort_cap = 0;
-            grid = F;
-        }
-        for (long f0 = 0; f0 < F; f0 += cap) {
-            const int fc = (int)(F - f0 < cap ? F - f0 : cap);
-            EvArgs g = a;
-            g.range = a.range + 2 * f0;
-            g.frames = a.frames + f0 * prm->H * prm->W * 3;
-            g.raw = a.raw ? a.raw + f0 * M2 : nullptr;
-            g.kept = a.kept ? a.kept + f0 * M2 : nullptr;
-            g.stats = a.stats ? a.stats + f0 : nullptr;
-            g.F = fc;
-            g.redo = flags;
-            EvArgs p = g;
-            p.bin_bytes = (int)pack10_bytes(prm->H, prm->W);
-            // one persistent workgroup per CU for the 10-bit kernel (it writes every frame's flag); the 32-bit kernel
-            // behind it walks the flags with one workgroup per CU as well and touches only the flagged frames
-            const int p10_cus = ec::cu_count() > 0 ? ec::cu_count() : 256;
-            const int wgs = fc < p10_cus ? fc : p10_cus;
-            const int p10_wgs = fc < p10_cus * p10_per_cu ? fc : p10_cus * p10_per_cu;
-            hipLaunchKernelGGL(events_pack10_kernel<EV>, dim3(p10_wgs), dim3(EV_THREADS), p10_lds, hs, p);
-            hipLaunchKernelGGL(events_to_frames_kernel<EV>, dim3(wgs), dim3(EV_THREADS), lds, hs, g);
-            EC_CHECK_HIP(hipGetLastError());
-        }
-        return EC_OK;
-    }
-    hipLaunchKernelGGL(events_to_frames_kernel<EV>, dim3(grid), dim3(EV_THREADS), lds, hs, a);
-    EC_CHECK_HIP(hipGetLastError());
     return EC_OK;
 }
 
@@ -1766,23 +1763,7 @@ extern "C" EC_API int ec_events_phase_times(unsigned long long *host, int frames
 
 extern "C" EC_API size_t ec_events_sort_workspace_bytes(const ec_events_params *prm)
 {
-    if (!prm || prm->H <= 0 || prm->W <= 0) return 0;
-    if (pack10_fits(prm->H, prm->W)) return 65536;    // per-frame redo flags of the 10-bit path
-    if (prm->max_frame_events <= 0) return 0;
-    {   // banded 10-bit path: the flags, then every CU's code regions
-        const B10Plan b10 = b10_plan(prm->H, prm->W, prm->max_frame_events);
-        const int cus_now = ec::cu_count() > 0 ? ec::cu_count() : 256;
-        if (b10.ok) return (size_t)B10_FLAG_BYTES + (size_t)cus_now * b10.region_bytes;
-    }
-    const long row_bytes = (long)prm->W * 2 * 4;
-    const long cache_bytes = ((long)prm->max_frame_events * 4 + 15) / 16 * 16;
-    const long left = (long)EV_BIN_BYTES - cache_bytes;
-    if (left >= row_bytes && ec::ceil_div(prm->H, (int)(left / row_bytes)) <= 8) return 0;   // LDS cache
-    if (row_bytes * prm->H <= EV_BIN_BYTES) return 0;                                        // one band
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return (size_t)cus * (size_t)prm->max_frame_events * 4;
+    return prm ? events_plan(prm->H, prm->W, prm->max_frame_events, 0, false, events_cus()).worth_bytes : 0;
 }
 
 extern "C" EC_API int ec_events_to_frames(const float *events, const int64_t *frame_range, int F,
@@ -1803,18 +1784,16 @@ extern "C" EC_API int ec_events_to_frames_packed(const uint64_t *events, const i
                                    stream);
 }
 
+extern "C" EC_API int ec_center_events(float *events, const int64_t *sample_range, int B, int H, int W,
+                                       ec_stream_t stream)
+{
+    return center_events<float4, center_events_kernel>("ec_center_events", events, sample_range, B, H, W, stream);
+}
+
 extern "C" EC_API int ec_center_events_packed(uint64_t *events, const int64_t *sample_range, int B,
                                               int H, int W, ec_stream_t stream)
 {
-    EC_REQUIRE(B >= 0 && H > 0 && W > 0, "ec_center_events_packed: bad arguments");
-    if (B == 0) return EC_OK;
-    EC_REQUIRE(events && sample_range, "ec_center_events_packed: null buffer");
-    EC_REQUIRE(((uintptr_t)events & 7) == 0, "ec_center_events_packed: events must be 8-byte aligned");
-    hipLaunchKernelGGL(center_packed_kernel, dim3(B), dim3(1024), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<packed_t *>(events),
-                       reinterpret_cast<const long long *>(sample_range), H, W);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return center_events<packed_t, center_packed_kernel>("ec_center_events_packed", events, sample_range, B, H, W, stream);
 }
 
 extern "C" EC_API int ec_pack_events(const float *events, int64_t n, uint64_t *packed,

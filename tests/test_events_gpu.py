@@ -382,3 +382,109 @@ def test_ragged_batches_through_the_persistent_kernels(shape, hint, hip):
             continue
         want = oe.events2frames(evs[i], 'event_count', 'event_histogram', shape=shape, N=max(lengths[i], 1), grayscale=False)
         np.testing.assert_array_equal(got[i], want[0])
+
+
+# ---- the caller's workspace is shorter than asked: the only launches that go round the chunk loop more than once ----
+STAT_KEYS = ('sum', 'sumsq', 'nnz', 'max_kept', 'dropped', 'ambiguous')
+STATS_DTYPE = np.dtype([('sum', '<u8'), ('sumsq', '<u8'), ('nnz', '<u4'), ('max_kept', '<u4'), ('dropped', '<u4'),
+                        ('ambiguous', '<u4'), ('thr', '<f8')])
+_short_ws_cases = {}
+
+
+def short_ws_case(name):
+    """(shape, events [n, 4], frame lengths, oracle frames / raw / kept per frame), computed once per process.  An empty
+    frame has no oracle (the reference raises on it): its entries are None."""
+    if name in _short_ws_cases:
+        return _short_ws_cases[name]
+    from eventclip_amd.synthetic import make_events
+    from oracle import events as oe
+    rng = np.random.default_rng(77)
+    if name == 'whole':           # 24 x 36: whole frame as 10-bit counts; 256 flags per chunk -> 256 + 256 + 188 frames
+        shape, lengths = (24, 36), rng.integers(0, 41, size=700)
+        evs = [make_events(int(n), shape, seed=1000 + i, hot_pixels=0) for i, n in enumerate(lengths)]
+        for f in (300, 600):      # 1100 events of one polarity on one pixel: past the 10-bit field, flagged, redone
+            hot = np.tile(np.array([[5 + f % 7, 11, 0.31, 1.]], np.float32), (1100, 1))
+            evs[f] = np.concatenate([evs[f], hot])
+            lengths[f] += 1100
+    else:                         # 260 x 240 does not fit whole: two row bands of 130 rows
+        shape, lengths = (260, 240), rng.integers(1500, 2001, size=5)
+        evs = [make_events(int(n), shape, seed=2000 + i) for i, n in enumerate(lengths)]
+    want = [oe.events2frames(e, 'event_count', 'event_histogram', shape=shape, N=len(e), grayscale=False, return_counts=True)
+            if len(e) else None for e in evs]
+    assert all(w is None or w[0].shape[0] == 1 for w in want)
+    _short_ws_cases[name] = (shape, np.concatenate(evs), [int(n) for n in lengths], want)
+    return _short_ws_cases[name]
+
+
+def launch_with_workspace(shape, ev, lengths, ws_bytes, counts_and_stats, max_frame_events):
+    """ec_events_to_frames through the C ABI with a workspace of exactly ws_bytes (0: none); the bytes behind it stay 0xA5."""
+    import torch
+    from eventclip_amd import _lib, vis
+    F, (H, W) = len(lengths), shape
+    ends = np.cumsum(lengths)
+    r = torch.tensor(np.stack([ends - np.array(lengths), ends], 1), dtype=torch.int64).cuda()
+    e = torch.from_numpy(ev).cuda()
+    frames = torch.empty((F, H, W, 3), dtype=torch.uint8, device='cuda')
+    raw = kept = stats = None
+    if counts_and_stats:
+        raw = torch.empty((F, H, W, 2), dtype=torch.int32, device='cuda')
+        kept = torch.empty((F, H, W, 2), dtype=torch.int32, device='cuda')
+        stats = torch.zeros((F, STATS_DTYPE.itemsize), dtype=torch.uint8, device='cuda')
+    prm = vis.make_params(shape, grayscale=False, max_frame_events=max_frame_events)
+    ws = torch.full((ws_bytes + 4096,), 0xA5, dtype=torch.uint8, device='cuda')
+    if ws_bytes:
+        prm.sort_workspace, prm.sort_workspace_bytes = ws.data_ptr(), ws_bytes
+    _lib.launch('ec_events_to_frames', e, r, F, prm, frames, raw, kept, stats)
+    torch.cuda.synchronize()
+    assert bool((ws[ws_bytes:] == 0xA5).all()), 'the launch wrote behind the workspace it was given'
+    if not counts_and_stats:
+        return frames.cpu().numpy(), None, None, None
+    return frames.cpu().numpy(), raw.cpu().numpy(), kept.cpu().numpy(), stats.cpu().numpy().view(STATS_DTYPE).reshape(F)
+
+
+def check_against_oracle(got, want, empty):
+    """frames, raw, kept, stats of a launch against the per-frame oracle; empty frames against `empty` (frame, raw, kept)."""
+    frames, raw, kept, stats = got
+    for f, w in enumerate(want):
+        wf, wr, wk = (w[0][0], w[1][0], w[2][0]) if w is not None else empty
+        np.testing.assert_array_equal(frames[f], wf, err_msg=f'frame {f}')
+        if raw is None:
+            continue
+        np.testing.assert_array_equal(raw[f], wr, err_msg=f'raw {f}')
+        np.testing.assert_array_equal(kept[f], wk, err_msg=f'kept {f}')
+        wr = wr.astype(np.int64)
+        have = tuple(int(stats[k][f]) for k in STAT_KEYS)
+        assert have == (int(wr.sum()), int((wr * wr).sum()), int((wr > 0).sum()), int(wk.max()), 0, 0), f'stats {f}'
+
+
+@pytest.mark.parametrize('ws_bytes', [256, 255], ids=['three_chunks', 'no_front_kernel'])
+@pytest.mark.parametrize('counts_and_stats', [False, True], ids=['frames_only', 'counts_stats'])
+def test_short_workspace_whole_frame_path(ws_bytes, counts_and_stats, hip):
+    """700 frames of a 24 x 36 sensor with 256 bytes of workspace: the whole-frame 10-bit kernel takes them in chunks of
+    256, 256 and 188 frames, each with the 32-bit kernel behind it, which finishes the overflowing frames 300 and 600
+    with their chunk's offsets into the ranges, frames, counts and statistics.  With 255 bytes the 32-bit kernel runs
+    alone.  Both bit for bit what the oracle gives frame by frame."""
+    shape, ev, lengths, want = short_ws_case('whole')
+    assert lengths[300] > 1100 and lengths[600] > 1100 and 0 in lengths
+    got = launch_with_workspace(shape, ev, lengths, ws_bytes, counts_and_stats, max(lengths))
+    # a frame without events (the reference raises on one): what the launch without a workspace makes of it
+    ref = launch_with_workspace(shape, ev[:1], [0, 1], 0, True, max(lengths))
+    check_against_oracle(got, want, (ref[0][0], ref[1][0], ref[2][0]))
+
+
+@pytest.mark.parametrize('one_region', [True, False], ids=['one_region', 'one_byte_less'])
+def test_short_workspace_banded_path(one_region, hip):
+    """A 260 x 240 sensor (two row bands of 10-bit counts) with the flags and ONE workgroup's region of workspace: one
+    workgroup of the banded kernel walks all five frames.  With one byte less there is no banded kernel.  Frames only,
+    bit for bit the oracle's."""
+    import ctypes
+    from eventclip_amd import _lib
+    shape, ev, lengths, want = short_ws_case('banded')
+    prm = _lib.EcEventsParams()
+    prm.H, prm.W, prm.max_frame_events = shape[0], shape[1], 2000
+    cus = ctypes.c_int(0)
+    _lib.check(hip.ec_device_info(ctypes.byref(cus), None, 0), 'ec_device_info')
+    region = (int(hip.ec_events_sort_workspace_bytes(ctypes.byref(prm))) - 65536) // cus.value
+    assert region == 2 * 16 * 128 * 4                      # [band][wave][64 * ceil(2000 / 1024)] words
+    got = launch_with_workspace(shape, ev, lengths, 65536 + region - (0 if one_region else 1), False, 2000)
+    check_against_oracle(got, want, None)
