@@ -1,4 +1,5 @@
-// events -> polarity-histogram frames on gfx950.
+// events -> polarity-histogram frames on gfx950 (and, in the last section, -> time-surface frames: the second
+// representation shares parse(), the packed format and the block reductions of this file).
 //
 // Replaces /root/reference/datasets/vis.py make_event_histogram (:6-41) +
 // parse_events (:44-52) as driven by events2frames (:75-117).
@@ -27,6 +28,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "eventclip_time_surface.h"
 
 // numpy evaluates every ufunc with one rounding per operation: no FMA contraction anywhere in
 // this file (the one fused multiply-add of the reference is written out explicitly).
@@ -1750,6 +1752,280 @@ int launch_events(const void *events, const int64_t *frame_range, int F, const e
     return EC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// events -> time-surface frames (include/eventclip_time_surface.h states the definition, steps 1 - 7).
+//
+// The surface of a row band lives in LDS as one 32-bit word per (pixel, polarity), filled with LDS atomic max: a counted
+// event stores tick + 1 -- with reverse_t, 2^30 - tick, so that the earliest tick is the largest word -- and 0 is
+// "untouched".  A maximum does not depend on the order of the events.  A sensor that does not fit is cut into row bands
+// (N-Caltech: 3, N-ImageNet: 16); there is no HBM intermediate, so every band scans all events of its frame, and the only
+// global writes are the frame and the two debug outputs.
+// One 1024-thread workgroup owns one (frame, band) at a time and walks items blockIdx.x, + gridDim.x, ...  It needs t0 / t1
+// over ALL events of the frame before it can colour a pixel, and has them for nothing: the one scan that fills its band
+// also takes the frame's tallies (t0, t1, dropped, counted), one block reduction behind it; band 0 writes the stats.  Per
+// (frame, band) rather than per frame with a loop over the bands: the work is the same scan per band either way, a small
+// batch of a large sensor spreads over bands x frames compute units, and the kernel has no second form of its scan.
+// One workgroup per compute unit: at ~100 VGPRs a second 1024-thread workgroup does not fit a CU's registers.
+// Measured (profiles/time_surface.md): an item costs 22 - 39 us whatever its event count, so the multi-band sensors fall
+// short of the histogram path by about their band count.  Bands of a frame kept on one XCD for its L2, and two register
+// buffers of events in flight, were both measured and moved it by 7 % at most: neither bandwidth nor load latency bounds it.
+// ---------------------------------------------------------------------------------------------
+constexpr unsigned TS_TICK_MAX = (1u << 30) - 1;          // EC_PACKED_T's range
+constexpr unsigned TS_REVERSED = 1u << 30;                // reverse_t: the word of tick t is TS_REVERSED - t, in 1 .. 2^30
+
+struct TsArgs {
+    const void *events;      // float4 (x, y, t, p) or packed 8-byte events
+    const long long *range;  // [F,2]
+    int H, W, F;
+    int exp_decay, background_mask, flip_x, negate_p, reverse_t;
+    double tau_us;
+    double red[3], blue[3];
+    int same_as[3];          // channel k has the colours of channel same_as[k] < k (a gray map: 0, 0, 0), else k
+    uint8_t *frames;
+    int *last;               // optional [F,H,W,2]
+    ec_surface_stats *stats; // optional [F]
+    int rows_per_band, bands, band_bytes;
+};
+
+// step 2: the event's tick
+__device__ __forceinline__ unsigned tick_of(const float4 e)
+{
+    double tu = __builtin_rint((double)e.z * 1e6);        // (pack_events_kernel's rule)
+    tu = tu < 0. ? 0. : (tu > (double)TS_TICK_MAX ? (double)TS_TICK_MAX : tu);
+    return (unsigned)tu;
+}
+__device__ __forceinline__ unsigned tick_of(const packed_t e) { return (unsigned)(e >> 34); }
+
+// the frame's reduction: per-thread tallies in, the frame's values in every thread out
+struct TsTally {
+    unsigned hi, lo;         // max of tick + 1, max of TS_REVERSED - tick over the counted events; 0 = none
+    unsigned dropped, counted;
+};
+__device__ __forceinline__ TsTally block_tally(const TsTally t, unsigned long long *scratch)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = (unsigned long long)wave_max_dpp(t.hi) | ((unsigned long long)wave_max_dpp(t.lo) << 32);
+    const unsigned long long s = (unsigned long long)wave_sum_u32(t.dropped) | ((unsigned long long)wave_sum_u32(t.counted) << 32);
+    __syncthreads();
+    if (lane == 0) scratch[wave] = m, scratch[EV_WAVES + wave] = s;
+    __syncthreads();
+    TsTally r = {0, 0, 0, 0};
+#pragma unroll
+    for (int w = 0; w < EV_WAVES; w++) {
+        const unsigned long long a = scratch[w], b = scratch[EV_WAVES + w];
+        const unsigned hi = (unsigned)a, lo = (unsigned)(a >> 32);
+        r.hi = hi > r.hi ? hi : r.hi, r.lo = lo > r.lo ? lo : r.lo;
+        r.dropped += (unsigned)b, r.counted += (unsigned)(b >> 32);
+    }
+    return r;
+}
+
+// steps 1 - 4 for the events of a frame and the rows [y0, y1): one LDS atomic per counted event of the band, and the
+// frame's tallies
+template <typename EV>
+__device__ __forceinline__ void surface_band(const EV *ev, long long n, int y0, int y1, const TsArgs &a, unsigned *state,
+                                             TsTally &t)
+{
+    const int H = a.H, W = a.W;
+    // eight loads in flight per thread (a slot past the end re-reads the last event and is masked)
+    for (long long i = threadIdx.x; i < n; i += 8 * EV_THREADS) {
+        EV e[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const long long j = i + (long long)k * EV_THREADS;
+            e[k] = ev[j < n ? j : n - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            int x, y, p;
+            parse(e[k], W, a.flip_x, a.negate_p, x, y, p);
+            const bool there = i + (long long)k * EV_THREADS < n && p != 0;
+            const bool inside = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
+            const unsigned tick = tick_of(e[k]);
+            t.dropped += there && !inside;
+            t.counted += there && inside;
+            const unsigned hi = there && inside ? tick + 1u : 0u, lo = there && inside ? TS_REVERSED - tick : 0u;
+            t.hi = hi > t.hi ? hi : t.hi, t.lo = lo > t.lo ? lo : t.lo;
+            if (there && inside && y >= y0 && y < y1)
+                atomicMax(&state[((y - y0) * W + x) * 2 + (p < 0 ? 1 : 0)], a.reverse_t ? TS_REVERSED - tick : tick + 1u);
+        }
+    }
+}
+
+// steps 5 - 7 for one pixel: its two state words -> three bytes; l[] receives L (-1 = untouched)
+struct TsFrame {
+    unsigned t0, t1;
+    double span;
+};
+__device__ __forceinline__ void surface_pixel(unsigned s0, unsigned s1, const TsFrame &fr, const TsArgs &a, uint8_t out[3],
+                                              int l[2])
+{
+    double v[2];
+    const unsigned s[2] = {s0, s1};
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        v[c] = 0., l[c] = -1;
+        if (s[c] == 0) continue;
+        const unsigned L = a.reverse_t ? TS_REVERSED - s[c] : s[c] - 1u;
+        const unsigned age = a.reverse_t ? L - fr.t0 : fr.t1 - L;
+        l[c] = (int)L;
+        if (a.exp_decay) {
+            const double q = (double)age / a.tau_us;
+            v[c] = exp(-q);
+        } else {
+            const unsigned span = fr.t1 - fr.t0;
+            v[c] = span == 0 ? 1. : (double)(span - age) / fr.span;
+        }
+    }
+    double w = 0.;
+    if (a.background_mask) {
+        w = v[0] + v[1];
+        if (w > 1.) w = 1.;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (a.same_as[k] != k) {                             // (uniform) the same operations on the same operands
+            out[k] = a.same_as[k] == 0 ? out[0] : out[1];    // (no runtime index into the registers)
+            continue;
+        }
+        const double tp = v[0] * a.red[k];
+        const double tn = v[1] * a.blue[k];
+        double img = tp + tn;
+        if (a.background_mask) {
+            const double t1 = img * w;
+            const double om = 1. - w;
+            const double t2 = 255. * om;
+            img = t1 + t2;
+        }
+        out[k] = (uint8_t)(int)__builtin_rint(img);
+    }
+}
+
+template <typename EV>
+__global__ __launch_bounds__(EV_THREADS) void time_surface_kernel(const TsArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned *state = reinterpret_cast<unsigned *>(smem);
+    unsigned long long *scratch = reinterpret_cast<unsigned long long *>(smem + a.band_bytes);
+    const int H = a.H, W = a.W, rpb = a.rows_per_band;
+    const long long M = (long long)H * W;
+
+    for (long long item = blockIdx.x; item < (long long)a.F * a.bands; item += gridDim.x) {
+        const int f = (int)(item / a.bands), b = (int)(item % a.bands);
+        const long long e0 = a.range[2 * f], n = a.range[2 * f + 1] - e0;
+        const EV *ev = reinterpret_cast<const EV *>(a.events) + e0;
+        uint8_t *out = a.frames + (long long)f * M * 3;
+        TsFrame fr = {0, 0, 0.};
+        const int y0 = b * rpb, y1 = min(H, y0 + rpb);
+        const int npix = (y1 - y0) * W;
+        for (int i = threadIdx.x; i < a.band_bytes / 16; i += EV_THREADS) reinterpret_cast<uint4 *>(state)[i] = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+        TsTally t = {0, 0, 0, 0};
+        surface_band(ev, n, y0, y1, a, state, t);
+        t = block_tally(t, scratch);                                      // (its first barrier ends the band's atomics)
+        if (t.counted) fr.t0 = TS_REVERSED - t.lo, fr.t1 = t.hi - 1u;
+        fr.span = (double)(fr.t1 - fr.t0);
+        if (a.stats && b == 0 && threadIdx.x == 0) {
+            ec_surface_stats st;
+            st.dropped = t.dropped, st.counted = t.counted, st.t0 = fr.t0, st.t1 = fr.t1;
+            a.stats[f] = st;
+        }
+        uint8_t *o = out + (long long)y0 * W * 3;
+        int *lo = a.last ? a.last + ((long long)f * M + (long long)y0 * W) * 2 : nullptr;
+        if ((W & 3) == 0) {
+            // 4 pixels = 12 bytes = three dwords per thread, 4-byte aligned
+            for (int g = threadIdx.x; g < npix / 4; g += EV_THREADS) {
+                unsigned words[3];
+                uint8_t *bytes = reinterpret_cast<uint8_t *>(words);
+                const uint4 ca = *reinterpret_cast<const uint4 *>(&state[g * 8]);
+                const uint4 cb = *reinterpret_cast<const uint4 *>(&state[g * 8 + 4]);
+                const unsigned s[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
+                int l[8];
+#pragma unroll
+                for (int k = 0; k < 4; k++) surface_pixel(s[2 * k], s[2 * k + 1], fr, a, bytes + 3 * k, l + 2 * k);
+                unsigned *dst = reinterpret_cast<unsigned *>(o + (long long)g * 12);
+                dst[0] = words[0];
+                dst[1] = words[1];
+                dst[2] = words[2];
+                if (lo) {
+#pragma unroll
+                    for (int k = 0; k < 8; k++) lo[(long long)g * 8 + k] = l[k];
+                }
+            }
+        } else {
+            for (int q = threadIdx.x; q < npix; q += EV_THREADS) {
+                uint8_t px[3];
+                int l[2];
+                surface_pixel(state[2 * q], state[2 * q + 1], fr, a, px, l);
+                o[3 * q] = px[0];
+                o[3 * q + 1] = px[1];
+                o[3 * q + 2] = px[2];
+                if (lo) lo[2 * q] = l[0], lo[2 * q + 1] = l[1];
+            }
+        }
+        __syncthreads();                                                  // the band is read: the next item may zero it
+    }
+}
+
+// Row bands of 8 bytes per pixel: as many rows as fit EV_BIN_BYTES, evened out over the bands; the reduction scratch behind.
+struct TsPlan {
+    int rows_per_band, bands, band_bytes, lds;
+};
+inline TsPlan time_surface_plan(int H, int W)
+{
+    TsPlan p = {};
+    const long row_bytes = (long)W * 2 * 4;
+    p.bands = ec::ceil_div(H, (int)std::min<long>(H, EV_BIN_BYTES / row_bytes));
+    p.rows_per_band = ec::ceil_div(H, p.bands);
+    p.band_bytes = (int)((p.rows_per_band * row_bytes + 15) / 16 * 16);
+    p.lds = p.band_bytes + EV_REDUCE_BYTES;
+    return p;
+}
+
+template <typename EV>
+int launch_time_surface(const void *events, const int64_t *frame_range, int F, const ec_time_surface_params *prm,
+                        uint8_t *frames, int32_t *last, ec_surface_stats *stats, ec_stream_t stream)
+{
+    EC_REQUIRE(prm != nullptr, "ec_events_to_time_surface: params is null");
+    EC_REQUIRE(F >= 0, "ec_events_to_time_surface: F=%d", F);
+    if (F == 0) return EC_OK;
+    EC_REQUIRE(events && frame_range && frames, "ec_events_to_time_surface: null buffer");
+    EC_REQUIRE(prm->H > 0 && prm->W > 0, "ec_events_to_time_surface: bad shape (%d,%d)", prm->H, prm->W);
+    EC_REQUIRE(((uintptr_t)events & (sizeof(EV) - 1)) == 0,
+               "ec_events_to_time_surface: events must be %d-byte aligned", (int)sizeof(EV));
+    EC_REQUIRE(((uintptr_t)frames & 3) == 0 && ((uintptr_t)last & 3) == 0, "ec_events_to_time_surface: frames and last must be 4-byte aligned");
+    EC_REQUIRE((long)prm->W * 2 * 4 <= EV_BIN_BYTES, "ec_events_to_time_surface: W=%d too wide for one LDS row band", prm->W);
+    EC_REQUIRE(prm->decay == EC_DECAY_LINEAR || prm->decay == EC_DECAY_EXP, "ec_events_to_time_surface: unknown decay %d", prm->decay);
+    EC_REQUIRE(prm->decay != EC_DECAY_EXP || prm->tau_us > 0., "ec_events_to_time_surface: tau_us=%g must be positive", prm->tau_us);
+
+    const TsPlan plan = time_surface_plan(prm->H, prm->W);
+    TsArgs a = {};
+    a.events = events;
+    a.range = reinterpret_cast<const long long *>(frame_range);
+    a.H = prm->H, a.W = prm->W, a.F = F;
+    a.exp_decay = prm->decay == EC_DECAY_EXP;
+    a.tau_us = prm->tau_us;
+    a.background_mask = prm->background_mask;
+    a.flip_x = prm->flip_x, a.negate_p = prm->negate_p, a.reverse_t = prm->reverse_t;
+    for (int c = 0; c < 3; c++) {
+        a.red[c] = (double)prm->red[c], a.blue[c] = (double)prm->blue[c];
+        a.same_as[c] = c;
+        for (int d = c - 1; d >= 0; d--)
+            if (prm->red[d] == prm->red[c] && prm->blue[d] == prm->blue[c]) a.same_as[c] = d;
+    }
+    a.frames = frames, a.last = last, a.stats = stats;
+    a.rows_per_band = plan.rows_per_band, a.bands = plan.bands, a.band_bytes = plan.band_bytes;
+
+    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(time_surface_kernel<EV>), EV_LDS_TOTAL)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // algorithmic bytes: 16 B (packed: 8 B) per event in + 3*H*W out, as launch_events states them
+    ec::ProfScope prof(ec::PROF_TIME_SURFACE, hs, 0,
+                       (double)F * prm->H * prm->W * 3.0 + (double)(prm->total_events > 0 ? prm->total_events : 0) * sizeof(EV));
+    hipLaunchKernelGGL(time_surface_kernel<EV>, dim3((unsigned)std::min<long>((long)F * plan.bands, events_cus())), dim3(EV_THREADS), plan.lds, hs, a);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
 }  // namespace
 
 #ifdef EC_EVENTS_DIAG
@@ -1782,6 +2058,20 @@ extern "C" EC_API int ec_events_to_frames_packed(const uint64_t *events, const i
 {
     return launch_events<packed_t>(events, frame_range, F, prm, frames, raw_counts, kept_counts, stats,
                                    stream);
+}
+
+extern "C" EC_API int ec_events_to_time_surface(const float *events, const int64_t *frame_range, int F,
+                                                const ec_time_surface_params *prm, uint8_t *frames, int32_t *last,
+                                                ec_surface_stats *stats, ec_stream_t stream)
+{
+    return launch_time_surface<float4>(events, frame_range, F, prm, frames, last, stats, stream);
+}
+
+extern "C" EC_API int ec_events_to_time_surface_packed(const uint64_t *events, const int64_t *frame_range, int F,
+                                                       const ec_time_surface_params *prm, uint8_t *frames, int32_t *last,
+                                                       ec_surface_stats *stats, ec_stream_t stream)
+{
+    return launch_time_surface<packed_t>(events, frame_range, F, prm, frames, last, stats, stream);
 }
 
 extern "C" EC_API int ec_center_events(float *events, const int64_t *sample_range, int B, int H, int W,

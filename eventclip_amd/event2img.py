@@ -25,7 +25,10 @@ class Event2ImagePipeline:
     resolution, max_n: the event dataset's constants (caltech.py:52-58 etc.).
     quantize_args: same dict as the reference's configs (``max_imgs``, ``N``,
         ``split_method``, ``convert_method``, ``grayscale``, ``count_non_zero``,
-        ``background_mask``).
+        ``background_mask``).  ``convert_method`` is ``'event_histogram'`` or ``'time_surface'`` (not in the
+        reference: the latest-timestamp frames of include/eventclip_time_surface.h), which reads ``decay``
+        (``'linear'``, the default, or ``'exp'``) and ``tau`` (seconds, 0.03) and accepts but ignores ``thresh``,
+        ``count_non_zero`` and ``float_stage``: it has no hot-pixel threshold and no frame maximum.
     n_px: CLIP input resolution.  patch/kpad/dtype: when given, ``__call__`` emits the
         16-bit im2col rows for ``CLIP.encode_patches`` instead of fp32 images.
     frames_u8: emit the resized + cropped uint8 frames (``frames_u8`` [Fv, R, R, 3]) instead, the input of
@@ -39,7 +42,7 @@ class Event2ImagePipeline:
         self.split_method = qa['split_method']
         self.event_rep = qa['convert_method']
         assert self.split_method == 'event_count'                       # event2img.py:69
-        if self.event_rep != 'event_histogram':                          # vis.py:113
+        if self.event_rep not in vis.CONVERT_METHODS:                    # vis.py:113
             raise NotImplementedError(f'{self.event_rep} not implemented!')
         self.N = int(qa['N'])
         max_imgs = round(max_n / self.N)                                 # event2img.py:70
@@ -51,6 +54,10 @@ class Event2ImagePipeline:
         self.background_mask = bool(qa.get('background_mask', True))
         # not a key of the reference's configs: which numpy the frames should agree with (vis.py:27)
         self.float_stage = qa.get('float_stage', vis.DEFAULT_FLOAT_STAGE)
+        # convert_method='time_surface' only
+        self.decay, self.tau = qa.get('decay', 'linear'), float(qa.get('tau', 0.03))
+        if self.decay not in vis.DECAYS:
+            raise ValueError(f"decay {self.decay!r}: 'linear' or 'exp'")
         self.n_px, self.patch, self.kpad, self.dtype = int(n_px), patch, kpad, dtype
         self.frames_u8 = bool(frames_u8)
         assert not (self.frames_u8 and self.patch), 'frames_u8 and patch rows are two different outputs'
@@ -71,7 +78,8 @@ class Event2ImagePipeline:
         row_idx int32 [B, T], valid_mask bool [B, T]) as CPU tensors; row_idx[b, t] is the
         compact frame number of view t of sample b, or -1 for a padded view.
         tflip: chunk the time-reversed stream (utils.py:26-35): chunk [a, b) of the reversed
-        order covers rows [n - b, n - a) of the stored order (a histogram ignores order).
+        order covers rows [n - b, n - a) of the stored order (a histogram ignores order, and a time surface
+        takes the reversed time as ``reverse_t``).
         starts: first event row of every sample when the samples are not back to back (after
         eventclip_amd.augment.augment_events_device has dropped events)."""
         T = self.max_imgs
@@ -101,12 +109,17 @@ class Event2ImagePipeline:
         return fr, ri, ri >= 0
 
     def frames(self, events, frame_range, hflip=False, tflip=False, total_events=0):
-        """uint8 [Fv, H, W, 3] for the planned views (vis.events2frames, batched)."""
-        out = vis.events_to_frames_device(
-            events, frame_range, self.resolution, grayscale=self.grayscale, thresh=self.thresh,
-            count_non_zero=self.count_non_zero, background_mask=self.background_mask,
-            return_stats=self.strict, max_frame_events=self.N, flip_x=hflip, negate_p=tflip,
-            float_stage=self.float_stage, total_events=total_events)
+        """uint8 [Fv, H, W, 3] for the planned views (vis.events2frames, batched).  The time flip of a time surface
+        (utils.py:26-35: t' = t_last - t, p' = -p) is reverse_t with negate_p on the stored rows."""
+        common = dict(grayscale=self.grayscale, background_mask=self.background_mask, return_stats=self.strict,
+                      max_frame_events=self.N, flip_x=hflip, negate_p=tflip, total_events=total_events)
+        if self.event_rep == 'time_surface':
+            out = vis.time_surface_device(events, frame_range, self.resolution, decay=self.decay, tau=self.tau,
+                                          reverse_t=tflip, **common)
+        else:
+            out = vis.events_to_frames_device(
+                events, frame_range, self.resolution, thresh=self.thresh, count_non_zero=self.count_non_zero,
+                float_stage=self.float_stage, **common)
         if self.strict:
             frames, stats = out
             if int(stats['dropped'].sum()) > 0:

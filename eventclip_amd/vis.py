@@ -7,11 +7,14 @@ Same names and argument meaning as the reference:
   kernel behind ``ec_events_to_frames``.
 * ``split_event_count(t, N)`` (vis.py:55-72), ``parse_events`` (vis.py:44-52).
 
-plus the batched device entry ``events_to_frames_device`` used by the pipeline.
+plus the batched device entries ``events_to_frames_device`` (polarity histogram) and ``time_surface_device``
+(latest-timestamp frames, ``convert_method='time_surface'``: not in the reference, defined in
+include/eventclip_time_surface.h) used by the pipeline.
 There is no CPU fallback.
 """
 import collections
 import ctypes
+import os
 
 import numpy as np
 
@@ -241,13 +244,100 @@ def events_to_frames_device(events, frame_range, shape, grayscale=True, thresh=1
     return res[0] if len(res) == 1 else tuple(res)
 
 
+# ---- time-surface frames (include/eventclip_time_surface.h: the definition, steps 1 - 7) ----
+SURFACE_HEADER = os.path.join(os.path.dirname(_lib.HEADER), 'eventclip_time_surface.h')
+with open(SURFACE_HEADER) as _f:
+    # bound as _lib binds the main header; that header's #include stands for what the reader wants from it, the version
+    _, _surface_constants, _surface_structs, SURFACE_SIGNATURES = _lib.read_header(
+        _f.read().replace('#include "eventclip_hip.h"', f'#define EC_ABI_VERSION {_lib.ABI_VERSION}'))
+EcTimeSurfaceParams, EcSurfaceStats = _surface_structs['EcTimeSurfaceParams'], _surface_structs['EcSurfaceStats']
+DECAYS = {'linear': _surface_constants['EC_DECAY_LINEAR'], 'exp': _surface_constants['EC_DECAY_EXP']}
+SURFACE_STATS_DTYPE = np.dtype([('dropped', '<u4'), ('counted', '<u4'), ('t0', '<u4'), ('t1', '<u4')])
+CONVERT_METHODS = ('event_histogram', 'time_surface')
+
+
+def surface_lib():
+    """The loaded library with the entries of eventclip_time_surface.h typed (``_lib.launch`` finds them there)."""
+    handle = _lib.lib()
+    for name, (res, args) in SURFACE_SIGNATURES.items():
+        fn = getattr(handle, name)
+        fn.restype, fn.argtypes = res, args
+    return handle
+
+
+def time_surface_params(shape, red, blue, decay, tau, background_mask, max_frame_events, flip_x, negate_p, reverse_t,
+                        total_events):
+    """EcTimeSurfaceParams: what ``time_surface_device`` and the custom op both fill.  tau in seconds."""
+    if decay not in DECAYS:
+        raise ValueError(f"decay {decay!r}: 'linear' (timestamp image) or 'exp' (time surface)")
+    p = EcTimeSurfaceParams()
+    p.H, p.W = int(shape[0]), int(shape[1])
+    p.decay, p.tau_us = DECAYS[decay], float(tau) * 1e6
+    p.background_mask = int(bool(background_mask))
+    p.max_frame_events = int(max_frame_events)
+    p.flip_x, p.negate_p, p.reverse_t = int(bool(flip_x)), int(bool(negate_p)), int(bool(reverse_t))
+    p.total_events = int(total_events)
+    for c in range(3):
+        p.red[c] = int(red[c])
+        p.blue[c] = int(blue[c])
+    return p
+
+
+def time_surface_device(events, frame_range, shape, decay='linear', tau=0.03, grayscale=True, background_mask=True,
+                        return_last=False, return_stats=False, out=None, max_frame_events=0, flip_x=False,
+                        negate_p=False, reverse_t=False, total_events=0):
+    """Batched device entry of the time-surface frames; events and frame_range as ``events_to_frames_device`` takes them.
+
+    decay: 'linear', the timestamp image (a pixel's latest event scaled to the frame's time span), or 'exp', the time
+           surface exp(-age / tau) with tau in seconds.
+    reverse_t: keep each pixel's EARLIEST event and age from the frame's first: with negate_p and frame ranges of the
+           reversed order, the time flip of test-time augmentation.
+    Returns uint8 CUDA tensor [F, H, W, 3] (+ last int32 [F, H, W, 2], -1 where untouched, and a stats structured
+    array -- dropped, counted, t0, t1 -- when asked).
+    """
+    import torch
+    dev = _lib.require_gpu()
+    H, W = shape
+    packed = is_packed(events)
+    assert events.is_cuda and events.is_contiguous()
+    assert packed or (events.dtype == torch.float32 and events.dim() == 2 and events.shape[1] == 4)
+    assert frame_range.is_cuda and frame_range.dtype == torch.int64 and frame_range.is_contiguous()
+    F = int(frame_range.shape[0])
+    red, blue = colour_map(grayscale)
+    if out is None and not return_last and not return_stats:
+        # the production form: the registered custom op (eventclip_hip::events_to_time_surface)
+        from . import torch_ops  # noqa: F401  (registers the namespace)
+        return torch.ops.eventclip_hip.events_to_time_surface(
+            events, frame_range, int(H), int(W), decay, float(tau), [int(v) for v in red], [int(v) for v in blue],
+            bool(background_mask), int(max_frame_events), bool(flip_x), bool(negate_p), bool(reverse_t),
+            int(total_events))
+    # debug form (the surface itself, per-frame statistics, caller-owned output): straight to the C ABI
+    frames = out if out is not None else torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    last = torch.empty((F, H, W, 2), dtype=torch.int32, device=dev) if return_last else None
+    stats = torch.zeros((F, ctypes.sizeof(EcSurfaceStats)), dtype=torch.uint8, device=dev) if return_stats else None
+    prm = time_surface_params(shape, red, blue, decay, tau, background_mask, max_frame_events, flip_x, negate_p,
+                              reverse_t, total_events)
+    surface_lib()
+    _lib.launch('ec_events_to_time_surface_packed' if packed else 'ec_events_to_time_surface', events, frame_range, F,
+                prm, frames, last, stats)
+    res = [frames]
+    if return_last:
+        res.append(last)
+    if return_stats:
+        res.append(stats.cpu().numpy().view(SURFACE_STATS_DTYPE).reshape(F))
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 def events2frames(events, split_method, convert_method, shape=(180, 240), **kwargs):
-    """Drop-in for the reference's events2frames (vis.py:75-117): numpy in, numpy out."""
+    """Drop-in for the reference's events2frames (vis.py:75-117): numpy in, numpy out.
+
+    convert_method='time_surface' (not in the reference) takes ``decay`` ('linear' or 'exp') and ``tau`` (seconds) and
+    ignores ``thresh``, ``count_non_zero`` and ``float_stage``: there is no hot-pixel threshold and no frame maximum."""
     import torch
     grayscale = kwargs.pop('grayscale', True)
     ev = parse_events(events)
     assert split_method == 'event_count'                 # vis.py:90
-    if convert_method != 'event_histogram':              # vis.py:113
+    if convert_method not in CONVERT_METHODS:            # vis.py:113
         raise NotImplementedError(f'{convert_method} not implemented!')
     N = int(kwargs['N'])
     if ev.shape[0] == 0:
@@ -256,13 +346,17 @@ def events2frames(events, split_method, convert_method, shape=(180, 240), **kwar
     dev = _lib.require_gpu()
     ev_d = torch.from_numpy(ev).to(dev)
     rng = torch.tensor(np.stack([idx0, idx1], 1), dtype=torch.int64, device=dev)
-    frames, stats = events_to_frames_device(
-        ev_d, rng, shape, grayscale=grayscale, thresh=float(kwargs.get('thresh', 10.)),
-        count_non_zero=kwargs.get('count_non_zero', False),
-        background_mask=kwargs.get('background_mask', True), return_stats=True,
-        max_frame_events=max(b - a for a, b in zip(idx0, idx1)),
-        float_stage=kwargs.get('float_stage', DEFAULT_FLOAT_STAGE),
-        total_events=sum(b - a for a, b in zip(idx0, idx1)))
+    common = dict(grayscale=grayscale, background_mask=kwargs.get('background_mask', True), return_stats=True,
+                  max_frame_events=max(b - a for a, b in zip(idx0, idx1)),
+                  total_events=sum(b - a for a, b in zip(idx0, idx1)))
+    if convert_method == 'time_surface':
+        frames, stats = time_surface_device(ev_d, rng, shape, decay=kwargs.get('decay', 'linear'),
+                                            tau=float(kwargs.get('tau', 0.03)), **common)
+    else:
+        frames, stats = events_to_frames_device(
+            ev_d, rng, shape, thresh=float(kwargs.get('thresh', 10.)),
+            count_non_zero=kwargs.get('count_non_zero', False),
+            float_stage=kwargs.get('float_stage', DEFAULT_FLOAT_STAGE), **common)
     if int(stats['dropped'].sum()) > 0:
         # the reference's bincount/reshape raises on such input (vis.py:11)
         raise ValueError('events2frames: events outside the sensor '

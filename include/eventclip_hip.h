@@ -64,13 +64,15 @@ EC_API const char *ec_last_error(void);
  *        struct of an older caller meant; 1 = exact GELU, x Phi(x)); ec_split16's gelu argument takes 2
  *   608  + ec_vit_train_backward_image / _image_scratch_bytes, ec_patch_embed_backward, ec_unpatchify: the vision tower
  *        differentiated with respect to its input image (additive: no struct or argument list changed)
+ *   609  + ec_events_to_time_surface / _packed with ec_time_surface_params and ec_surface_stats, declared in
+ *        eventclip_time_surface.h next to this file (additive: nothing in this header changed but this number)
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does; its ctypes bindings are
  * derived from this header when it is imported, so THIS file is the only statement of the ABI.) */
-#define EC_ABI_VERSION 608
+#define EC_ABI_VERSION 609
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);

@@ -1,0 +1,279 @@
+"""The yardstick of the time-surface frames (include/eventclip_time_surface.h, steps 1 - 7): the definition restated twice
+in int64 / float64 numpy (``oracle``: vectorised, ``oracle_loop``: one event after the other), a numpy model of the
+kernel's structure with switches that plant faults (``kernel_model``), the case tables, and the one check function
+(``check``) the CPU and the GPU tests share.  The reference has no such representation: these restatements ARE the
+reference answer."""
+import functools
+
+import numpy as np
+
+from eventclip_amd import vis
+from eventclip_amd.synthetic import make_events
+
+TICK_MAX = (1 << 30) - 1
+TIE_WINDOW = 1e-9          # |img - (k + 0.5)| within this: either neighbouring byte passes (exp frames only)
+MAX_TIES = 8               # ... for at most this many pixels of a case
+
+
+# ---- steps 1 - 2 ----------------------------------------------------------------------------------------------------
+def parse(events, shape, flip_x=False, negate_p=False):
+    """float [n, 4] rows or packed uint64 [n] -> int64 x, y, p (sign), tick."""
+    H, W = shape
+    if vis.is_packed(events):
+        e = np.asarray(events).astype(np.uint64)
+        x, y = (e & np.uint64(0xffff)).astype(np.int64), ((e >> np.uint64(16)) & np.uint64(0xffff)).astype(np.int64)
+        code = ((e >> np.uint64(32)) & np.uint64(3)).astype(np.int64)
+        p = np.where(code == 0, 0, np.where(code == 1, 1, -1))
+        tick = (e >> np.uint64(34)).astype(np.int64)
+        if flip_x:
+            x = W - 1 - x
+    else:
+        ev = np.asarray(events, dtype=np.float32)
+        xf = np.float32(W - 1) - ev[:, 0] if flip_x else ev[:, 0]           # in float32, before the truncation
+        x, y, p = np.trunc(xf).astype(np.int64), np.trunc(ev[:, 1]).astype(np.int64), np.trunc(ev[:, 3]).astype(np.int64)
+        tick = np.clip(np.rint(ev[:, 2].astype(np.float64) * 1e6), 0, TICK_MAX).astype(np.int64)
+    return x, y, -p if negate_p else p, tick
+
+
+# ---- steps 5 - 7, shared by both restatements (they differ in how they reach L, t0, t1) -------------------------------
+def colour(L, t0, t1, decay, tau, grayscale, background_mask, reverse_t, exp=np.exp, clip_w=True):
+    """L int64 [H, W, 2] (-1 = untouched) -> (uint8 [H, W, 3], the float64 image before rounding)."""
+    touched = L >= 0
+    age = np.where(touched, (L - t0) if reverse_t else (t1 - L), 0)
+    span = t1 - t0
+    if decay == 'linear':
+        v = np.ones(L.shape) if span == 0 else (span - age).astype(np.float64) / np.float64(span)
+    else:
+        v = exp(-(age.astype(np.float64) / (np.float64(tau) * 1e6)))
+    v = np.where(touched, v, 0.)
+    red, blue = (c.astype(np.float64) for c in vis.colour_map(grayscale))
+    img = v[..., 0:1] * red + v[..., 1:2] * blue
+    if background_mask:
+        w = v[..., 0:1] + v[..., 1:2]
+        if clip_w:
+            w = np.minimum(w, 1.)
+        img = img * w + 255. * (1. - w)
+    return np.rint(img).astype(np.int64).astype(np.uint8), img
+
+
+def _result(F, shape):
+    H, W = shape
+    return dict(frames=np.zeros((F, H, W, 3), np.uint8), pre=np.zeros((F, H, W, 3)), last=np.full((F, H, W, 2), -1, np.int32),
+                stats=np.zeros(F, vis.SURFACE_STATS_DTYPE))
+
+
+def oracle(events, ranges, shape, decay='linear', tau=0.03, grayscale=True, background_mask=True, flip_x=False,
+           negate_p=False, reverse_t=False):
+    """The definition, vectorised (np.maximum.at / np.minimum.at)."""
+    H, W = shape
+    x, y, p, tick = parse(events, shape, flip_x, negate_p)
+    out = _result(len(ranges), shape)
+    for f, (b, e) in enumerate(ranges):
+        xs, ys, ps, ts = x[b:e], y[b:e], p[b:e], tick[b:e]
+        inside = (xs >= 0) & (xs < W) & (ys >= 0) & (ys < H)
+        counted = (ps != 0) & inside
+        idx = ((ys * W + xs) * 2 + (ps < 0))[counted]
+        tc = ts[counted]
+        t0, t1 = (int(tc.min()), int(tc.max())) if tc.size else (0, 0)
+        if reverse_t:
+            L = np.full(H * W * 2, np.iinfo(np.int64).max)
+            np.minimum.at(L, idx, tc)
+            L[L == np.iinfo(np.int64).max] = -1
+        else:
+            L = np.full(H * W * 2, -1, np.int64)
+            np.maximum.at(L, idx, tc)
+        L = L.reshape(H, W, 2)
+        out['frames'][f], out['pre'][f] = colour(L, t0, t1, decay, tau, grayscale, background_mask, reverse_t)
+        out['last'][f] = L
+        out['stats'][f] = (int(((ps != 0) & ~inside).sum()), int(counted.sum()), t0, t1)
+    return out
+
+
+def oracle_loop(events, ranges, shape, decay='linear', tau=0.03, grayscale=True, background_mask=True, flip_x=False,
+                negate_p=False, reverse_t=False):
+    """The definition, one event after the other."""
+    H, W = shape
+    x, y, p, tick = (a.tolist() for a in parse(events, shape, flip_x, negate_p))
+    out = _result(len(ranges), shape)
+    for f, (b, e) in enumerate(ranges):
+        L = np.full((H, W, 2), -1, np.int64)
+        dropped = counted = 0
+        t0 = t1 = None
+        for i in range(b, e):
+            if p[i] == 0:
+                continue
+            if not (0 <= x[i] < W and 0 <= y[i] < H):
+                dropped += 1
+                continue
+            counted += 1
+            t0 = tick[i] if t0 is None or tick[i] < t0 else t0
+            t1 = tick[i] if t1 is None or tick[i] > t1 else t1
+            c = 0 if p[i] > 0 else 1
+            old = L[y[i], x[i], c]
+            if old < 0 or (tick[i] < old if reverse_t else tick[i] > old):
+                L[y[i], x[i], c] = tick[i]
+        t0, t1 = (0, 0) if t0 is None else (t0, t1)
+        out['frames'][f], out['pre'][f] = colour(L, t0, t1, decay, tau, grayscale, background_mask, reverse_t)
+        out['last'][f] = L
+        out['stats'][f] = (dropped, counted, t0, t1)
+    return out
+
+
+# ---- a model of the kernel, with faults to plant ----------------------------------------------------------------------
+FAULTS = ('skipped_event_moves_t1', 'tick0_is_untouched', 'min_for_max', 'band_last_row_missing', 'w_not_clipped', 'exp_float32')
+
+
+def kernel_model(events, ranges, shape, decay='linear', tau=0.03, grayscale=True, background_mask=True, flip_x=False,
+                 negate_p=False, reverse_t=False, rows_per_band=7, fault=None):
+    """The kernel's structure in numpy: row bands of 32-bit words filled by a maximum, tick + 1 (reverse_t: 2^30 - tick)
+    with 0 as untouched, t0 / t1 from one reduction over the frame.  Without a fault it computes the definition."""
+    assert fault is None or fault in FAULTS
+    H, W = shape
+    x, y, p, tick = parse(events, shape, flip_x, negate_p)
+    out = _result(len(ranges), shape)
+    for f, (b, e) in enumerate(ranges):
+        xs, ys, ps, ts = x[b:e], y[b:e], p[b:e], tick[b:e]
+        inside = (xs >= 0) & (xs < W) & (ys >= 0) & (ys < H)
+        counted = (ps != 0) & inside
+        hi = np.where(counted | (fault == 'skipped_event_moves_t1'), ts + 1, 0).max(initial=0)
+        lo = np.where(counted, (1 << 30) - ts, 0).max(initial=0)
+        t0, t1 = ((1 << 30) - int(lo), int(hi) - 1) if counted.any() else (0, 0)
+        word = (1 << 30) - ts if reverse_t else ts + (0 if fault == 'tick0_is_untouched' else 1)
+        L = np.full((H, W, 2), -1, np.int64)
+        for y0 in range(0, H, rows_per_band):
+            y1 = min(H, y0 + rows_per_band)
+            band = counted & (ys >= y0) & (ys < (y1 - 1 if fault == 'band_last_row_missing' else y1))
+            idx = (((ys - y0) * W + xs) * 2 + (ps < 0))[band]
+            state = np.zeros((y1 - y0) * W * 2, np.int64)
+            if fault == 'min_for_max':
+                state[:] = np.iinfo(np.int64).max
+                np.minimum.at(state, idx, word[band])
+                state[state == np.iinfo(np.int64).max] = 0
+            else:
+                np.maximum.at(state, idx, word[band])
+            dec = (1 << 30) - state if reverse_t else state - (0 if fault == 'tick0_is_untouched' else 1)
+            L[y0:y1] = np.where(state == 0, -1, dec).reshape(y1 - y0, W, 2)
+        exp = (lambda q: np.exp(q.astype(np.float32)).astype(np.float64)) if fault == 'exp_float32' else np.exp
+        out['frames'][f], out['pre'][f] = colour(L, t0, t1, decay, tau, grayscale, background_mask, reverse_t, exp=exp,
+                                                 clip_w=fault != 'w_not_clipped')
+        out['last'][f] = L
+        out['stats'][f] = (int(((ps != 0) & ~inside).sum()), int(counted.sum()), t0, t1)
+    return out
+
+
+# ---- the check -------------------------------------------------------------------------------------------------------
+def check(got, want, decay):
+    """got: dict with any of frames, last, stats (from the kernel, or from kernel_model); want: an oracle's result.
+    last, t0, t1, dropped and counted exactly; linear frames exactly; exp frames exactly except where the oracle's
+    float64 value lies within TIE_WINDOW of k + 0.5 -- there either neighbour passes, and at most MAX_TIES pixels of
+    the case may lie there.  The window is a condition on the oracle's value, not a tolerance on the kernel's: a
+    float64 exp that is a few ulp off moves the value by ~1e-13."""
+    if got.get('last') is not None:
+        np.testing.assert_array_equal(got['last'], want['last'])
+    if got.get('stats') is not None:
+        for k in ('dropped', 'counted', 't0', 't1'):
+            np.testing.assert_array_equal(got['stats'][k], want['stats'][k], err_msg=k)
+    if got.get('frames') is None:
+        return 0
+    assert got['frames'].dtype == np.uint8 and got['frames'].shape == want['frames'].shape
+    if decay == 'linear':
+        np.testing.assert_array_equal(got['frames'], want['frames'])
+        return 0
+    pre = want['pre']
+    tie = np.abs(pre - (np.floor(pre) + 0.5)) <= TIE_WINDOW
+    n_ties = int(tie.any(axis=-1).sum())
+    assert n_ties <= MAX_TIES, f'{n_ties} pixels within {TIE_WINDOW} of a tie: pick another seed'
+    g = got['frames'].astype(np.int64)
+    ok = np.where(tie, (g == np.floor(pre)) | (g == np.floor(pre) + 1), g == want['frames'])
+    assert ok.all(), f'{int((~ok).sum())} bytes differ, first at {tuple(np.argwhere(~ok)[0])}'
+    return n_ties
+
+
+# ---- cases -----------------------------------------------------------------------------------------------------------
+# Directed cases put their timestamps on the grid of 1/64 s = 15 625 us: exact in float32, with exact float32 differences
+# and integer ticks, so that an explicitly time-flipped array (t' = t_last - t in float32) has exactly the ticks
+# t_last - tick, and the float rows and their packed form agree without a word about rounding.
+GRID = 64.
+GEOMETRIES = ((36, 52), (100, 120), (180, 240), (480, 640))        # one band, one band, 3 bands, 16 bands
+FRAME_LENGTHS = (0, 1, 63, 64, 1023, 1024, 1025, 4097, 8193)       # the 8 x 1024 load unroll and its tails
+
+
+def _rows(x, y, k, p):
+    return np.stack([np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(k, np.float64) / GRID,
+                     np.asarray(p, np.float64)], 1).astype(np.float32)
+
+
+def _case(name, shape, events, ranges=None, tau=2.0, packable=True):
+    return dict(name=name, shape=shape, events=events, ranges=ranges or [(0, len(events))], tau=tau, packable=packable)
+
+
+def case_rows(shape):
+    """An event on every row (x = y % W, polarity alternating) plus the four corners, distinct ticks in shuffled order:
+    an event on both sides of every band boundary whatever the band height, unsorted."""
+    H, W = shape
+    y = np.concatenate([np.arange(H), [0, 0, H - 1, H - 1]])
+    x = np.concatenate([np.arange(H) % W, [0, W - 1, 0, W - 1]])
+    p = np.where(np.arange(len(y)) % 2 == 0, 1, -1)
+    k = np.random.default_rng(H).permutation(len(y)) + 1
+    return _case(f'rows{H}x{W}', shape, _rows(x, y, k, p), tau=len(y) / GRID / 3)
+
+
+def _scatter(n, shape, seed, ticks):
+    H, W = shape
+    rng = np.random.default_rng(seed)
+    return _rows(rng.integers(0, W, n), rng.integers(0, H, n), rng.integers(0, ticks, n), np.where(rng.random(n) < 0.5, 1, -1))
+
+
+def _exp_edge_events(shape, tau, n=32):
+    """Events at t32 <= 8 s, one pixel each, whose age below the last event (t = 8 s, tick 8 000 000) puts
+    127 exp(-age / tau) so close to k + 0.5 that an exp evaluated in float32 rounds to the other byte -- and further than
+    1e-7 from it, so that check's tie window plays no part: what tells a float32 exp from the float64 one.  The search
+    runs over the ticks the float32 timestamps really have (1 us is about one float32 step at 8 s)."""
+    H, W = shape
+    found = []
+    for start in range(1, 8000000, 1000000):
+        t32 = ((8000000 - np.arange(start, start + 1000000)) * 1e-6).astype(np.float32)
+        age = 8000000 - np.clip(np.rint(t32.astype(np.float64) * 1e6), 0, TICK_MAX)
+        q = -(age / (np.float64(tau) * 1e6))
+        pre, pre32 = 127. * np.exp(q), 127. * np.exp(q.astype(np.float32)).astype(np.float64)
+        found += t32[(np.rint(pre) != np.rint(pre32)) & (np.abs(pre - np.floor(pre) - 0.5) > 1e-7)].tolist()
+        if len(found) >= n:
+            break
+    t = np.array(found[:n] + [8.0])
+    i = np.arange(len(t))
+    return np.stack([i % W, i // W, t, np.ones(len(t))], 1).astype(np.float32)
+
+
+@functools.lru_cache(None)
+def cases():
+    s = (36, 52)
+    H, W = s
+    out = [case_rows(g) for g in GEOMETRIES]
+    # a width that is no multiple of 4 takes the pixel-by-pixel store path
+    out += [case_rows((37, 53)), _case('odd', (37, 53), _scatter(3000, (37, 53), 4, 500), tau=3.)]
+    out.append(_case('lengths', s, _scatter(max(FRAME_LENGTHS), s, 1, 4000), [(0, n) for n in FRAME_LENGTHS], tau=20.))
+    rng = np.random.default_rng(2)
+    out.append(_case('pile', s, _rows(np.full(5000, 7), np.full(5000, 5), rng.integers(0, 50, 5000),
+                                      np.where(rng.random(5000) < 0.5, 1, -1)), tau=0.3))
+    # ticks 0 and 2^30 - 1; a float t of 2000 s clips to the latter; pixel (1, 1) holds tick 0 alone: touched, not background
+    out.append(_case('sentinel', s, _rows([1, 2, 2, 3, 3, 4], [1, 2, 2, 3, 3, 4], [0, 0, 2000 * GRID, 5, 2000 * GRID, 640],
+                                          [1, -1, -1, 1, 1, -1]), tau=300.))
+    out.append(_case('same_tick', s, _rows([3, 3, 9, 9, 20], [4, 4, 30, 30, 35], [192] * 5, [1, -1, 1, 1, -1])))
+    # p == 0 and out-of-sensor events carry the smallest and the largest t: t0, t1 stay 10 and 20 on the grid
+    out.append(_case('skip', s, _rows([5, W + 5, 6, 7, 8, 3, 9], [5, 5, 6, 7, H, 3, 9], [1, 2, 10, 20, 90, 99, 15],
+                                      [0, 1, 1, -1, -1, 0, 1])))
+    # truncation toward zero, before and after flip_x: x = 5.9 -> 5 (flipped 45.1 -> 45), x = -0.5 -> 0 (flipped 51.5 -> 51)
+    out.append(_case('frac', s, _rows([5.9, -0.5, 51.9, -1.0], [3.7, 0.2, 35.9, 4], [1, 2, 3, 4], [1, -1, 1, 1]), packable=False))
+    # more frames than compute units: the grid trips.  Overlapping ranges
+    out.append(_case('many', s, _scatter(600 * 25 + 25, s, 3, 3000), [(25 * i, 25 * i + 50) for i in range(600)], tau=10.))
+    out.append(_case('exp_edge', s, _exp_edge_events(s, tau=2.0), tau=2.0))
+    # several frames of several bands: the (frame, band) items dealt out over the workgroups, 3 bands x 41 frames
+    out.append(_case('banded_frames', (180, 240), _scatter(41 * 150 + 150, (180, 240), 6, 3000),
+                     [(150 * i, 150 * i + 300) for i in range(41)], tau=10.))
+    for name, g, n in (('n_cars', (100, 120), 12500), ('n_caltech', (180, 240), 20000), ('n_imagenet', (480, 640), 3000)):
+        out.append(_case(name, g, make_events(n, g, seed=7), tau=0.03))
+    return {c['name']: c for c in out}
+
+
+def packed(case):
+    return vis.pack_events(case['events'])
