@@ -1,5 +1,5 @@
-// events -> polarity-histogram frames on gfx950 (and, in the last section, -> time-surface frames: the second
-// representation shares parse(), the packed format and the block reductions of this file).
+// events -> polarity-histogram frames on gfx950 (and, in the last two sections, -> time-surface and -> voxel-grid frames:
+// the other representations share parse(), the packed format and the block reductions of this file).
 //
 // Replaces /root/reference/datasets/vis.py make_event_histogram (:6-41) +
 // parse_events (:44-52) as driven by events2frames (:75-117).
@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "eventclip_time_surface.h"
+#include "eventclip_voxel_grid.h"
 
 // numpy evaluates every ufunc with one rounding per operation: no FMA contraction anywhere in
 // this file (the one fused multiply-add of the reference is written out explicitly).
@@ -2026,6 +2027,279 @@ int launch_time_surface(const void *events, const int64_t *frame_range, int F, c
     return EC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// events -> voxel-grid frames (include/eventclip_voxel_grid.h states the definition, steps 1 - 7).
+//
+// G of a row band lives in LDS as one int32 per (pixel, bin), filled with integer LDS atomic adds: two per counted event,
+// on neighbouring words (neighbouring banks).  Integer sums do not depend on the order of the events.
+// Two values have to exist before the part that uses them: t0 / t1 before any event is binned, the frame's peak before any
+// byte is written.  Both are reductions over the whole frame, so ONE 1024-thread workgroup owns a whole frame (frames
+// blockIdx.x, + gridDim.x, ...) and walks its row bands itself: nothing is ever awaited from another workgroup, and the
+// library needs no scratch in device memory.  Per frame:
+//   pass 0   one scan of the events for t0, t1, dropped, counted (the time surface's tallies and block reduction);
+//   pass 1   per band: zero the band, scan the events, bin those of the band; then read the band once for max |G| and,
+//            when the caller asked for grid, store it (the band is a contiguous piece of [H, W, B]);
+//   peak     one block reduction;
+//   pass 2   the bytes: of a one-band sensor straight from the LDS band of pass 1; of a banded sensor from the grid the
+//            workgroup itself wrote (behind a workgroup barrier: one compute unit, one L1), or, when the caller gave no
+//            grid, by binning every band a second time.
+// Traffic beyond the algorithmic 16 n (packed 8 n) + 3 H W bytes per frame: the events are read 1 + bands times (2 bands + 1
+// without grid on a banded sensor) -- from L2 / MALL after the first -- and grid costs 4 B H W written plus, banded, as
+// much read back.  N-Cars has 1 band at B = 3, N-Caltech 4, N-ImageNet 24.
+// The floors of steps 3 and 6 are float64 products with the reciprocal, fixed up by one step either way against the exact
+// 64-bit integer products (floor_ratio): exact, and without a 64-bit integer division per event and per byte.
+// ---------------------------------------------------------------------------------------------
+struct VgArgs {
+    const void *events;      // float4 (x, y, t, p) or packed 8-byte events
+    const long long *range;  // [F,2]
+    int H, W, F, B;
+    int background_mask, flip_x, negate_p, reverse_t;
+    uint8_t *frames;         // optional [F,H,W,3] (B == 3)
+    int *grid;               // optional [F,H,W,B]
+    ec_voxel_stats *stats;   // optional [F]
+    int rows_per_band, bands, band_bytes;
+};
+
+struct VgFrame {
+    unsigned t0, t1, span;
+    unsigned scale;          // (B - 1) * 256: u of an event at d == span
+    double inv_span;
+};
+
+// floor(num / den) for num < 2^53, den > 0 and a quotient below 2^31; inv = 1. / (double)den.  The product is within
+// 2^-51 relative of the quotient, far less than 1 absolute, so its truncation is the floor or a neighbour of it.
+__device__ __forceinline__ unsigned floor_ratio(unsigned long long num, unsigned long long den, double inv)
+{
+    unsigned q = (unsigned)((double)num * inv);
+    if ((unsigned long long)q * den > num) q--;
+    else if ((unsigned long long)(q + 1u) * den <= num) q++;
+    return q;
+}
+
+// steps 1 - 2 over the events of a frame: the tallies behind t0, t1, dropped, counted
+template <typename EV>
+__device__ __forceinline__ void voxel_tally(const EV *ev, long long n, const VgArgs &a, TsTally &t)
+{
+    const int H = a.H, W = a.W;
+    for (long long i = threadIdx.x; i < n; i += 8 * EV_THREADS) {
+        EV e[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const long long j = i + (long long)k * EV_THREADS;
+            e[k] = ev[j < n ? j : n - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            int x, y, p;
+            parse(e[k], W, a.flip_x, a.negate_p, x, y, p);
+            const bool there = i + (long long)k * EV_THREADS < n && p != 0;
+            const bool inside = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
+            const unsigned tick = tick_of(e[k]);
+            t.dropped += there && !inside;
+            t.counted += there && inside;
+            const unsigned hi = there && inside ? tick + 1u : 0u, lo = there && inside ? TS_REVERSED - tick : 0u;
+            t.hi = hi > t.hi ? hi : t.hi, t.lo = lo > t.lo ? lo : t.lo;
+        }
+    }
+}
+
+// steps 3 - 4 for the rows [y0, y1): the band zeroed, then two LDS atomic adds per counted event of the band (one when
+// f == 0).  u is clamped to `scale`, which the exact floor never exceeds: b <= B - 1, and b == B - 1 only with f == 0.
+template <typename EV>
+__device__ __forceinline__ void voxel_band(const EV *ev, long long n, int y0, int y1, const VgArgs &a, const VgFrame &fr,
+                                           int *state)
+{
+    const int H = a.H, W = a.W, B = a.B;
+    for (int i = threadIdx.x; i < a.band_bytes / 16; i += EV_THREADS) reinterpret_cast<uint4 *>(state)[i] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    for (long long i = threadIdx.x; i < n; i += 8 * EV_THREADS) {
+        EV e[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const long long j = i + (long long)k * EV_THREADS;
+            e[k] = ev[j < n ? j : n - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            int x, y, p;
+            parse(e[k], W, a.flip_x, a.negate_p, x, y, p);
+            const bool there = i + (long long)k * EV_THREADS < n && p != 0;
+            const bool inside = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
+            if (!(there && inside && y >= y0 && y < y1)) continue;
+            const unsigned tick = tick_of(e[k]);
+            const unsigned d = a.reverse_t ? fr.t1 - tick : tick - fr.t0;
+            unsigned u = fr.span ? floor_ratio((unsigned long long)d * fr.scale, fr.span, fr.inv_span) : 0u;
+            u = u < fr.scale ? u : fr.scale;
+            const int b = (int)(u >> 8), f = (int)(u & 255u), s = p > 0 ? 1 : -1;
+            int *g = &state[((y - y0) * W + x) * B + b];
+            atomicAdd(g, s * (256 - f));
+            if (f) atomicAdd(g + 1, s * f);
+        }
+    }
+    __syncthreads();
+}
+
+// step 6 for one pixel
+__device__ __forceinline__ void voxel_pixel(int g0, int g1, int g2, unsigned m, double inv_2m, int background_mask, uint8_t out[3])
+{
+    const int g[3] = {g0, g1, g2};
+    const bool empty = (g0 | g1 | g2) == 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        unsigned byte = 128u;
+        if (m) byte = floor_ratio(255ull * (unsigned long long)((long long)g[k] + (long long)m) + m, 2ull * m, inv_2m);
+        out[k] = (uint8_t)(background_mask && empty ? 255u : byte);
+    }
+}
+
+// step 6 for npix pixels of [.., 3] words at src (the LDS band or the grid in device memory) -> 3 npix bytes at o
+__device__ __forceinline__ void voxel_colour(const int *src, int npix, int W, unsigned m, int background_mask, uint8_t *o)
+{
+    const double inv_2m = m ? 1. / (2. * (double)m) : 0.;
+    if ((W & 3) == 0 && ((uintptr_t)src & 15) == 0) {
+        // 4 pixels = 48 bytes in, 12 bytes = three dwords out per thread
+        for (int g = threadIdx.x; g < npix / 4; g += EV_THREADS) {
+            unsigned words[3];
+            uint8_t *bytes = reinterpret_cast<uint8_t *>(words);
+            const int4 ca = *reinterpret_cast<const int4 *>(&src[g * 12]);
+            const int4 cb = *reinterpret_cast<const int4 *>(&src[g * 12 + 4]);
+            const int4 cc = *reinterpret_cast<const int4 *>(&src[g * 12 + 8]);
+            voxel_pixel(ca.x, ca.y, ca.z, m, inv_2m, background_mask, bytes);
+            voxel_pixel(ca.w, cb.x, cb.y, m, inv_2m, background_mask, bytes + 3);
+            voxel_pixel(cb.z, cb.w, cc.x, m, inv_2m, background_mask, bytes + 6);
+            voxel_pixel(cc.y, cc.z, cc.w, m, inv_2m, background_mask, bytes + 9);
+            unsigned *dst = reinterpret_cast<unsigned *>(o + (long long)g * 12);
+            dst[0] = words[0];
+            dst[1] = words[1];
+            dst[2] = words[2];
+        }
+    } else {
+        for (int q = threadIdx.x; q < npix; q += EV_THREADS) {
+            uint8_t px[3];
+            voxel_pixel(src[3 * q], src[3 * q + 1], src[3 * q + 2], m, inv_2m, background_mask, px);
+            o[3 * q] = px[0];
+            o[3 * q + 1] = px[1];
+            o[3 * q + 2] = px[2];
+        }
+    }
+}
+
+template <typename EV>
+__global__ __launch_bounds__(EV_THREADS) void voxel_grid_kernel(const VgArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int *state = reinterpret_cast<int *>(smem);
+    unsigned long long *scratch = reinterpret_cast<unsigned long long *>(smem + a.band_bytes);
+    const int H = a.H, W = a.W, B = a.B, rpb = a.rows_per_band;
+    const long long M = (long long)H * W;
+
+    for (int f = blockIdx.x; f < a.F; f += gridDim.x) {
+        const long long e0 = a.range[2 * f], n = a.range[2 * f + 1] - e0;
+        const EV *ev = reinterpret_cast<const EV *>(a.events) + e0;
+        // pass 0
+        TsTally t = {0, 0, 0, 0};
+        voxel_tally(ev, n, a, t);
+        t = block_tally(t, scratch);
+        VgFrame fr = {0, 0, 0, (unsigned)(B - 1) * 256u, 0.};
+        if (t.counted) fr.t0 = TS_REVERSED - t.lo, fr.t1 = t.hi - 1u;
+        fr.span = fr.t1 - fr.t0;
+        fr.inv_span = fr.span ? 1. / (double)fr.span : 0.;
+        // passes 1 and 2 over the bands, through one copy of the scan: pass 1 bins every band and takes the peak (and
+        // stores grid), pass 2 writes the bytes -- from the band still in LDS (one band), from grid, or binned again
+        const bool rebin = a.bands > 1 && !a.grid;
+        unsigned peak = 0, m = 0;
+        for (int pass = 1; pass <= (a.frames ? 2 : 1); pass++) {
+            for (int b = 0; b < a.bands; b++) {
+                const int y0 = b * rpb, y1 = min(H, y0 + rpb);
+                const int nwords = (y1 - y0) * W * B;
+                int *g = a.grid ? a.grid + ((long long)f * M + (long long)y0 * W) * B : nullptr;
+                if (pass == 1 || rebin) voxel_band(ev, n, y0, y1, a, fr, state);
+                if (pass == 1) {
+                    for (int i = threadIdx.x; i < nwords; i += EV_THREADS) {
+                        const int v = state[i];
+                        const unsigned mag = (unsigned)(v < 0 ? -v : v);
+                        peak = mag > peak ? mag : peak;
+                        if (g) g[i] = v;
+                    }
+                } else {
+                    voxel_colour(a.bands > 1 && g ? g : state, (y1 - y0) * W, W, m, a.background_mask,
+                                 a.frames + ((long long)f * M + (long long)y0 * W) * 3);
+                }
+                if (a.bands > 1) __syncthreads();                          // the band is read: the next one may zero it
+            }
+            // (grid is read back by the workgroup that stored it, behind the barriers above and of the reduction: waves of
+            // one workgroup share their compute unit's L1, so workgroup scope is all the ordering this needs.  Fences at
+            // agent scope here were measured: they write back the whole L2 and took the N-Caltech launch from 1.1 to 4.4 ms.)
+            if (pass == 1) m = block_max_u32(peak, scratch);
+        }
+        if (a.stats && threadIdx.x == 0) {
+            ec_voxel_stats st;
+            st.dropped = t.dropped, st.counted = t.counted, st.t0 = fr.t0, st.t1 = fr.t1, st.peak = m;
+            a.stats[f] = st;
+        }
+        __syncthreads();                                                   // the band is read: the next frame may zero it
+    }
+}
+
+// Row bands of 4 B bytes per pixel: as many rows as fit EV_BIN_BYTES, evened out over the bands; the reduction scratch
+// behind.  bands == 0: the entry points refuse this sensor.
+struct VgPlan {
+    int rows_per_band, bands, band_bytes, lds;
+};
+inline VgPlan voxel_grid_plan(int H, int W, int B)
+{
+    VgPlan p = {};
+    if (H <= 0 || W <= 0 || B < EC_VOXEL_MIN_BINS || B > EC_VOXEL_MAX_BINS) return p;
+    const long row_bytes = (long)W * B * 4;
+    if (row_bytes > EV_BIN_BYTES) return p;
+    p.bands = ec::ceil_div(H, (int)std::min<long>(H, EV_BIN_BYTES / row_bytes));
+    p.rows_per_band = ec::ceil_div(H, p.bands);
+    p.band_bytes = (int)((p.rows_per_band * row_bytes + 15) / 16 * 16);
+    p.lds = p.band_bytes + EV_REDUCE_BYTES;
+    return p;
+}
+
+template <typename EV>
+int launch_voxel_grid(const void *events, const int64_t *frame_range, int F, const ec_voxel_grid_params *prm,
+                      uint8_t *frames, int32_t *grid, ec_voxel_stats *stats, ec_stream_t stream)
+{
+    EC_REQUIRE(prm != nullptr, "ec_events_to_voxel_grid: params is null");
+    EC_REQUIRE(F >= 0, "ec_events_to_voxel_grid: F=%d", F);
+    if (F == 0) return EC_OK;
+    EC_REQUIRE(events && frame_range, "ec_events_to_voxel_grid: null buffer");
+    EC_REQUIRE(frames || grid, "ec_events_to_voxel_grid: neither frames nor grid");
+    EC_REQUIRE(prm->H > 0 && prm->W > 0, "ec_events_to_voxel_grid: bad shape (%d,%d)", prm->H, prm->W);
+    EC_REQUIRE(prm->bins >= EC_VOXEL_MIN_BINS && prm->bins <= EC_VOXEL_MAX_BINS, "ec_events_to_voxel_grid: bins=%d outside %d .. %d",
+               prm->bins, (int)EC_VOXEL_MIN_BINS, (int)EC_VOXEL_MAX_BINS);
+    EC_REQUIRE(!frames || prm->bins == 3, "ec_events_to_voxel_grid: frames need bins == 3, not %d", prm->bins);
+    EC_REQUIRE(prm->max_frame_events <= EC_VOXEL_MAX_FRAME_EVENTS, "ec_events_to_voxel_grid: max_frame_events=%d above %d",
+               prm->max_frame_events, (int)EC_VOXEL_MAX_FRAME_EVENTS);
+    EC_REQUIRE(((uintptr_t)events & (sizeof(EV) - 1)) == 0,
+               "ec_events_to_voxel_grid: events must be %d-byte aligned", (int)sizeof(EV));
+    EC_REQUIRE(((uintptr_t)frames & 3) == 0 && ((uintptr_t)grid & 3) == 0 && ((uintptr_t)stats & 3) == 0,
+               "ec_events_to_voxel_grid: frames, grid and stats must be 4-byte aligned");
+    const VgPlan plan = voxel_grid_plan(prm->H, prm->W, prm->bins);
+    EC_REQUIRE(plan.bands > 0, "ec_events_to_voxel_grid: W=%d too wide for one LDS row band at bins=%d", prm->W, prm->bins);
+
+    VgArgs a = {};
+    a.events = events;
+    a.range = reinterpret_cast<const long long *>(frame_range);
+    a.H = prm->H, a.W = prm->W, a.F = F, a.B = prm->bins;
+    a.background_mask = prm->background_mask;
+    a.flip_x = prm->flip_x, a.negate_p = prm->negate_p, a.reverse_t = prm->reverse_t;
+    a.frames = frames, a.grid = grid, a.stats = stats;
+    a.rows_per_band = plan.rows_per_band, a.bands = plan.bands, a.band_bytes = plan.band_bytes;
+
+    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(voxel_grid_kernel<EV>), EV_LDS_TOTAL)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // algorithmic bytes: 16 B (packed: 8 B) per event in + 3*H*W out, as launch_events states them
+    ec::ProfScope prof(ec::PROF_VOXEL_GRID, hs, 0,
+                       (double)F * prm->H * prm->W * 3.0 + (double)(prm->total_events > 0 ? prm->total_events : 0) * sizeof(EV));
+    hipLaunchKernelGGL(voxel_grid_kernel<EV>, dim3((unsigned)std::min<long>(F, events_cus())), dim3(EV_THREADS), plan.lds, hs, a);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
 }  // namespace
 
 #ifdef EC_EVENTS_DIAG
@@ -2073,6 +2347,22 @@ extern "C" EC_API int ec_events_to_time_surface_packed(const uint64_t *events, c
 {
     return launch_time_surface<packed_t>(events, frame_range, F, prm, frames, last, stats, stream);
 }
+
+extern "C" EC_API int ec_events_to_voxel_grid(const float *events, const int64_t *frame_range, int F,
+                                              const ec_voxel_grid_params *prm, uint8_t *frames, int32_t *grid,
+                                              ec_voxel_stats *stats, ec_stream_t stream)
+{
+    return launch_voxel_grid<float4>(events, frame_range, F, prm, frames, grid, stats, stream);
+}
+
+extern "C" EC_API int ec_events_to_voxel_grid_packed(const uint64_t *events, const int64_t *frame_range, int F,
+                                                     const ec_voxel_grid_params *prm, uint8_t *frames, int32_t *grid,
+                                                     ec_voxel_stats *stats, ec_stream_t stream)
+{
+    return launch_voxel_grid<packed_t>(events, frame_range, F, prm, frames, grid, stats, stream);
+}
+
+extern "C" EC_API int ec_voxel_grid_bands(int H, int W, int bins) { return voxel_grid_plan(H, W, bins).bands; }
 
 extern "C" EC_API int ec_center_events(float *events, const int64_t *sample_range, int B, int H, int W,
                                        ec_stream_t stream)

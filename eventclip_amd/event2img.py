@@ -28,7 +28,9 @@ class Event2ImagePipeline:
         ``background_mask``).  ``convert_method`` is ``'event_histogram'`` or ``'time_surface'`` (not in the
         reference: the latest-timestamp frames of include/eventclip_time_surface.h), which reads ``decay``
         (``'linear'``, the default, or ``'exp'``) and ``tau`` (seconds, 0.03) and accepts but ignores ``thresh``,
-        ``count_non_zero`` and ``float_stage``: it has no hot-pixel threshold and no frame maximum.
+        ``count_non_zero`` and ``float_stage``: it has no hot-pixel threshold and no frame maximum.  Or
+        ``'voxel_grid'`` (not in the reference either: the temporal-bin frames of include/eventclip_voxel_grid.h),
+        which reads ``bins`` (3, the only value with an image form) and ignores those three and ``grayscale``.
     n_px: CLIP input resolution.  patch/kpad/dtype: when given, ``__call__`` emits the
         16-bit im2col rows for ``CLIP.encode_patches`` instead of fp32 images.
     frames_u8: emit the resized + cropped uint8 frames (``frames_u8`` [Fv, R, R, 3]) instead, the input of
@@ -58,6 +60,11 @@ class Event2ImagePipeline:
         self.decay, self.tau = qa.get('decay', 'linear'), float(qa.get('tau', 0.03))
         if self.decay not in vis.DECAYS:
             raise ValueError(f"decay {self.decay!r}: 'linear' or 'exp'")
+        # convert_method='voxel_grid' only
+        self.bins = int(qa.get('bins', 3))
+        if self.event_rep == 'voxel_grid' and self.bins != 3:
+            raise ValueError(f'bins={self.bins}: voxel-grid frames have 3 temporal bins, one per colour channel '
+                             '(vis.voxel_grid_device returns the grid of 2 .. 8 bins)')
         self.n_px, self.patch, self.kpad, self.dtype = int(n_px), patch, kpad, dtype
         self.frames_u8 = bool(frames_u8)
         assert not (self.frames_u8 and self.patch), 'frames_u8 and patch rows are two different outputs'
@@ -109,13 +116,16 @@ class Event2ImagePipeline:
         return fr, ri, ri >= 0
 
     def frames(self, events, frame_range, hflip=False, tflip=False, total_events=0):
-        """uint8 [Fv, H, W, 3] for the planned views (vis.events2frames, batched).  The time flip of a time surface
-        (utils.py:26-35: t' = t_last - t, p' = -p) is reverse_t with negate_p on the stored rows."""
+        """uint8 [Fv, H, W, 3] for the planned views (vis.events2frames, batched).  The time flip of a time surface or
+        a voxel grid (utils.py:26-35: t' = t_last - t, p' = -p) is reverse_t with negate_p on the stored rows."""
         common = dict(grayscale=self.grayscale, background_mask=self.background_mask, return_stats=self.strict,
                       max_frame_events=self.N, flip_x=hflip, negate_p=tflip, total_events=total_events)
         if self.event_rep == 'time_surface':
             out = vis.time_surface_device(events, frame_range, self.resolution, decay=self.decay, tau=self.tau,
                                           reverse_t=tflip, **common)
+        elif self.event_rep == 'voxel_grid':
+            del common['grayscale']                                       # channel k is temporal bin k
+            out = vis.voxel_grid_device(events, frame_range, self.resolution, bins=self.bins, reverse_t=tflip, **common)
         else:
             out = vis.events_to_frames_device(
                 events, frame_range, self.resolution, thresh=self.thresh, count_non_zero=self.count_non_zero,

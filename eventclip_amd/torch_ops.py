@@ -8,6 +8,7 @@ mirrors of the reference's interface (vis / preprocess / clip / adapter / clip_c
 
     torch.ops.eventclip_hip.events_to_frames   ec_events_to_frames[_packed]    datasets/vis.py:75-117
     torch.ops.eventclip_hip.events_to_time_surface   ec_events_to_time_surface[_packed]   (no counterpart: eventclip_time_surface.h)
+    torch.ops.eventclip_hip.events_to_voxel_grid     ec_events_to_voxel_grid[_packed]     (no counterpart: eventclip_voxel_grid.h)
     torch.ops.eventclip_hip.preprocess         ec_preprocess                   datasets/event2img.py:119-122
     torch.ops.eventclip_hip.vit_encode         ec_vit_encode                   models/clip_cls.py:101
     torch.ops.eventclip_hip.text_encode        ec_text_encode                  models/clip_cls.py:84
@@ -112,6 +113,30 @@ def events_to_time_surface(events: torch.Tensor, frame_range: torch.Tensor, H: i
 @events_to_time_surface.register_fake
 def _(events, frame_range, H, W, decay, tau, red, blue, background_mask, max_frame_events, flip_x, negate_p,
       reverse_t, total_events):
+    return events.new_empty((frame_range.shape[0], H, W, 3), dtype=torch.uint8)
+
+
+@custom_op(f'{NAMESPACE}::events_to_voxel_grid', mutates_args=(), device_types='cuda')
+def events_to_voxel_grid(events: torch.Tensor, frame_range: torch.Tensor, H: int, W: int, bins: int,
+                         background_mask: bool, max_frame_events: int, flip_x: bool, negate_p: bool, reverse_t: bool,
+                         total_events: int) -> torch.Tensor:
+    """events float32 [n, 4] or packed int64 [n]; frame_range int64 [F, 2] -> uint8 [F, H, W, 3]: the temporal-bin
+    frames of include/eventclip_voxel_grid.h (bins == 3).  A sensor of more than one row band is coloured from its grid,
+    which lives in a temporary of torch's allocator for the length of the call."""
+    from . import vis
+    F = int(frame_range.shape[0])
+    prm = vis.voxel_grid_params((H, W), bins, background_mask, max_frame_events, flip_x, negate_p, reverse_t, total_events)
+    frames = torch.empty((F, H, W, 3), dtype=torch.uint8, device=events.device)
+    grid = None
+    if vis.voxel_grid_bands((H, W), bins) > 1:
+        grid = torch.empty((F, H, W, bins), dtype=torch.int32, device=events.device)
+    _lib.launch('ec_events_to_voxel_grid_packed' if vis.is_packed(events) else 'ec_events_to_voxel_grid', events,
+                frame_range, F, prm, frames, grid, None)
+    return frames
+
+
+@events_to_voxel_grid.register_fake
+def _(events, frame_range, H, W, bins, background_mask, max_frame_events, flip_x, negate_p, reverse_t, total_events):
     return events.new_empty((frame_range.shape[0], H, W, 3), dtype=torch.uint8)
 
 
@@ -671,5 +696,5 @@ def _vit_image_backward(ctx, d_feats, d_tape):
 vit_image_fwd.register_autograd(_vit_image_backward, setup_context=_vit_image_setup)
 
 
-OPS = ('events_to_frames', 'events_to_time_surface', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode',
+OPS = ('events_to_frames', 'events_to_time_surface', 'events_to_voxel_grid', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode',
        'classify_bwd', 'adapter_train_fwd', 'adapter_train_bwd', 'vit_train_fwd', 'vit_train_bwd', 'vit_image_fwd', 'vit_image_bwd')

@@ -7,9 +7,10 @@ Same names and argument meaning as the reference:
   kernel behind ``ec_events_to_frames``.
 * ``split_event_count(t, N)`` (vis.py:55-72), ``parse_events`` (vis.py:44-52).
 
-plus the batched device entries ``events_to_frames_device`` (polarity histogram) and ``time_surface_device``
+plus the batched device entries ``events_to_frames_device`` (polarity histogram), ``time_surface_device``
 (latest-timestamp frames, ``convert_method='time_surface'``: not in the reference, defined in
-include/eventclip_time_surface.h) used by the pipeline.
+include/eventclip_time_surface.h) and ``voxel_grid_device`` (temporal-bin frames, ``convert_method='voxel_grid'``:
+not in the reference either, defined in include/eventclip_voxel_grid.h) used by the pipeline.
 There is no CPU fallback.
 """
 import collections
@@ -253,7 +254,7 @@ with open(SURFACE_HEADER) as _f:
 EcTimeSurfaceParams, EcSurfaceStats = _surface_structs['EcTimeSurfaceParams'], _surface_structs['EcSurfaceStats']
 DECAYS = {'linear': _surface_constants['EC_DECAY_LINEAR'], 'exp': _surface_constants['EC_DECAY_EXP']}
 SURFACE_STATS_DTYPE = np.dtype([('dropped', '<u4'), ('counted', '<u4'), ('t0', '<u4'), ('t1', '<u4')])
-CONVERT_METHODS = ('event_histogram', 'time_surface')
+CONVERT_METHODS = ('event_histogram', 'time_surface', 'voxel_grid')
 
 
 def surface_lib():
@@ -328,11 +329,104 @@ def time_surface_device(events, frame_range, shape, decay='linear', tau=0.03, gr
     return res[0] if len(res) == 1 else tuple(res)
 
 
+# ---- voxel-grid frames (include/eventclip_voxel_grid.h: the definition, steps 1 - 7) ----
+VOXEL_HEADER = os.path.join(os.path.dirname(_lib.HEADER), 'eventclip_voxel_grid.h')
+with open(VOXEL_HEADER) as _f:
+    _, _voxel_constants, _voxel_structs, VOXEL_SIGNATURES = _lib.read_header(
+        _f.read().replace('#include "eventclip_hip.h"', f'#define EC_ABI_VERSION {_lib.ABI_VERSION}'))
+EcVoxelGridParams, EcVoxelStats = _voxel_structs['EcVoxelGridParams'], _voxel_structs['EcVoxelStats']
+VOXEL_BINS = (_voxel_constants['EC_VOXEL_MIN_BINS'], _voxel_constants['EC_VOXEL_MAX_BINS'])
+VOXEL_MAX_FRAME_EVENTS = _voxel_constants['EC_VOXEL_MAX_FRAME_EVENTS']
+VOXEL_STATS_DTYPE = np.dtype([('dropped', '<u4'), ('counted', '<u4'), ('t0', '<u4'), ('t1', '<u4'), ('peak', '<u4')])
+
+
+def voxel_lib():
+    """The loaded library with the entries of eventclip_voxel_grid.h typed (``_lib.launch`` finds them there)."""
+    handle = _lib.lib()
+    for name, (res, args) in VOXEL_SIGNATURES.items():
+        fn = getattr(handle, name)
+        fn.restype, fn.argtypes = res, args
+    return handle
+
+
+def voxel_grid_bands(shape, bins=3):
+    """Row bands the kernel cuts a sensor into (``ec_voxel_grid_bands``; host only, 0 = refused)."""
+    return int(voxel_lib().ec_voxel_grid_bands(int(shape[0]), int(shape[1]), int(bins)))
+
+
+def voxel_grid_params(shape, bins, background_mask, max_frame_events, flip_x, negate_p, reverse_t, total_events):
+    """EcVoxelGridParams: what ``voxel_grid_device`` and the custom op both fill."""
+    if not VOXEL_BINS[0] <= int(bins) <= VOXEL_BINS[1]:
+        raise ValueError(f'bins={bins}: {VOXEL_BINS[0]} .. {VOXEL_BINS[1]}')
+    if int(max_frame_events) > VOXEL_MAX_FRAME_EVENTS:
+        raise ValueError(f'max_frame_events={max_frame_events}: a voxel-grid frame holds at most {VOXEL_MAX_FRAME_EVENTS} '
+                         'events (256 per event in int32)')
+    p = EcVoxelGridParams()
+    p.H, p.W, p.bins = int(shape[0]), int(shape[1]), int(bins)
+    p.background_mask = int(bool(background_mask))
+    p.max_frame_events = int(max_frame_events)
+    p.flip_x, p.negate_p, p.reverse_t = int(bool(flip_x)), int(bool(negate_p)), int(bool(reverse_t))
+    p.total_events = int(total_events)
+    return p
+
+
+def voxel_grid_device(events, frame_range, shape, bins=3, background_mask=True, return_grid=False, return_stats=False,
+                      out=None, max_frame_events=0, flip_x=False, negate_p=False, reverse_t=False, total_events=0):
+    """Batched device entry of the voxel-grid frames; events and frame_range as ``events_to_frames_device`` takes them.
+
+    bins: temporal bins B, 2 .. 8.  Every event spreads its signed unit (256) over the two bins nearest to its place in
+          the frame's time span.  Frames exist for B == 3 (channel k = bin k, 128 = zero, scaled to the frame's peak
+          |G|); any other B gives the grid alone and wants ``return_grid``.
+    reverse_t: the place is counted back from the frame's last event: with negate_p and frame ranges of the reversed
+          order, the time flip of test-time augmentation.
+    Returns uint8 CUDA tensor [F, H, W, 3] (B == 3; + grid int32 [F, H, W, B] and a stats structured array -- dropped,
+    counted, t0, t1, peak -- when asked), or the grid (+ stats) alone when B != 3.
+    """
+    import torch
+    dev = _lib.require_gpu()
+    H, W = shape
+    packed = is_packed(events)
+    assert events.is_cuda and events.is_contiguous()
+    assert packed or (events.dtype == torch.float32 and events.dim() == 2 and events.shape[1] == 4)
+    assert frame_range.is_cuda and frame_range.dtype == torch.int64 and frame_range.is_contiguous()
+    F, bins = int(frame_range.shape[0]), int(bins)
+    if bins != 3 and not return_grid:
+        raise ValueError(f'bins={bins}: the image form exists for 3 bins only; ask for the grid (return_grid=True)')
+    if bins != 3 and out is not None:
+        raise ValueError(f'bins={bins}: `out` is the image, which exists for 3 bins only')
+    if out is None and not return_grid and not return_stats:
+        # the production form: the registered custom op (eventclip_hip::events_to_voxel_grid)
+        from . import torch_ops  # noqa: F401  (registers the namespace)
+        return torch.ops.eventclip_hip.events_to_voxel_grid(
+            events, frame_range, int(H), int(W), bins, bool(background_mask), int(max_frame_events), bool(flip_x),
+            bool(negate_p), bool(reverse_t), int(total_events))
+    # debug form (the grid itself, per-frame statistics, caller-owned output): straight to the C ABI
+    prm = voxel_grid_params(shape, bins, background_mask, max_frame_events, flip_x, negate_p, reverse_t, total_events)
+    frames = None
+    if bins == 3:
+        frames = out if out is not None else torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    # (a banded sensor's bytes are coloured from its grid: without one the kernel bins every band twice)
+    want_grid = return_grid or (frames is not None and voxel_grid_bands(shape, bins) > 1)
+    grid = torch.empty((F, H, W, bins), dtype=torch.int32, device=dev) if want_grid else None
+    stats = torch.zeros((F, ctypes.sizeof(EcVoxelStats)), dtype=torch.uint8, device=dev) if return_stats else None
+    voxel_lib()
+    _lib.launch('ec_events_to_voxel_grid_packed' if packed else 'ec_events_to_voxel_grid', events, frame_range, F, prm,
+                frames, grid, stats)
+    res = [frames] if frames is not None else []
+    if return_grid:
+        res.append(grid)
+    if return_stats:
+        res.append(stats.cpu().numpy().view(VOXEL_STATS_DTYPE).reshape(F))
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 def events2frames(events, split_method, convert_method, shape=(180, 240), **kwargs):
     """Drop-in for the reference's events2frames (vis.py:75-117): numpy in, numpy out.
 
     convert_method='time_surface' (not in the reference) takes ``decay`` ('linear' or 'exp') and ``tau`` (seconds) and
-    ignores ``thresh``, ``count_non_zero`` and ``float_stage``: there is no hot-pixel threshold and no frame maximum."""
+    ignores ``thresh``, ``count_non_zero`` and ``float_stage``: there is no hot-pixel threshold and no frame maximum.
+    convert_method='voxel_grid' (not in the reference) takes ``bins`` (3: the image form has three channels) and ignores
+    those three and ``grayscale``: channel k is temporal bin k."""
     import torch
     grayscale = kwargs.pop('grayscale', True)
     ev = parse_events(events)
@@ -352,6 +446,12 @@ def events2frames(events, split_method, convert_method, shape=(180, 240), **kwar
     if convert_method == 'time_surface':
         frames, stats = time_surface_device(ev_d, rng, shape, decay=kwargs.get('decay', 'linear'),
                                             tau=float(kwargs.get('tau', 0.03)), **common)
+    elif convert_method == 'voxel_grid':
+        if int(kwargs.get('bins', 3)) != 3:
+            raise ValueError(f"bins={kwargs['bins']}: voxel-grid frames have 3 bins, one per colour channel "
+                             '(voxel_grid_device returns the grid of 2 .. 8 bins)')
+        del common['grayscale']
+        frames, stats = voxel_grid_device(ev_d, rng, shape, bins=3, **common)
     else:
         frames, stats = events_to_frames_device(
             ev_d, rng, shape, thresh=float(kwargs.get('thresh', 10.)),

@@ -1,0 +1,281 @@
+"""The yardstick of the voxel-grid frames (include/eventclip_voxel_grid.h, steps 1 - 7): the definition restated twice in
+int64 numpy (``oracle``: vectorised with np.add.at, ``oracle_loop``: one event after the other, Python integers), a
+numpy model of the kernel's structure with switches that plant faults (``kernel_model``), the case table, the explicit
+rewriting of a stream that the three flags stand for (``rewrite``), and the one check function (``check``) the CPU and
+the GPU tests share.  The reference has no such representation: these restatements ARE the reference answer, and
+every comparison is exact -- the definition has no float stage."""
+import functools
+
+import numpy as np
+
+import time_surface_ref as ts
+from eventclip_amd import vis
+
+TICK_MAX = ts.TICK_MAX
+parse = ts.parse                      # steps 1 - 2 are the time surface's, word for word
+
+
+def _result(F, shape, bins):
+    H, W = shape
+    return dict(grid=np.zeros((F, H, W, bins), np.int32), stats=np.zeros(F, vis.VOXEL_STATS_DTYPE),
+                frames=np.zeros((F, H, W, 3), np.uint8) if bins == 3 else None)
+
+
+def colour(G, m, background_mask, any_zero=False):
+    """step 6: int64 G [..., 3] and the peak m -> uint8 [..., 3]."""
+    G = G.astype(np.int64)
+    m = np.int64(m)
+    byte = np.full(G.shape, 128, np.int64) if m == 0 else (255 * (G + m) + m) // (2 * m)
+    if background_mask:
+        empty = (G == 0).any(axis=-1) if any_zero else (G == 0).all(axis=-1)
+        byte = np.where(empty[..., None], 255, byte)
+    assert byte.min() >= 0 and byte.max() <= 255
+    return byte.astype(np.uint8)
+
+
+def oracle(events, ranges, shape, bins=3, background_mask=True, flip_x=False, negate_p=False, reverse_t=False):
+    """The definition, vectorised (np.add.at)."""
+    H, W = shape
+    B = int(bins)
+    x, y, p, tick = parse(events, shape, flip_x, negate_p)
+    out = _result(len(ranges), shape, B)
+    for f, (b, e) in enumerate(ranges):
+        xs, ys, ps, tk = x[b:e], y[b:e], p[b:e], tick[b:e]
+        inside = (xs >= 0) & (xs < W) & (ys >= 0) & (ys < H)
+        counted = (ps != 0) & inside
+        tc = tk[counted]
+        t0, t1 = (int(tc.min()), int(tc.max())) if tc.size else (0, 0)
+        span = t1 - t0
+        d = (t1 - tc) if reverse_t else (tc - t0)
+        u = d * ((B - 1) * 256) // span if span else np.zeros_like(d)
+        bin_, frac = u >> 8, u & 255
+        s = np.where(ps[counted] > 0, 1, -1)
+        pix = (ys * W + xs)[counted] * B
+        G = np.zeros(H * W * B, np.int64)
+        np.add.at(G, pix + bin_, s * (256 - frac))
+        up = frac > 0
+        np.add.at(G, (pix + bin_ + 1)[up], (s * frac)[up])
+        assert np.abs(G).max(initial=0) < 2 ** 31
+        G = G.reshape(H, W, B)
+        m = int(np.abs(G).max(initial=0))
+        out['grid'][f] = G
+        out['stats'][f] = (int(((ps != 0) & ~inside).sum()), int(counted.sum()), t0, t1, m)
+        if B == 3:
+            out['frames'][f] = colour(G, m, background_mask)
+    return out
+
+
+def oracle_loop(events, ranges, shape, bins=3, background_mask=True, flip_x=False, negate_p=False, reverse_t=False):
+    """The definition, one event after the other, in Python's integers."""
+    H, W = shape
+    B = int(bins)
+    x, y, p, tick = (a.tolist() for a in parse(events, shape, flip_x, negate_p))
+    out = _result(len(ranges), shape, B)
+    for f, (b, e) in enumerate(ranges):
+        kept, dropped = [], 0
+        for i in range(b, e):
+            if p[i] == 0:
+                continue
+            if not (0 <= x[i] < W and 0 <= y[i] < H):
+                dropped += 1
+                continue
+            kept.append(i)
+        t0 = min((tick[i] for i in kept), default=0)
+        t1 = max((tick[i] for i in kept), default=0)
+        span = t1 - t0
+        G = [[[0] * B for _ in range(W)] for _ in range(H)]
+        for i in kept:
+            d = t1 - tick[i] if reverse_t else tick[i] - t0
+            u = d * (B - 1) * 256 // span if span else 0
+            bb, fr = u >> 8, u & 255
+            s = 1 if p[i] > 0 else -1
+            G[y[i]][x[i]][bb] += s * (256 - fr)
+            if fr > 0:
+                G[y[i]][x[i]][bb + 1] += s * fr             # (an IndexError here would be the definition's own fault)
+        G = np.array(G, np.int64).reshape(H, W, B)
+        m = max((abs(v) for v in G.reshape(-1).tolist()), default=0)
+        out['grid'][f] = G
+        out['stats'][f] = (dropped, len(kept), t0, t1, m)
+        if B == 3:
+            frame = np.zeros((H, W, 3), np.uint8)
+            for yy in range(H):
+                for xx in range(W):
+                    g = G[yy, xx].tolist()
+                    if background_mask and g == [0, 0, 0]:
+                        frame[yy, xx] = 255
+                    else:
+                        frame[yy, xx] = [128 if m == 0 else (255 * (v + m) + m) // (2 * m) for v in g]
+            out['frames'][f] = frame
+    return out
+
+
+# ---- a model of the kernel, with faults to plant ----------------------------------------------------------------------
+FAULTS = ('end_event_out_of_range', 'end_event_dropped', 'round_not_floor', 't0_over_all_events', 'reverse_mirrored',
+          'peak_per_band', 'lost_sign', 'mask_any_zero')
+
+
+def kernel_model(events, ranges, shape, bins=3, background_mask=True, flip_x=False, negate_p=False, reverse_t=False,
+                 rows_per_band=7, fault=None):
+    """The kernel's structure in numpy: t0 / t1 from a reduction in front, row bands of int32 words filled by integer
+    adds, the peak over all bands, the bytes behind it.  Without a fault it computes the definition."""
+    assert fault is None or fault in FAULTS
+    H, W = shape
+    B = int(bins)
+    scale = (B - 1) * 256
+    x, y, p, tick = parse(events, shape, flip_x, negate_p)
+    out = _result(len(ranges), shape, B)
+    for f, (b, e) in enumerate(ranges):
+        xs, ys, ps, tk = x[b:e], y[b:e], p[b:e], tick[b:e]
+        inside = (xs >= 0) & (xs < W) & (ys >= 0) & (ys < H)
+        counted = (ps != 0) & inside
+        timed = np.ones_like(counted) if fault == 't0_over_all_events' else counted
+        t0, t1 = (int(tk[timed].min()), int(tk[timed].max())) if counted.any() else (0, 0)
+        span = t1 - t0
+        d = (t1 - tk) if reverse_t else (tk - t0)
+        if fault == 'reverse_mirrored' and reverse_t:
+            u = scale - ((tk - t0) * scale // span if span else np.zeros_like(d))
+        elif fault == 'round_not_floor':
+            u = (2 * d * scale + span) // (2 * span) if span else np.zeros_like(d)
+        else:
+            u = d * scale // span if span else np.zeros_like(d)
+        bin_, frac = u >> 8, u & 255
+        s = np.ones_like(ps) if fault == 'lost_sign' else np.where(ps > 0, 1, -1)
+        G = np.zeros((H, W, B), np.int64)
+        band_peaks = []
+        for y0 in range(0, H, rows_per_band):
+            y1 = min(H, y0 + rows_per_band)
+            band = counted & (ys >= y0) & (ys < y1)
+            if fault == 'end_event_dropped':
+                band &= bin_ + 1 < B
+            state = np.zeros((y1 - y0) * W * B + 1, np.int64)      # (+ 1: where an out-of-range add of the last pixel lands)
+            at = (((ys - y0) * W + xs) * B + bin_)[band]
+            if fault == 'end_event_out_of_range':                  # u == scale lands one word further
+                at = at + (u[band] == scale)
+            np.add.at(state, at, (s * (256 - frac))[band])
+            up = band & (frac > 0)
+            np.add.at(state, (((ys - y0) * W + xs) * B + bin_ + 1)[up], (s * frac)[up])
+            G[y0:y1] = state[:-1].reshape(y1 - y0, W, B)
+            band_peaks.append((y0, y1, int(np.abs(G[y0:y1]).max(initial=0))))
+        m = max(pk for _, _, pk in band_peaks)
+        out['grid'][f] = G
+        out['stats'][f] = (int(((ps != 0) & ~inside).sum()), int(counted.sum()), t0, t1, m)
+        if B == 3:
+            for y0, y1, pk in band_peaks:
+                out['frames'][f, y0:y1] = colour(G[y0:y1], pk if fault == 'peak_per_band' else m, background_mask,
+                                                 any_zero=fault == 'mask_any_zero')
+    return out
+
+
+# ---- the check -------------------------------------------------------------------------------------------------------
+STATS = ('dropped', 'counted', 't0', 't1', 'peak')
+
+
+def check(got, want, stats=STATS):
+    """got: dict with any of grid, stats, frames (from the kernel, or from kernel_model); want: an oracle's result.
+    Everything exactly: the definition is integer arithmetic from the tick to the byte."""
+    if got.get('grid') is not None:
+        assert got['grid'].dtype == np.int32 and got['grid'].shape == want['grid'].shape
+        np.testing.assert_array_equal(got['grid'], want['grid'], err_msg='grid')
+    if got.get('stats') is not None:
+        for k in stats:
+            np.testing.assert_array_equal(got['stats'][k], want['stats'][k], err_msg=k)
+    if got.get('frames') is not None:
+        assert want['frames'] is not None, 'frames exist for bins == 3 only'
+        assert got['frames'].dtype == np.uint8 and got['frames'].shape == want['frames'].shape
+        np.testing.assert_array_equal(got['frames'], want['frames'], err_msg='frames')
+
+
+def check_rewritten(got, want):
+    """As ``check``, for a ``want`` computed on a ``rewrite``-n stream: its time axis is shifted, so of t0 / t1 only
+    the span compares."""
+    check(got, want, stats=('dropped', 'counted', 'peak'))
+    if got.get('stats') is not None:
+        np.testing.assert_array_equal(got['stats']['t1'].astype(np.int64) - got['stats']['t0'],
+                                      want['stats']['t1'].astype(np.int64) - want['stats']['t0'], err_msg='span')
+
+
+def rewrite(events, shape, flip_x=False, negate_p=False, reverse_t=False):
+    """The stream the flags stand for, written out (float rows on the 1/64 s grid, where every step is exact):
+    x' = W - 1 - x, p' = -p, t' = T - t with T the largest t of the array (any T moves t0 and t1 alike)."""
+    ev = np.array(events, np.float32, copy=True)
+    if flip_x:
+        ev[:, 0] = np.float32(shape[1] - 1) - ev[:, 0]
+    if negate_p:
+        ev[:, 3] = -ev[:, 3]
+    if reverse_t:
+        ev[:, 2] = ev[:, 2].max() - ev[:, 2]
+    return ev
+
+
+# ---- cases -----------------------------------------------------------------------------------------------------------
+# Timestamps lie on the grid of 1/64 s = 15 625 us (time_surface_ref._rows): exact in float32 with integer ticks and exact
+# differences, so float rows, their packed form and a rewritten stream agree without a word about rounding.
+def _case(name, shape, bins, events, ranges=None, packable=True):
+    return dict(name=name, shape=shape, bins=bins, events=events, ranges=ranges or [(0, len(events))], packable=packable)
+
+
+def _rows_and_scatter(shape, n, seed, ticks):
+    """An event on every row and in the four corners (both sides of every band boundary, whatever the band height) and
+    n scattered ones, shuffled."""
+    ev = np.concatenate([ts.case_rows(shape)['events'], ts._scatter(n, shape, seed, ticks)])
+    return ev[np.random.default_rng(seed).permutation(len(ev))]
+
+
+# (shape, bins) -> the band count the kernel is expected to use (asserted through ec_voxel_grid_bands on the GPU box)
+BANDS = {((36, 52), 2): 1, ((36, 52), 3): 1, ((36, 52), 8): 1, ((100, 120), 3): 1, ((181, 240), 3): 4,
+         ((480, 640), 3): 24, ((100, 640), 8): 15}
+
+
+@functools.lru_cache(None)
+def cases():
+    s = (36, 52)
+    H, W = s
+    out = []
+    # band counts: 1; 4 with a partial last band (46 + 46 + 46 + 43 rows); 24; 15 with a partial last band at 8 bins
+    out.append(_case('cars', (100, 120), 3, _rows_and_scatter((100, 120), 4000, 11, 3000)))
+    out.append(_case('bands4', (181, 240), 3, _rows_and_scatter((181, 240), 3000, 12, 3000),
+                     [(0, 2000), (1500, 3185)]))
+    out.append(_case('bands24', (480, 640), 3, _rows_and_scatter((480, 640), 3000, 13, 3000), [(0, 3484), (100, 1800)]))
+    out.append(_case('bands15x8', (100, 640), 8, _rows_and_scatter((100, 640), 3000, 14, 3000)))
+    for B in (2, 3, 8):
+        out.append(_case(f'small{B}', s, B, _rows_and_scatter(s, 3000, 20 + B, 2000), [(0, 1500), (1500, 3040)]))
+    # span == 0
+    out.append(_case('single', s, 3, ts._rows([7], [5], [33], [-1])))
+    out.append(_case('same_tick', s, 3, ts._rows([3, 3, 9, 9, 20], [4, 4, 30, 30, 35], [192] * 5, [1, 1, 1, -1, -1])))
+    # m == 0: an empty frame, a frame of p == 0 and out-of-sensor events only
+    out.append(_case('nothing', s, 3, ts._rows([5, W + 5, 6, 7, W], [5, 5, H, 7, 2], [1, 2, 10, 20, 5], [0, 1, -1, 0, 1]),
+                     [(0, 0), (0, 5)]))
+    # events exactly at t0 and at t1 (several of each, both signs), and between
+    out.append(_case('ends', s, 3, ts._rows([1, 2, 3, 4, 5, 6, 7, 51], [1, 2, 3, 4, 5, 6, 7, 35],
+                                            [10, 10, 1010, 1010, 1010, 333, 700, 10], [1, -1, 1, 1, -1, 1, -1, 1])))
+    # ticks up to 2^30 - 1 (a float t of 2000 s clips to it) over a span of 2^30 - 1: d * (B - 1) * 256 reaches 2^41
+    rng = np.random.default_rng(5)
+    k = np.concatenate([[0, 2000 * 64, 2000 * 64], rng.integers(60000, 68719, 1500), rng.integers(0, 68719, 1500)])
+    out.append(_case('wide', s, 8, ts._rows(rng.integers(0, W, len(k)), rng.integers(0, H, len(k)), k,
+                                            np.where(rng.random(len(k)) < 0.5, 1, -1))))
+    out.append(_case('wide3', s, 3, out[-1]['events']))
+    # the floor's edge: span = 512 grid steps and 2 * 256 sub-bins: u = d / 15625 exactly, for every event
+    k = np.concatenate([[0, 512], rng.integers(0, 513, 2000)])
+    out.append(_case('floor_edge', s, 3, ts._rows(rng.integers(0, W, len(k)), rng.integers(0, H, len(k)), k + 40,
+                                                  np.where(rng.random(len(k)) < 0.5, 1, -1))))
+    # pixel (4, 9) cancels in every bin (each + has its - on the same tick); pixel (5, 9) cancels in sum but not per bin
+    out.append(_case('cancel', s, 3, ts._rows([9, 9, 9, 9, 9, 9, 9, 9, 0, 51], [4, 4, 4, 4, 4, 4, 5, 5, 0, 35],
+                                              [100, 100, 355, 355, 612, 612, 100, 612, 100, 612],
+                                              [1, -1, -1, 1, 1, -1, 1, -1, 1, 1])))
+    ev = ts._scatter(1500, s, 6, 2000)
+    ev[:, 3] = -1
+    out.append(_case('negative_only', s, 3, ev))
+    # overlapping ranges, ranges with gaps between them, an empty range in the middle
+    out.append(_case('ranges', s, 3, ts._scatter(3000, s, 7, 2000), [(0, 500), (250, 900), (900, 900), (1500, 2000), (2900, 3000)]))
+    # p == 0 and out-of-sensor events carry the smallest and the largest t: t0, t1 stay 10 and 20 on the grid
+    out.append(_case('skip', s, 3, ts._rows([5, W + 5, 6, 7, 8, 3, 9], [5, 5, 6, 7, H, 3, 9], [1, 2, 10, 20, 90, 99, 15],
+                                            [0, 1, 1, -1, -1, 0, 1])))
+    # truncation toward zero, before and after flip_x (time_surface_ref's case)
+    out.append(_case('frac', s, 3, ts._rows([5.9, -0.5, 51.9, -1.0], [3.7, 0.2, 35.9, 4], [1, 2, 3, 4], [1, -1, 1, 1]), packable=False))
+    # more frames than compute units: the workgroups walk on.  Overlapping ranges
+    out.append(_case('many', s, 3, ts._scatter(600 * 25 + 25, s, 3, 3000), [(25 * i, 25 * i + 50) for i in range(600)]))
+    return {c['name']: c for c in out}
+
+
+def packed(case):
+    return vis.pack_events(case['events'])
