@@ -1,5 +1,6 @@
-// events -> polarity-histogram frames on gfx950 (and, in the last two sections, -> time-surface and -> voxel-grid frames:
-// the other representations share parse(), the packed format and the block reductions of this file).
+// events -> polarity-histogram frames on gfx950 (and, in the last three sections, -> time-surface and -> voxel-grid frames
+// and the background-activity filter in front of all three: they share parse(), the packed format and the block
+// reductions of this file).
 //
 // Replaces /root/reference/datasets/vis.py make_event_histogram (:6-41) +
 // parse_events (:44-52) as driven by events2frames (:75-117).
@@ -30,6 +31,7 @@
 #include "common.h"
 #include "eventclip_time_surface.h"
 #include "eventclip_voxel_grid.h"
+#include "eventclip_denoise.h"
 
 // numpy evaluates every ufunc with one rounding per operation: no FMA contraction anywhere in
 // this file (the one fused multiply-add of the reference is written out explicitly).
@@ -2300,6 +2302,295 @@ int launch_voxel_grid(const void *events, const int64_t *frame_range, int F, con
     return EC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// background-activity denoising (include/eventclip_denoise.h states the definition, steps 1 - 5).
+//
+// supported(i) asks every neighbour pixel "did you fire in [tick_i - dt, tick_i]?".  A per-pixel latest-timestamp map
+// answers that only for events taken in time order -- sequential, and wrong on unsorted rows.  Here the ticks are SORTED BY
+// PIXEL instead (a counting sort), and an event scans its neighbours' lists: exact, and independent of the row order.
+// One 1024-thread workgroup owns a whole sample (samples blockIdx.x, + gridDim.x, ...) and walks its row bands itself;
+// a band is rows [y0, y1) extended by a halo of r rows on either side, so that every neighbour of a band's event is in
+// the band's lists.  Per band:
+//   count    one LDS word per pixel of the extended band, LDS atomic adds over the counted events;
+//   scan     a block-wide exclusive scan turns the counts into list offsets (word q + 1 holds the start of pixel q);
+//   scatter  every counted event of the extended band takes a place with an LDS atomic add on its pixel's word -- a cursor,
+//            which ends as the END of the list, i.e. the start of the next pixel's: word q is then the start of pixel q and
+//            word q + 1 its end, with no second array -- and stores its tick there, in the workgroup's own slot of the
+//            workspace: plain stores, read back by the same workgroup behind a barrier (one compute unit, one L1: the
+//            scoping voxel_grid_kernel uses for its own grid);
+//   query    every counted event of the band proper scans, per neighbour row, the ticks of pixels x - r .. x + r, which
+//            are ONE contiguous run of the sorted array (two runs in its own row, around its own pixel), leaves at the
+//            first supporter and writes its keep byte into the workspace.
+// Then one in-order pass compacts the survivors: a ballot gives the place inside the wave, the waves' counts go through
+// LDS (augment_events_kernel's scheme); each thread reads the keep bytes it wrote itself.
+// No global atomics, no waiting on another workgroup; every loop is bounded by the range or by a count read from LDS, and
+// the list offsets never exceed the sample's length, which the kernel checks against the slot's capacity first.
+// Traffic: the events are read 3 bands + 1 times (L2 / MALL after the first), the ticks written and read once per band.
+// ---------------------------------------------------------------------------------------------
+constexpr int DN_PIX_WORDS = 32 * 1024;                // LDS words of the offsets: the pixels of an extended band + 1
+constexpr int DN_LDS_BYTES = DN_PIX_WORDS * 4 + EV_REDUCE_BYTES;
+
+struct DnArgs {
+    const void *events;      // float4 (x, y, t, p) or packed 8-byte events
+    const long long *range;  // [B,2]
+    int H, W, B, r;
+    unsigned dt;
+    void *out;               // the survivors, same type as events
+    long long *counts;       // [B]
+    uint8_t *keep;           // optional [n_events_total]
+    ec_denoise_stats *stats; // optional [B]
+    unsigned char *ws;       // slot g of workgroup g: cap ticks (u32), then cap keep bytes
+    long long slot_bytes;
+    int cap;                 // max_sample_events
+    int rows_per_band, bands;
+};
+
+// f(event, row) for every row of [0, n): eight loads in flight per thread, row j always with thread j % EV_THREADS
+template <typename EV, typename F>
+__device__ __forceinline__ void for_events(const EV *ev, long long n, F f)
+{
+    for (long long i = threadIdx.x; i < n; i += 8 * EV_THREADS) {
+        EV e[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const long long j = i + (long long)k * EV_THREADS;
+            e[k] = ev[j < n ? j : n - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const long long j = i + (long long)k * EV_THREADS;
+            if (j < n) f(e[k], j);
+        }
+    }
+}
+
+// steps 1 and 3: the pixel of a counted event
+template <typename EV>
+__device__ __forceinline__ bool counted_pixel(const EV e, int H, int W, int &x, int &y)
+{
+    int p;
+    parse(e, W, 0, 0, x, y, p);
+    return p != 0 && (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
+}
+
+// v[0 .. n) -> its exclusive prefix sums, in place.  Every thread owns `chunk` consecutive words (odd: neighbouring threads
+// on different banks); the threads' sums meet in a wave scan and the waves' in scratch.
+__device__ void block_exclusive_scan(unsigned *v, int n, unsigned long long *scratch)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int chunk = ((n + EV_THREADS - 1) / EV_THREADS) | 1;
+    const int lo = min(n, (int)threadIdx.x * chunk), hi = min(n, lo + chunk);
+    unsigned s = 0;
+    for (int i = lo; i < hi; i++) s += v[i];
+    unsigned inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(inc, o, 64);
+        inc += lane >= o ? t : 0u;
+    }
+    __syncthreads();
+    if (lane == 63) scratch[wave] = inc;
+    __syncthreads();
+    unsigned run = inc - s;
+#pragma unroll
+    for (int w = 0; w < EV_WAVES; w++) run += w < wave ? (unsigned)scratch[w] : 0u;
+    for (int i = lo; i < hi; i++) {
+        const unsigned c = v[i];
+        v[i] = run;
+        run += c;
+    }
+    __syncthreads();
+}
+
+// is there a tick in [ti - dt, ti] among ticks[k0 .. k1)?  Four loads in flight (the last ones clamped to k1 - 1, a repeat
+// that changes nothing): the lists are short, and one load after the other was a trip to L2 each (profiles/denoise.md).
+__device__ __forceinline__ bool any_support(const unsigned *ticks, unsigned k0, unsigned k1, unsigned ti, unsigned dt)
+{
+    for (unsigned k = k0; k < k1; k += 4) {
+        const unsigned last = k1 - 1;
+        const unsigned t0 = ticks[k], t1 = ticks[min(k + 1, last)], t2 = ticks[min(k + 2, last)], t3 = ticks[min(k + 3, last)];
+        const bool s0 = t0 <= ti && ti - t0 <= dt, s1 = t1 <= ti && ti - t1 <= dt;
+        const bool s2 = t2 <= ti && ti - t2 <= dt, s3 = t3 <= ti && ti - t3 <= dt;
+        if (s0 | s1 | s2 | s3) return true;
+    }
+    return false;
+}
+
+template <typename EV>
+__global__ __launch_bounds__(EV_THREADS) void denoise_kernel(const DnArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned *offs = reinterpret_cast<unsigned *>(smem);       // word 0 stays 0; word q + 1 belongs to pixel q
+    unsigned long long *scratch = reinterpret_cast<unsigned long long *>(smem + DN_PIX_WORDS * 4);
+    int *wave_cnt = reinterpret_cast<int *>(scratch);          // [2][EV_WAVES] of the compaction
+    const int H = a.H, W = a.W, r = a.r;
+    const unsigned dt = a.dt;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned *ticks = reinterpret_cast<unsigned *>(a.ws + (long long)blockIdx.x * a.slot_bytes);
+    uint8_t *flags = reinterpret_cast<uint8_t *>(ticks + a.cap);
+
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const long long e0 = a.range[2 * b], n = a.range[2 * b + 1] - e0;
+        if (n < 0 || n > (long long)a.cap) {                   // longer than the slot: not filtered (the header says so)
+            if (threadIdx.x == 0) {
+                a.counts[b] = -1;
+                if (a.stats) a.stats[b] = ec_denoise_stats{0, 0, 0};
+            }
+            continue;
+        }
+        const EV *ev = reinterpret_cast<const EV *>(a.events) + e0;
+        for (int band = 0; band < a.bands && n > 0; band++) {
+            const int y0 = band * a.rows_per_band, y1 = min(H, y0 + a.rows_per_band);
+            const int ylo = max(0, y0 - r), yhi = min(H, y1 + r);
+            const int npix = (yhi - ylo) * W;                  // < DN_PIX_WORDS by the plan
+            for (int i = threadIdx.x; i <= npix; i += EV_THREADS) offs[i] = 0;
+            __syncthreads();
+            for_events(ev, n, [&](const EV e, long long) {
+                int x, y;
+                if (counted_pixel(e, H, W, x, y) && y >= ylo && y < yhi) atomicAdd(&offs[1 + (y - ylo) * W + x], 1u);
+            });
+            __syncthreads();
+            block_exclusive_scan(offs + 1, npix, scratch);
+            for_events(ev, n, [&](const EV e, long long) {
+                int x, y;
+                if (counted_pixel(e, H, W, x, y) && y >= ylo && y < yhi) {
+                    const unsigned pos = atomicAdd(&offs[1 + (y - ylo) * W + x], 1u);
+                    if (pos < (unsigned)a.cap) ticks[pos] = tick_of(e);    // (always: pos < the band's events <= n <= cap)
+                }
+            });
+            __syncthreads();                                   // the ticks are stored: this workgroup may read them
+            for_events(ev, n, [&](const EV e, long long j) {
+                int x, y;
+                if (!(counted_pixel(e, H, W, x, y) && y >= y0 && y < y1)) return;
+                const unsigned ti = tick_of(e);
+                const int xa = max(0, x - r), xb = min(W - 1, x + r);
+                bool s = false;
+                for (int yy = max(0, y - r); yy <= min(H - 1, y + r) && !s; yy++) {
+                    const unsigned *row = offs + (yy - ylo) * W;       // row[q]: start of pixel q, row[q + 1]: its end
+                    if (yy != y) {
+                        s = any_support(ticks, row[xa], row[xb + 1], ti, dt);
+                    } else {
+                        s = any_support(ticks, row[xa], row[x], ti, dt) || any_support(ticks, row[x + 1], row[xb + 1], ti, dt);
+                    }
+                }
+                flags[j] = s ? 1 : 0;
+            });
+            __syncthreads();                                   // the offsets are read: the next band may zero them
+        }
+        // step 5: the survivors in stored order.  flags[i] was written by this thread (for_events' row-to-thread rule).
+        EV *dst = reinterpret_cast<EV *>(a.out) + e0;
+        long long done = 0;
+        unsigned kept = 0, removed = 0, passed = 0;
+        int buf = 0;
+        for (long long t0 = 0; t0 < n; t0 += EV_THREADS, buf ^= 1) {
+            const long long i = t0 + threadIdx.x;
+            bool ok = false;
+            EV e = {};
+            if (i < n) {
+                e = ev[i];
+                int x, y;
+                const bool cnt = counted_pixel(e, H, W, x, y);
+                ok = !cnt || flags[i] != 0;
+                kept += cnt && ok, removed += cnt && !ok, passed += !cnt;
+                if (a.keep) a.keep[e0 + i] = ok ? 1 : 0;
+            }
+            const unsigned long long mask = __ballot(ok);
+            const int before = __popcll(mask & ((1ull << lane) - 1ull));
+            if (lane == 0) wave_cnt[buf * EV_WAVES + wave] = __popcll(mask);
+            __syncthreads();
+            int base = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < EV_WAVES; w++) {
+                const int c = wave_cnt[buf * EV_WAVES + w];
+                base += w < wave ? c : 0;
+                total += c;
+            }
+            if (ok) dst[done + base + before] = e;
+            done += total;
+        }
+        if (a.stats) {
+            const unsigned long long kr = block_sum_u64((unsigned long long)kept | ((unsigned long long)removed << 32), scratch);
+            const unsigned long long ps = block_sum_u64(passed, scratch);
+            if (threadIdx.x == 0) a.stats[b] = ec_denoise_stats{(unsigned)kr, (unsigned)(kr >> 32), (unsigned)ps};
+        }
+        if (threadIdx.x == 0) a.counts[b] = done;
+        __syncthreads();                                       // scratch is read: the next sample may write it
+    }
+}
+
+// Row bands: as many rows as DN_PIX_WORDS - 1 pixels hold, 2 r of them halo, evened out over the bands.  A sensor that
+// fits whole has one band and no halo.  bands == 0: the entry points refuse this sensor or radius.
+struct DnPlan {
+    int rows_per_band, bands;
+};
+inline DnPlan denoise_plan(int H, int W, int r)
+{
+    DnPlan p = {};
+    if (H <= 0 || W <= 0 || W > 65536 || r < EC_DENOISE_MIN_RADIUS || r > EC_DENOISE_MAX_RADIUS) return p;
+    const int rows = (DN_PIX_WORDS - 1) / W;
+    if (H <= rows) {
+        p.bands = 1, p.rows_per_band = H;
+    } else if (rows >= 2 * r + 1) {
+        p.bands = ec::ceil_div(H, rows - 2 * r);
+        p.rows_per_band = ec::ceil_div(H, p.bands);
+    }
+    return p;
+}
+
+inline size_t denoise_slot_bytes(int cap) { return (size_t)cap * 4 + ((size_t)cap + 15) / 16 * 16; }
+
+inline size_t denoise_workspace_bytes(const ec_denoise_params *prm, int B)
+{
+    if (!prm || B <= 0 || prm->max_sample_events <= 0 || denoise_plan(prm->H, prm->W, prm->radius).bands == 0) return 0;
+    return denoise_slot_bytes(prm->max_sample_events) * (size_t)std::min<int>(B, EC_DENOISE_MAX_GROUPS);
+}
+
+template <typename EV>
+int launch_denoise(const void *events, const int64_t *sample_range, int B, const ec_denoise_params *prm, void *events_out,
+                   int64_t *counts, uint8_t *keep, ec_denoise_stats *stats, void *workspace, size_t workspace_bytes,
+                   ec_stream_t stream)
+{
+    EC_REQUIRE(prm != nullptr, "ec_denoise_events: params is null");
+    EC_REQUIRE(B >= 0, "ec_denoise_events: B=%d", B);
+    if (B == 0) return EC_OK;
+    EC_REQUIRE(events && sample_range && events_out && counts && workspace, "ec_denoise_events: null buffer");
+    EC_REQUIRE(events != events_out, "ec_denoise_events: in-place operation is not supported");
+    EC_REQUIRE(prm->H > 0 && prm->W > 0, "ec_denoise_events: bad shape (%d,%d)", prm->H, prm->W);
+    EC_REQUIRE(prm->radius >= EC_DENOISE_MIN_RADIUS && prm->radius <= EC_DENOISE_MAX_RADIUS,
+               "ec_denoise_events: radius=%d outside %d .. %d", prm->radius, (int)EC_DENOISE_MIN_RADIUS, (int)EC_DENOISE_MAX_RADIUS);
+    EC_REQUIRE(prm->dt_us <= (uint32_t)EC_DENOISE_MAX_DT_US, "ec_denoise_events: dt_us=%u above %d", prm->dt_us, (int)EC_DENOISE_MAX_DT_US);
+    EC_REQUIRE(prm->max_sample_events > 0, "ec_denoise_events: max_sample_events=%d (a bound: it sizes the workspace)",
+               prm->max_sample_events);
+    EC_REQUIRE((((uintptr_t)events | (uintptr_t)events_out) & (sizeof(EV) - 1)) == 0,
+               "ec_denoise_events: events and events_out must be %d-byte aligned", (int)sizeof(EV));
+    EC_REQUIRE(((uintptr_t)counts & 7) == 0 && ((uintptr_t)stats & 3) == 0 && ((uintptr_t)workspace & 15) == 0,
+               "ec_denoise_events: counts must be 8-byte, stats 4-byte and workspace 16-byte aligned");
+    const DnPlan plan = denoise_plan(prm->H, prm->W, prm->radius);
+    EC_REQUIRE(plan.bands > 0, "ec_denoise_events: W=%d too wide for an LDS band of %d rows", prm->W, 2 * prm->radius + 1);
+    const size_t need = denoise_workspace_bytes(prm, B);
+    if (workspace_bytes < need)
+        return ec::fail(EC_ERR_WORKSPACE, "ec_denoise_events: workspace %zu < %zu bytes (ec_denoise_workspace_bytes)", workspace_bytes, need);
+
+    DnArgs a = {};
+    a.events = events;
+    a.range = reinterpret_cast<const long long *>(sample_range);
+    a.H = prm->H, a.W = prm->W, a.B = B, a.r = prm->radius;
+    a.dt = prm->dt_us;
+    a.out = events_out, a.counts = reinterpret_cast<long long *>(counts), a.keep = keep, a.stats = stats;
+    a.ws = static_cast<unsigned char *>(workspace);
+    a.slot_bytes = (long long)denoise_slot_bytes(prm->max_sample_events);
+    a.cap = prm->max_sample_events;
+    a.rows_per_band = plan.rows_per_band, a.bands = plan.bands;
+
+    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(denoise_kernel<EV>), EV_LDS_TOTAL)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // algorithmic bytes: every event read once and at most written once
+    ec::ProfScope prof(ec::PROF_DENOISE, hs, 0, 2.0 * (double)(prm->total_events > 0 ? prm->total_events : 0) * sizeof(EV));
+    hipLaunchKernelGGL(denoise_kernel<EV>, dim3((unsigned)std::min<int>(B, EC_DENOISE_MAX_GROUPS)), dim3(EV_THREADS), DN_LDS_BYTES, hs, a);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
 }  // namespace
 
 #ifdef EC_EVENTS_DIAG
@@ -2363,6 +2654,25 @@ extern "C" EC_API int ec_events_to_voxel_grid_packed(const uint64_t *events, con
 }
 
 extern "C" EC_API int ec_voxel_grid_bands(int H, int W, int bins) { return voxel_grid_plan(H, W, bins).bands; }
+
+extern "C" EC_API int ec_denoise_events(const float *events, const int64_t *sample_range, int B, const ec_denoise_params *prm,
+                                        float *events_out, int64_t *counts, uint8_t *keep, ec_denoise_stats *stats,
+                                        void *workspace, size_t workspace_bytes, ec_stream_t stream)
+{
+    return launch_denoise<float4>(events, sample_range, B, prm, events_out, counts, keep, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" EC_API int ec_denoise_events_packed(const uint64_t *events, const int64_t *sample_range, int B,
+                                               const ec_denoise_params *prm, uint64_t *events_out, int64_t *counts,
+                                               uint8_t *keep, ec_denoise_stats *stats, void *workspace,
+                                               size_t workspace_bytes, ec_stream_t stream)
+{
+    return launch_denoise<packed_t>(events, sample_range, B, prm, events_out, counts, keep, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" EC_API size_t ec_denoise_workspace_bytes(const ec_denoise_params *prm, int B) { return denoise_workspace_bytes(prm, B); }
+
+extern "C" EC_API int ec_denoise_bands(int H, int W, int radius) { return denoise_plan(H, W, radius).bands; }
 
 extern "C" EC_API int ec_center_events(float *events, const int64_t *sample_range, int B, int H, int W,
                                        ec_stream_t stream)

@@ -31,6 +31,9 @@ class Event2ImagePipeline:
         ``count_non_zero`` and ``float_stage``: it has no hot-pixel threshold and no frame maximum.  Or
         ``'voxel_grid'`` (not in the reference either: the temporal-bin frames of include/eventclip_voxel_grid.h),
         which reads ``bins`` (3, the only value with an image form) and ignores those three and ``grayscale``.
+        ``denoise`` (not in the reference; absent or ``None`` = off): ``dict(dt=seconds, radius=1)`` puts the
+        background-activity filter of include/eventclip_denoise.h in front of whichever form is chosen: an event stays
+        only if a neighbouring pixel fired in the ``dt`` before it, and the chunks are cut from the survivors.
     n_px: CLIP input resolution.  patch/kpad/dtype: when given, ``__call__`` emits the
         16-bit im2col rows for ``CLIP.encode_patches`` instead of fp32 images.
     frames_u8: emit the resized + cropped uint8 frames (``frames_u8`` [Fv, R, R, 3]) instead, the input of
@@ -65,6 +68,14 @@ class Event2ImagePipeline:
         if self.event_rep == 'voxel_grid' and self.bins != 3:
             raise ValueError(f'bins={self.bins}: voxel-grid frames have 3 temporal bins, one per colour channel '
                              '(vis.voxel_grid_device returns the grid of 2 .. 8 bins)')
+        # the background-activity filter in front of every form (None = off: nothing below changes)
+        self.max_n = int(max_n)
+        self.denoise = qa.get('denoise')
+        if self.denoise is not None:
+            if not isinstance(self.denoise, dict) or 'dt' not in self.denoise or set(self.denoise) - {'dt', 'radius'}:
+                raise ValueError(f"denoise {self.denoise!r}: dict(dt=seconds, radius=1)")
+            self.denoise = dict(dt=float(self.denoise['dt']), radius=int(self.denoise.get('radius', 1)))
+            vis.denoise_params(self.resolution, vis.denoise_dt_us(self.denoise['dt']), self.denoise['radius'], 1)
         self.n_px, self.patch, self.kpad, self.dtype = int(n_px), patch, kpad, dtype
         self.frames_u8 = bool(frames_u8)
         assert not (self.frames_u8 and self.patch), 'frames_u8 and patch rows are two different outputs'
@@ -150,13 +161,34 @@ class Event2ImagePipeline:
             cat = np.concatenate([vis.parse_events(e) for e in host], axis=0)
         return torch.from_numpy(cat).to(dev), n_events
 
-    def __call__(self, events, n_events=None, hflip=False, tflip=False, center=False, starts=None):
+    def filter(self, events, n_events, starts=None):
+        """quantize_args['denoise']: the survivors of every sample, compacted at the sample's unchanged first row.
+        -> (events_out, filtered counts, starts).  The window looks into the stored past; flips are view transforms and
+        come after."""
+        n = np.asarray(n_events, dtype=np.int64)
+        o0 = np.asarray(starts if starts is not None else np.concatenate([[0], np.cumsum(n)[:-1]]), dtype=np.int64)
+        too_long = np.flatnonzero(n > self.max_n)
+        if len(too_long):
+            raise ValueError(f'denoise: samples {too_long.tolist()} hold more than max_n={self.max_n} events')
+        sr = torch.tensor(np.stack([o0, o0 + n], 1), dtype=torch.int64)
+        out, counts = vis.denoise_events_device(events, sr, self.resolution, self.denoise['dt'], self.denoise['radius'])
+        counts = counts.cpu().numpy()
+        emptied = np.flatnonzero((counts <= 0) & (n > 0))
+        if len(emptied):
+            raise ValueError(f"denoise: no event of samples {emptied.tolist()} has a neighbour within dt={self.denoise['dt']} s "
+                             f"(radius {self.denoise['radius']}): the filter would empty them")
+        return out, [int(c) for c in counts], o0
+
+    def __call__(self, events, n_events=None, hflip=False, tflip=False, center=False, starts=None, filtered=False):
         """events: list of per-sample float32 [n_i, 4] arrays/tensors (or packed uint64 [n_i],
         vis.pack_events), or one CUDA tensor [sum n_i, 4] (packed: int64 [sum n_i]) with
         ``n_events`` giving the per-sample counts.
         hflip / tflip: the test-time-augmentation views of event2img.py:94-112;
         center: apply center_events (utils.py:38-57, in place) first, as the N-Caltech /
         N-ImageNet readers do (caltech.py:176).
+        With ``quantize_args['denoise']`` the events are filtered after centring and before chunking (``filtered``: they
+        are the filter's survivors already, as ``tta`` passes them), and the result gains ``n_events``, the filtered
+        counts.
 
         Returns a dict with ``valid_mask`` [B, T] (CUDA bool), ``row_idx`` [B, T] (CUDA
         int32) and either ``patches`` [Fv, G, kpad] (fused path), ``frames_u8`` [Fv, R, R, 3] or ``img``
@@ -171,11 +203,15 @@ class Event2ImagePipeline:
             offs = np.stack([o0, o0 + np.asarray(n_events)], 1)
             sr = torch.tensor(offs, dtype=torch.int64, device=dev)
             vis.center_events_device(events, sr, self.resolution)
+        if self.denoise is not None and not filtered:
+            events, n_events, starts = self.filter(events, n_events, starts)
         fr, ri, vm = self.plan(n_events, tflip=tflip, starts=starts)
         fr_d = fr.to(dev)
         frames = self.frames(events, fr_d, hflip=hflip, tflip=tflip,
                              total_events=int((fr[:, 1] - fr[:, 0]).sum()))
         out = dict(valid_mask=vm.to(dev), row_idx=ri.to(dev))
+        if self.denoise is not None:
+            out['n_events'] = [int(n) for n in n_events]
         if self.augment:
             frames = self._augment_frames(frames, ri)
         if self.frames_u8:
@@ -210,7 +246,10 @@ class Event2ImagePipeline:
         h+t-flip, as a list of batches in that order."""
         if isinstance(events, (list, tuple)):
             events, n_events = self._concat(events, _lib.require_gpu())
-        return [self(events, n_events, hflip=h, tflip=t)
+        starts = None
+        if self.denoise is not None:      # once, on the stored rows: the four views are views of the same survivors
+            events, n_events, starts = self.filter(events, n_events)
+        return [self(events, n_events, hflip=h, tflip=t, starts=starts, filtered=True)
                 for h, t in ((False, False), (True, False), (False, True), (True, True))]
 
 

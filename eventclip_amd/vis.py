@@ -10,7 +10,8 @@ Same names and argument meaning as the reference:
 plus the batched device entries ``events_to_frames_device`` (polarity histogram), ``time_surface_device``
 (latest-timestamp frames, ``convert_method='time_surface'``: not in the reference, defined in
 include/eventclip_time_surface.h) and ``voxel_grid_device`` (temporal-bin frames, ``convert_method='voxel_grid'``:
-not in the reference either, defined in include/eventclip_voxel_grid.h) used by the pipeline.
+not in the reference either, defined in include/eventclip_voxel_grid.h) used by the pipeline, and in front of all three
+``denoise_events_device`` / ``denoise_events`` (the background-activity filter of include/eventclip_denoise.h).
 There is no CPU fallback.
 """
 import collections
@@ -420,19 +421,142 @@ def voxel_grid_device(events, frame_range, shape, bins=3, background_mask=True, 
     return res[0] if len(res) == 1 else tuple(res)
 
 
+# ---- background-activity denoising (include/eventclip_denoise.h: the definition, steps 1 - 5) ----
+DENOISE_HEADER = os.path.join(os.path.dirname(_lib.HEADER), 'eventclip_denoise.h')
+with open(DENOISE_HEADER) as _f:
+    _, _denoise_constants, _denoise_structs, DENOISE_SIGNATURES = _lib.read_header(
+        _f.read().replace('#include "eventclip_hip.h"', f'#define EC_ABI_VERSION {_lib.ABI_VERSION}'))
+EcDenoiseParams, EcDenoiseStats = _denoise_structs['EcDenoiseParams'], _denoise_structs['EcDenoiseStats']
+DENOISE_RADIUS = (_denoise_constants['EC_DENOISE_MIN_RADIUS'], _denoise_constants['EC_DENOISE_MAX_RADIUS'])
+DENOISE_MAX_DT_US = _denoise_constants['EC_DENOISE_MAX_DT_US']
+DENOISE_STATS_DTYPE = np.dtype([('kept', '<u4'), ('removed', '<u4'), ('passed', '<u4')])
+
+_denoise_scratch = collections.defaultdict(_lib.Scratch)   # device index -> the filter's workspace, reused by every call
+
+
+def denoise_lib():
+    """The loaded library with the entries of eventclip_denoise.h typed (``_lib.launch`` finds them there)."""
+    handle = _lib.lib()
+    for name, (res, args) in DENOISE_SIGNATURES.items():
+        fn = getattr(handle, name)
+        fn.restype, fn.argtypes = res, args
+    return handle
+
+
+def denoise_dt_us(dt):
+    """The support window: seconds -> the integer microseconds of ``ec_denoise_params.dt_us``."""
+    dt_us = int(round(float(dt) * 1e6))
+    if not 0 <= dt_us <= DENOISE_MAX_DT_US:
+        raise ValueError(f'dt={dt} s: the support window is 0 .. {DENOISE_MAX_DT_US} microseconds')
+    return dt_us
+
+
+def denoise_params(shape, dt_us, radius, max_sample_events, total_events=0):
+    """EcDenoiseParams: what ``denoise_events_device`` and the custom op both fill."""
+    if not DENOISE_RADIUS[0] <= int(radius) <= DENOISE_RADIUS[1]:
+        raise ValueError(f'radius={radius}: {DENOISE_RADIUS[0]} .. {DENOISE_RADIUS[1]}')
+    if not 0 <= int(dt_us) <= DENOISE_MAX_DT_US:
+        raise ValueError(f'dt_us={dt_us}: 0 .. {DENOISE_MAX_DT_US}')
+    p = EcDenoiseParams()
+    p.H, p.W, p.radius, p.dt_us = int(shape[0]), int(shape[1]), int(radius), int(dt_us)
+    p.max_sample_events = max(1, int(max_sample_events))
+    p.total_events = int(total_events)
+    return p
+
+
+def denoise_workspace_bytes(prm, B):
+    """``ec_denoise_workspace_bytes``: host only, 0 for parameters the entry points refuse."""
+    return int(denoise_lib().ec_denoise_workspace_bytes(ctypes.byref(prm), int(B)))
+
+
+def denoise_launch(events, sample_range, prm, events_out, counts, keep=None, stats=None):
+    """The C ABI call with the workspace this module keeps per device (the custom op and the debug form share it)."""
+    import torch
+    B = int(sample_range.shape[0])
+    need = denoise_workspace_bytes(prm, B)
+    key = events.device.index if events.device.index is not None else torch.cuda.current_device()
+    ws = _denoise_scratch[key].get(max(need, 256), torch.device('cuda', key))
+    _lib.launch('ec_denoise_events_packed' if is_packed(events) else 'ec_denoise_events', events, sample_range, B, prm,
+                events_out, counts, keep, stats, ws, ws.numel())
+
+
+def denoise_events_device(events, sample_range, shape, dt, radius=1, return_mask=False, return_stats=False):
+    """Batched device entry of the background-activity filter (include/eventclip_denoise.h).
+
+    events:       float32 CUDA tensor [n_total, 4] or packed events, int64 CUDA tensor [n_total]; not modified.
+    sample_range: int64 tensor [B, 2] of (begin, end) rows per sample (disjoint), on the host or the device.
+    dt:           the support window in SECONDS (no default: it is the sensor's and the scene's); radius 1 .. 3.
+    An event stays if a pixel within ``radius`` (not its own) fired in the ``dt`` before it; rows the frame kernels would
+    not count (p == 0, outside the sensor) pass through.
+    Returns (events_out, counts): the survivors of sample b are events_out[begin_b : begin_b + counts[b]], in stored
+    order, the rows behind them unspecified; counts int64 CUDA [B].  + keep uint8 CUDA [n_total] (1 = written; rows outside
+    every sample 0) with ``return_mask``, + a stats structured array (kept, removed, passed) with ``return_stats``.
+    """
+    import torch
+    dev = _lib.require_gpu()
+    packed = is_packed(events)
+    assert events.is_cuda and events.is_contiguous()
+    assert packed or (events.dtype == torch.float32 and events.dim() == 2 and events.shape[1] == 4)
+    assert sample_range.dtype == torch.int64 and sample_range.dim() == 2 and sample_range.shape[1] == 2
+    B = int(sample_range.shape[0])
+    dt_us = denoise_dt_us(dt)
+    if not return_mask and not return_stats:
+        # the production form: the registered custom op (eventclip_hip::events_denoise)
+        from . import torch_ops  # noqa: F401  (registers the namespace)
+        return torch.ops.eventclip_hip.events_denoise(events, sample_range.to(dev).contiguous(), int(shape[0]), int(shape[1]),
+                                                      dt_us, int(radius))
+    host = sample_range.cpu()
+    lengths = host[:, 1] - host[:, 0]
+    prm = denoise_params(shape, dt_us, radius, int(lengths.max()) if B else 1, int(lengths.sum()) if B else 0)
+    events_out = torch.empty_like(events)
+    counts = torch.zeros((B,), dtype=torch.int64, device=dev)
+    keep = torch.zeros((int(events.shape[0]),), dtype=torch.uint8, device=dev) if return_mask else None
+    stats = torch.zeros((B, ctypes.sizeof(EcDenoiseStats)), dtype=torch.uint8, device=dev) if return_stats else None
+    denoise_launch(events, sample_range.to(dev).contiguous(), prm, events_out, counts, keep, stats)
+    res = [events_out, counts]
+    if return_mask:
+        res.append(keep)
+    if return_stats:
+        res.append(stats.cpu().numpy().view(DENOISE_STATS_DTYPE).reshape(B))
+    return tuple(res)
+
+
+def denoise_events(events, resolution, dt, radius=1):
+    """The filter for one sample, numpy in, numpy out: [n, 4] rows (or the dict form, or packed uint64 [n]) -> the
+    surviving rows in stored order."""
+    import torch
+    dev = _lib.require_gpu()
+    if not isinstance(events, dict) and is_packed(np.asarray(events)):
+        arr = np.ascontiguousarray(events)
+        ev = torch.from_numpy(arr.view(np.int64)).to(dev)
+    else:
+        arr = parse_events(events)
+        ev = torch.from_numpy(arr).to(dev)
+    rng = torch.tensor([[0, ev.shape[0]]], dtype=torch.int64)
+    if ev.shape[0] == 0:
+        return arr.copy()
+    out, counts = denoise_events_device(ev, rng, resolution, dt, radius)
+    return out[:int(counts[0])].cpu().numpy().view(arr.dtype)
+
+
 def events2frames(events, split_method, convert_method, shape=(180, 240), **kwargs):
     """Drop-in for the reference's events2frames (vis.py:75-117): numpy in, numpy out.
 
     convert_method='time_surface' (not in the reference) takes ``decay`` ('linear' or 'exp') and ``tau`` (seconds) and
     ignores ``thresh``, ``count_non_zero`` and ``float_stage``: there is no hot-pixel threshold and no frame maximum.
     convert_method='voxel_grid' (not in the reference) takes ``bins`` (3: the image form has three channels) and ignores
-    those three and ``grayscale``: channel k is temporal bin k."""
+    those three and ``grayscale``: channel k is temporal bin k.
+    ``denoise=dict(dt=seconds, radius=1)`` (not in the reference) runs the background-activity filter of
+    include/eventclip_denoise.h first: the chunks are cut from the survivors."""
     import torch
     grayscale = kwargs.pop('grayscale', True)
+    denoise = kwargs.pop('denoise', None)
     ev = parse_events(events)
     assert split_method == 'event_count'                 # vis.py:90
     if convert_method not in CONVERT_METHODS:            # vis.py:113
         raise NotImplementedError(f'{convert_method} not implemented!')
+    if denoise is not None:
+        ev = denoise_events(ev, shape, denoise['dt'], denoise.get('radius', 1))
     N = int(kwargs['N'])
     if ev.shape[0] == 0:
         raise IndexError('events2frames: empty event array')

@@ -1,0 +1,343 @@
+"""The yardstick of the background-activity filter (include/eventclip_denoise.h, steps 1 - 5): the definition restated
+twice (``oracle``: vectorised, one sort of the keys pixel * 2^31 + tick and one searchsorted pair per neighbour offset;
+``oracle_loop``: a plain double loop over Python integers, for the small cases), a numpy model of the kernel's structure
+-- row bands with a halo, per-band sorted lists -- with switches that plant faults (``kernel_model``), the case table,
+and the one check function (``check``) the CPU and the GPU tests share.  The reference has no such filter: these
+restatements ARE the reference answer, and every comparison is exact -- the definition has no float stage."""
+import functools
+
+import numpy as np
+
+import time_surface_ref as ts
+from eventclip_amd import synthetic, vis
+
+TICK_MAX = ts.TICK_MAX
+GUARD = 0xA5                                # every byte no call may write
+STATS_DTYPE = np.dtype([('kept', '<u4'), ('removed', '<u4'), ('passed', '<u4')])
+SHAPES = ((100, 120), (180, 240), (480, 640), (37, 53))
+FAULTS = ('own_pixel', 'open_window', 'future', 'no_halo', 'uncounted_support', 'x_wrap', 'manhattan', 'reorder')
+
+
+def parse(events, shape):
+    """steps 1 - 3: int64 x, y, tick and the bool `counted` (no flip, no negation)."""
+    H, W = shape
+    x, y, p, tick = ts.parse(events, shape)
+    inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+    return x, y, tick, (p != 0) & inside, inside
+
+
+def offsets(radius, manhattan=False):
+    """the (dx, dy) of the neighbour pixels: Chebyshev distance 1 .. r, never the own pixel"""
+    r = int(radius)
+    return [(dx, dy) for dy in range(-r, r + 1) for dx in range(-r, r + 1)
+            if (dx, dy) != (0, 0) and (not manhattan or abs(dx) + abs(dy) <= r)]
+
+
+def guarded(events, ranges):
+    """The four outputs as a call finds them: every byte GUARD."""
+    ev = np.asarray(events)
+    return dict(events_out=np.frombuffer(bytes([GUARD]) * ev.nbytes, ev.dtype).reshape(ev.shape).copy(),
+                counts=np.frombuffer(bytes([GUARD]) * 8 * len(ranges), np.int64).copy(),
+                keep=np.full(ev.shape[0], GUARD, np.uint8),
+                stats=np.frombuffer(bytes([GUARD]) * STATS_DTYPE.itemsize * len(ranges), STATS_DTYPE).copy())
+
+
+def write_sample(out, events, s, b, e, counted, supported, reorder=False):
+    """step 5 for sample s = rows [b, e)"""
+    keep = supported | ~counted
+    rows = np.flatnonzero(keep) + b
+    if reorder:
+        rows = rows[::-1]
+    out['events_out'][b:b + len(rows)] = np.asarray(events)[rows]
+    out['counts'][s] = len(rows)
+    out['keep'][b:e] = keep
+    out['stats'][s] = (int((counted & supported).sum()), int((counted & ~supported).sum()), int((~counted).sum()))
+
+
+def oracle(events, ranges, shape, dt_us, radius):
+    """The definition, vectorised: the counted events' keys pixel * 2^31 + tick sorted once per sample; per neighbour
+    offset the number of keys in [pixel' * 2^31 + tick - dt, pixel' * 2^31 + tick] is one searchsorted pair."""
+    H, W = shape
+    dt = int(dt_us)
+    x, y, tick, counted, _ = parse(events, shape)
+    out = guarded(events, ranges)
+    for s, (b, e) in enumerate(ranges):
+        c = counted[b:e]
+        xs, ys, tk = x[b:e][c], y[b:e][c], tick[b:e][c]
+        keys = np.sort(((ys * W + xs) << 31) + tk)
+        sup = np.zeros(len(tk), bool)
+        for dx, dy in offsets(radius):
+            xn, yn = xs + dx, ys + dy
+            ok = (xn >= 0) & (xn < W) & (yn >= 0) & (yn < H)
+            base = (yn * W + xn) << 31
+            lo = np.searchsorted(keys, base + np.maximum(tk - dt, 0), 'left')
+            hi = np.searchsorted(keys, base + tk, 'right')
+            sup |= ok & (hi > lo)
+        supported = np.zeros(e - b, bool)
+        supported[c] = sup
+        write_sample(out, events, s, b, e, c, supported)
+    return out
+
+
+def oracle_loop(events, ranges, shape, dt_us, radius, rows=None):
+    """The definition as it is written: for every i, every j, in Python's integers.  -> {row: supported} for the counted
+    rows of every sample, or of ``rows`` only (the large cases are checked on a draw of rows, each against every j)."""
+    dt, r = int(dt_us), int(radius)
+    x, y, tick, counted, _ = (a.tolist() for a in parse(events, shape))
+    want = None if rows is None else set(int(i) for i in rows)
+    out = {}
+    for b, e in ranges:
+        js = [(x[j], y[j], tick[j], j) for j in range(b, e) if counted[j]]
+        for xi, yi, ti, i in js:
+            if want is not None and i not in want:
+                continue
+            sup = False
+            for xj, yj, tj, j in js:
+                if j != i and max(abs(xj - xi), abs(yj - yi)) <= r and (xj, yj) != (xi, yi) and ti - dt <= tj <= ti:
+                    sup = True
+                    break
+            out[i] = sup
+    return out
+
+
+def kernel_model(events, ranges, shape, dt_us, radius, rows_per_band=None, fault=None):
+    """The kernel's structure in numpy: per sample, row bands of ``rows_per_band`` rows extended by a halo of r rows; per
+    band the events of the extended band sorted by band-local pixel, the events of the band proper asking their
+    neighbours' lists.  ``fault`` plants one of FAULTS."""
+    assert fault is None or fault in FAULTS
+    H, W = shape
+    dt, r = int(dt_us), int(radius)
+    rpb = int(rows_per_band or H)
+    x, y, tick, counted, inside = parse(events, shape)
+    out = guarded(events, ranges)
+    offs = offsets(r, manhattan=fault == 'manhattan')
+    if fault == 'own_pixel':
+        offs = offs + [(0, 0)]
+    for s, (b, e) in enumerate(ranges):
+        c = counted[b:e]
+        lists = inside[b:e] if fault == 'uncounted_support' else c          # who stands in the lists
+        xs, ys, tk = x[b:e], y[b:e], tick[b:e]
+        supported = np.zeros(e - b, bool)
+        for y0 in range(0, H, rpb):
+            y1 = min(H, y0 + rpb)
+            ylo, yhi = (y0, y1) if fault == 'no_halo' else (max(0, y0 - r), min(H, y1 + r))
+            npix = (yhi - ylo) * W
+            member = lists & (ys >= ylo) & (ys < yhi)
+            keys = np.sort((((ys - ylo) * W + xs)[member] << 31) + tk[member])
+            ask = np.flatnonzero(c & (ys >= y0) & (ys < y1))
+            xa, ya, ta = xs[ask], ys[ask], tk[ask]
+            sup = np.zeros(len(ask), bool)
+            for dx, dy in offs:
+                xn, yn = xa + dx, ya + dy
+                q = (yn - ylo) * W + xn
+                ok = (yn >= ylo) & (yn < yhi) & (q >= 0) & (q < npix)
+                if fault != 'x_wrap':
+                    ok &= (xn >= 0) & (xn < W)
+                first = ta - dt + 1 if fault == 'open_window' else ta - dt
+                last = ta + dt if fault == 'future' else ta
+                lo = np.searchsorted(keys, (q << 31) + np.maximum(first, 0), 'left')
+                hi = np.searchsorted(keys, (q << 31) + np.minimum(last, TICK_MAX), 'right')
+                sup |= ok & (hi - lo > (1 if (dx, dy) == (0, 0) else 0))    # (the own pixel's list holds the event itself)
+            supported[ask] = sup
+        write_sample(out, events, s, b, e, c, supported, reorder=fault == 'reorder')
+    return out
+
+
+def check(got, want):
+    """Exact, byte for byte, guards included: every output that `got` holds (None = not asked for)."""
+    for k in ('counts', 'keep', 'stats', 'events_out'):
+        if got.get(k) is None:
+            continue
+        g, w = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
+        assert g.shape == w.shape and g.dtype.itemsize == w.dtype.itemsize, (k, g.shape, w.shape, g.dtype, w.dtype)
+        gb, wb = g.reshape(-1).view(np.uint8), w.reshape(-1).view(np.uint8)
+        if not np.array_equal(gb, wb):
+            at = int(np.flatnonzero(gb != wb)[0]) // max(1, g.dtype.itemsize * (g[0].size if g.ndim > 1 else 1))
+            raise AssertionError(f'{k}: {int((gb != wb).sum())} bytes differ, first in element {at}: '
+                                 f'got {g[at]!r}, want {w[at]!r}')
+
+
+# ---- the case table ----------------------------------------------------------------------------------------------------
+def rows(x, y, tick, p=None):
+    """float32 [n, 4] rows whose ticks are exactly `tick` (t = tick / 1e6 must survive float32: asserted)."""
+    x, y, tick = np.asarray(x, np.int64), np.asarray(y, np.int64), np.asarray(tick, np.int64)
+    p = np.where(np.arange(len(x)) % 2 == 0, 1., -1.) if p is None else np.asarray(p, np.float64)
+    ev = np.stack([x, y, tick / 1e6, p], 1).astype(np.float32)
+    back = np.clip(np.rint(ev[:, 2].astype(np.float64) * 1e6), 0, TICK_MAX).astype(np.int64)
+    assert np.array_equal(back, tick), 'a tick that float32 seconds cannot carry'
+    return ev
+
+
+def _case(samples, shape, dt_us, radius, gaps=None, random=False, packable=True, expect=None):
+    """samples: list of [n_i, 4] arrays -> one event array and the ranges; gaps: rows of filler in front of every sample
+    (outside every range: never read, never written)"""
+    parts, ranges, at = [], [], 0
+    for i, s in enumerate(samples):
+        g = 0 if gaps is None else int(gaps[i % len(gaps)])
+        if g:
+            parts.append(rows(np.full(g, 1), np.full(g, 1), np.full(g, 7)))
+            at += g
+        parts.append(np.asarray(s, np.float32).reshape(-1, 4))
+        ranges.append((at, at + len(s)))
+        at += len(s)
+    ev = np.concatenate(parts) if parts else np.zeros((0, 4), np.float32)
+    return dict(events=np.ascontiguousarray(ev), ranges=ranges, shape=tuple(shape), dt_us=int(dt_us), radius=int(radius),
+                random=random, packable=packable, expect=expect)
+
+
+def _directed(shape, r, dt):
+    """One tiny sample per property, all in one launch; -> (samples, expected keep per sample)."""
+    H, W = shape
+    S, K = [], []
+
+    def add(x, y, tick, keep, p=None):
+        S.append(rows(x, y, tick, p))
+        K.append(list(keep))
+
+    cx, cy = W // 2, H // 2
+    add([cx], [cy], [500], [0])                                                  # a lone event
+    add([cx, cx + 1], [cy, cy], [500, 500], [1, 1])                              # equal ticks: both kept
+    add([cx, cx + 1], [cy, cy], [500, 500 + dt], [0, 1])                         # exactly dt apart
+    add([cx, cx + 1], [cy, cy], [500, 501 + dt], [0, 0])                         # dt + 1 apart
+    add([cx + 1, cx], [cy, cy], [500 + dt, 500], [1, 0])                         # ... and the later one stored first
+    add([cx] * 6, [cy] * 6, [500, 500, 501, 502, 502, 503], [0] * 6)             # repeats on one pixel, no neighbour
+    for dx, dy in ((r, 0), (0, r), (r, r), (-r, r), (-r, 0), (0, -r), (r, -r), (-r, -r), (r, 1 - r), (r - 1, -r)):
+        add([cx, cx + dx], [cy, cy + dy], [500, 510], [0, 1])                    # a supporter at distance exactly r
+    for dx, dy in ((r + 1, 0), (0, r + 1), (r + 1, r + 1), (-r - 1, r), (r, -r - 1), (-r - 1, -r - 1)):
+        add([cx, cx + dx], [cy, cy + dy], [500, 510], [0, 0])                    # ... and at r + 1
+    for x0, y0 in ((0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1), (cx, 0), (cx, H - 1), (0, cy), (W - 1, cy)):
+        x1, y1 = x0 + (1 if x0 == 0 else -1), y0 + (1 if y0 == 0 else -1)        # corners and edges: the inner diagonal
+        add([x0, x1], [y0, y1], [500, 505], [0, 1])
+        add([x1, x0], [y1, y0], [500, 505], [0, 1])
+        add([x0, x0], [y0, y0], [500, 505], [0, 0])                              # alone on the border: nothing outside
+    # x = 0 against x = W - 1 of the row above / below: neighbours only for an index that wraps
+    add([0, W - 1], [cy, cy - 1], [500, 505], [0, 0])
+    add([W - 1, 0], [cy, cy + 1], [500, 505], [0, 0])
+    # p == 0 rows and rows outside the sensor beside a lone event: they pass (1) and support nothing
+    add([cx, cx + 1, cx, W, cx], [cy, cy, cy + 1, cy, H + 3], [500, 499, 500, 500, 500], [0, 1, 1, 1, 1], p=[1, 0, 0, 1, -1])
+    add([], [], [], [])                                                          # an empty sample
+    return S, K
+
+
+def _bar(shape, r, dt):
+    """A vertical bar whose pixels fire together, six times; noise on a lattice of step r + 1 at least r + 1 away from the
+    bar, every noise pixel firing once: the keep mask is the bar mask by construction."""
+    H, W = shape
+    bx, ys = W // 2, np.arange(H // 4, 3 * H // 4)
+    xs, yy, tt, bar = [], [], [], []
+    for k in range(6):
+        xs += [bx] * len(ys)
+        yy += ys.tolist()
+        tt += [1000 + 3 * dt * k] * len(ys)
+        bar += [1] * len(ys)
+    gx, gy = np.meshgrid(np.arange(0, W, r + 1), np.arange(0, H, r + 1))
+    gx, gy = gx.reshape(-1), gy.reshape(-1)
+    far = (np.abs(gx - bx) >= r + 1) & (np.abs(gx - bx) <= 60)                   # (a strip: the large sensors stay small cases)
+    gx, gy = gx[far], gy[far]
+    xs += gx.tolist()
+    yy += gy.tolist()
+    tt += (1000 + (np.arange(len(gx)) * 7) % (18 * dt)).tolist()
+    bar += [0] * len(gx)
+    order = np.random.default_rng(11).permutation(len(xs))
+    ev = rows(np.array(xs)[order], np.array(yy)[order], np.array(tt)[order])
+    return ev, np.array(bar)[order]
+
+
+def _row_pairs(shape, r, dist):
+    """For EVERY row boundary y | y + 1: one pair across it at Chebyshev distance `dist` (<= r), `dt` apart exactly, the
+    pairs 1000 ticks apart from each other; whichever band cut a kernel makes, a pair straddles it.  The later one of a
+    pair is kept, the earlier removed; which of the two rows holds the later one alternates."""
+    H, W = shape
+    xs, ys, tt, keep = [], [], [], []
+    for y in range(H - 1):
+        ya = min(max(y - (dist - 1) // 2, 0), H - 1 - dist)
+        yb = ya + dist
+        assert ya <= y < yb < H
+        xa = (7 * y) % W
+        xb = min(W - 1, xa + dist) if y % 3 else max(0, xa - dist)
+        first, second = ((xa, ya), (xb, yb)) if y % 2 else ((xb, yb), (xa, ya))
+        xs += [first[0], second[0]]
+        ys += [first[1], second[1]]
+        tt += [1000 * (y + 1), 1000 * (y + 1) + 100]
+        keep += [0, 1]
+    return rows(xs, ys, tt), np.array(keep)
+
+
+@functools.lru_cache(None)
+def cases():
+    """name -> dict(events float32 [n, 4], ranges, shape, dt_us, radius, random, packable, expect).  `expect`: the keep
+    bytes of every row inside a range, known by construction (None where only the restatements say)."""
+    C = {}
+    small = (37, 53)
+    # random streams (synthetic.make_events, at most 20 000 events a sample): 10 % .. 90 % kept, asserted by the CPU test
+    for name, shape, n, max_t, r, dt in (('rand_small_r1', small, 3000, 0.05, 1, 2000), ('rand_small_r2', small, 3000, 0.05, 2, 500),
+                                         ('rand_small_r3', small, 3000, 0.05, 3, 500), ('rand_100_r1', (100, 120), 8000, 0.05, 1, 5000),
+                                         ('rand_180_r2', (180, 240), 20000, 0.05, 2, 2500), ('rand_480_r1', (480, 640), 20000, 0.05, 1, 50000),
+                                         ('rand_480_r3', (480, 640), 20000, 0.05, 3, 12000)):
+        C[name] = _case([synthetic.make_events(n, shape, seed=2, max_t=max_t)], shape, dt, r, random=True)
+    three = [synthetic.make_events(n, (180, 240), seed=5 + i, max_t=0.05) for i, n in enumerate((9000, 15000, 4000))]
+    C['rand_180_r1_three'] = _case(three, (180, 240), 10000, 1, random=True)
+    shuffled = synthetic.make_events(6000, (100, 120), seed=9, max_t=0.05, p_zero_frac=0.1)
+    C['rand_100_unsorted'] = _case([shuffled[np.random.default_rng(3).permutation(len(shuffled))]], (100, 120), 8000, 1, random=True)
+    # directed
+    for shape, r in ((small, 1), (small, 2), (small, 3), ((100, 120), 1), ((180, 240), 2), ((480, 640), 3)):
+        S, K = _directed(shape, r, 100)
+        C[f'directed_{shape[0]}_r{r}'] = _case(S, shape, 100, r, expect=np.concatenate([np.array(k, np.int64) for k in K]))
+    C['dt0'] = _case([rows([5, 6, 9, 10, 20], [5, 5, 5, 5, 5], [300, 300, 300, 301, 300])], small, 0, 1, expect=np.array([1, 1, 0, 0, 0]))
+    C['extremes'] = _case([rows([5, 6, 30, 31], [5, 5, 5, 5], [0, 5, 5, 1])], small, TICK_MAX, 1,
+                          expect=np.array([0, 1, 1, 0]))
+    C['extremes']['events'][1:3, 2] = 2000.                                     # float seconds past the clip: tick 2^30 - 1
+    rng = np.random.default_rng(21)
+    hot_t = np.sort(rng.integers(0, 50000, 2000))
+    side_t = np.array([40, 10000, 20000, 30000, 49990])
+    hot = rows([10] * 2000 + [11] * 5, [10] * 2005, np.concatenate([hot_t, side_t]))
+    C['hot'] = _case([hot[rng.permutation(2005)]], small, 200, 1)               # 2000 events on one pixel, 5 beside it
+    for shape, r in ((small, 1), ((100, 120), 2), ((180, 240), 3), ((480, 640), 2)):
+        ev, bar = _bar(shape, r, 50)
+        C[f'bar_{shape[0]}_r{r}'] = _case([ev], shape, 50, r, expect=bar)
+    for shape in SHAPES:
+        for r, dist in ((1, 1), (3, 3)):
+            ev, keep = _row_pairs(shape, r, dist)
+            C[f'rows_{shape[0]}_r{r}'] = _case([ev], shape, 100, r, expect=keep)
+    pool = synthetic.make_events(9000, small, seed=4, max_t=0.1)
+    lens, at, S = (0, 1, 2, 63, 64, 65, 1023, 1024, 1025, 4097), 0, []
+    for n in lens:
+        S.append(pool[at:at + n])
+        at += n
+    C['lengths'] = _case(S, small, 1500, 1)
+    many = synthetic.make_events(600 * 40, small, seed=6, max_t=0.02 * 600)
+    C['many'] = _case([many[40 * i:40 * i + 40] for i in range(600)], small, 20000, 3)      # 600 samples in one launch
+    g = synthetic.make_events(3000, small, seed=8, max_t=0.05)
+    C['gapped'] = _case([g[:900], g[900:2300], g[2300:2301], g[2301:]], small, 2000, 1, gaps=(5, 0, 130, 1))
+    sk = synthetic.make_events(2500, small, seed=10, max_t=0.05, p_zero_frac=0.15)
+    out_of = np.random.default_rng(5).random(2500)
+    sk[out_of < 0.05, 0] = small[1]                                              # x == W, and y == H + 3: outside the sensor
+    sk[out_of > 0.96, 1] = small[0] + 3
+    C['skip'] = _case([sk], small, 2500, 1)
+    fr = synthetic.make_events(2000, small, seed=12, max_t=0.05)
+    fr[:, 0] += np.float32(0.7) * (np.arange(2000) % 3 == 0)                     # truncating casts: 3.7 -> 3
+    fr[::17, 0] = -0.5                                                           # -> 0: inside
+    fr[::19, 1] = -1.0                                                           # outside
+    fr[::23, 3] = 0.4                                                            # p -> 0: not counted
+    C['frac'] = _case([fr], small, 2500, 1, packable=False)
+    return C
+
+
+def max_sample_events(c):
+    return max([e - b for b, e in c['ranges']] + [1])
+
+
+def packed(c):
+    """the case's events as packed uint64 (vis.pack_events: the same ticks by the same rule)"""
+    return vis.pack_events(c['events'])
+
+
+def expected_keep(c):
+    """`expect` laid out like the keep output: GUARD outside every range"""
+    keep = np.full(len(c['events']), GUARD, np.uint8)
+    at = 0
+    for b, e in c['ranges']:
+        keep[b:e] = c['expect'][at:at + e - b]
+        at += e - b
+    assert at == len(c['expect'])
+    return keep

@@ -1,0 +1,312 @@
+"""The background-activity filter (csrc/events.hip: denoise_kernel) and the layers above it on the MI355X, against the
+restatement of the definition in tests/denoise_ref.py: every case of its table, float rows and packed events; the
+survivors, counts, keep bytes and stats exactly, with guard bytes wherever the call may not write."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import denoise_ref as dn
+
+pytestmark = pytest.mark.gpu
+
+GUARD = dn.GUARD
+TAIL = 64              # guard rows behind the last event, and one guard sample behind the last
+
+
+@functools.lru_cache(None)
+def want(name, packed=False):
+    """The oracle's answer, computed once and shared."""
+    c = dn.cases()[name]
+    return dn.oracle(dn.packed(c) if packed else c['events'], c['ranges'], c['shape'], c['dt_us'], c['radius'])
+
+
+def launch(events, ranges, shape, dt_us, radius, outputs=('keep', 'stats'), cap=None):
+    """Straight to the C ABI on numpy events (float32 [n, 4] or uint64 [n]); every output prefilled with GUARD, TAIL rows
+    and one sample longer than the launch may write.  -> dict(events_out, counts, keep, stats) as numpy (None where not
+    asked for), shaped like the oracle's."""
+    import torch
+    from eventclip_amd import _lib, vis
+    packed = vis.is_packed(events)
+    n, B = len(events), len(ranges)
+    ev = torch.from_numpy(events.view(np.int64) if packed else events).cuda()
+    rng = torch.tensor(ranges, dtype=torch.int64).reshape(-1, 2).cuda()
+    fill = int(np.frombuffer(bytes([GUARD]) * 8, np.int64)[0])
+    out = torch.full((n + TAIL,), fill, dtype=torch.int64, device='cuda') if packed else \
+        torch.full(((n + TAIL) * 16,), GUARD, dtype=torch.uint8, device='cuda').view(torch.float32).view(-1, 4)
+    counts = torch.full((B + 1,), fill, dtype=torch.int64, device='cuda')
+    keep = torch.full((n + TAIL,), GUARD, dtype=torch.uint8, device='cuda') if 'keep' in outputs else None
+    stats = torch.full((B + 1, ctypes.sizeof(vis.EcDenoiseStats)), GUARD, dtype=torch.uint8, device='cuda') if 'stats' in outputs else None
+    longest = max([e - b for b, e in ranges] + [1])
+    prm = vis.denoise_params(shape, dt_us, radius, cap or longest, sum(e - b for b, e in ranges))
+    ws = torch.empty((max(256, vis.denoise_workspace_bytes(prm, B)),), dtype=torch.uint8, device='cuda')
+    _lib.launch('ec_denoise_events_packed' if packed else 'ec_denoise_events', ev, rng, B, prm, out, counts, keep, stats,
+                ws, ws.numel())
+    torch.cuda.synchronize()
+    assert (out.reshape(-1).view(torch.uint8)[n * (8 if packed else 16):] == GUARD).all(), 'events_out written past the last event'
+    assert counts[B] == fill, 'counts written past the last sample'
+    assert keep is None or (keep[n:] == GUARD).all(), 'keep written past the last event'
+    assert stats is None or (stats[B] == GUARD).all(), 'stats written past the last sample'
+    return dict(events_out=out[:n].cpu().numpy().view(np.uint64 if packed else np.float32), counts=counts[:B].cpu().numpy(),
+                keep=None if keep is None else keep[:n].cpu().numpy(),
+                stats=None if stats is None else stats[:B].cpu().numpy().view(dn.STATS_DTYPE).reshape(B))
+
+
+def run(name, packed=False, outputs=('keep', 'stats')):
+    c = dn.cases()[name]
+    return launch(dn.packed(c) if packed else c['events'], c['ranges'], c['shape'], c['dt_us'], c['radius'], outputs)
+
+
+def test_band_counts(hip):
+    """one band (the two small sensors), two (180 x 240) and ten / eleven with a partial last band (480 x 640)"""
+    from eventclip_amd import vis
+    lib = vis.denoise_lib()
+    assert [lib.ec_denoise_bands(H, W, r) for (H, W), r in (((37, 53), 3), ((100, 120), 1), ((180, 240), 2), ((480, 640), 1),
+                                                           ((480, 640), 3))] == [1, 1, 2, 10, 11]
+    assert 480 % -(-480 // 11) != 0
+
+
+@pytest.mark.parametrize('name', sorted(dn.cases()))
+def test_every_case_float_and_packed(name, hip):
+    """Random streams at the four shapes and r = 1, 2, 3; the directed properties (lone, equal ticks, dt and dt + 1,
+    repeats, distance r and r + 1, corners, edges, the wrapped index, uncounted rows), dt = 0, the tick range's ends, a hot
+    pixel, the bar, a pair across every row boundary, sample lengths around the wave, the tile and the unroll, 600
+    samples, gapped ranges, skipped rows, truncating coordinates."""
+    c = dn.cases()[name]
+    for packed in ((False, True) if c['packable'] else (False,)):
+        got = run(name, packed)
+        dn.check(got, want(name, packed))
+        if c['expect'] is not None:
+            np.testing.assert_array_equal(got['keep'], dn.expected_keep(c))
+
+
+@pytest.mark.parametrize('name', ['rand_small_r3', 'rand_180_r2', 'rand_480_r3', 'lengths', 'many', 'gapped', 'skip'])
+def test_each_optional_output_alone(name, hip):
+    for outputs in ((), ('keep',), ('stats',)):
+        dn.check(run(name, False, outputs), want(name))
+        dn.check(run(name, True, outputs), want(name, True))
+
+
+@pytest.mark.parametrize('name', ['rand_small_r2', 'rand_180_r1_three', 'rand_480_r1', 'hot', 'skip', 'bar_180_r3', 'lengths'])
+def test_input_the_caller_shuffles_gives_the_same_keep_set(name, hip):
+    c = dn.cases()[name]
+    perm = np.arange(len(c['events']))
+    rng = np.random.default_rng(7)
+    for b, e in c['ranges']:
+        perm[b:e] = b + rng.permutation(e - b)
+    for packed in (False, True):
+        ev = (dn.packed(c) if packed else c['events'])[perm]
+        got = launch(ev, c['ranges'], c['shape'], c['dt_us'], c['radius'])
+        w = want(name, packed)
+        np.testing.assert_array_equal(got['keep'], w['keep'][perm])
+        np.testing.assert_array_equal(got['counts'], w['counts'])
+        np.testing.assert_array_equal(got['stats'], w['stats'])
+        dn.check(got, dn.oracle(ev, c['ranges'], c['shape'], c['dt_us'], c['radius']))
+
+
+def test_a_sample_longer_than_the_bound_is_not_filtered_and_nothing_else_is_touched(hip):
+    """max_sample_events sizes the workspace: a longer sample gets counts -1 and zero stats, stays unwritten, and the
+    samples beside it are filtered as ever."""
+    c = dn.cases()['gapped']                                             # lengths 900, 1400, 1, 699
+    got = launch(c['events'], c['ranges'], c['shape'], c['dt_us'], c['radius'], cap=900)
+    w = {k: v.copy() for k, v in want('gapped').items()}
+    b, e = c['ranges'][1]
+    w['counts'][1], w['stats'][1] = -1, (0, 0, 0)
+    w['keep'][b:e] = GUARD
+    w['events_out'][b:e].reshape(-1).view(np.uint8)[:] = GUARD
+    dn.check(got, w)
+
+
+def test_b_zero_and_the_refusals_write_nothing(hip):
+    import torch
+    from eventclip_amd import _lib, vis
+    lib = vis.denoise_lib()
+    ev = torch.zeros((64, 4), dtype=torch.float32, device='cuda')
+    rng = torch.tensor([[0, 64]], dtype=torch.int64, device='cuda')
+    out = torch.full((64 * 16,), GUARD, dtype=torch.uint8, device='cuda')
+    counts = torch.full((8,), GUARD, dtype=torch.uint8, device='cuda')
+    keep = torch.full((64,), GUARD, dtype=torch.uint8, device='cuda')
+    stats = torch.full((12,), GUARD, dtype=torch.uint8, device='cuda')
+    ws = torch.full((4096,), GUARD, dtype=torch.uint8, device='cuda')
+
+    def call(B, p, o=out, ws_bytes=4096, e=ev):
+        return lib.ec_denoise_events(e.data_ptr(), rng.data_ptr(), B, ctypes.byref(p), o.data_ptr(), counts.data_ptr(), keep.data_ptr(),
+                                     stats.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr())
+
+    prm = vis.denoise_params((8, 8), 100, 1, 64)
+    assert call(0, prm) == _lib.EC_OK
+    bad_r, bad_dt, bad_cap = (vis.denoise_params((8, 8), 100, 1, 64) for _ in range(3))
+    bad_r.radius, bad_dt.dt_us, bad_cap.max_sample_events = 4, 2 ** 30, 0
+    assert call(1, bad_r) == _lib.EC_ERR_INVALID and b'radius=4' in lib.ec_last_error()
+    assert call(1, bad_dt) == _lib.EC_ERR_INVALID and b'dt_us=' in lib.ec_last_error()
+    assert call(1, bad_cap) == _lib.EC_ERR_INVALID and b'max_sample_events=0' in lib.ec_last_error()
+    assert call(1, prm, o=ev) == _lib.EC_ERR_INVALID and b'in-place' in lib.ec_last_error()
+    assert call(1, prm, e=ev.view(-1)[1:]) == _lib.EC_ERR_INVALID and b'16-byte aligned' in lib.ec_last_error()
+    assert call(1, prm, ws_bytes=319) == _lib.EC_ERR_WORKSPACE and b'workspace 319 < 320 bytes' in lib.ec_last_error()
+    torch.cuda.synchronize()
+    for t in (out, counts, keep, stats, ws):
+        assert (t == GUARD).all()
+    assert call(1, prm) == _lib.EC_OK
+    torch.cuda.synchronize()
+    assert counts.view(torch.int64)[0] == 64 and (keep == 1).all() and (out == 0).all()        # p == 0: every row passes
+    assert stats.view(torch.int32).tolist() == [0, 0, 64]
+
+
+def test_the_op_against_the_c_abi_under_fake_tensors_and_opcheck(hip):
+    import torch
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    from eventclip_amd import torch_ops, vis  # noqa: F401
+    with FakeTensorMode():
+        sr = torch.zeros(5, 2, dtype=torch.int64, device='cuda')
+        for ev in (torch.empty(1000, 4, device='cuda'), torch.empty(1000, dtype=torch.int64, device='cuda')):
+            out, counts = torch.ops.eventclip_hip.events_denoise(ev, sr, 181, 240, 5000, 2)
+            assert out.shape == ev.shape and out.dtype == ev.dtype and counts.shape == (5,) and counts.dtype == torch.int64
+    for name in ('gapped', 'rand_180_r1_three', 'lengths'):
+        c = dn.cases()[name]
+        rng = torch.tensor(c['ranges'], dtype=torch.int64).cuda()
+        for packed in (False, True):
+            events = torch.from_numpy(dn.packed(c).view(np.int64) if packed else c['events']).cuda()
+            w = want(name, packed)
+            out, counts = torch.ops.eventclip_hip.events_denoise(events, rng, *c['shape'], c['dt_us'], c['radius'])
+            np.testing.assert_array_equal(counts.cpu().numpy(), w['counts'])
+            o = out.cpu().numpy().view(w['events_out'].dtype)
+            written = np.zeros(len(o), bool)
+            for (b, e), n in zip(c['ranges'], w['counts']):
+                np.testing.assert_array_equal(o[b:b + n].view(np.uint8), w['events_out'][b:b + n].view(np.uint8))
+                written[b:b + n] = True
+            assert not o[~written].view(np.uint8).any()                  # the op's other rows are zero
+            # the same through the device entry, which goes to the C ABI itself when asked for the mask or the stats
+            out2, counts2, keep, stats = vis.denoise_events_device(events, rng.cpu(), c['shape'], c['dt_us'] / 1e6, c['radius'],
+                                                                   return_mask=True, return_stats=True)
+            out3, counts3 = vis.denoise_events_device(events, rng, c['shape'], c['dt_us'] / 1e6, c['radius'])
+            assert torch.equal(counts2, counts) and torch.equal(counts3, counts) and torch.equal(out3, out)
+            inside = w['keep'] != GUARD
+            np.testing.assert_array_equal(keep.cpu().numpy()[inside], w['keep'][inside])
+            assert not keep.cpu().numpy()[~inside].any()
+            np.testing.assert_array_equal(stats, w['stats'])
+            for (b, e), n in zip(c['ranges'], w['counts']):
+                assert torch.equal(out2[b:b + n], out[b:b + n])
+    c = dn.cases()['rand_small_r1']
+    rng = torch.tensor(c['ranges'], dtype=torch.int64).cuda()
+    for events in (torch.from_numpy(c['events']).cuda(), torch.from_numpy(dn.packed(c).view(np.int64)).cuda()):
+        torch.library.opcheck(torch.ops.eventclip_hip.events_denoise.default, (events, rng, 37, 53, c['dt_us'], c['radius']))
+
+
+def _survivors(c, packed=False):
+    w = want_of(c, packed)
+    ev = dn.packed(c) if packed else c['events']
+    return [ev[b:e][w['keep'][b:e] == 1] for b, e in c['ranges']]
+
+
+def want_of(c, packed=False):
+    return dn.oracle(dn.packed(c) if packed else c['events'], c['ranges'], c['shape'], c['dt_us'], c['radius'])
+
+
+def test_numpy_drop_ins_against_the_oracle_and_the_frame_oracles(hip):
+    """vis.denoise_events, and events2frames(denoise=...) = the oracle's survivors through the existing frame oracles."""
+    import time_surface_ref as ts
+    import voxel_grid_ref as vg
+    from eventclip_amd import vis
+    from oracle import events as oe
+    for name in ('rand_small_r2', 'rand_100_r1', 'frac', 'skip'):
+        c = dn.cases()[name]
+        surv = _survivors(c)[0]
+        got = vis.denoise_events(c['events'], c['shape'], c['dt_us'] / 1e6, c['radius'])
+        assert got.dtype == np.float32 and got.tobytes() == surv.tobytes()
+        if c['packable']:
+            got = vis.denoise_events(dn.packed(c), c['shape'], c['dt_us'] / 1e6, c['radius'])
+            assert got.dtype == np.uint64 and got.tobytes() == _survivors(c, True)[0].tobytes()
+    d = dict(zip('xytp', dn.cases()['rand_small_r2']['events'].T))
+    assert vis.denoise_events(d, (37, 53), 500e-6, 2).tobytes() == _survivors(dn.cases()['rand_small_r2'])[0].tobytes()
+    assert vis.denoise_events(np.zeros((0, 4), np.float32), (37, 53), 1e-3).shape == (0, 4)
+    for name, N in (('rand_small_r1', 400), ('rand_100_r1', 1000)):
+        c = dn.cases()[name]
+        surv = _survivors(c)[0]
+        dz = dict(dt=c['dt_us'] / 1e6, radius=c['radius'])
+        i0, i1 = vis.chunk_bounds(len(surv), N)
+        assert len(i0) >= 3 and len(vis.chunk_bounds(len(c['events']), N)[0]) > len(i0)        # the filter moves every boundary
+        ranges = list(zip(i0, i1))
+        np.testing.assert_array_equal(vis.events2frames(c['events'], 'event_count', 'event_histogram', shape=c['shape'], N=N, denoise=dz),
+                                      oe.events2frames(surv, 'event_count', 'event_histogram', shape=c['shape'], N=N))
+        np.testing.assert_array_equal(vis.events2frames(c['events'], 'event_count', 'time_surface', shape=c['shape'], N=N, denoise=dz),
+                                      ts.oracle(surv, ranges, c['shape'])['frames'])
+        np.testing.assert_array_equal(vis.events2frames(c['events'], 'event_count', 'voxel_grid', shape=c['shape'], N=N, denoise=dz),
+                                      vg.oracle(surv, ranges, c['shape'], 3)['frames'])
+        np.testing.assert_array_equal(vis.events2frames(c['events'], 'event_count', 'event_histogram', shape=c['shape'], N=N, denoise=None),
+                                      vis.events2frames(c['events'], 'event_count', 'event_histogram', shape=c['shape'], N=N))
+
+
+QA = dict(max_imgs=6, N=300, split_method='event_count', grayscale=False, count_non_zero=False, background_mask=True)
+DZ = dict(dt=0.002, radius=1)
+
+
+def _samples(shape=(36, 52)):
+    from eventclip_amd import synthetic
+    return [synthetic.make_events(n, shape, seed=20 + i, max_t=0.05, hot_pixels=2) for i, n in enumerate((3000, 1200, 2000))]
+
+
+@pytest.mark.parametrize('method', ['event_histogram', 'time_surface', 'voxel_grid'])
+def test_pipeline_with_denoise_is_the_unfiltered_pipeline_on_the_oracles_survivors(method, hip):
+    import torch
+    from eventclip_amd import vis
+    from eventclip_amd.event2img import Event2ImagePipeline
+    shape = (36, 52)
+    samples = _samples()
+    plain = Event2ImagePipeline(shape, 3000, dict(QA, convert_method=method), n_px=32)
+    pipe = Event2ImagePipeline(shape, 3000, dict(QA, convert_method=method, denoise=DZ), n_px=32)
+    surv = []
+    for s in samples:
+        w = dn.oracle(s, [(0, len(s))], shape, 2000, 1)
+        surv.append(s[w['keep'] == 1])
+        assert 0.05 < len(surv[-1]) / len(s) < 0.9 and len(vis.chunk_bounds(len(surv[-1]), 300)[0]) <= 6
+    got, ref = pipe(samples), plain(surv)
+    assert got['n_events'] == [len(s) for s in surv] and 'n_events' not in ref
+    for k in ('img', 'valid_mask', 'row_idx'):
+        assert torch.equal(got[k], ref[k]), k
+    assert got['valid_mask'].sum() == sum(len(vis.chunk_bounds(len(s), 300)[0]) for s in surv)
+    # the four views come from ONE filtering: the views of the survivors, not the survivors of the views
+    views, ref_views = pipe.tta(samples), plain.tta(surv)
+    for v, r in zip(views, ref_views):
+        assert torch.equal(v['img'], r['img']) and v['n_events'] == got['n_events']
+    assert torch.equal(pipe(samples, hflip=True, tflip=True)['img'], ref_views[3]['img'])
+    # packed events, centring first, and a caller's own starts
+    packed = [vis.pack_events(s) for s in samples]
+    assert torch.equal(pipe(packed)['img'], got['img'])
+    c_got, c_plain = pipe(samples, center=True), plain(samples, center=True)
+    from oracle import event_utils as eu
+    centred = [eu.center_events(s.copy(), shape) for s in samples]              # (the oracle centres in place)
+    c_surv = [s[dn.oracle(s, [(0, len(s))], shape, 2000, 1)['keep'] == 1] for s in centred]
+    assert torch.equal(c_got['img'], plain(c_surv)['img']) and c_got['n_events'] == [len(s) for s in c_surv]
+    assert not torch.equal(c_got['img'], c_plain['img'])
+    gap = np.zeros((17, 4), np.float32)
+    cat = torch.from_numpy(np.concatenate([gap, samples[0], gap, gap, samples[1], samples[2], gap])).cuda()
+    starts = [17, 17 + len(samples[0]) + 34, 17 + len(samples[0]) + 34 + len(samples[1])]
+    g2 = pipe(cat, [len(s) for s in samples], starts=starts)
+    assert torch.equal(g2['img'], got['img']) and g2['n_events'] == got['n_events']
+
+
+def test_pipeline_refusals_and_the_untouched_paths(hip):
+    import torch
+    from eventclip_amd.event2img import Event2ImagePipeline
+    shape = (36, 52)
+    samples = _samples()
+    qa = dict(QA, convert_method='event_histogram', max_imgs=10)         # every chunk a view: no random subset
+    # a quantize_args without the key, or with None: bytes identical to today's, and no new key in the result
+    a, b = Event2ImagePipeline(shape, 3000, qa, n_px=32)(samples), Event2ImagePipeline(shape, 3000, dict(qa, denoise=None), n_px=32)(samples)
+    assert set(a) == set(b) == {'valid_mask', 'row_idx', 'img'} and all(torch.equal(a[k], b[k]) for k in a)
+    pipe = Event2ImagePipeline(shape, 3000, dict(qa, denoise=DZ), n_px=32)
+    # a sample the filter empties: one event per pixel on a lattice no neighbour reaches
+    ys, xs = np.meshgrid(np.arange(0, 36, 2), np.arange(0, 52, 2), indexing='ij')
+    lonely = dn.rows(xs.reshape(-1), ys.reshape(-1), np.arange(xs.size) * 10)
+    with pytest.raises(ValueError, match=r'samples \[1, 3\].*dt=0.002'):
+        pipe([samples[0], lonely, samples[1], lonely[:5]])
+    with pytest.raises(ValueError, match=r'samples \[1\].*dt=0.002'):
+        pipe.tta([samples[0], lonely])
+    # a sample longer than max_n
+    short = Event2ImagePipeline(shape, 1500, dict(qa, denoise=DZ), n_px=32)
+    with pytest.raises(ValueError, match=r'samples \[0, 2\] hold more than max_n=1500'):
+        short(samples)
+    assert Event2ImagePipeline(shape, 1500, qa, n_px=32)(samples)['img'].shape[0] == 3          # ... only with the filter
+    with pytest.raises(IndexError):                                      # an empty sample stays what it was
+        pipe([samples[0], np.zeros((0, 4), np.float32)])
