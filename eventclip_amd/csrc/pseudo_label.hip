@@ -9,7 +9,9 @@
 //   * the view-mean distribution (:148) gives the label and its confidence (:155), which must
 //     exceed conf_thresh (:156-158).
 // One workgroup per sample; the V x K probabilities are read once (HBM-bound, 4 B per class-view).
-// Ties resolve to the lowest class index like torch.argmax / torch.max.
+// Ties resolve to the lowest class index like torch.argmax / torch.max, and like them a NaN is the maximum: a row that
+// holds one (the classifier's 0 / 0 for a sample without a valid view is a row of nothing else) has max_prob NaN, the
+// first NaN's index as its label, and is never selected (NaN > conf_thresh is false).
 #include "common.h"
 
 namespace {
@@ -24,8 +26,10 @@ struct Best {
 
 __device__ __forceinline__ Best better(Best a, Best b)
 {
-    // NaN never wins; equal values keep the lower index
-    if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
+    // NaN wins over every number, as in torch.max; equal values, two NaNs among them, keep the lower index
+    const bool an = a.v != a.v, bn = b.v != b.v;
+    if (an != bn) return bn ? b : a;
+    if (b.v > a.v || ((bn || b.v == a.v) && b.i < a.i)) return b;
     return a;
 }
 

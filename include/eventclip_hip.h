@@ -710,7 +710,9 @@ EC_API int ec_adapter_forward(const ec_adapter_weights *w, const float *feats,
  * test-time augmentation, event2img.py:94-112; V = 1 without).  Outputs per sample: the view-mean
  * distribution (optional, [B, K]), its argmax and maximum, and selected = 1 when
  * max > conf_thresh, and (tta_consistent) every view predicts the same class, and (tta_min_prob)
- * the smallest per-view top probability > conf_thresh. */
+ * the smallest per-view top probability > conf_thresh.  Ties go to the lowest class index and a NaN is
+ * the maximum, as in torch.max: a sample whose view-mean holds a NaN gets max_prob = NaN, pred = the
+ * first NaN's index, selected = 0. */
 EC_API int ec_pseudo_label(const float *probs, int B, int V, int K, float conf_thresh,
                            int tta_consistent, int tta_min_prob, float *mean_probs, int32_t *pred,
                            float *max_prob, uint8_t *selected, ec_stream_t stream);
