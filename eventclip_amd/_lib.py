@@ -47,8 +47,9 @@ _DECLARATION = re.compile(r'(EC_DEVICE\s+)?(?:const\s+)?(\w+)\b\s*(.*)', re.S)  
 _DECLARATOR = re.compile(r'(\*?)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?')               # [*] name [[literal]]
 
 
-def read_header(text):
-    """The header's text -> (abi_version, {EC_*: int}, {'EcName': Structure subclass}, {'ec_name': (restype, argtypes)}).
+def read_header(text, filename='eventclip_hip.h'):
+    """The header's text -> (abi_version, {EC_*: int}, {'EcName': Structure subclass}, {'ec_name': (restype, argtypes)});
+    ``filename`` is the name its errors go under.
 
     Pointers: ``char *`` is ``c_char_p``; a pointer to a header struct is ``POINTER(thatStruct)`` unless the parameter
     is marked EC_DEVICE (an array in device memory: the caller passes its address); every other pointer, and an array
@@ -57,7 +58,7 @@ def read_header(text):
         return ' ' + '\n' * m.group().count('\n')
 
     def fail(pos, why):
-        raise HeaderError(f'eventclip_hip.h:{text.count(chr(10), 0, pos) + 1}: {why}')
+        raise HeaderError(f'{filename}:{text.count(chr(10), 0, pos) + 1}: {why}')
 
     def parts(m, group, sep):
         """The sep-separated parts of a match's group, stripped, each with its position in the text."""
@@ -160,10 +161,32 @@ def activation_code(name):
 
 
 _lib = None
+_bound = {}                 # side header's file name -> what bind_header read from it
 
 
 class HipLibraryError(RuntimeError):
     pass
+
+
+def _set_types(handle, signatures):
+    for name, (res, args) in signatures.items():
+        fn = getattr(handle, name)
+        fn.restype = res
+        fn.argtypes = args
+
+
+def bind_header(filename):
+    """A side header, include/``filename`` -> (constants, structs, signatures), read as the main header is; its
+    ``#include "eventclip_hip.h"`` stands for what the reader wants from that header, the version.  The entries it
+    declares are typed on the library's handle when ``lib()`` loads it, or here if it is loaded already: ``launch`` and
+    ``getattr(lib(), name)`` find them typed whoever asks first.  Binding a header again returns what the first time read."""
+    if filename not in _bound:
+        with open(os.path.join(os.path.dirname(HEADER), filename)) as f:
+            text = f.read().replace('#include "eventclip_hip.h"', f'#define EC_ABI_VERSION {ABI_VERSION}')
+        _bound[filename] = read_header(text, filename)[1:]
+        if _lib is not None:
+            _set_types(_lib, _bound[filename][2])
+    return _bound[filename]
 
 
 def lib():
@@ -182,10 +205,9 @@ def lib():
         if os.path.exists(bundled):
             ctypes.CDLL(bundled, mode=ctypes.RTLD_GLOBAL)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
+        _set_types(handle, SIGNATURES)
+        for _, _, signatures in _bound.values():
+            _set_types(handle, signatures)
         # the header this module read against the one the library was built from (include/eventclip_hip.h, EC_ABI_CHECK)
         rc = handle.ec_abi_check(ABI_VERSION, *(ctypes.sizeof(_structs[t]) for t in (
             'EcGemmArgs', 'EcBlockWeights', 'EcVitWeights', 'EcTextWeights', 'EcEventsParams', 'EcAdapterWeights')))

@@ -1670,15 +1670,43 @@ inline EvPlan events_plan(int H, int W, int max_frame_events, size_t ws_bytes, b
     return p;
 }
 
+// What every launch_* opens with, under the entry's name: params, the count (`letter`: F frames or B samples), nothing to do
+// for a count of 0, the buffers the entry cannot do without.  True: the entry returns rc at once (refused, or EC_OK for 0).
+inline bool launch_is_over(const char *name, const void *prm, char letter, int count, bool buffers, int &rc)
+{
+    rc = prm == nullptr ? ec::fail(EC_ERR_INVALID, "%s: params is null", name)
+         : count < 0    ? ec::fail(EC_ERR_INVALID, "%s: %c=%d", name, letter, count)
+         : count == 0 || buffers ? EC_OK : ec::fail(EC_ERR_INVALID, "%s: null buffer", name);
+    return rc != EC_OK || count == 0;
+}
+
+// algorithmic bytes of a launch: 16 B (packed: 8 B) per event in + 3*H*W out per frame.  The ranges live
+// on the device; the caller states their total length in prm->total_events (0 = unknown: only the output part is reported)
+template <typename EV>
+inline double event_bytes(int F, int H, int W, int64_t total_events)
+{
+    return (double)F * H * W * 3.0 + (double)(total_events > 0 ? total_events : 0) * sizeof(EV);
+}
+
+// One launch of a band-walking kernel (1024 threads, the full LDS as its limit) on `stream`, under the profiler's class
+template <typename ARGS>
+int launch_form(void (*kernel)(const ARGS), long grid, int lds, ec::ProfClass cls, double bytes, ec_stream_t stream, const ARGS &a)
+{
+    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), EV_LDS_TOTAL)) return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    ec::ProfScope prof(cls, hs, 0, bytes);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(EV_THREADS), lds, hs, a);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
 template <typename EV>
 int launch_events(const void *events, const int64_t *frame_range, int F, const ec_events_params *prm,
                   uint8_t *frames, int32_t *raw_counts, int32_t *kept_counts, ec_frame_stats *stats,
                   ec_stream_t stream)
 {
-    EC_REQUIRE(prm != nullptr, "ec_events_to_frames: params is null");
-    EC_REQUIRE(F >= 0, "ec_events_to_frames: F=%d", F);
-    if (F == 0) return EC_OK;
-    EC_REQUIRE(events && frame_range && frames, "ec_events_to_frames: null buffer");
+    int rc;
+    if (launch_is_over("ec_events_to_frames", prm, 'F', F, events && frame_range && frames, rc)) return rc;
     EC_REQUIRE(prm->H > 0 && prm->W > 0, "ec_events_to_frames: bad shape (%d,%d)", prm->H, prm->W);
     EC_REQUIRE(((uintptr_t)events & (sizeof(EV) - 1)) == 0,
                "ec_events_to_frames: events must be %d-byte aligned", (int)sizeof(EV));
@@ -1723,16 +1751,11 @@ int launch_events(const void *events, const int64_t *frame_range, int F, const e
     void (*const front)(const EvArgs) = plan.path == EvPlan::WHOLE10 ? events_pack10_kernel<EV>
                                         : plan.path == EvPlan::BAND10 ? events_band10_kernel<EV> : nullptr;
     // (the full LDS as every kernel's limit: one attribute call each)
-    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(events_to_frames_kernel<EV>), EV_LDS_TOTAL)) return rc;
+    if ((rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(events_to_frames_kernel<EV>), EV_LDS_TOTAL))) return rc;
     if (front)
-        if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(front), EV_LDS_TOTAL)) return rc;
+        if ((rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(front), EV_LDS_TOTAL))) return rc;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    // algorithmic bytes: 16 B (packed: 8 B) per event in + 3*H*W out.  The frame
-    // ranges live on the device; the caller states their total length in prm->total_events (0 =
-    // unknown: only the output part is reported then)
-    ec::ProfScope prof(ec::PROF_EVENTS, hs, 0,
-                       (double)F * prm->H * prm->W * 3.0 +
-                           (double)(prm->total_events > 0 ? prm->total_events : 0) * sizeof(EV));
+    ec::ProfScope prof(ec::PROF_EVENTS, hs, 0, event_bytes<EV>(F, prm->H, prm->W, prm->total_events));
     // per chunk of frames: the 10-bit kernel, if any, then the 32-bit kernel for the frames it flagged (none, for ordinary
     // data: its workgroups return at once).  Without a front kernel the one chunk is all F frames
     const long M = (long)prm->H * prm->W;
@@ -1756,41 +1779,15 @@ int launch_events(const void *events, const int64_t *frame_range, int F, const e
 }
 
 // ---------------------------------------------------------------------------------------------
-// events -> time-surface frames (include/eventclip_time_surface.h states the definition, steps 1 - 7).
-//
-// The surface of a row band lives in LDS as one 32-bit word per (pixel, polarity), filled with LDS atomic max: a counted
-// event stores tick + 1 -- with reverse_t, 2^30 - tick, so that the earliest tick is the largest word -- and 0 is
-// "untouched".  A maximum does not depend on the order of the events.  A sensor that does not fit is cut into row bands
-// (N-Caltech: 3, N-ImageNet: 16); there is no HBM intermediate, so every band scans all events of its frame, and the only
-// global writes are the frame and the two debug outputs.
-// One 1024-thread workgroup owns one (frame, band) at a time and walks items blockIdx.x, + gridDim.x, ...  It needs t0 / t1
-// over ALL events of the frame before it can colour a pixel, and has them for nothing: the one scan that fills its band
-// also takes the frame's tallies (t0, t1, dropped, counted), one block reduction behind it; band 0 writes the stats.  Per
-// (frame, band) rather than per frame with a loop over the bands: the work is the same scan per band either way, a small
-// batch of a large sensor spreads over bands x frames compute units, and the kernel has no second form of its scan.
-// One workgroup per compute unit: at ~100 VGPRs a second 1024-thread workgroup does not fit a CU's registers.
-// Measured (profiles/time_surface.md): an item costs 22 - 39 us whatever its event count, so the multi-band sensors fall
-// short of the histogram path by about their band count.  Bands of a frame kept on one XCD for its L2, and two register
-// buffers of events in flight, were both measured and moved it by 7 % at most: neither bandwidth nor load latency bounds it.
+// Shared by the band-walking kernels of the three sections below (time surface, voxel grid, denoise) and their host sides:
+// the scan of a range's events, the counted-event test, the frame's tallies, the band in LDS and its plan, the bytes out.
+// (What every launch_* opens with stands in front of launch_events, its first user.)  The histogram kernels above have
+// their own forms of these steps and are not touched.
 // ---------------------------------------------------------------------------------------------
 constexpr unsigned TS_TICK_MAX = (1u << 30) - 1;          // EC_PACKED_T's range
 constexpr unsigned TS_REVERSED = 1u << 30;                // reverse_t: the word of tick t is TS_REVERSED - t, in 1 .. 2^30
 
-struct TsArgs {
-    const void *events;      // float4 (x, y, t, p) or packed 8-byte events
-    const long long *range;  // [F,2]
-    int H, W, F;
-    int exp_decay, background_mask, flip_x, negate_p, reverse_t;
-    double tau_us;
-    double red[3], blue[3];
-    int same_as[3];          // channel k has the colours of channel same_as[k] < k (a gray map: 0, 0, 0), else k
-    uint8_t *frames;
-    int *last;               // optional [F,H,W,2]
-    ec_surface_stats *stats; // optional [F]
-    int rows_per_band, bands, band_bytes;
-};
-
-// step 2: the event's tick
+// the event's tick
 __device__ __forceinline__ unsigned tick_of(const float4 e)
 {
     double tu = __builtin_rint((double)e.z * 1e6);        // (pack_events_kernel's rule)
@@ -1799,11 +1796,59 @@ __device__ __forceinline__ unsigned tick_of(const float4 e)
 }
 __device__ __forceinline__ unsigned tick_of(const packed_t e) { return (unsigned)(e >> 34); }
 
+// the event with p == 0 unless `there`: a row that nothing counts (one select: of p, or of the packed event's upper half)
+__device__ __forceinline__ float4 only_if(bool there, float4 e) { e.w = there ? e.w : 0.f; return e; }
+__device__ __forceinline__ packed_t only_if(bool there, packed_t e)
+{
+    return (e & 0xffffffffull) | ((packed_t)(there ? (unsigned)(e >> 32) : 0u) << 32);
+}
+
+// f(event, row) for every row of [0, n): eight loads in flight per thread, row j always with thread j % EV_THREADS.  A slot
+// past the end re-reads the last event and hands it on with p == 0, without a branch around f: f sees a few rows >= n, none
+// of them counted.  (Measured against handing f a `there` flag instead, profiles/event_forms_refactor.jsonl: the flag was
+// about 1 % slower on float rows in the large sensors' time surfaces and voxel frames, 1 % faster on packed voxel grids.)
+template <typename EV, typename F>
+__device__ __forceinline__ void for_events(const EV *ev, long long n, F f)
+{
+    for (long long i = threadIdx.x; i < n; i += 8 * EV_THREADS) {
+        EV e[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const long long j = i + (long long)k * EV_THREADS;
+            e[k] = ev[j < n ? j : n - 1];
+        }
+        // (the loads stay whole and here: moved down into a branch of f as single dwords, the first one waited for all eight)
+        __asm__ volatile("" ::: "memory");
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const long long j = i + (long long)k * EV_THREADS;
+            f(only_if(j < n, e[k]), j);
+        }
+    }
+}
+
+// Is the event counted: p != 0 and inside the sensor?  x, y, p are parse()'s; an event that is not counted was dropped
+// (p != 0, outside) or is none at all (p == 0).
+template <typename EV>
+__device__ __forceinline__ bool counted_event(const EV e, int H, int W, int flip_x, int negate_p, int &x, int &y, int &p)
+{
+    parse(e, W, flip_x, negate_p, x, y, p);
+    return p != 0 && (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
+}
+
 // the frame's reduction: per-thread tallies in, the frame's values in every thread out
 struct TsTally {
     unsigned hi, lo;         // max of tick + 1, max of TS_REVERSED - tick over the counted events; 0 = none
     unsigned dropped, counted;
 };
+// one event (counted_event's answer and p, its tick) into a thread's tallies
+__device__ __forceinline__ void tally_event(TsTally &t, bool counted, int p, unsigned tick)
+{
+    t.dropped += !counted && p != 0;
+    t.counted += counted;
+    const unsigned hi = counted ? tick + 1u : 0u, lo = counted ? TS_REVERSED - tick : 0u;
+    t.hi = hi > t.hi ? hi : t.hi, t.lo = lo > t.lo ? lo : t.lo;
+}
 __device__ __forceinline__ TsTally block_tally(const TsTally t, unsigned long long *scratch)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1822,6 +1867,105 @@ __device__ __forceinline__ TsTally block_tally(const TsTally t, unsigned long lo
     }
     return r;
 }
+// the reduced tallies -> the first and the last tick of the frame's counted events (0, 0 without any)
+struct FrameSpan {
+    unsigned t0, t1;
+};
+__device__ __forceinline__ FrameSpan frame_span(const TsTally t)
+{
+    return t.counted ? FrameSpan{TS_REVERSED - t.lo, t.hi - 1u} : FrameSpan{0u, 0u};
+}
+
+// the band in LDS (band_bytes: a multiple of 16) to zero, visible to the workgroup
+__device__ __forceinline__ void zero_band(void *state, int band_bytes)
+{
+    for (int i = threadIdx.x; i < band_bytes / 16; i += EV_THREADS) reinterpret_cast<uint4 *>(state)[i] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+}
+
+// npix pixels of WPP state words each at src (the LDS band, or device memory) -> 3 npix bytes at o (a whole number of rows
+// into a 4-byte aligned frame); pixel(q, its WPP words, its three bytes) is the one pixel.  Where the rows are whole groups
+// of four pixels and src is 16-byte aligned, a thread takes four pixels: WPP 16-byte loads in, 12 bytes = three dwords out.
+template <int WPP, typename F>
+__device__ __forceinline__ void store_pixels(const unsigned *src, int npix, int W, uint8_t *o, F pixel)
+{
+    if ((W & 3) == 0 && ((uintptr_t)src & 15) == 0) {
+        for (int g = threadIdx.x; g < npix / 4; g += EV_THREADS) {
+            unsigned words[3], s[4 * WPP];
+            uint8_t *bytes = reinterpret_cast<uint8_t *>(words);
+#pragma unroll
+            for (int k = 0; k < WPP; k++) {
+                const uint4 c = *reinterpret_cast<const uint4 *>(&src[(g * WPP + k) * 4]);
+                s[4 * k] = c.x, s[4 * k + 1] = c.y, s[4 * k + 2] = c.z, s[4 * k + 3] = c.w;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) pixel(4 * g + k, s + WPP * k, bytes + 3 * k);
+            unsigned *dst = reinterpret_cast<unsigned *>(o + (long long)g * 12);
+            dst[0] = words[0];
+            dst[1] = words[1];
+            dst[2] = words[2];
+        }
+    } else {
+        for (int q = threadIdx.x; q < npix; q += EV_THREADS) {
+            unsigned s[WPP];
+            uint8_t px[3];
+#pragma unroll
+            for (int k = 0; k < WPP; k++) s[k] = src[WPP * q + k];
+            pixel(q, s, px);
+            o[3 * q] = px[0];
+            o[3 * q + 1] = px[1];
+            o[3 * q + 2] = px[2];
+        }
+    }
+}
+
+// Row bands of row_bytes per sensor row: as many rows as fit EV_BIN_BYTES, evened out over the bands, the band rounded up to
+// 16 bytes, the reduction scratch behind.  bands == 0: refused (no sensor, or a row wider than a band).
+struct RowBands {
+    int rows_per_band, bands, band_bytes, lds;
+};
+inline RowBands row_bands(int H, long row_bytes)
+{
+    RowBands p = {};
+    if (H <= 0 || row_bytes <= 0 || row_bytes > EV_BIN_BYTES) return p;
+    p.bands = ec::ceil_div(H, (int)std::min<long>(H, EV_BIN_BYTES / row_bytes));
+    p.rows_per_band = ec::ceil_div(H, p.bands);
+    p.band_bytes = (int)((p.rows_per_band * row_bytes + 15) / 16 * 16);
+    p.lds = p.band_bytes + EV_REDUCE_BYTES;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// events -> time-surface frames (include/eventclip_time_surface.h states the definition, steps 1 - 7).
+//
+// The surface of a row band lives in LDS as one 32-bit word per (pixel, polarity), filled with LDS atomic max: a counted
+// event stores tick + 1 -- with reverse_t, 2^30 - tick, so that the earliest tick is the largest word -- and 0 is
+// "untouched".  A maximum does not depend on the order of the events.  A sensor that does not fit is cut into row bands
+// (N-Caltech: 3, N-ImageNet: 16); there is no HBM intermediate, so every band scans all events of its frame, and the only
+// global writes are the frame and the two debug outputs.
+// One 1024-thread workgroup owns one (frame, band) at a time and walks items blockIdx.x, + gridDim.x, ...  It needs t0 / t1
+// over ALL events of the frame before it can colour a pixel, and has them for nothing: the one scan that fills its band
+// also takes the frame's tallies (t0, t1, dropped, counted), one block reduction behind it; band 0 writes the stats.  Per
+// (frame, band) rather than per frame with a loop over the bands: the work is the same scan per band either way, a small
+// batch of a large sensor spreads over bands x frames compute units, and the kernel has no second form of its scan.
+// One workgroup per compute unit: at ~100 VGPRs a second 1024-thread workgroup does not fit a CU's registers.
+// Measured (profiles/time_surface.md): an item costs 22 - 39 us whatever its event count, so the multi-band sensors fall
+// short of the histogram path by about their band count.  Bands of a frame kept on one XCD for its L2, and two register
+// buffers of events in flight, were both measured and moved it by 7 % at most: neither bandwidth nor load latency bounds it.
+// ---------------------------------------------------------------------------------------------
+struct TsArgs {
+    const void *events;      // float4 (x, y, t, p) or packed 8-byte events
+    const long long *range;  // [F,2]
+    int H, W, F;
+    int exp_decay, background_mask, flip_x, negate_p, reverse_t;
+    double tau_us;
+    double red[3], blue[3];
+    int same_as[3];          // channel k has the colours of channel same_as[k] < k (a gray map: 0, 0, 0), else k
+    uint8_t *frames;
+    int *last;               // optional [F,H,W,2]
+    ec_surface_stats *stats; // optional [F]
+    int rows_per_band, bands, band_bytes;
+};
 
 // steps 1 - 4 for the events of a frame and the rows [y0, y1): one LDS atomic per counted event of the band, and the
 // frame's tallies
@@ -1829,30 +1973,14 @@ template <typename EV>
 __device__ __forceinline__ void surface_band(const EV *ev, long long n, int y0, int y1, const TsArgs &a, unsigned *state,
                                              TsTally &t)
 {
-    const int H = a.H, W = a.W;
-    // eight loads in flight per thread (a slot past the end re-reads the last event and is masked)
-    for (long long i = threadIdx.x; i < n; i += 8 * EV_THREADS) {
-        EV e[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const long long j = i + (long long)k * EV_THREADS;
-            e[k] = ev[j < n ? j : n - 1];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            int x, y, p;
-            parse(e[k], W, a.flip_x, a.negate_p, x, y, p);
-            const bool there = i + (long long)k * EV_THREADS < n && p != 0;
-            const bool inside = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
-            const unsigned tick = tick_of(e[k]);
-            t.dropped += there && !inside;
-            t.counted += there && inside;
-            const unsigned hi = there && inside ? tick + 1u : 0u, lo = there && inside ? TS_REVERSED - tick : 0u;
-            t.hi = hi > t.hi ? hi : t.hi, t.lo = lo > t.lo ? lo : t.lo;
-            if (there && inside && y >= y0 && y < y1)
-                atomicMax(&state[((y - y0) * W + x) * 2 + (p < 0 ? 1 : 0)], a.reverse_t ? TS_REVERSED - tick : tick + 1u);
-        }
-    }
+    for_events(ev, n, [&](const EV e, long long) {
+        int x, y, p;
+        const bool counted = counted_event(e, a.H, a.W, a.flip_x, a.negate_p, x, y, p);
+        const unsigned tick = tick_of(e);
+        tally_event(t, counted, p, tick);
+        if (counted && y >= y0 && y < y1)
+            atomicMax(&state[((y - y0) * a.W + x) * 2 + (p < 0 ? 1 : 0)], a.reverse_t ? TS_REVERSED - tick : tick + 1u);
+    });
 }
 
 // steps 5 - 7 for one pixel: its two state words -> three bytes; l[] receives L (-1 = untouched)
@@ -1918,81 +2046,34 @@ __global__ __launch_bounds__(EV_THREADS) void time_surface_kernel(const TsArgs a
         const long long e0 = a.range[2 * f], n = a.range[2 * f + 1] - e0;
         const EV *ev = reinterpret_cast<const EV *>(a.events) + e0;
         uint8_t *out = a.frames + (long long)f * M * 3;
-        TsFrame fr = {0, 0, 0.};
         const int y0 = b * rpb, y1 = min(H, y0 + rpb);
-        const int npix = (y1 - y0) * W;
-        for (int i = threadIdx.x; i < a.band_bytes / 16; i += EV_THREADS) reinterpret_cast<uint4 *>(state)[i] = make_uint4(0, 0, 0, 0);
-        __syncthreads();
+        zero_band(state, a.band_bytes);
         TsTally t = {0, 0, 0, 0};
         surface_band(ev, n, y0, y1, a, state, t);
         t = block_tally(t, scratch);                                      // (its first barrier ends the band's atomics)
-        if (t.counted) fr.t0 = TS_REVERSED - t.lo, fr.t1 = t.hi - 1u;
-        fr.span = (double)(fr.t1 - fr.t0);
+        const FrameSpan sp = frame_span(t);
+        const TsFrame fr = {sp.t0, sp.t1, (double)(sp.t1 - sp.t0)};
         if (a.stats && b == 0 && threadIdx.x == 0) {
             ec_surface_stats st;
             st.dropped = t.dropped, st.counted = t.counted, st.t0 = fr.t0, st.t1 = fr.t1;
             a.stats[f] = st;
         }
-        uint8_t *o = out + (long long)y0 * W * 3;
         int *lo = a.last ? a.last + ((long long)f * M + (long long)y0 * W) * 2 : nullptr;
-        if ((W & 3) == 0) {
-            // 4 pixels = 12 bytes = three dwords per thread, 4-byte aligned
-            for (int g = threadIdx.x; g < npix / 4; g += EV_THREADS) {
-                unsigned words[3];
-                uint8_t *bytes = reinterpret_cast<uint8_t *>(words);
-                const uint4 ca = *reinterpret_cast<const uint4 *>(&state[g * 8]);
-                const uint4 cb = *reinterpret_cast<const uint4 *>(&state[g * 8 + 4]);
-                const unsigned s[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
-                int l[8];
-#pragma unroll
-                for (int k = 0; k < 4; k++) surface_pixel(s[2 * k], s[2 * k + 1], fr, a, bytes + 3 * k, l + 2 * k);
-                unsigned *dst = reinterpret_cast<unsigned *>(o + (long long)g * 12);
-                dst[0] = words[0];
-                dst[1] = words[1];
-                dst[2] = words[2];
-                if (lo) {
-#pragma unroll
-                    for (int k = 0; k < 8; k++) lo[(long long)g * 8 + k] = l[k];
-                }
-            }
-        } else {
-            for (int q = threadIdx.x; q < npix; q += EV_THREADS) {
-                uint8_t px[3];
-                int l[2];
-                surface_pixel(state[2 * q], state[2 * q + 1], fr, a, px, l);
-                o[3 * q] = px[0];
-                o[3 * q + 1] = px[1];
-                o[3 * q + 2] = px[2];
-                if (lo) lo[2 * q] = l[0], lo[2 * q + 1] = l[1];
-            }
-        }
+        store_pixels<2>(state, (y1 - y0) * W, W, out + (long long)y0 * W * 3, [&](int q, const unsigned *s, uint8_t *px) {
+            int l[2];
+            surface_pixel(s[0], s[1], fr, a, px, l);
+            if (lo) lo[2 * (long long)q] = l[0], lo[2 * (long long)q + 1] = l[1];
+        });
         __syncthreads();                                                  // the band is read: the next item may zero it
     }
-}
-
-// Row bands of 8 bytes per pixel: as many rows as fit EV_BIN_BYTES, evened out over the bands; the reduction scratch behind.
-struct TsPlan {
-    int rows_per_band, bands, band_bytes, lds;
-};
-inline TsPlan time_surface_plan(int H, int W)
-{
-    TsPlan p = {};
-    const long row_bytes = (long)W * 2 * 4;
-    p.bands = ec::ceil_div(H, (int)std::min<long>(H, EV_BIN_BYTES / row_bytes));
-    p.rows_per_band = ec::ceil_div(H, p.bands);
-    p.band_bytes = (int)((p.rows_per_band * row_bytes + 15) / 16 * 16);
-    p.lds = p.band_bytes + EV_REDUCE_BYTES;
-    return p;
 }
 
 template <typename EV>
 int launch_time_surface(const void *events, const int64_t *frame_range, int F, const ec_time_surface_params *prm,
                         uint8_t *frames, int32_t *last, ec_surface_stats *stats, ec_stream_t stream)
 {
-    EC_REQUIRE(prm != nullptr, "ec_events_to_time_surface: params is null");
-    EC_REQUIRE(F >= 0, "ec_events_to_time_surface: F=%d", F);
-    if (F == 0) return EC_OK;
-    EC_REQUIRE(events && frame_range && frames, "ec_events_to_time_surface: null buffer");
+    int rc;
+    if (launch_is_over("ec_events_to_time_surface", prm, 'F', F, events && frame_range && frames, rc)) return rc;
     EC_REQUIRE(prm->H > 0 && prm->W > 0, "ec_events_to_time_surface: bad shape (%d,%d)", prm->H, prm->W);
     EC_REQUIRE(((uintptr_t)events & (sizeof(EV) - 1)) == 0,
                "ec_events_to_time_surface: events must be %d-byte aligned", (int)sizeof(EV));
@@ -2001,7 +2082,7 @@ int launch_time_surface(const void *events, const int64_t *frame_range, int F, c
     EC_REQUIRE(prm->decay == EC_DECAY_LINEAR || prm->decay == EC_DECAY_EXP, "ec_events_to_time_surface: unknown decay %d", prm->decay);
     EC_REQUIRE(prm->decay != EC_DECAY_EXP || prm->tau_us > 0., "ec_events_to_time_surface: tau_us=%g must be positive", prm->tau_us);
 
-    const TsPlan plan = time_surface_plan(prm->H, prm->W);
+    const RowBands plan = row_bands(prm->H, (long)prm->W * 2 * 4);          // 8 bytes per pixel
     TsArgs a = {};
     a.events = events;
     a.range = reinterpret_cast<const long long *>(frame_range);
@@ -2019,14 +2100,8 @@ int launch_time_surface(const void *events, const int64_t *frame_range, int F, c
     a.frames = frames, a.last = last, a.stats = stats;
     a.rows_per_band = plan.rows_per_band, a.bands = plan.bands, a.band_bytes = plan.band_bytes;
 
-    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(time_surface_kernel<EV>), EV_LDS_TOTAL)) return rc;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    // algorithmic bytes: 16 B (packed: 8 B) per event in + 3*H*W out, as launch_events states them
-    ec::ProfScope prof(ec::PROF_TIME_SURFACE, hs, 0,
-                       (double)F * prm->H * prm->W * 3.0 + (double)(prm->total_events > 0 ? prm->total_events : 0) * sizeof(EV));
-    hipLaunchKernelGGL(time_surface_kernel<EV>, dim3((unsigned)std::min<long>((long)F * plan.bands, events_cus())), dim3(EV_THREADS), plan.lds, hs, a);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return launch_form(time_surface_kernel<EV>, std::min<long>((long)F * plan.bands, events_cus()), plan.lds, ec::PROF_TIME_SURFACE,
+                       event_bytes<EV>(F, prm->H, prm->W, prm->total_events), stream, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2078,66 +2153,25 @@ __device__ __forceinline__ unsigned floor_ratio(unsigned long long num, unsigned
     return q;
 }
 
-// steps 1 - 2 over the events of a frame: the tallies behind t0, t1, dropped, counted
-template <typename EV>
-__device__ __forceinline__ void voxel_tally(const EV *ev, long long n, const VgArgs &a, TsTally &t)
-{
-    const int H = a.H, W = a.W;
-    for (long long i = threadIdx.x; i < n; i += 8 * EV_THREADS) {
-        EV e[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const long long j = i + (long long)k * EV_THREADS;
-            e[k] = ev[j < n ? j : n - 1];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            int x, y, p;
-            parse(e[k], W, a.flip_x, a.negate_p, x, y, p);
-            const bool there = i + (long long)k * EV_THREADS < n && p != 0;
-            const bool inside = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
-            const unsigned tick = tick_of(e[k]);
-            t.dropped += there && !inside;
-            t.counted += there && inside;
-            const unsigned hi = there && inside ? tick + 1u : 0u, lo = there && inside ? TS_REVERSED - tick : 0u;
-            t.hi = hi > t.hi ? hi : t.hi, t.lo = lo > t.lo ? lo : t.lo;
-        }
-    }
-}
-
 // steps 3 - 4 for the rows [y0, y1): the band zeroed, then two LDS atomic adds per counted event of the band (one when
 // f == 0).  u is clamped to `scale`, which the exact floor never exceeds: b <= B - 1, and b == B - 1 only with f == 0.
 template <typename EV>
 __device__ __forceinline__ void voxel_band(const EV *ev, long long n, int y0, int y1, const VgArgs &a, const VgFrame &fr,
                                            int *state)
 {
-    const int H = a.H, W = a.W, B = a.B;
-    for (int i = threadIdx.x; i < a.band_bytes / 16; i += EV_THREADS) reinterpret_cast<uint4 *>(state)[i] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    for (long long i = threadIdx.x; i < n; i += 8 * EV_THREADS) {
-        EV e[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const long long j = i + (long long)k * EV_THREADS;
-            e[k] = ev[j < n ? j : n - 1];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            int x, y, p;
-            parse(e[k], W, a.flip_x, a.negate_p, x, y, p);
-            const bool there = i + (long long)k * EV_THREADS < n && p != 0;
-            const bool inside = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
-            if (!(there && inside && y >= y0 && y < y1)) continue;
-            const unsigned tick = tick_of(e[k]);
-            const unsigned d = a.reverse_t ? fr.t1 - tick : tick - fr.t0;
-            unsigned u = fr.span ? floor_ratio((unsigned long long)d * fr.scale, fr.span, fr.inv_span) : 0u;
-            u = u < fr.scale ? u : fr.scale;
-            const int b = (int)(u >> 8), f = (int)(u & 255u), s = p > 0 ? 1 : -1;
-            int *g = &state[((y - y0) * W + x) * B + b];
-            atomicAdd(g, s * (256 - f));
-            if (f) atomicAdd(g + 1, s * f);
-        }
-    }
+    zero_band(state, a.band_bytes);
+    for_events(ev, n, [&](const EV e, long long) {
+        int x, y, p;
+        if (!(counted_event(e, a.H, a.W, a.flip_x, a.negate_p, x, y, p) && y >= y0 && y < y1)) return;
+        const unsigned tick = tick_of(e);
+        const unsigned d = a.reverse_t ? fr.t1 - tick : tick - fr.t0;
+        unsigned u = fr.span ? floor_ratio((unsigned long long)d * fr.scale, fr.span, fr.inv_span) : 0u;
+        u = u < fr.scale ? u : fr.scale;
+        const int b = (int)(u >> 8), f = (int)(u & 255u), s = p > 0 ? 1 : -1;
+        int *g = &state[((y - y0) * a.W + x) * a.B + b];
+        atomicAdd(g, s * (256 - f));
+        if (f) atomicAdd(g + 1, s * f);
+    });
     __syncthreads();
 }
 
@@ -2158,32 +2192,9 @@ __device__ __forceinline__ void voxel_pixel(int g0, int g1, int g2, unsigned m, 
 __device__ __forceinline__ void voxel_colour(const int *src, int npix, int W, unsigned m, int background_mask, uint8_t *o)
 {
     const double inv_2m = m ? 1. / (2. * (double)m) : 0.;
-    if ((W & 3) == 0 && ((uintptr_t)src & 15) == 0) {
-        // 4 pixels = 48 bytes in, 12 bytes = three dwords out per thread
-        for (int g = threadIdx.x; g < npix / 4; g += EV_THREADS) {
-            unsigned words[3];
-            uint8_t *bytes = reinterpret_cast<uint8_t *>(words);
-            const int4 ca = *reinterpret_cast<const int4 *>(&src[g * 12]);
-            const int4 cb = *reinterpret_cast<const int4 *>(&src[g * 12 + 4]);
-            const int4 cc = *reinterpret_cast<const int4 *>(&src[g * 12 + 8]);
-            voxel_pixel(ca.x, ca.y, ca.z, m, inv_2m, background_mask, bytes);
-            voxel_pixel(ca.w, cb.x, cb.y, m, inv_2m, background_mask, bytes + 3);
-            voxel_pixel(cb.z, cb.w, cc.x, m, inv_2m, background_mask, bytes + 6);
-            voxel_pixel(cc.y, cc.z, cc.w, m, inv_2m, background_mask, bytes + 9);
-            unsigned *dst = reinterpret_cast<unsigned *>(o + (long long)g * 12);
-            dst[0] = words[0];
-            dst[1] = words[1];
-            dst[2] = words[2];
-        }
-    } else {
-        for (int q = threadIdx.x; q < npix; q += EV_THREADS) {
-            uint8_t px[3];
-            voxel_pixel(src[3 * q], src[3 * q + 1], src[3 * q + 2], m, inv_2m, background_mask, px);
-            o[3 * q] = px[0];
-            o[3 * q + 1] = px[1];
-            o[3 * q + 2] = px[2];
-        }
-    }
+    store_pixels<3>(reinterpret_cast<const unsigned *>(src), npix, W, o, [&](int, const unsigned *s, uint8_t *px) {
+        voxel_pixel((int)s[0], (int)s[1], (int)s[2], m, inv_2m, background_mask, px);
+    });
 }
 
 template <typename EV>
@@ -2198,14 +2209,17 @@ __global__ __launch_bounds__(EV_THREADS) void voxel_grid_kernel(const VgArgs a)
     for (int f = blockIdx.x; f < a.F; f += gridDim.x) {
         const long long e0 = a.range[2 * f], n = a.range[2 * f + 1] - e0;
         const EV *ev = reinterpret_cast<const EV *>(a.events) + e0;
-        // pass 0
+        // pass 0 (steps 1 - 2): the tallies behind t0, t1, dropped, counted
         TsTally t = {0, 0, 0, 0};
-        voxel_tally(ev, n, a, t);
+        for_events(ev, n, [&](const EV e, long long) {
+            int x, y, p;
+            const bool counted = counted_event(e, H, W, a.flip_x, a.negate_p, x, y, p);
+            tally_event(t, counted, p, tick_of(e));
+        });
         t = block_tally(t, scratch);
-        VgFrame fr = {0, 0, 0, (unsigned)(B - 1) * 256u, 0.};
-        if (t.counted) fr.t0 = TS_REVERSED - t.lo, fr.t1 = t.hi - 1u;
-        fr.span = fr.t1 - fr.t0;
-        fr.inv_span = fr.span ? 1. / (double)fr.span : 0.;
+        const FrameSpan sp = frame_span(t);
+        const unsigned span = sp.t1 - sp.t0;
+        const VgFrame fr = {sp.t0, sp.t1, span, (unsigned)(B - 1) * 256u, span ? 1. / (double)span : 0.};
         // passes 1 and 2 over the bands, through one copy of the scan: pass 1 bins every band and takes the peak (and
         // stores grid), pass 2 writes the bytes -- from the band still in LDS (one band), from grid, or binned again
         const bool rebin = a.bands > 1 && !a.grid;
@@ -2243,32 +2257,19 @@ __global__ __launch_bounds__(EV_THREADS) void voxel_grid_kernel(const VgArgs a)
     }
 }
 
-// Row bands of 4 B bytes per pixel: as many rows as fit EV_BIN_BYTES, evened out over the bands; the reduction scratch
-// behind.  bands == 0: the entry points refuse this sensor.
-struct VgPlan {
-    int rows_per_band, bands, band_bytes, lds;
-};
-inline VgPlan voxel_grid_plan(int H, int W, int B)
+// Row bands of 4 B bytes per pixel.  bands == 0: the entry points refuse this sensor or bin count.
+inline RowBands voxel_grid_plan(int H, int W, int B)
 {
-    VgPlan p = {};
-    if (H <= 0 || W <= 0 || B < EC_VOXEL_MIN_BINS || B > EC_VOXEL_MAX_BINS) return p;
-    const long row_bytes = (long)W * B * 4;
-    if (row_bytes > EV_BIN_BYTES) return p;
-    p.bands = ec::ceil_div(H, (int)std::min<long>(H, EV_BIN_BYTES / row_bytes));
-    p.rows_per_band = ec::ceil_div(H, p.bands);
-    p.band_bytes = (int)((p.rows_per_band * row_bytes + 15) / 16 * 16);
-    p.lds = p.band_bytes + EV_REDUCE_BYTES;
-    return p;
+    if (W <= 0 || B < EC_VOXEL_MIN_BINS || B > EC_VOXEL_MAX_BINS) return RowBands{};
+    return row_bands(H, (long)W * B * 4);
 }
 
 template <typename EV>
 int launch_voxel_grid(const void *events, const int64_t *frame_range, int F, const ec_voxel_grid_params *prm,
                       uint8_t *frames, int32_t *grid, ec_voxel_stats *stats, ec_stream_t stream)
 {
-    EC_REQUIRE(prm != nullptr, "ec_events_to_voxel_grid: params is null");
-    EC_REQUIRE(F >= 0, "ec_events_to_voxel_grid: F=%d", F);
-    if (F == 0) return EC_OK;
-    EC_REQUIRE(events && frame_range, "ec_events_to_voxel_grid: null buffer");
+    int rc;
+    if (launch_is_over("ec_events_to_voxel_grid", prm, 'F', F, events && frame_range, rc)) return rc;
     EC_REQUIRE(frames || grid, "ec_events_to_voxel_grid: neither frames nor grid");
     EC_REQUIRE(prm->H > 0 && prm->W > 0, "ec_events_to_voxel_grid: bad shape (%d,%d)", prm->H, prm->W);
     EC_REQUIRE(prm->bins >= EC_VOXEL_MIN_BINS && prm->bins <= EC_VOXEL_MAX_BINS, "ec_events_to_voxel_grid: bins=%d outside %d .. %d",
@@ -2280,7 +2281,7 @@ int launch_voxel_grid(const void *events, const int64_t *frame_range, int F, con
                "ec_events_to_voxel_grid: events must be %d-byte aligned", (int)sizeof(EV));
     EC_REQUIRE(((uintptr_t)frames & 3) == 0 && ((uintptr_t)grid & 3) == 0 && ((uintptr_t)stats & 3) == 0,
                "ec_events_to_voxel_grid: frames, grid and stats must be 4-byte aligned");
-    const VgPlan plan = voxel_grid_plan(prm->H, prm->W, prm->bins);
+    const RowBands plan = voxel_grid_plan(prm->H, prm->W, prm->bins);
     EC_REQUIRE(plan.bands > 0, "ec_events_to_voxel_grid: W=%d too wide for one LDS row band at bins=%d", prm->W, prm->bins);
 
     VgArgs a = {};
@@ -2292,14 +2293,8 @@ int launch_voxel_grid(const void *events, const int64_t *frame_range, int F, con
     a.frames = frames, a.grid = grid, a.stats = stats;
     a.rows_per_band = plan.rows_per_band, a.bands = plan.bands, a.band_bytes = plan.band_bytes;
 
-    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(voxel_grid_kernel<EV>), EV_LDS_TOTAL)) return rc;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    // algorithmic bytes: 16 B (packed: 8 B) per event in + 3*H*W out, as launch_events states them
-    ec::ProfScope prof(ec::PROF_VOXEL_GRID, hs, 0,
-                       (double)F * prm->H * prm->W * 3.0 + (double)(prm->total_events > 0 ? prm->total_events : 0) * sizeof(EV));
-    hipLaunchKernelGGL(voxel_grid_kernel<EV>, dim3((unsigned)std::min<long>(F, events_cus())), dim3(EV_THREADS), plan.lds, hs, a);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return launch_form(voxel_grid_kernel<EV>, std::min<long>(F, events_cus()), plan.lds, ec::PROF_VOXEL_GRID,
+                       event_bytes<EV>(F, prm->H, prm->W, prm->total_events), stream, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2344,34 +2339,6 @@ struct DnArgs {
     int cap;                 // max_sample_events
     int rows_per_band, bands;
 };
-
-// f(event, row) for every row of [0, n): eight loads in flight per thread, row j always with thread j % EV_THREADS
-template <typename EV, typename F>
-__device__ __forceinline__ void for_events(const EV *ev, long long n, F f)
-{
-    for (long long i = threadIdx.x; i < n; i += 8 * EV_THREADS) {
-        EV e[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const long long j = i + (long long)k * EV_THREADS;
-            e[k] = ev[j < n ? j : n - 1];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const long long j = i + (long long)k * EV_THREADS;
-            if (j < n) f(e[k], j);
-        }
-    }
-}
-
-// steps 1 and 3: the pixel of a counted event
-template <typename EV>
-__device__ __forceinline__ bool counted_pixel(const EV e, int H, int W, int &x, int &y)
-{
-    int p;
-    parse(e, W, 0, 0, x, y, p);
-    return p != 0 && (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
-}
 
 // v[0 .. n) -> its exclusive prefix sums, in place.  Every thread owns `chunk` consecutive words (odd: neighbouring threads
 // on different banks); the threads' sums meet in a wave scan and the waves' in scratch.
@@ -2446,22 +2413,22 @@ __global__ __launch_bounds__(EV_THREADS) void denoise_kernel(const DnArgs a)
             for (int i = threadIdx.x; i <= npix; i += EV_THREADS) offs[i] = 0;
             __syncthreads();
             for_events(ev, n, [&](const EV e, long long) {
-                int x, y;
-                if (counted_pixel(e, H, W, x, y) && y >= ylo && y < yhi) atomicAdd(&offs[1 + (y - ylo) * W + x], 1u);
+                int x, y, p;
+                if (counted_event(e, H, W, 0, 0, x, y, p) && y >= ylo && y < yhi) atomicAdd(&offs[1 + (y - ylo) * W + x], 1u);
             });
             __syncthreads();
             block_exclusive_scan(offs + 1, npix, scratch);
             for_events(ev, n, [&](const EV e, long long) {
-                int x, y;
-                if (counted_pixel(e, H, W, x, y) && y >= ylo && y < yhi) {
+                int x, y, p;
+                if (counted_event(e, H, W, 0, 0, x, y, p) && y >= ylo && y < yhi) {
                     const unsigned pos = atomicAdd(&offs[1 + (y - ylo) * W + x], 1u);
                     if (pos < (unsigned)a.cap) ticks[pos] = tick_of(e);    // (always: pos < the band's events <= n <= cap)
                 }
             });
             __syncthreads();                                   // the ticks are stored: this workgroup may read them
             for_events(ev, n, [&](const EV e, long long j) {
-                int x, y;
-                if (!(counted_pixel(e, H, W, x, y) && y >= y0 && y < y1)) return;
+                int x, y, p;
+                if (!(counted_event(e, H, W, 0, 0, x, y, p) && y >= y0 && y < y1)) return;
                 const unsigned ti = tick_of(e);
                 const int xa = max(0, x - r), xb = min(W - 1, x + r);
                 bool s = false;
@@ -2488,8 +2455,8 @@ __global__ __launch_bounds__(EV_THREADS) void denoise_kernel(const DnArgs a)
             EV e = {};
             if (i < n) {
                 e = ev[i];
-                int x, y;
-                const bool cnt = counted_pixel(e, H, W, x, y);
+                int x, y, p;
+                const bool cnt = counted_event(e, H, W, 0, 0, x, y, p);
                 ok = !cnt || flags[i] != 0;
                 kept += cnt && ok, removed += cnt && !ok, passed += !cnt;
                 if (a.keep) a.keep[e0 + i] = ok ? 1 : 0;
@@ -2550,10 +2517,8 @@ int launch_denoise(const void *events, const int64_t *sample_range, int B, const
                    int64_t *counts, uint8_t *keep, ec_denoise_stats *stats, void *workspace, size_t workspace_bytes,
                    ec_stream_t stream)
 {
-    EC_REQUIRE(prm != nullptr, "ec_denoise_events: params is null");
-    EC_REQUIRE(B >= 0, "ec_denoise_events: B=%d", B);
-    if (B == 0) return EC_OK;
-    EC_REQUIRE(events && sample_range && events_out && counts && workspace, "ec_denoise_events: null buffer");
+    int rc;
+    if (launch_is_over("ec_denoise_events", prm, 'B', B, events && sample_range && events_out && counts && workspace, rc)) return rc;
     EC_REQUIRE(events != events_out, "ec_denoise_events: in-place operation is not supported");
     EC_REQUIRE(prm->H > 0 && prm->W > 0, "ec_denoise_events: bad shape (%d,%d)", prm->H, prm->W);
     EC_REQUIRE(prm->radius >= EC_DENOISE_MIN_RADIUS && prm->radius <= EC_DENOISE_MAX_RADIUS,
@@ -2582,13 +2547,9 @@ int launch_denoise(const void *events, const int64_t *sample_range, int B, const
     a.cap = prm->max_sample_events;
     a.rows_per_band = plan.rows_per_band, a.bands = plan.bands;
 
-    if (int rc = ec::ensure_dynamic_lds(reinterpret_cast<const void *>(denoise_kernel<EV>), EV_LDS_TOTAL)) return rc;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
     // algorithmic bytes: every event read once and at most written once
-    ec::ProfScope prof(ec::PROF_DENOISE, hs, 0, 2.0 * (double)(prm->total_events > 0 ? prm->total_events : 0) * sizeof(EV));
-    hipLaunchKernelGGL(denoise_kernel<EV>, dim3((unsigned)std::min<int>(B, EC_DENOISE_MAX_GROUPS)), dim3(EV_THREADS), DN_LDS_BYTES, hs, a);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return launch_form(denoise_kernel<EV>, std::min<int>(B, EC_DENOISE_MAX_GROUPS), DN_LDS_BYTES, ec::PROF_DENOISE,
+                       2.0 * event_bytes<EV>(0, 0, 0, prm->total_events), stream, a);
 }
 
 }  // namespace

@@ -105,7 +105,6 @@ def events_to_time_surface(events: torch.Tensor, frame_range: torch.Tensor, H: i
     frames = torch.empty((F, H, W, 3), dtype=torch.uint8, device=events.device)
     prm = vis.time_surface_params((H, W), red, blue, decay, tau, background_mask, max_frame_events, flip_x, negate_p,
                                   reverse_t, total_events)
-    vis.surface_lib()
     _lib.launch('ec_events_to_time_surface_packed' if vis.is_packed(events) else 'ec_events_to_time_surface', events,
                 frame_range, F, prm, frames, None, None)
     return frames

@@ -191,6 +191,25 @@ def pack_events_device(events, return_bad=False):
     return (out, int(bad.item())) if return_bad else out
 
 
+def _check_device_events(events, ranges, on_device=True):
+    """What every device entry asks of (events, frame_range / sample_range) -> (the device, whether events are packed).
+    on_device=False: the ranges may live on the host (the filter moves them itself)."""
+    import torch
+    dev = _lib.require_gpu()
+    packed = is_packed(events)
+    assert events.is_cuda and events.is_contiguous()
+    assert packed or (events.dtype == torch.float32 and events.dim() == 2 and events.shape[1] == 4)
+    if on_device:
+        assert ranges.is_cuda and ranges.dtype == torch.int64 and ranges.is_contiguous()
+    else:
+        assert ranges.dtype == torch.int64 and ranges.dim() == 2 and ranges.shape[1] == 2
+    return dev, packed
+
+
+def _first_or_tuple(res):
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 def events_to_frames_device(events, frame_range, shape, grayscale=True, thresh=10.,
                             count_non_zero=False, background_mask=True, return_counts=False,
                             return_stats=False, out=None, max_frame_events=0, flip_x=False,
@@ -208,12 +227,8 @@ def events_to_frames_device(events, frame_range, shape, grayscale=True, thresh=1
     stats structured array when asked).
     """
     import torch
-    dev = _lib.require_gpu()
+    dev, packed = _check_device_events(events, frame_range)
     H, W = shape
-    packed = is_packed(events)
-    assert events.is_cuda and events.is_contiguous()
-    assert packed or (events.dtype == torch.float32 and events.dim() == 2 and events.shape[1] == 4)
-    assert frame_range.is_cuda and frame_range.dtype == torch.int64 and frame_range.is_contiguous()
     F = int(frame_range.shape[0])
     if out is None and not return_counts and not return_stats and sort_workspace:
         # the production form: the registered custom op (eventclip_hip::events_to_frames)
@@ -243,28 +258,18 @@ def events_to_frames_device(events, frame_range, shape, grayscale=True, thresh=1
         dt = np.dtype([('sum', '<u8'), ('sumsq', '<u8'), ('nnz', '<u4'), ('max_kept', '<u4'),
                        ('dropped', '<u4'), ('ambiguous', '<u4'), ('thr', '<f8')])
         res.append(stats.cpu().numpy().view(dt).reshape(F))
-    return res[0] if len(res) == 1 else tuple(res)
+    return _first_or_tuple(res)
 
 
 # ---- time-surface frames (include/eventclip_time_surface.h: the definition, steps 1 - 7) ----
 SURFACE_HEADER = os.path.join(os.path.dirname(_lib.HEADER), 'eventclip_time_surface.h')
-with open(SURFACE_HEADER) as _f:
-    # bound as _lib binds the main header; that header's #include stands for what the reader wants from it, the version
-    _, _surface_constants, _surface_structs, SURFACE_SIGNATURES = _lib.read_header(
-        _f.read().replace('#include "eventclip_hip.h"', f'#define EC_ABI_VERSION {_lib.ABI_VERSION}'))
+_surface_constants, _surface_structs, SURFACE_SIGNATURES = _lib.bind_header(os.path.basename(SURFACE_HEADER))
 EcTimeSurfaceParams, EcSurfaceStats = _surface_structs['EcTimeSurfaceParams'], _surface_structs['EcSurfaceStats']
 DECAYS = {'linear': _surface_constants['EC_DECAY_LINEAR'], 'exp': _surface_constants['EC_DECAY_EXP']}
 SURFACE_STATS_DTYPE = np.dtype([('dropped', '<u4'), ('counted', '<u4'), ('t0', '<u4'), ('t1', '<u4')])
 CONVERT_METHODS = ('event_histogram', 'time_surface', 'voxel_grid')
-
-
-def surface_lib():
-    """The loaded library with the entries of eventclip_time_surface.h typed (``_lib.launch`` finds them there)."""
-    handle = _lib.lib()
-    for name, (res, args) in SURFACE_SIGNATURES.items():
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = res, args
-    return handle
+# the names callers once had to go through to find a side header's entries typed: the handle itself, typed for everyone
+surface_lib = voxel_lib = denoise_lib = _lib.lib
 
 
 def time_surface_params(shape, red, blue, decay, tau, background_mask, max_frame_events, flip_x, negate_p, reverse_t,
@@ -298,12 +303,8 @@ def time_surface_device(events, frame_range, shape, decay='linear', tau=0.03, gr
     array -- dropped, counted, t0, t1 -- when asked).
     """
     import torch
-    dev = _lib.require_gpu()
+    dev, packed = _check_device_events(events, frame_range)
     H, W = shape
-    packed = is_packed(events)
-    assert events.is_cuda and events.is_contiguous()
-    assert packed or (events.dtype == torch.float32 and events.dim() == 2 and events.shape[1] == 4)
-    assert frame_range.is_cuda and frame_range.dtype == torch.int64 and frame_range.is_contiguous()
     F = int(frame_range.shape[0])
     red, blue = colour_map(grayscale)
     if out is None and not return_last and not return_stats:
@@ -319,7 +320,6 @@ def time_surface_device(events, frame_range, shape, decay='linear', tau=0.03, gr
     stats = torch.zeros((F, ctypes.sizeof(EcSurfaceStats)), dtype=torch.uint8, device=dev) if return_stats else None
     prm = time_surface_params(shape, red, blue, decay, tau, background_mask, max_frame_events, flip_x, negate_p,
                               reverse_t, total_events)
-    surface_lib()
     _lib.launch('ec_events_to_time_surface_packed' if packed else 'ec_events_to_time_surface', events, frame_range, F,
                 prm, frames, last, stats)
     res = [frames]
@@ -327,32 +327,21 @@ def time_surface_device(events, frame_range, shape, decay='linear', tau=0.03, gr
         res.append(last)
     if return_stats:
         res.append(stats.cpu().numpy().view(SURFACE_STATS_DTYPE).reshape(F))
-    return res[0] if len(res) == 1 else tuple(res)
+    return _first_or_tuple(res)
 
 
 # ---- voxel-grid frames (include/eventclip_voxel_grid.h: the definition, steps 1 - 7) ----
 VOXEL_HEADER = os.path.join(os.path.dirname(_lib.HEADER), 'eventclip_voxel_grid.h')
-with open(VOXEL_HEADER) as _f:
-    _, _voxel_constants, _voxel_structs, VOXEL_SIGNATURES = _lib.read_header(
-        _f.read().replace('#include "eventclip_hip.h"', f'#define EC_ABI_VERSION {_lib.ABI_VERSION}'))
+_voxel_constants, _voxel_structs, VOXEL_SIGNATURES = _lib.bind_header(os.path.basename(VOXEL_HEADER))
 EcVoxelGridParams, EcVoxelStats = _voxel_structs['EcVoxelGridParams'], _voxel_structs['EcVoxelStats']
 VOXEL_BINS = (_voxel_constants['EC_VOXEL_MIN_BINS'], _voxel_constants['EC_VOXEL_MAX_BINS'])
 VOXEL_MAX_FRAME_EVENTS = _voxel_constants['EC_VOXEL_MAX_FRAME_EVENTS']
 VOXEL_STATS_DTYPE = np.dtype([('dropped', '<u4'), ('counted', '<u4'), ('t0', '<u4'), ('t1', '<u4'), ('peak', '<u4')])
 
 
-def voxel_lib():
-    """The loaded library with the entries of eventclip_voxel_grid.h typed (``_lib.launch`` finds them there)."""
-    handle = _lib.lib()
-    for name, (res, args) in VOXEL_SIGNATURES.items():
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = res, args
-    return handle
-
-
 def voxel_grid_bands(shape, bins=3):
     """Row bands the kernel cuts a sensor into (``ec_voxel_grid_bands``; host only, 0 = refused)."""
-    return int(voxel_lib().ec_voxel_grid_bands(int(shape[0]), int(shape[1]), int(bins)))
+    return int(_lib.lib().ec_voxel_grid_bands(int(shape[0]), int(shape[1]), int(bins)))
 
 
 def voxel_grid_params(shape, bins, background_mask, max_frame_events, flip_x, negate_p, reverse_t, total_events):
@@ -384,12 +373,8 @@ def voxel_grid_device(events, frame_range, shape, bins=3, background_mask=True, 
     counted, t0, t1, peak -- when asked), or the grid (+ stats) alone when B != 3.
     """
     import torch
-    dev = _lib.require_gpu()
+    dev, packed = _check_device_events(events, frame_range)
     H, W = shape
-    packed = is_packed(events)
-    assert events.is_cuda and events.is_contiguous()
-    assert packed or (events.dtype == torch.float32 and events.dim() == 2 and events.shape[1] == 4)
-    assert frame_range.is_cuda and frame_range.dtype == torch.int64 and frame_range.is_contiguous()
     F, bins = int(frame_range.shape[0]), int(bins)
     if bins != 3 and not return_grid:
         raise ValueError(f'bins={bins}: the image form exists for 3 bins only; ask for the grid (return_grid=True)')
@@ -410,7 +395,6 @@ def voxel_grid_device(events, frame_range, shape, bins=3, background_mask=True, 
     want_grid = return_grid or (frames is not None and voxel_grid_bands(shape, bins) > 1)
     grid = torch.empty((F, H, W, bins), dtype=torch.int32, device=dev) if want_grid else None
     stats = torch.zeros((F, ctypes.sizeof(EcVoxelStats)), dtype=torch.uint8, device=dev) if return_stats else None
-    voxel_lib()
     _lib.launch('ec_events_to_voxel_grid_packed' if packed else 'ec_events_to_voxel_grid', events, frame_range, F, prm,
                 frames, grid, stats)
     res = [frames] if frames is not None else []
@@ -418,29 +402,18 @@ def voxel_grid_device(events, frame_range, shape, bins=3, background_mask=True, 
         res.append(grid)
     if return_stats:
         res.append(stats.cpu().numpy().view(VOXEL_STATS_DTYPE).reshape(F))
-    return res[0] if len(res) == 1 else tuple(res)
+    return _first_or_tuple(res)
 
 
 # ---- background-activity denoising (include/eventclip_denoise.h: the definition, steps 1 - 5) ----
 DENOISE_HEADER = os.path.join(os.path.dirname(_lib.HEADER), 'eventclip_denoise.h')
-with open(DENOISE_HEADER) as _f:
-    _, _denoise_constants, _denoise_structs, DENOISE_SIGNATURES = _lib.read_header(
-        _f.read().replace('#include "eventclip_hip.h"', f'#define EC_ABI_VERSION {_lib.ABI_VERSION}'))
+_denoise_constants, _denoise_structs, DENOISE_SIGNATURES = _lib.bind_header(os.path.basename(DENOISE_HEADER))
 EcDenoiseParams, EcDenoiseStats = _denoise_structs['EcDenoiseParams'], _denoise_structs['EcDenoiseStats']
 DENOISE_RADIUS = (_denoise_constants['EC_DENOISE_MIN_RADIUS'], _denoise_constants['EC_DENOISE_MAX_RADIUS'])
 DENOISE_MAX_DT_US = _denoise_constants['EC_DENOISE_MAX_DT_US']
 DENOISE_STATS_DTYPE = np.dtype([('kept', '<u4'), ('removed', '<u4'), ('passed', '<u4')])
 
 _denoise_scratch = collections.defaultdict(_lib.Scratch)   # device index -> the filter's workspace, reused by every call
-
-
-def denoise_lib():
-    """The loaded library with the entries of eventclip_denoise.h typed (``_lib.launch`` finds them there)."""
-    handle = _lib.lib()
-    for name, (res, args) in DENOISE_SIGNATURES.items():
-        fn = getattr(handle, name)
-        fn.restype, fn.argtypes = res, args
-    return handle
 
 
 def denoise_dt_us(dt):
@@ -466,7 +439,7 @@ def denoise_params(shape, dt_us, radius, max_sample_events, total_events=0):
 
 def denoise_workspace_bytes(prm, B):
     """``ec_denoise_workspace_bytes``: host only, 0 for parameters the entry points refuse."""
-    return int(denoise_lib().ec_denoise_workspace_bytes(ctypes.byref(prm), int(B)))
+    return int(_lib.lib().ec_denoise_workspace_bytes(ctypes.byref(prm), int(B)))
 
 
 def denoise_launch(events, sample_range, prm, events_out, counts, keep=None, stats=None):
@@ -493,11 +466,7 @@ def denoise_events_device(events, sample_range, shape, dt, radius=1, return_mask
     every sample 0) with ``return_mask``, + a stats structured array (kept, removed, passed) with ``return_stats``.
     """
     import torch
-    dev = _lib.require_gpu()
-    packed = is_packed(events)
-    assert events.is_cuda and events.is_contiguous()
-    assert packed or (events.dtype == torch.float32 and events.dim() == 2 and events.shape[1] == 4)
-    assert sample_range.dtype == torch.int64 and sample_range.dim() == 2 and sample_range.shape[1] == 2
+    dev, _ = _check_device_events(events, sample_range, on_device=False)
     B = int(sample_range.shape[0])
     dt_us = denoise_dt_us(dt)
     if not return_mask and not return_stats:
@@ -518,7 +487,7 @@ def denoise_events_device(events, sample_range, shape, dt, radius=1, return_mask
         res.append(keep)
     if return_stats:
         res.append(stats.cpu().numpy().view(DENOISE_STATS_DTYPE).reshape(B))
-    return tuple(res)
+    return _first_or_tuple(res)
 
 
 def denoise_events(events, resolution, dt, radius=1):

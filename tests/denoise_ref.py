@@ -305,6 +305,9 @@ def cases():
         S.append(pool[at:at + n])
         at += n
     C['lengths'] = _case(S, small, 1500, 1)
+    # ... and around the scan's 8 x 1024 rows per round; a random stream: the CPU test asserts its share of kept events
+    pool = synthetic.make_events(8191 + 8192 + 8193, small, seed=14, max_t=0.3)
+    C['lengths_unroll'] = _case([pool[:8191], pool[8191:8191 + 8192], pool[8191 + 8192:]], small, 1500, 1, random=True)
     many = synthetic.make_events(600 * 40, small, seed=6, max_t=0.02 * 600)
     C['many'] = _case([many[40 * i:40 * i + 40] for i in range(600)], small, 20000, 3)      # 600 samples in one launch
     g = synthetic.make_events(3000, small, seed=8, max_t=0.05)

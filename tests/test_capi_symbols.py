@@ -184,6 +184,36 @@ def test_reader_refuses_what_it_cannot_read():
         _lib.read_header('enum { EC_A = 0 };')
 
 
+def test_side_headers_are_bound_whatever_the_call_order(monkeypatch):
+    """Importing vis binds the three side headers; every entry they declare is then typed on the handle ``lib()`` returns,
+    whether the library was loaded before the binding or is loaded after it, and with no call in between.  Binding a
+    header again changes nothing; a side header's errors carry its own name; _lib's own tables stay the main header's."""
+    import pytest
+    from eventclip_amd import vis
+    tables = {'eventclip_time_surface.h': vis.SURFACE_SIGNATURES, 'eventclip_voxel_grid.h': vis.VOXEL_SIGNATURES,
+              'eventclip_denoise.h': vis.DENOISE_SIGNATURES}
+    assert [os.path.basename(h) for h in (vis.SURFACE_HEADER, vis.VOXEL_HEADER, vis.DENOISE_HEADER)] == list(tables)
+    assert all(len(t) >= 2 for t in tables.values()) and not any(set(t) & set(_lib.SIGNATURES) for t in tables.values())
+
+    def typed(handle):
+        for table in tables.values():
+            for name, (res, args) in table.items():
+                fn = getattr(handle, name)
+                assert fn.restype is res and list(fn.argtypes) == args, name
+    typed(_lib.lib())
+    monkeypatch.setattr(_lib, '_lib', None)                    # ... and on a handle loaded after the binding
+    fresh = _lib.lib()
+    typed(fresh)
+    for filename, table in tables.items():                     # again, now with the library loaded: the very same tables
+        constants, structs, signatures = _lib.bind_header(filename)
+        assert signatures is table and set(structs) and all(k.startswith('EC_') for k in constants)
+        assert not set(structs) & set(vars(_lib)) and not set(constants) & set(vars(_lib))
+    typed(fresh)
+    assert fresh.ec_voxel_grid_bands(100, 120, 3) == 1 and fresh.ec_denoise_bands(37, 53, 1) == 1
+    with pytest.raises(_lib.HeaderError, match=r'eventclip_side\.h:4: .*not a declaration form'):
+        _lib.read_header(SNIPPET + 'int ec_global;', 'eventclip_side.h')
+
+
 def test_version_and_error_string():
     lib = _lib.lib()
     assert lib.ec_version() == _lib.ABI_VERSION == header_abi_version()

@@ -60,8 +60,8 @@ def run(name, packed=False, outputs=('keep', 'stats')):
 
 def test_band_counts(hip):
     """one band (the two small sensors), two (180 x 240) and ten / eleven with a partial last band (480 x 640)"""
-    from eventclip_amd import vis
-    lib = vis.denoise_lib()
+    from eventclip_amd import _lib, vis  # noqa: F401  (vis binds eventclip_denoise.h)
+    lib = _lib.lib()
     assert [lib.ec_denoise_bands(H, W, r) for (H, W), r in (((37, 53), 3), ((100, 120), 1), ((180, 240), 2), ((480, 640), 1),
                                                            ((480, 640), 3))] == [1, 1, 2, 10, 11]
     assert 480 % -(-480 // 11) != 0
@@ -121,7 +121,7 @@ def test_a_sample_longer_than_the_bound_is_not_filtered_and_nothing_else_is_touc
 def test_b_zero_and_the_refusals_write_nothing(hip):
     import torch
     from eventclip_amd import _lib, vis
-    lib = vis.denoise_lib()
+    lib = _lib.lib()
     ev = torch.zeros((64, 4), dtype=torch.float32, device='cuda')
     rng = torch.tensor([[0, 64]], dtype=torch.int64, device='cuda')
     out = torch.full((64 * 16,), GUARD, dtype=torch.uint8, device='cuda')

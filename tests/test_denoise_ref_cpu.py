@@ -193,7 +193,7 @@ def test_header_declares_the_entries_and_the_library_exports_them(tmp_path):
 def test_the_workspace_query_the_bands_and_the_host_side_refusals():
     """ec_denoise_workspace_bytes and ec_denoise_bands are host only.  The entry points check their arguments before they
     touch the device: every refusal comes back with its code and its message."""
-    lib = vis.denoise_lib()
+    lib = _lib.lib()
     # 32 K LDS words less one: a sensor that fits has one band and no halo, a larger one bands of rows - 2 r
     for (shape, r), bands in {((37, 53), 1): 1, ((100, 120), 3): 1, ((180, 240), 1): 2, ((180, 240), 3): 2, ((480, 640), 1): 10,
                               ((480, 640), 3): 11, ((1, 32767), 1): 1, ((2, 32767), 1): 0, ((3, 16383), 1): 0, ((8, 8), 0): 0, ((8, 8), 4): 0,

@@ -42,7 +42,6 @@ def run(name, packed, decay, grayscale=True, background_mask=True, **flags):
     prm = vis.time_surface_params(c['shape'], red, blue, decay, c['tau'], background_mask, max(e - b for b, e in c['ranges']),
                                   flags.get('flip_x', False), flags.get('negate_p', False), flags.get('reverse_t', False),
                                   sum(e - b for b, e in c['ranges']))
-    vis.surface_lib()
     _lib.launch('ec_events_to_time_surface_packed' if packed else 'ec_events_to_time_surface', ev, rng, F, prm, frames, last, stats)
     torch.cuda.synchronize()
     assert (frames[F] == GUARD).all() and (last[F] == -0x5A5A5A5A).all() and (stats[F] == GUARD).all(), 'wrote past the last frame'
@@ -191,7 +190,7 @@ def test_refusals(hip):
     decay, tau_us <= 0 in exp mode; F == 0 is EC_OK whatever the buffers."""
     import torch
     from eventclip_amd import _lib, vis
-    lib = vis.surface_lib()
+    lib = _lib.lib()
     ev = torch.zeros((64, 4), dtype=torch.float32, device='cuda')
     pk = torch.zeros((64,), dtype=torch.int64, device='cuda')
     rng = torch.tensor([[0, 64]], dtype=torch.int64, device='cuda')

@@ -39,7 +39,6 @@ def run(name, packed=False, background_mask=True, outputs=('frames', 'grid', 'st
     stats = torch.full((F + 1, ctypes.sizeof(vis.EcVoxelStats)), GUARD, dtype=torch.uint8, device='cuda') if 'stats' in outputs else None
     prm = vis.voxel_grid_params(c['shape'], B, background_mask, max(e - b for b, e in c['ranges']), flags.get('flip_x', False),
                                 flags.get('negate_p', False), flags.get('reverse_t', False), sum(e - b for b, e in c['ranges']))
-    vis.voxel_lib()
     _lib.launch('ec_events_to_voxel_grid_packed' if packed else 'ec_events_to_voxel_grid', ev, rng, F, prm, frames, grid, stats)
     torch.cuda.synchronize()
     assert frames is None or (frames[F] == GUARD).all(), 'frames written past the last frame'
@@ -70,7 +69,8 @@ def test_every_case_float_and_packed(name, hip):
     """Band counts 1 / 4 / 24 / 15 (cars, bands4, bands24, bands15x8), bins 2 / 3 / 8 (small*), span == 0 (single,
     same_tick), m == 0 (nothing: grey, white under the mask), events at t0 and t1 (ends), the 64-bit product (wide,
     wide3), the floor's edge (floor_edge), the cancelling pixel (cancel), negative_only, overlapping and gapped
-    ranges (ranges), skip, frac, more frames than compute units (many).  Forward and with all three flags, mask on
+    ranges (ranges), skip, frac, more frames than compute units (many), frame lengths around the
+    scan's unroll (lengths).  Forward and with all three flags, mask on
     and off, every output."""
     c = vg.cases()[name]
     for packed in ((False, True) if c['packable'] else (False,)):
@@ -103,7 +103,7 @@ def test_f_zero_and_the_device_side_refusals(hip):
     """F == 0 is EC_OK and touches nothing; a refused call touches nothing either."""
     import torch
     from eventclip_amd import _lib, vis
-    lib = vis.voxel_lib()
+    lib = _lib.lib()
     ev = torch.zeros((64, 4), dtype=torch.float32, device='cuda')
     rng = torch.tensor([[0, 64]], dtype=torch.int64, device='cuda')
     frames = torch.full((2, 8, 8, 3), GUARD, dtype=torch.uint8, device='cuda')

@@ -199,7 +199,7 @@ def test_the_band_query_and_the_host_side_refusals():
         assert vis.voxel_grid_bands(shape, B) == bands, (shape, B)
     assert vis.voxel_grid_bands((8, 8), 1) == vis.voxel_grid_bands((8, 8), 9) == vis.voxel_grid_bands((0, 8), 3) == 0
     assert vis.voxel_grid_bands((8, 13312), 3) == 8 and vis.voxel_grid_bands((8, 13313), 3) == 0       # 156 KB / 12 bytes
-    lib = vis.voxel_lib()
+    lib = _lib.lib()
     big = np.zeros(64, np.uint8)                                          # an aligned address; no refused call reads it
     addr = big.ctypes.data + (-big.ctypes.data) % 16
 

@@ -195,7 +195,7 @@ def check(got, want, decay):
 # t_last - tick, and the float rows and their packed form agree without a word about rounding.
 GRID = 64.
 GEOMETRIES = ((36, 52), (100, 120), (180, 240), (480, 640))        # one band, one band, 3 bands, 16 bands
-FRAME_LENGTHS = (0, 1, 63, 64, 1023, 1024, 1025, 4097, 8193)       # the 8 x 1024 load unroll and its tails
+FRAME_LENGTHS = (0, 1, 63, 64, 1023, 1024, 1025, 4097, 8191, 8192, 8193)      # the 8 x 1024 load unroll and its tails
 
 
 def _rows(x, y, k, p):

@@ -274,6 +274,8 @@ def cases():
     out.append(_case('frac', s, 3, ts._rows([5.9, -0.5, 51.9, -1.0], [3.7, 0.2, 35.9, 4], [1, 2, 3, 4], [1, -1, 1, 1]), packable=False))
     # more frames than compute units: the workgroups walk on.  Overlapping ranges
     out.append(_case('many', s, 3, ts._scatter(600 * 25 + 25, s, 3, 3000), [(25 * i, 25 * i + 50) for i in range(600)]))
+    # frame lengths around the scan's 8 x 1024 rows per round and its tails (prefixes of one stream; the first frame is empty)
+    out.append(_case('lengths', s, 3, ts._scatter(8193, s, 8, 2000), [(0, n) for n in (0, 1, 1023, 1024, 1025, 8191, 8192, 8193)]))
     return {c['name']: c for c in out}
 
 

@@ -36,7 +36,7 @@ def main():
     uniq, B = 8, a.samples
     lines = [f'| geometry | bands (r 1 / r 3) | events / sample | layout | variant | ms / {B} samples | M events / s | GB/s algorithmic | kept |',
              '|---|---|---|---|---|---|---|---|---|']
-    lib = vis.denoise_lib()
+    lib = _lib.lib()
     for name in ('n_cars', 'n_caltech', 'n_imagenet'):
         g = GEOMETRY[name]
         (H, W), n, N = g['resolution'], g['max_n'], g['N']

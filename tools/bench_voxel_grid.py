@@ -48,7 +48,6 @@ def main():
             grid = torch.empty((a.frames, H, W, 3), dtype=torch.int32, device='cuda')
             prm = vis.voxel_grid_params(shape, 3, True, n, False, False, False, a.frames * n)
             entry = 'ec_events_to_voxel_grid_packed' if packed else 'ec_events_to_voxel_grid'
-            vis.voxel_lib()
             variants = (('histogram', lambda: vis.events_to_frames_device(e, rng, shape, **kw)),
                         ('time surface, linear', lambda: vis.time_surface_device(e, rng, shape, decay='linear', **kw)),
                         ('voxel grid, frames (op)', lambda: vis.voxel_grid_device(e, rng, shape, **kw)),
