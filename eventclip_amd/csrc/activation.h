@@ -1,6 +1,6 @@
 // Exact GELU, x * Phi(x) (torch.nn.GELU(), open_clip's CLIPs without a -quickgelu suffix, Hugging Face
-// hidden_act "gelu"), for the GEMM epilogues (gemm.hip), the split row kernel (layernorm.hip) and the training
-// tower (vit_train.hip).  QuickGELU, the default everywhere, stays where it was in those files.
+// hidden_act "gelu"), for the GEMM epilogues (gemm.hip, forward and training) and the split row kernel
+// (layernorm.hip).  QuickGELU, the default everywhere, stays where it was in those files.
 //
 // Phi comes from Abramowitz & Stegun 7.1.26,
 //     erfc(z) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) exp(-z^2) + eps(z),  t = 1 / (1 + p z),  |eps| <= 1.5e-7,

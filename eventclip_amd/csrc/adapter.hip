@@ -19,6 +19,7 @@
 // T x T attention is done with scalar loops.  fp32 throughout, as the reference's
 // adapter (clip_cls.py:281-288).
 #include "common.h"
+#include "rowops.h"
 
 namespace {
 
@@ -78,17 +79,13 @@ __device__ void layer_norm(const float *in, float *out, int T, int W, const floa
     for (int t = wave; t < T; t += AD_THREADS / 64) {
         float s = 0.f;
         for (int c = lane; c < W; c += 64) s += in[t * W + c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        const float mean = s / (float)W;
+        const float mean = ec::wave_sum(s) / (float)W;
         float q = 0.f;
         for (int c = lane; c < W; c += 64) {
             const float d = in[t * W + c] - mean;
             q += d * d;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-        const float rstd = 1.f / sqrtf(q / (float)W + 1e-5f);
+        const float rstd = 1.f / sqrtf(ec::wave_sum(q) / (float)W + 1e-5f);
         for (int c = lane; c < W; c += 64) out[t * W + c] = (in[t * W + c] - mean) * rstd * g[c] + b[c];
     }
     __syncthreads();

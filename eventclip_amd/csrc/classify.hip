@@ -19,26 +19,18 @@
 //   classify_aggregate   per sample: logit = logit_scale 2^-e 2^-e' raw (powers of two: exact), softmax per view,
 //                        aggregation over the valid views.
 #include "common.h"
+#include "rowops.h"
 
 namespace {
+
+using ec::wave_max;
+using ec::wave_sum;
 
 constexpr int CL_THREADS = 256;
 constexpr int CL_MAXT = 16;
 
-__device__ __forceinline__ float wave_red_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_red_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// block-wide reduction of T values at once; red: [4][CL_MAXT] floats
+// block-wide reduction of T values at once; red: [4][CL_MAXT] floats.  The four wave results are combined pairwise
+// (train.hip's block_sum_f adds them in sequence: other bits)
 template <bool MAX>
 __device__ void block_reduce(float (&v)[CL_MAXT], int T, float *red)
 {
@@ -47,7 +39,7 @@ __device__ void block_reduce(float (&v)[CL_MAXT], int T, float *red)
 #pragma unroll
     for (int t = 0; t < CL_MAXT; t++)
         if (t < T) {
-            const float r = MAX ? wave_red_max(v[t]) : wave_red_sum(v[t]);
+            const float r = MAX ? wave_max(v[t]) : wave_sum(v[t]);
             if (lane == 0) red[wave * CL_MAXT + t] = r;
         }
     __syncthreads();
@@ -73,7 +65,7 @@ __global__ __launch_bounds__(256) void classify_prep_rows(const float *feats, in
         const float v = f[c];
         ss = fmaf(v, v, ss), mx = fmaxf(mx, fabsf(v));
     }
-    ss = wave_red_sum(ss), mx = wave_red_max(mx);
+    ss = wave_sum(ss), mx = wave_max(mx);
     // F.normalize(p=2, dim=-1, eps=1e-12): v / max(||v||, eps), the division as the reference does it
     const float d = normalize ? fmaxf(sqrtf(ss), 1e-12f) : 1.f;
     if (normalize) mx = mx / d;

@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/eventclip_hip.h"
 
@@ -51,5 +52,14 @@ int cu_count();
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
+
+// The runtime 16-bit dtype as a template argument: f(std::integral_constant<int, EC_F16 or EC_BF16>()) -> f's code.
+// Inside f, `decltype(dt)::value` names the kernels' DT; any other dtype is refused in `who`'s name.
+template <typename F> int dispatch16(int dtype, const char *who, F &&f)
+{
+    if (dtype == EC_F16) return f(std::integral_constant<int, EC_F16>());
+    if (dtype == EC_BF16) return f(std::integral_constant<int, EC_BF16>());
+    return fail(EC_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+}
 
 }  // namespace ec

@@ -13,13 +13,40 @@
 #include "activation.h"
 #include "common.h"
 #include "mfma.h"
+#include "rowops.h"
 #include "tower_ops.h"
 
 namespace {
 
 using namespace ec;
 
-constexpr int LN_MAXV = 8;  // float4 per lane: width <= 2048
+// ---- what the entry points below share: the rules of the row layout and the two launch shapes ----
+// a LayerNorm row lives in LN_MAXV float4 per lane (rowops.h)
+inline bool ln_width_ok(int width) { return width % 4 == 0 && width <= LN_MAXV * 256; }
+int ln_check_shape(const char *who, int rows, int width)
+{
+    EC_REQUIRE(rows >= 0 && width > 0 && ln_width_ok(width), "%s: width=%d must be a multiple of 4 and <= %d", who, width,
+               LN_MAXV * 256);
+    return EC_OK;
+}
+// rows are read and written in four-element vectors
+inline bool strides_ok(long ldx, long ldo) { return ldx % 4 == 0 && ldo % 4 == 0; }
+
+// one wave per row, four rows to a workgroup of 256
+template <typename K, typename... A> int launch_rows(K kern, long rows, hipStream_t s, A... args)
+{
+    hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(rows, 4L)), dim3(256), 0, s, args...);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+// grid-stride kernels over `pieces` thread-sized pieces: 256 to a workgroup, at most `cap` workgroups
+template <typename K, typename... A> int launch_flat(K kern, long pieces, long cap, hipStream_t s, A... args)
+{
+    const long wgs = ceil_div(pieces, 256L);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(wgs < cap ? wgs : cap)), dim3(256), 0, s, args...);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
 
 // base pointers against the vector width a kernel reads or writes them with (NULL, an optional buffer left out, passes):
 // 16 bytes for fp32 (float4), 8 for a 16-bit plane (four elements), 4 for e4m3 (four bytes)
@@ -28,50 +55,6 @@ inline bool aligned16(const void *a, const void *b = nullptr, const void *c = nu
                       const void *e = nullptr)
 {
     return aligned(a, 16) && aligned(b, 16) && aligned(c, 16) && aligned(d, 16) && aligned(e, 16);
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// normalises the lane-resident row in place: v = (v - mean) * rstd * gamma + beta
-__device__ __forceinline__ void ln_row(float4 (&v)[LN_MAXV], int nv, int width, int lane,
-                                       const float *gamma, const float *beta, float eps)
-{
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; i++)
-        if (i < nv) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    const float mean = wave_sum(s) / (float)width;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; i++)
-        if (i < nv) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (c * c + d * d);
-        }
-    const float rstd = 1.f / __builtin_sqrtf(wave_sum(q) / (float)width + eps);
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; i++)
-        if (i < nv) {
-            const int c = (i * 64 + lane) * 4;
-            const float4 g = *reinterpret_cast<const float4 *>(gamma + c);
-            const float4 b = *reinterpret_cast<const float4 *>(beta + c);
-            v[i].x = (v[i].x - mean) * rstd * g.x + b.x;
-            v[i].y = (v[i].y - mean) * rstd * g.y + b.y;
-            v[i].z = (v[i].z - mean) * rstd * g.z + b.z;
-            v[i].w = (v[i].w - mean) * rstd * g.w + b.w;
-        }
-}
-
-// lanes cover the row in float4 units: unit u = i*64 + lane, valid if u*4 < width
-__device__ __forceinline__ int units(int width, int lane)
-{
-    const int total = width / 4;
-    return (total - lane + 63) / 64;  // number of i with i*64 + lane < total
 }
 
 // HLIN: the row arrives as the two planes of the folded chain's residual stream (x = hi plane in DT, x_lo = fp16 lo plane,
@@ -331,24 +314,17 @@ namespace ec_tower {
 int vit_embed_hl(const float *patch, const float *cls, const float *pos, const float *gamma, const float *beta,
                  int n_img, int seq, int width, float eps, void *x_hi, void *x_lo, int dtype, ec_stream_t stream)
 {
-    EC_REQUIRE(width % 4 == 0 && width <= LN_MAXV * 256 && seq >= 2, "vit_embed_hl: bad shape");
+    EC_REQUIRE(ln_width_ok(width) && seq >= 2, "vit_embed_hl: bad shape");
     if (n_img == 0) return EC_OK;
     EC_REQUIRE(patch && cls && pos && gamma && beta && x_hi && x_lo, "vit_embed_hl: null buffer");
     EC_REQUIRE(aligned16(patch, cls, pos, gamma, beta) && aligned(x_hi, 8) && aligned(x_lo, 8), "vit_embed_hl: misaligned buffer");
     const long rows = (long)n_img * seq;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_EMBED, s, 0, (double)rows * width * 8.0);
-    const dim3 grid((unsigned)ec::ceil_div(rows, 4L));
-    if (dtype == EC_F16)
-        hipLaunchKernelGGL(vit_embed_kernel<EC_F16>, grid, dim3(256), 0, s, patch, cls, pos, gamma, beta, n_img, seq, width,
-                           eps, (float *)x_hi, (float *)nullptr, (_Float16 *)x_lo);
-    else if (dtype == EC_BF16)
-        hipLaunchKernelGGL(vit_embed_kernel<EC_BF16>, grid, dim3(256), 0, s, patch, cls, pos, gamma, beta, n_img, seq, width,
-                           eps, (float *)x_hi, (float *)nullptr, (_Float16 *)x_lo);
-    else
-        return ec::fail(EC_ERR_INVALID, "vit_embed_hl: unknown dtype %d", dtype);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return ec::dispatch16(dtype, "vit_embed_hl", [&](auto dt) {
+        return launch_rows(vit_embed_kernel<decltype(dt)::value>, rows, s, patch, cls, pos, gamma, beta, n_img, seq, width, eps,
+                           (float *)x_hi, (float *)nullptr, (_Float16 *)x_lo);
+    });
 }
 
 // fp32 residual stream -> the folded chain's planes: hi in `dtype`, lo ALWAYS fp16 (ec_vit_weights.precise_blocks: the
@@ -358,17 +334,11 @@ int split_hl(const float *x, long n, void *x_hi, void *x_lo, int dtype, ec_strea
     EC_REQUIRE(n >= 0 && n % 4 == 0 && x && x_hi && x_lo, "split_hl: bad arguments");
     EC_REQUIRE(aligned(x, 16) && aligned(x_hi, 8) && aligned(x_lo, 8), "split_hl: misaligned buffer");
     if (n == 0) return EC_OK;
-    const unsigned grid = (unsigned)((n / 4 + 255) / 256 < 65536 ? (n / 4 + 255) / 256 : 65536);
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)n * 8.0);
-    if (dtype == EC_F16)
-        hipLaunchKernelGGL((split16_kernel<EC_F16, true>), dim3(grid), dim3(256), 0, s, x, n, 0, x_hi, x_lo);
-    else if (dtype == EC_BF16)
-        hipLaunchKernelGGL((split16_kernel<EC_BF16, true>), dim3(grid), dim3(256), 0, s, x, n, 0, x_hi, x_lo);
-    else
-        return ec::fail(EC_ERR_INVALID, "split_hl: unknown dtype %d", dtype);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return ec::dispatch16(dtype, "split_hl", [&](auto dt) {
+        return launch_flat(split16_kernel<decltype(dt)::value, true>, n / 4, 65536, s, x, n, 0, x_hi, x_lo);
+    });
 }
 
 int join_hl_rows(const void *x_hi, const void *x_lo, long ld, int rows, int width, float *out, int dtype, ec_stream_t stream)
@@ -378,16 +348,10 @@ int join_hl_rows(const void *x_hi, const void *x_lo, long ld, int rows, int widt
     EC_REQUIRE(x_hi && x_lo && out, "join_hl_rows: null buffer");
     EC_REQUIRE(aligned(x_hi, 8) && aligned(x_lo, 8) && aligned(out, 16), "join_hl_rows: misaligned buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long n4 = (long)rows * (width / 4);
-    const unsigned grid = (unsigned)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    if (dtype == EC_F16)
-        hipLaunchKernelGGL(join_hl_kernel<EC_F16>, dim3(grid), dim3(256), 0, s, x_hi, (const _Float16 *)x_lo, ld, rows, width, out);
-    else if (dtype == EC_BF16)
-        hipLaunchKernelGGL(join_hl_kernel<EC_BF16>, dim3(grid), dim3(256), 0, s, x_hi, (const _Float16 *)x_lo, ld, rows, width, out);
-    else
-        return ec::fail(EC_ERR_INVALID, "join_hl_rows: unknown dtype %d", dtype);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return ec::dispatch16(dtype, "join_hl_rows", [&](auto dt) {
+        return launch_flat(join_hl_kernel<decltype(dt)::value>, (long)rows * (width / 4), 4096, s, x_hi, (const _Float16 *)x_lo, ld,
+                           rows, width, out);
+    });
 }
 
 }  // namespace ec_tower
@@ -411,14 +375,9 @@ EC_API int ec_row_stats(const void *x16, long ldx, int rows, int width, float ep
     EC_REQUIRE(x16 && stats && ldx % 8 == 0 && ((uintptr_t)x16 & 15) == 0, "ec_row_stats: null or misaligned buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)rows * width * 2.0);
-    if (dtype == EC_F16)
-        hipLaunchKernelGGL(row_stats_kernel<EC_F16>, dim3(ec::ceil_div(rows, 4)), dim3(256), 0, s, x16, ldx, rows, width, eps, stats);
-    else if (dtype == EC_BF16)
-        hipLaunchKernelGGL(row_stats_kernel<EC_BF16>, dim3(ec::ceil_div(rows, 4)), dim3(256), 0, s, x16, ldx, rows, width, eps, stats);
-    else
-        return ec::fail(EC_ERR_INVALID, "ec_row_stats: unknown dtype %d", dtype);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return ec::dispatch16(dtype, "ec_row_stats", [&](auto dt) {
+        return launch_rows(row_stats_kernel<decltype(dt)::value>, rows, s, x16, ldx, rows, width, eps, stats);
+    });
 }
 
 EC_API int ec_row_stats_merge(const float *sums, int rows, int groups, int width, float eps, float *stats,
@@ -443,96 +402,64 @@ EC_API int ec_split16(const float *x, long n, int gelu, void *hi16, void *lo16, 
     if (n == 0) return EC_OK;
     EC_REQUIRE(x && hi16 && lo16, "ec_split16: null buffer");
     EC_REQUIRE(aligned(x, 16) && aligned(hi16, 8) && aligned(lo16, 8), "ec_split16: misaligned buffer");
-    const unsigned grid = (unsigned)((n / 4 + 255) / 256 < 65536 ? (n / 4 + 255) / 256 : 65536);
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)n * 8.0);
-    if (gelu == 2 && dtype == EC_F16)
-        hipLaunchKernelGGL((split16_kernel<EC_F16, false, true>), dim3(grid), dim3(256), 0, s, x, n, gelu, hi16, lo16);
-    else if (gelu == 2 && dtype == EC_BF16)
-        hipLaunchKernelGGL((split16_kernel<EC_BF16, false, true>), dim3(grid), dim3(256), 0, s, x, n, gelu, hi16, lo16);
-    else if (dtype == EC_F16)
-        hipLaunchKernelGGL(split16_kernel<EC_F16>, dim3(grid), dim3(256), 0, s, x, n, gelu, hi16, lo16);
-    else if (dtype == EC_BF16)
-        hipLaunchKernelGGL(split16_kernel<EC_BF16>, dim3(grid), dim3(256), 0, s, x, n, gelu, hi16,
-                           lo16);
-    else
-        return ec::fail(EC_ERR_INVALID, "ec_split16: unknown dtype %d", dtype);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return ec::dispatch16(dtype, "ec_split16", [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return launch_flat(gelu == 2 ? split16_kernel<DT, false, true> : split16_kernel<DT>, n / 4, 65536, s, x, n, gelu, hi16, lo16);
+    });
 }
 
 EC_API int ec_layernorm_split(const float *x, long ldx, const int32_t *row_idx, const float *gamma,
                               const float *beta, int rows, int width, float eps, void *out16,
                               void *out16_lo, long ldo, int dtype, ec_stream_t stream)
 {
-    EC_REQUIRE(rows >= 0 && width > 0 && width % 4 == 0 && width <= LN_MAXV * 256,
-               "ec_layernorm: width=%d must be a multiple of 4 and <= %d", width, LN_MAXV * 256);
+    if (int rc = ln_check_shape("ec_layernorm", rows, width)) return rc;
     if (rows == 0) return EC_OK;
     EC_REQUIRE(x && gamma && beta && out16, "ec_layernorm: null buffer");
-    EC_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0, "ec_layernorm: strides must be multiples of 4");
+    EC_REQUIRE(strides_ok(ldx, ldo), "ec_layernorm: strides must be multiples of 4");
     EC_REQUIRE(aligned16(x, gamma, beta) && aligned(out16, 8) && aligned(out16_lo, 8), "ec_layernorm: misaligned buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(ec::ceil_div(rows, 4)), block(256);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)rows * width * 6.0);
-    if (dtype == EC_F16)
-        hipLaunchKernelGGL((layernorm_kernel<EC_F16, false>), grid, block, 0, s, x, (const _Float16 *)nullptr, ldx, row_idx, gamma,
-                           beta, rows, width, eps, out16, ldo, out16_lo);
-    else if (dtype == EC_BF16)
-        hipLaunchKernelGGL((layernorm_kernel<EC_BF16, false>), grid, block, 0, s, x, (const _Float16 *)nullptr, ldx, row_idx, gamma,
-                           beta, rows, width, eps, out16, ldo, out16_lo);
-    else
-        return ec::fail(EC_ERR_INVALID, "ec_layernorm: unknown dtype %d", dtype);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return ec::dispatch16(dtype, "ec_layernorm", [&](auto dt) {
+        return launch_rows(layernorm_kernel<decltype(dt)::value, false>, rows, s, x, (const _Float16 *)nullptr, ldx, row_idx, gamma,
+                           beta, rows, width, eps, out16, ldo, out16_lo, (void *)nullptr, 1.f, 1.f);
+    });
 }
 
 EC_API int ec_layernorm_hl(const void *x_hi, const void *x_lo, long ldx, const float *gamma, const float *beta, int rows,
                            int width, float eps, void *out16, void *out16_lo, long ldo, int dtype, ec_stream_t stream)
 {
-    EC_REQUIRE(rows >= 0 && width > 0 && width % 4 == 0 && width <= LN_MAXV * 256,
-               "ec_layernorm_hl: width=%d must be a multiple of 4 and <= %d", width, LN_MAXV * 256);
+    if (int rc = ln_check_shape("ec_layernorm_hl", rows, width)) return rc;
     if (rows == 0) return EC_OK;
     EC_REQUIRE(x_hi && x_lo && gamma && beta && out16 && out16_lo, "ec_layernorm_hl: null buffer");
-    EC_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0, "ec_layernorm_hl: strides must be multiples of 4");
+    EC_REQUIRE(strides_ok(ldx, ldo), "ec_layernorm_hl: strides must be multiples of 4");
     EC_REQUIRE(aligned(x_hi, 8) && aligned(x_lo, 8) && aligned16(gamma, beta) && aligned(out16, 8) && aligned(out16_lo, 8),
                "ec_layernorm_hl: misaligned buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(ec::ceil_div(rows, 4)), block(256);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)rows * width * 8.0);
-    const _Float16 *lo = static_cast<const _Float16 *>(x_lo);
-    if (dtype == EC_F16)
-        hipLaunchKernelGGL((layernorm_kernel<EC_F16, true>), grid, block, 0, s, x_hi, lo, ldx, (const int *)nullptr, gamma, beta,
-                           rows, width, eps, out16, ldo, out16_lo);
-    else if (dtype == EC_BF16)
-        hipLaunchKernelGGL((layernorm_kernel<EC_BF16, true>), grid, block, 0, s, x_hi, lo, ldx, (const int *)nullptr, gamma, beta,
-                           rows, width, eps, out16, ldo, out16_lo);
-    else
-        return ec::fail(EC_ERR_INVALID, "ec_layernorm_hl: unknown dtype %d", dtype);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return ec::dispatch16(dtype, "ec_layernorm_hl", [&](auto dt) {
+        return launch_rows(layernorm_kernel<decltype(dt)::value, true>, rows, s, x_hi, (const _Float16 *)x_lo, ldx,
+                           (const int *)nullptr, gamma, beta, rows, width, eps, out16, ldo, out16_lo, (void *)nullptr, 1.f, 1.f);
+    });
 }
 
 EC_API int ec_layernorm_hl8(const void *x_hi, const void *x_lo, long ldx, const float *gamma, const float *beta, int rows,
                             int width, float eps, void *out16, void *out_lo8, void *out_hi8, long ldo, int lo_exp, int hi_exp,
                             ec_stream_t stream)
 {
-    EC_REQUIRE(rows >= 0 && width > 0 && width % 4 == 0 && width <= LN_MAXV * 256,
-               "ec_layernorm_hl8: width=%d must be a multiple of 4 and <= %d", width, LN_MAXV * 256);
+    if (int rc = ln_check_shape("ec_layernorm_hl8", rows, width)) return rc;
     if (rows == 0) return EC_OK;
     EC_REQUIRE(x_hi && x_lo && gamma && beta && out16 && out_lo8, "ec_layernorm_hl8: null buffer");
-    EC_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0 && ldo >= width, "ec_layernorm_hl8: strides must be multiples of 4 (ldo >= width)");
+    EC_REQUIRE(strides_ok(ldx, ldo) && ldo >= width, "ec_layernorm_hl8: strides must be multiples of 4 (ldo >= width)");
     EC_REQUIRE(aligned(x_hi, 8) && aligned(x_lo, 8) && aligned16(gamma, beta) && aligned(out16, 8) && aligned(out_lo8, 4) &&
                    aligned(out_hi8, 4),
                "ec_layernorm_hl8: misaligned buffer");
     EC_REQUIRE(lo_exp >= -60 && lo_exp <= 60 && hi_exp >= -60 && hi_exp <= 60, "ec_layernorm_hl8: exponents outside -60 .. 60");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(ec::ceil_div(rows, 4)), block(256);
     ec::ProfScope prof(ec::PROF_LAYERNORM, s, 0, (double)rows * width * (out_hi8 ? 8.0 : 7.0));
-    hipLaunchKernelGGL((layernorm_kernel<EC_F16, true, true>), grid, block, 0, s, x_hi, static_cast<const _Float16 *>(x_lo), ldx,
-                       (const int *)nullptr, gamma, beta, rows, width, eps, out16, ldo, out_lo8, out_hi8, ldexpf(1.f, lo_exp),
-                       ldexpf(1.f, hi_exp));
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return launch_rows(layernorm_kernel<EC_F16, true, true>, rows, s, x_hi, (const _Float16 *)x_lo, ldx, (const int *)nullptr, gamma,
+                       beta, rows, width, eps, out16, ldo, out_lo8, out_hi8, ldexpf(1.f, lo_exp), ldexpf(1.f, hi_exp));
 }
 
 EC_API int ec_vit_embed(const float *patch, const float *cls, const float *pos, const float *gamma,
@@ -546,17 +473,15 @@ EC_API int ec_vit_embed_train(const float *patch, const float *cls, const float 
                               const float *beta, int n_img, int seq, int width, float eps, float *x,
                               float *pre, ec_stream_t stream)
 {
-    EC_REQUIRE(width % 4 == 0 && width <= LN_MAXV * 256 && seq >= 2, "ec_vit_embed: bad shape");
+    EC_REQUIRE(ln_width_ok(width) && seq >= 2, "ec_vit_embed: bad shape");
     if (n_img == 0) return EC_OK;
     EC_REQUIRE(patch && cls && pos && gamma && beta && x, "ec_vit_embed: null buffer");
     EC_REQUIRE(aligned16(patch, cls, pos, gamma, beta) && aligned16(x, pre), "ec_vit_embed: misaligned buffer");
     const long rows = (long)n_img * seq;
-    ec::ProfScope prof(ec::PROF_EMBED, static_cast<hipStream_t>(stream), 0, (double)rows * width * 8.0);
-    hipLaunchKernelGGL(vit_embed_kernel<-1>, dim3((unsigned)ec::ceil_div(rows, 4L)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), patch, cls, pos, gamma, beta, n_img, seq,
-                       width, eps, x, pre, (_Float16 *)nullptr);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ec::ProfScope prof(ec::PROF_EMBED, s, 0, (double)rows * width * 8.0);
+    return launch_rows(vit_embed_kernel<-1>, rows, s, patch, cls, pos, gamma, beta, n_img, seq, width, eps, x, pre,
+                       (_Float16 *)nullptr);
 }
 
 /* the tower drivers' internal entry points (tower_ops.h), exported so that they can be tested on their own */
@@ -585,12 +510,9 @@ EC_API int ec_text_embed(const int32_t *tokens, const float *table, const float 
     EC_REQUIRE(tokens && table && pos && x, "ec_text_embed: null buffer");
     EC_REQUIRE(aligned(tokens, 4) && aligned16(table, pos, x), "ec_text_embed: misaligned buffer");
     const long rows = (long)n_txt * ctx;
-    ec::ProfScope prof(ec::PROF_EMBED, static_cast<hipStream_t>(stream), 0, (double)rows * width * 8.0);
-    hipLaunchKernelGGL(text_embed_kernel, dim3((unsigned)ec::ceil_div(rows, 4L)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), tokens, table, pos, n_txt, ctx, width,
-                       vocab, x);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ec::ProfScope prof(ec::PROF_EMBED, s, 0, (double)rows * width * 8.0);
+    return launch_rows(text_embed_kernel, rows, s, tokens, table, pos, n_txt, ctx, width, vocab, x);
 }
 
 }  // extern "C"

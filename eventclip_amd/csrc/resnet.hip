@@ -9,6 +9,7 @@
 // attention pool's projections are the KS = 1 case (a plain row-major GEMM over pixel rows).
 #include "common.h"
 #include "mfma.h"
+#include "rowops.h"
 
 #include <initializer_list>
 
@@ -264,14 +265,14 @@ __global__ __launch_bounds__(64) void attnpool_attend_kernel(const typename T16<
         ps[t] = s;
         mx = fmaxf(mx, s);
     }
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_max(mx);
     float sum = 0.f;
     for (int t = d; t < L; t += 64) {
         const float e = __expf(ps[t] - mx);
         ps[t] = e;
         sum += e;
     }
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    sum = wave_sum(sum);
     __syncthreads();
     const E *vb = kb + C + d;
     float acc = 0.f;

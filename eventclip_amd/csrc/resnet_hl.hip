@@ -15,6 +15,7 @@
 // MFMAs triple.  Everything between the convolutions is fp32.  f16 only.
 #include "common.h"
 #include "mfma.h"
+#include "rowops.h"
 
 namespace ec {
 namespace {
@@ -291,13 +292,14 @@ __global__ __launch_bounds__(64) void attnpool_attend_hl_kernel(const _Float16 *
         ps[t] = s;
         mx = fmaxf(mx, s);
     }
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_max(mx);
     float sum = 0.f;
     for (int t = d; t < L; t += 64) {
         const float e = __expf(ps[t] - mx);
         ps[t] = e;
         sum += e;
     }
+    // (rowops.h's wave_sum, written out: through the call this kernel's scalar code comes out in another order)
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
     __syncthreads();
     const long vb = kb + C + d;

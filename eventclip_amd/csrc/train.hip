@@ -18,27 +18,20 @@
 // own gradient goes back into the vision tower (ec_ft_loss_grad, models/clip_cls_ft.py:196-256).
 #include "common.h"
 #include "mfma.h"
+#include "rowops.h"
 
 namespace {
+
+using ec::wave_max;
+using ec::wave_sum;
 
 constexpr int TR_THREADS = 256;
 constexpr int TR_WAVES = TR_THREADS / 64;
 
-__device__ __forceinline__ float wave_sum_f(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
+// the four wave results added in sequence (classify.hip's block_reduce pairs them: other bits)
 __device__ float block_sum_f(float v, float *red)
 {
-    v = wave_sum_f(v);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -49,7 +42,7 @@ __device__ float block_sum_f(float v, float *red)
 }
 __device__ float block_max_f(float v, float *red)
 {
-    v = wave_max_f(v);
+    v = wave_max(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -68,7 +61,7 @@ __global__ __launch_bounds__(64) void text_norm_kernel(const float *t, int D, fl
         const float x = t[(long)k * D + d];
         s += x * x;
     }
-    const float inv = 1.f / fmaxf(__builtin_sqrtf(wave_sum_f(s)), 1e-12f);
+    const float inv = 1.f / fmaxf(__builtin_sqrtf(wave_sum(s)), 1e-12f);
     for (int d = lane; d < D; d += 64) u[(long)k * D + d] = t[(long)k * D + d] * inv;
     if (lane == 0) inv_norm[k] = inv;
 }
@@ -89,7 +82,7 @@ __global__ __launch_bounds__(TR_THREADS) void fs_normalize_kernel(const float *f
     float s = 0.f;
     if (ok && normalize)
         for (int d = lane; d < D; d += 64) s += f[d] * f[d];
-    float inv = ok ? 1.f / fmaxf(__builtin_sqrtf(wave_sum_f(s)), 1e-12f) : 0.f;
+    float inv = ok ? 1.f / fmaxf(__builtin_sqrtf(wave_sum(s)), 1e-12f) : 0.f;
     if (ok && !normalize) inv = 1.f;
     for (int d = lane; d < D; d += 64) Fn[(long)r * D + d] = ok ? f[d] * inv : 0.f;
 }
@@ -159,10 +152,10 @@ __global__ __launch_bounds__(TR_THREADS) void fs_loss_grad_kernel(
         for (int v = wave; v < T; v += TR_WAVES) {
             float mx = -INFINITY;
             for (int k = lane; k < K; k += 64) mx = fmaxf(mx, lg[v * K + k]);
-            mx = wave_max_f(mx);
+            mx = wave_max(mx);
             float se = 0.f;
             for (int k = lane; k < K; k += 64) se += __expf(lg[v * K + k] - mx);
-            se = wave_sum_f(se);
+            se = wave_sum(se);
             if (lane == 0) vmax[v] = mx, vsum[v] = se, pvy[v] = __expf(lg[v * K + y] - mx) / se;
         }
         __syncthreads();
@@ -195,14 +188,14 @@ __global__ __launch_bounds__(64) void text_grad_finish_kernel(const float *u, co
     const int k = blockIdx.x, lane = threadIdx.x;
     float dot = 0.f;
     for (int d = lane; d < D; d += 64) dot += u[(long)k * D + d] * dU[(long)k * D + d];
-    dot = wave_sum_f(dot);
+    dot = wave_sum(dot);
     const float inv = inv_norm[k];
     for (int d = lane; d < D; d += 64)
         grad[(long)k * D + d] = (dU[(long)k * D + d] - u[(long)k * D + d] * dot) * inv;
     if (k == 0) {
         float s = 0.f;
         for (int b = lane; b < B; b += 64) s += loss_b[b];
-        s = wave_sum_f(s);
+        s = wave_sum(s);
         if (lane == 0) loss[0] = s / (float)B;                       // F.cross_entropy / nll_loss: mean
     }
 }
@@ -350,10 +343,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float *x, const float
     const float *xr = x + (long)r * N;
     float s = 0.f;
     for (int j = lane; j < N; j += 64) s += xr[j];
-    const float mean = wave_sum_f(s) / (float)N;
+    const float mean = wave_sum(s) / (float)N;
     float q = 0.f;
     for (int j = lane; j < N; j += 64) q += (xr[j] - mean) * (xr[j] - mean);
-    const float rs = 1.f / __builtin_sqrtf(wave_sum_f(q) / (float)N + 1e-5f);
+    const float rs = 1.f / __builtin_sqrtf(wave_sum(q) / (float)N + 1e-5f);
     for (int j = lane; j < N; j += 64) {
         const float h = (xr[j] - mean) * rs;
         xhat[(long)r * N + j] = h;
@@ -373,7 +366,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float *dy, const floa
         const float gy = dy[(long)r * N + j] * g[j];
         s1 += gy, s2 += gy * xhat[(long)r * N + j];
     }
-    s1 = wave_sum_f(s1) / (float)N, s2 = wave_sum_f(s2) / (float)N;
+    s1 = wave_sum(s1) / (float)N, s2 = wave_sum(s2) / (float)N;
     const float rs = rstd[r];
     for (int j = lane; j < N; j += 64) {
         const float v = rs * (dy[(long)r * N + j] * g[j] - s1 - xhat[(long)r * N + j] * s2);
@@ -526,8 +519,8 @@ __global__ __launch_bounds__(256) void normalize_bwd_kernel(const float *mixed, 
         const float m = mixed[mr * D + j];
         s += m * m, dot += fn[(long)r * D + j] * dfn[(long)r * D + j];
     }
-    float inv = ok ? scale / fmaxf(__builtin_sqrtf(wave_sum_f(s)), 1e-12f) : 0.f;
-    dot = wave_sum_f(dot);
+    float inv = ok ? scale / fmaxf(__builtin_sqrtf(wave_sum(s)), 1e-12f) : 0.f;
+    dot = wave_sum(dot);
     if (!normalize) inv = ok ? scale : 0.f, dot = 0.f;
     for (int j = lane; j < D; j += 64)
         dmixed[mr * D + j] = (dfn[(long)r * D + j] - fn[(long)r * D + j] * dot) * inv;
@@ -561,13 +554,13 @@ __global__ __launch_bounds__(TR_THREADS) void classify_dz_kernel(const float *fu
             if (!ok[v]) continue;
             float mx = -INFINITY;
             for (int k = lane; k < K; k += 64) mx = fmaxf(mx, fl[(long)v * K + k]);
-            mx = wave_max_f(mx);
+            mx = wave_max(mx);
             float se = 0.f, dot = 0.f;
             for (int k = lane; k < K; k += 64) {
                 const float e = expf(fl[(long)v * K + k] - mx);
                 se += e, dot += g[k] * e;
             }
-            se = wave_sum_f(se), dot = wave_sum_f(dot);
+            se = wave_sum(se), dot = wave_sum(dot);
             if (lane == 0) vmax[v] = mx, vsum[v] = se, vdot[v] = dot / se;
         }
     }

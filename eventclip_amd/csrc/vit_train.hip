@@ -26,9 +26,9 @@
 //   (LoRA on q k v o needs the attention weight gradients only: none of the MLP's dW GEMMs run);
 //   the image's gradient (ec_vit_train_backward_image) runs the chain down to the embedding whatever weight gradients
 //   are asked for: d image = unpatchify(d pre . conv1.weight), one more dX product and a permutation.
-#include "activation.h"
 #include "common.h"
 #include "mfma.h"
+#include "rowops.h"
 #include "tower_ops.h"
 
 namespace {
@@ -36,38 +36,20 @@ namespace {
 using namespace ec;
 using namespace ec_tower;
 
-constexpr int LN_MAXV = 8;   // float4 per lane: width <= 2048
 constexpr int SIZING_CUS = 256;
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int units(int width, int lane)
-{
-    const int total = width / 4;
-    return (total - lane + 63) / 64;
-}
-__device__ __forceinline__ float quick_gelu_f(float x)
-{
-    // x * sigmoid(1.702 x) with the exponential as __expf(-1.702 x): two multiplies in front of v_exp_f32.  NOT the GEMM
-    // epilogue's sequence (gemm.hip: quick_gelu folds -1.702 log2 e into one multiply): the two can differ in the last bit
-    return x * __builtin_amdgcn_rcpf(1.f + __expf(-1.702f * x));
-}
-
 // ------------------------------------------------------------------------------------------
-// Transposed 16-bit copies: dst_t[n][m] = f(src[row(m)][n]) for m < M, 0 for M <= m < Mp.
-// MODE 0: 16-bit source; 1: QuickGELU of a 16-bit source (3: the exact GELU, activation.h); 2: fp32 source, optionally also written row-major
-// as 16 bit (the dX GEMM's operand).  (The blocks' weight gradients no longer need these copies: weight_grad_rows.)
+// Transposed 16-bit copies: dst_t[n][m] = src[row(m)][n] (rounded to 16 bit) for m < M, 0 for M <= m < Mp.
+// MODE 0: 16-bit source; 2: fp32 source.  Only the patch embedding's weight gradient still needs them (the blocks'
+// weight gradients read the row-major activations: weight_grad_rows).
 // Logical row m reads source row (m / seq_out) * seq_in + seq_off + m % seq_out (seq_out = 0: row m):
 // the patch rows of the embedding gradient skip every sequence's class-token row.
 // ------------------------------------------------------------------------------------------
 template <int DT, int MODE>
 __global__ __launch_bounds__(256) void transpose_kernel(const void *src, long ld, int M, int N, int Mp, int seq_out,
-                                                        int seq_in, int seq_off, void *dst_t, void *dst_rm)
+                                                        int seq_in, int seq_off, void *dst_t)
 {
+    static_assert(MODE == 0 || MODE == 2, "transpose_kernel: 0 = 16-bit source, 2 = fp32 source");
     typedef typename T16<DT>::elem elem;
     typedef typename T16<DT>::v8 v8;
     constexpr int PITCH = 72;   // elements: 144-B rows, 16-B aligned
@@ -88,22 +70,12 @@ __global__ __launch_bounds__(256) void transpose_kernel(const void *src, long ld
                 const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
                 v[0] = to16(a.x, elem()), v[1] = to16(a.y, elem()), v[2] = to16(a.z, elem()), v[3] = to16(a.w, elem());
                 v[4] = to16(b.x, elem()), v[5] = to16(b.y, elem()), v[6] = to16(b.z, elem()), v[7] = to16(b.w, elem());
-                if (dst_rm) *reinterpret_cast<v8 *>((elem *)dst_rm + (long)m * N + n) = v;
             } else {
                 v = *reinterpret_cast<const v8 *>((const elem *)src + row * ld + n);
-                if (MODE == 1) {
-#pragma unroll
-                    for (int j = 0; j < 8; j++) v[j] = to16(quick_gelu_f((float)v[j]), elem());
-                }
-                if (MODE == 3) {
-#pragma unroll
-                    for (int j = 0; j < 8; j++) v[j] = to16(ec::gelu_erf((float)v[j]), elem());
-                }
             }
         }
-        if (dst_t) *reinterpret_cast<v8 *>(&tile[ml * PITCH + ch * 8]) = v;
+        *reinterpret_cast<v8 *>(&tile[ml * PITCH + ch * 8]) = v;
     }
-    if (!dst_t) return;
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < 2; it++) {
@@ -139,6 +111,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float *x, long ldx, c
         gm[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i < nv) gm[i] = *reinterpret_cast<const float4 *>(gamma + (i * 64 + lane) * 4);
     }
+    // statistics of its own, NOT ln_row's: this multiplies by 1 / width where ln_row divides by width, and the two round differently
     const float inv_w = 1.f / (float)width;
     for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
         float4 v[LN_MAXV], d[LN_MAXV];
@@ -228,32 +201,13 @@ __global__ __launch_bounds__(256) void ln_f32_kernel(const float *x, long ldx, c
     if (row >= rows) return;
     const int nv = units(width, lane);
     float4 v[LN_MAXV];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < LN_MAXV; i++)
-        if (i < nv) {
-            v[i] = *reinterpret_cast<const float4 *>(x + row * ldx + (i * 64 + lane) * 4);
-            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-        }
-    const float mean = wave_sum(s) / (float)width;
-    float q = 0.f;
+        if (i < nv) v[i] = *reinterpret_cast<const float4 *>(x + row * ldx + (i * 64 + lane) * 4);
+    ln_row(v, nv, width, lane, gamma, beta, eps);
 #pragma unroll
     for (int i = 0; i < LN_MAXV; i++)
-        if (i < nv) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (c * c + d * d);
-        }
-    const float rstd = 1.f / __builtin_sqrtf(wave_sum(q) / (float)width + eps);
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; i++)
-        if (i < nv) {
-            const int c = (i * 64 + lane) * 4;
-            const float4 g = *reinterpret_cast<const float4 *>(gamma + c);
-            const float4 b = *reinterpret_cast<const float4 *>(beta + c);
-            *reinterpret_cast<float4 *>(out + row * ldo + c) =
-                make_float4((v[i].x - mean) * rstd * g.x + b.x, (v[i].y - mean) * rstd * g.y + b.y,
-                            (v[i].z - mean) * rstd * g.z + b.z, (v[i].w - mean) * rstd * g.w + b.w);
-        }
+        if (i < nv) *reinterpret_cast<float4 *>(out + row * ldo + (i * 64 + lane) * 4) = v[i];
 }
 
 // column sums of a [M, N] matrix over row slabs: partial[slab][n] (bias gradients).  A workgroup owns 64 x 16
@@ -1061,18 +1015,16 @@ int check_geometry(const ec_vit_weights *w, const char *who)
 
 template <int MODE>
 int transpose(int dtype, const void *src, long ld, int M, int N, int Mp, int seq_out, int seq_in, int seq_off,
-              void *dst_t, void *dst_rm, hipStream_t s)
+              void *dst_t, hipStream_t s)
 {
     const dim3 grid((unsigned)(Mp / 64), (unsigned)((N + 63) / 64));
     ec::ProfScope prof(ec::PROF_TRANSPOSE, s, 0, (double)M * N * (MODE == 2 ? 4.0 : 2.0) + 2.0 * Mp * N);
-    if (dtype == EC_F16)
-        hipLaunchKernelGGL((transpose_kernel<EC_F16, MODE>), grid, dim3(256), 0, s, src, ld, M, N, Mp, seq_out, seq_in,
-                           seq_off, dst_t, dst_rm);
-    else
-        hipLaunchKernelGGL((transpose_kernel<EC_BF16, MODE>), grid, dim3(256), 0, s, src, ld, M, N, Mp, seq_out, seq_in,
-                           seq_off, dst_t, dst_rm);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return ec::dispatch16(dtype, "transpose", [&](auto dt) -> int {
+        hipLaunchKernelGGL((transpose_kernel<decltype(dt)::value, MODE>), grid, dim3(256), 0, s, src, ld, M, N, Mp, seq_out,
+                           seq_in, seq_off, dst_t);
+        EC_CHECK_HIP(hipGetLastError());
+        return EC_OK;
+    });
 }
 
 int reduce(const float *part, long stride, int P, long n, float *out, hipStream_t s)
@@ -1110,6 +1062,14 @@ template <typename T> int bias_grad(const T *src, long ld, int M, int N, const T
                            b.colpart);
     }
     return reduce(b.colpart, N, slabs, N, out, s);
+}
+// ... of a 16-bit matrix in the tower's dtype
+int bias_grad16(int dtype, const void *src, long ld, int M, int N, const TrainBufs &b, float *out, hipStream_t s)
+{
+    return ec::dispatch16(dtype, "bias gradient", [&](auto dt) {
+        typedef typename T16<decltype(dt)::value>::elem elem;
+        return bias_grad(static_cast<const elem *>(src), ld, M, N, b, out, s);
+    });
 }
 
 // dW[n_out, n_in] = A_t[n_out, Mp] . B_t[n_in, Mp]^T in K-batches, reduced into `out` (or, conv: folded)
@@ -1255,10 +1215,11 @@ int lora_grads(int dtype, const LoraJob *jobs, int n, int M, int W, int r, const
         slab = slab < b.lr_slab ? b.lr_slab : slab;
         const int slabs = (Mp + slab - 1) / slab;
         oa.slab_rows = slab, ra.slabs = slabs;
-        if (dtype == EC_F16)
-            launch_project<EC_F16>(pa, np, share_p, RT, s), launch_outer<EC_F16>(oa, no, slabs, share_o, RT, s);
-        else
-            launch_project<EC_BF16>(pa, np, share_p, RT, s), launch_outer<EC_BF16>(oa, no, slabs, share_o, RT, s);
+        EC_TRY(ec::dispatch16(dtype, "LoRA gradients", [&](auto dt) -> int {
+            constexpr int DT = decltype(dt)::value;
+            launch_project<DT>(pa, np, share_p, RT, s), launch_outer<DT>(oa, no, slabs, share_o, RT, s);
+            return EC_OK;
+        }));
         hipLaunchKernelGGL(lowrank_reduce_kernel, dim3((unsigned)(((long)r * W + 255) / 256), (unsigned)n), dim3(256), 0, s, ra);
     }
     EC_CHECK_HIP(hipGetLastError());
@@ -1274,12 +1235,11 @@ int ln_backward(const float *x, long ldx, const float *dy, long ldy, const float
     const bool want = dg || db;
     {
         ec::ProfScope prof(ec::PROF_LN_BWD, s, 0, (double)rows * W * (accumulate ? 16.0 : 12.0));
-        if (dtype == EC_BF16)
-            hipLaunchKernelGGL(ln_bwd_kernel<EC_BF16>, dim3((unsigned)wgs), dim3(256), 0, s, x, ldx, dy, ldy, gamma, rows, W,
-                               LN_EPS, dx, ldo, accumulate, want ? partials : (float *)nullptr, dx16);
-        else
-            hipLaunchKernelGGL(ln_bwd_kernel<EC_F16>, dim3((unsigned)wgs), dim3(256), 0, s, x, ldx, dy, ldy, gamma, rows, W,
-                               LN_EPS, dx, ldo, accumulate, want ? partials : (float *)nullptr, dx16);
+        EC_TRY(ec::dispatch16(dtype, "LayerNorm backward", [&](auto dt) -> int {
+            hipLaunchKernelGGL(ln_bwd_kernel<decltype(dt)::value>, dim3((unsigned)wgs), dim3(256), 0, s, x, ldx, dy, ldy, gamma,
+                               rows, W, LN_EPS, dx, ldo, accumulate, want ? partials : (float *)nullptr, dx16);
+            return EC_OK;
+        }));
     }
     EC_CHECK_HIP(hipGetLastError());
     // (d gamma | d beta lie side by side in a partial row; side by side in the gradient buffer too -> one launch)
@@ -1529,10 +1489,7 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
         if (q.fc2_b) EC_TRY(bias_grad<float>(b.dx, W, M, W, b, q.fc2_b, s));
         if (q.fc2_w) EC_TRY(weight_grad_rows(dt, b.dx16, W, b.gact[l], 4L * W, W, 4 * W, M, b, q.fc2_w, stream));
         EC_TRY(Gemm(M, 4 * W, W, dt, EC_EPI_GELU_BWD16, b.dx16, pt.fc2_wt, nullptr, b.g16).aux(b.u[l]).act(wt->activation).run(stream));
-        if (q.fc1_b) {
-            if (dt == EC_F16) EC_TRY(bias_grad<_Float16>((const _Float16 *)b.g16, 4L * W, M, 4 * W, b, q.fc1_b, s));
-            else EC_TRY(bias_grad<__bf16>((const __bf16 *)b.g16, 4L * W, M, 4 * W, b, q.fc1_b, s));
-        }
+        if (q.fc1_b) EC_TRY(bias_grad16(dt, b.g16, 4L * W, M, 4 * W, b, q.fc1_b, s));
         if (q.fc1_w) EC_TRY(weight_grad_rows(dt, b.g16, 4L * W, b.h2[l], W, 4 * W, W, M, b, q.fc1_w, stream));
         EC_TRY(gemm_rows32(M, W, 4 * W, dt, EC_EPI_STORE32, b.g16, pt.fc1_wt, b.dh32, nullptr, nullptr, b.part,
                            b.part_floats, stream));
@@ -1544,10 +1501,7 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
         EC_TRY(Gemm(M, W, W, dt, EC_EPI_STORE16, b.dx16, pt.out_wt, nullptr, b.da16).run(stream));
         EC_TRY(ec_attention_backward(b.qkv[l], b.att[l], b.lse[l], b.da16, b.g16, b.delta, n_img, S, W, w->heads, dt,
                                      stream));
-        if (q.qkv_b) {
-            if (dt == EC_F16) EC_TRY(bias_grad<_Float16>((const _Float16 *)b.g16, 3L * W, M, 3 * W, b, q.qkv_b, s));
-            else EC_TRY(bias_grad<__bf16>((const __bf16 *)b.g16, 3L * W, M, 3 * W, b, q.qkv_b, s));
-        }
+        if (q.qkv_b) EC_TRY(bias_grad16(dt, b.g16, 3L * W, M, 3 * W, b, q.qkv_b, s));
         const bool lora_qkv = has_lora(l, 0) || has_lora(l, 1) || has_lora(l, 2);
         if (q.qkv_w) EC_TRY(weight_grad_rows(dt, b.g16, 3L * W, b.h1[l], W, 3 * W, W, M, b, q.qkv_w, stream));
         if (lora_qkv || has_lora(l, 3)) {
@@ -1589,8 +1543,8 @@ static int backward_stages(const ec_vit_weights *w, const ec_vit_train_weights *
     }
     if (gr->conv_w) {
         const int R = n_img * G;
-        EC_TRY(transpose<2>(dt, b.dh32, W, R, W, Mp, G, S, 1, b.ta, nullptr, s));
-        EC_TRY(transpose<0>(dt, patches, w->kpad, R, w->kpad, Mp, 0, 0, 0, b.tb, nullptr, s));
+        EC_TRY(transpose<2>(dt, b.dh32, W, R, W, Mp, G, S, 1, b.ta, s));
+        EC_TRY(transpose<0>(dt, patches, w->kpad, R, w->kpad, Mp, 0, 0, 0, b.tb, s));
         EC_TRY(weight_grad(dt, b.ta, b.tb, W, w->kpad, b, gr->conv_w, 3 * w->patch * w->patch, stream));
     }
     if (image) EC_TRY(embed_data_grad(w, image->conv_wt, image->conv_wt_lo, b.dx16, n_img, d_pix, image->d_image, stream));
@@ -1697,14 +1651,11 @@ EC_API int ec_pack_weight16_batched(const ec_pack_item *items, int n_items, int 
     const dim3 grid((unsigned)((cols + 63) / 64), (unsigned)((rows + 63) / 64), (unsigned)n_items);
     hipStream_t s = static_cast<hipStream_t>(stream);
     ec::ProfScope prof(ec::PROF_PACK, s, 0, (double)rows * cols * 10.0 * n_items);
-    if (dtype == EC_F16)
-        hipLaunchKernelGGL(pack_weight_kernel<EC_F16>, grid, dim3(256), 0, s, items, rows, cols);
-    else if (dtype == EC_BF16)
-        hipLaunchKernelGGL(pack_weight_kernel<EC_BF16>, grid, dim3(256), 0, s, items, rows, cols);
-    else
-        return ec::fail(EC_ERR_INVALID, "ec_pack_weight16_batched: unknown dtype %d", dtype);
-    EC_CHECK_HIP(hipGetLastError());
-    return EC_OK;
+    return ec::dispatch16(dtype, "ec_pack_weight16_batched", [&](auto dt) -> int {
+        hipLaunchKernelGGL(pack_weight_kernel<decltype(dt)::value>, grid, dim3(256), 0, s, items, rows, cols);
+        EC_CHECK_HIP(hipGetLastError());
+        return EC_OK;
+    });
 }
 
 EC_API int ec_fingerprint_batched(const ec_span_item *items, int n_items, int64_t max_n, uint64_t *out, ec_stream_t stream)
