@@ -1,6 +1,6 @@
-// events -> polarity-histogram frames on gfx950 (and, in the last three sections, -> time-surface and -> voxel-grid frames
-// and the background-activity filter in front of all three: they share parse(), the packed format and the block
-// reductions of this file).
+// events -> polarity-histogram frames on gfx950 (and, in the last four sections, -> time-surface and -> voxel-grid frames,
+// the background-activity filter in front of all three and the fixed-duration windows that cut a stream into their ranges:
+// they share parse(), the packed format, the tick and the reductions of this file).
 //
 // Replaces /root/reference/datasets/vis.py make_event_histogram (:6-41) +
 // parse_events (:44-52) as driven by events2frames (:75-117).
@@ -32,6 +32,7 @@
 #include "eventclip_time_surface.h"
 #include "eventclip_voxel_grid.h"
 #include "eventclip_denoise.h"
+#include "eventclip_time_windows.h"
 
 // numpy evaluates every ufunc with one rounding per operation: no FMA contraction anywhere in
 // this file (the one fused multiply-add of the reference is written out explicitly).
@@ -2552,6 +2553,181 @@ int launch_denoise(const void *events, const int64_t *sample_range, int B, const
                        2.0 * event_bytes<EV>(0, 0, 0, prm->total_events), stream, a);
 }
 
+// ---------------------------------------------------------------------------------------------
+// fixed-duration event windows (include/eventclip_time_windows.h states the definition, steps 1 - 7).
+//
+// bounds[b, k] are counts of ticks below an edge, i.e. the first row at or above it.  In a sorted sample that row is the one
+// place where the ticks step over the edge: the thread holding row i looks at tick_{i-1} and tick_i -- which is also the
+// whole order check -- and, where the tick rises, writes i into every edge e with tick_{i-1} < e <= tick_i.  Row `begin` has
+// no predecessor (tick -inf), and one virtual row at `end` carries tick +inf: every edge of a sorted sample is written
+// exactly once, by a plain store, with no atomics on the bounds and no search.  The edges of kind `side` are an arithmetic
+// progression A + k stride (from_last: A - k stride), so the k of (tick_{i-1}, tick_i] are a range between two integer
+// divisions, clipped to the rows of bounds the sample owns; a silent gap makes one thread write all the edges inside it, at
+// most max_windows of each kind.
+// A sample's n + 1 rows are cut into slices of TW_SLICE rows; workgroup (sample, w) walks slices w, w + walkers, ...  (the
+// grid is sized from total_events, but whatever it is every slice is walked once).  Per slice a thread takes TW_UNROLL rows
+// TW_THREADS apart, all loads in flight at once (for_events' pattern); the predecessor's tick comes from the lane below, for
+// lane 0 from the wave below through LDS, and for the slice's first row from the one row before the slice.
+// Descents are counted per thread, summed per wave, and added with one atomic per wave that saw any; that wave also puts
+// windows to -1.  time_windows_init_kernel has zeroed both words before.
+// ---------------------------------------------------------------------------------------------
+constexpr int TW_SLICE = EC_TIME_WINDOWS_SLICE_ROWS, TW_UNROLL = EC_TIME_WINDOWS_UNROLL;
+constexpr int TW_THREADS = TW_SLICE / TW_UNROLL, TW_WAVES = TW_THREADS / 64;
+constexpr int TW_MAX_GROUPS = 4096;                    // workgroups of one launch, unless B alone is more
+static_assert(TW_THREADS * TW_UNROLL == TW_SLICE && TW_WAVES * 64 == TW_THREADS && TW_THREADS <= 1024, "slice = unroll x whole waves");
+
+struct TwArgs {
+    const void *events;      // float4 (x, y, t, p) or packed 8-byte events
+    const long long *range;  // [B,2]
+    int B, walkers;          // workgroups per sample
+    unsigned dt, stride;
+    unsigned magic;          // floor(x / stride) == (x * magic) >> shift for 0 <= x < 2^31 (tw_magic)
+    int shift;
+    int max_windows, from_last;
+    long long *bounds;       // [B, max_windows, 2]
+    ec_time_windows_stats *stats;
+};
+
+__global__ void time_windows_init_kernel(const TwArgs a)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    a.stats[b].windows = 0;                                              // an empty sample: this and nothing else
+    if (a.range[2 * b] < a.range[2 * b + 1]) a.stats[b].unsorted = 0;
+}
+
+// floor(x / stride) for 0 <= x < 2^31 -- the operands of every division below are a difference of two of tick, tick + 1 and
+// tick - dt, plus stride - 1 where the quotient is rounded up -- as a multiplication by the host's round-up reciprocal (Granlund & Montgomery 1994: magic = ceil(2^(31 + l) /
+// stride), l = ceil(log2 stride), is below 2^32 and exact for every 31-bit x; the product stays below 2^63).  A 32-bit
+// division is some 30 instructions, and a row asks for up to four.
+__device__ __forceinline__ long long tw_div(const TwArgs &a, long long x)
+{
+    return (long long)(((unsigned long long)(unsigned)x * a.magic) >> a.shift);
+}
+inline void tw_magic(unsigned stride, unsigned &magic, int &shift)
+{
+    int l = 0;
+    while ((1ull << l) < stride) l++;
+    shift = 31 + l;
+    magic = (unsigned)(((1ull << shift) + stride - 1) / stride);
+}
+
+// Row `row` (tick c, predecessor's tick p; first: no predecessor, last: the virtual row) into the edges it is the first
+// row at or above.  windows K of the sample are written: k in 0 .. K - 1.
+__device__ __forceinline__ void tw_scatter(const TwArgs &a, long long t_first, long long t_last, long long K, long long *bounds,
+                                           bool first, bool last, long long p, long long c, long long row)
+{
+    const long long dt = a.dt;
+    const unsigned stride = a.stride;
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+        long long klo, khi;
+        if (!a.from_last) {                            // edge k = A + k stride, rising with k
+            const long long A = t_first + (side ? dt : 0);
+            klo = first || p < A ? 0 : tw_div(a, p - A) + 1;
+            khi = last ? K - 1 : c < A ? -1 : min(tw_div(a, c - A), K - 1);
+        } else {                                       // edge k = A - k stride, falling with k: the first row with d < ...
+            const long long A = t_last + 1 - (side ? 0 : dt);
+            klo = last || A <= c ? 0 : tw_div(a, A - c + stride - 1);
+            khi = first ? K - 1 : A <= p ? -1 : min(tw_div(a, A - p + stride - 1) - 1, K - 1);
+        }
+        for (int k = (int)min(klo, K); k <= (int)khi; k++) bounds[2 * k + side] = row;          // (khi < K <= max_windows)
+    }
+}
+
+template <typename EV>
+__global__ __launch_bounds__(TW_THREADS) void time_windows_kernel(const TwArgs a)
+{
+    __shared__ unsigned tail[TW_UNROLL][TW_WAVES];     // the tick of every wave's last lane, per round
+    const int b = blockIdx.x / a.walkers, w = blockIdx.x - b * a.walkers;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long e0 = a.range[2 * b], n = a.range[2 * b + 1] - e0;
+    if (n <= 0 || (long long)w * TW_SLICE > n) return;                   // (uniform) rows 0 .. n: n is the virtual one
+    const EV *ev = reinterpret_cast<const EV *>(a.events) + e0;
+    const long long t_first = tick_of(ev[0]), t_last = tick_of(ev[n - 1]);
+    // (t_last < t_first only in an unsorted sample, whose bounds mean nothing: any count that keeps the stores in its rows)
+    const long long windows = t_last >= t_first ? tw_div(a, t_last - t_first) + 1 : 1;
+    const long long K = min(windows, (long long)a.max_windows);
+    long long *bounds = a.bounds + (long long)b * a.max_windows * 2;
+    unsigned descents = 0;
+    for (long long s = w; s * TW_SLICE <= n; s += a.walkers) {
+        const long long j0 = s * TW_SLICE + threadIdx.x;
+        EV e[TW_UNROLL];
+#pragma unroll
+        for (int k = 0; k < TW_UNROLL; k++) {
+            const long long j = j0 + (long long)k * TW_THREADS;
+            e[k] = ev[j < n ? j : n - 1];                                // (rows >= n re-read the last event)
+        }
+        unsigned before = 0;                                             // the one row before the slice (s TW_SLICE - 1 < n)
+        if (threadIdx.x == 0 && s > 0) before = tick_of(ev[s * TW_SLICE - 1]);
+        __asm__ volatile("" ::: "memory");
+        unsigned c[TW_UNROLL];
+#pragma unroll
+        for (int k = 0; k < TW_UNROLL; k++) {
+            c[k] = tick_of(e[k]);
+            if (lane == 63) tail[k][wave] = c[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < TW_UNROLL; k++) {
+            const long long j = j0 + (long long)k * TW_THREADS;
+            unsigned p = __shfl_up(c[k], 1, 64);
+            if (lane == 0) p = wave > 0 ? tail[k][wave - 1] : k > 0 ? tail[k - 1][TW_WAVES - 1] : before;
+            const bool first = j == 0, last = j == n;
+            if (j <= n) {
+                descents += !first && !last && c[k] < p;
+                if (first || last || c[k] > p) tw_scatter(a, t_first, t_last, K, bounds, first, last, p, c[k], e0 + j);
+            }
+        }
+        __syncthreads();                                                 // tail is read: the next slice may write it
+    }
+    const unsigned in_wave = wave_sum_u32(descents);
+    if (lane == 0 && in_wave > 0) {
+        atomicAdd(&a.stats[b].unsorted, in_wave);
+        atomicExch(&a.stats[b].windows, -1);
+    }
+    if (w == 0 && threadIdx.x == 0) {
+        a.stats[b].t_first = (unsigned)t_first, a.stats[b].t_last = (unsigned)t_last;
+        atomicCAS(&a.stats[b].windows, 0, (int)windows);                 // unless a wave has put -1 there (windows >= 1)
+    }
+}
+
+template <typename EV>
+int launch_time_windows(const char *name, const void *events, const int64_t *sample_range, int B, const ec_time_windows_params *prm,
+                        int64_t *bounds, ec_time_windows_stats *stats, ec_stream_t stream)
+{
+    int rc;
+    if (launch_is_over(name, prm, 'B', B, events && sample_range && bounds && stats, rc)) return rc;
+    EC_REQUIRE(prm->dt_us >= 1 && prm->dt_us <= (uint32_t)EC_TIME_WINDOWS_MAX_US, "%s: dt_us=%u outside 1 .. %d", name, prm->dt_us,
+               (int)EC_TIME_WINDOWS_MAX_US);
+    EC_REQUIRE(prm->stride_us >= 1 && prm->stride_us <= (uint32_t)EC_TIME_WINDOWS_MAX_US, "%s: stride_us=%u outside 1 .. %d", name,
+               prm->stride_us, (int)EC_TIME_WINDOWS_MAX_US);
+    EC_REQUIRE(prm->max_windows > 0, "%s: max_windows=%d", name, prm->max_windows);
+    EC_REQUIRE(((uintptr_t)events & (sizeof(EV) - 1)) == 0, "%s: events must be %d-byte aligned", name, (int)sizeof(EV));
+    EC_REQUIRE((((uintptr_t)sample_range | (uintptr_t)bounds) & 7) == 0 && ((uintptr_t)stats & 3) == 0,
+               "%s: sample_range and bounds must be 8-byte and stats 4-byte aligned", name);
+
+    TwArgs a = {};
+    a.events = events;
+    a.range = reinterpret_cast<const long long *>(sample_range);
+    a.B = B;
+    a.dt = prm->dt_us, a.stride = prm->stride_us;
+    tw_magic(a.stride, a.magic, a.shift);
+    a.max_windows = prm->max_windows, a.from_last = prm->from_last != 0;
+    a.bounds = reinterpret_cast<long long *>(bounds), a.stats = stats;
+    // no sample is longer than total_events: that many slices' worth of workgroups per sample, while the launch has them
+    const long most = std::max(1L, (long)TW_MAX_GROUPS / B);
+    a.walkers = (int)(prm->total_events > 0 ? std::min<long>(most, (long)(prm->total_events / TW_SLICE) + 1) : most);
+
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // algorithmic bytes: every event read once, every pair of bounds written once
+    ec::ProfScope prof(ec::PROF_EVENTS, hs, 0, event_bytes<EV>(0, 0, 0, prm->total_events) + 16.0 * B * prm->max_windows);
+    hipLaunchKernelGGL(time_windows_init_kernel, dim3((unsigned)ec::ceil_div(B, 256)), dim3(256), 0, hs, a);
+    hipLaunchKernelGGL(time_windows_kernel<EV>, dim3((unsigned)((long)B * a.walkers)), dim3(TW_THREADS), 0, hs, a);
+    EC_CHECK_HIP(hipGetLastError());
+    return EC_OK;
+}
+
 }  // namespace
 
 #ifdef EC_EVENTS_DIAG
@@ -2634,6 +2810,19 @@ extern "C" EC_API int ec_denoise_events_packed(const uint64_t *events, const int
 extern "C" EC_API size_t ec_denoise_workspace_bytes(const ec_denoise_params *prm, int B) { return denoise_workspace_bytes(prm, B); }
 
 extern "C" EC_API int ec_denoise_bands(int H, int W, int radius) { return denoise_plan(H, W, radius).bands; }
+
+extern "C" EC_API int ec_time_windows(const float *events, const int64_t *sample_range, int B, const ec_time_windows_params *prm,
+                                      int64_t *bounds, ec_time_windows_stats *stats, ec_stream_t stream)
+{
+    return launch_time_windows<float4>("ec_time_windows", events, sample_range, B, prm, bounds, stats, stream);
+}
+
+extern "C" EC_API int ec_time_windows_packed(const uint64_t *events, const int64_t *sample_range, int B,
+                                             const ec_time_windows_params *prm, int64_t *bounds, ec_time_windows_stats *stats,
+                                             ec_stream_t stream)
+{
+    return launch_time_windows<packed_t>("ec_time_windows_packed", events, sample_range, B, prm, bounds, stats, stream);
+}
 
 extern "C" EC_API int ec_center_events(float *events, const int64_t *sample_range, int B, int H, int W,
                                        ec_stream_t stream)

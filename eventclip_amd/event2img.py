@@ -7,7 +7,8 @@ The reference converts ONE sample per ``__getitem__`` in CPU worker processes:
 and the loader stacks samples into ``img [B, T, 3, R, R]``, ``valid_mask [B, T]``.
 Here a whole batch goes through two kernels (events->frames, preprocess) with the
 chunk bookkeeping (``split_event_count``, ``max_imgs``, padding, masks) done on the
-host from event counts alone.  No CPU fallback.
+host from event counts alone (``split_method='time_window'``: from the window bounds a third kernel
+finds on the device).  No CPU fallback.
 """
 import copy
 
@@ -34,6 +35,13 @@ class Event2ImagePipeline:
         ``denoise`` (not in the reference; absent or ``None`` = off): ``dict(dt=seconds, radius=1)`` puts the
         background-activity filter of include/eventclip_denoise.h in front of whichever form is chosen: an event stays
         only if a neighbouring pixel fired in the ``dt`` before it, and the chunks are cut from the survivors.
+        ``split_method`` is ``'event_count'`` (views of ``N`` events) or ``'time_window'`` (not in the reference: the
+        fixed-duration windows of include/eventclip_time_windows.h), which reads ``window`` (seconds, required), ``stride``
+        (seconds, default ``window``), ``min_events`` (1: a window with fewer rows is no view), ``max_windows`` (64: a
+        sample that spans more raises) and ``max_imgs`` (T itself, default 10) and ignores ``N``.  The events of a
+        sample must be sorted by time.  The result gains ``window_index`` [B, T] (CUDA int32): the window k of every
+        view, -1 for a padded one; window k starts ``k * stride`` after the sample's first event (with tflip: ends
+        ``k * stride`` before its last).
     n_px: CLIP input resolution.  patch/kpad/dtype: when given, ``__call__`` emits the
         16-bit im2col rows for ``CLIP.encode_patches`` instead of fp32 images.
     frames_u8: emit the resized + cropped uint8 frames (``frames_u8`` [Fv, R, R, 3]) instead, the input of
@@ -46,13 +54,26 @@ class Event2ImagePipeline:
         self.resolution = tuple(resolution)
         self.split_method = qa['split_method']
         self.event_rep = qa['convert_method']
-        assert self.split_method == 'event_count'                       # event2img.py:69
+        assert self.split_method in vis.SPLIT_METHODS                   # event2img.py:69, + 'time_window'
         if self.event_rep not in vis.CONVERT_METHODS:                    # vis.py:113
             raise NotImplementedError(f'{self.event_rep} not implemented!')
-        self.N = int(qa['N'])
-        max_imgs = round(max_n / self.N)                                 # event2img.py:70
-        max_max_imgs = qa.pop('max_imgs', 10)                            # event2img.py:71
-        self.max_imgs = max(min(max_imgs, max_max_imgs), 1)              # event2img.py:72
+        if self.split_method == 'time_window':
+            # views are windows of fixed duration (include/eventclip_time_windows.h); N is not read, T = max_imgs
+            if 'window' not in qa:
+                raise ValueError("split_method='time_window' reads quantize_args['window'] (seconds)")
+            self.window = float(qa['window'])
+            self.stride = float(qa['stride']) if qa.get('stride') is not None else self.window
+            vis.time_window_us(self.window), vis.time_window_us(self.stride, 'stride')
+            self.min_events, self.max_windows = int(qa.get('min_events', 1)), int(qa.get('max_windows', 64))
+            if self.min_events < 1 or self.max_windows < 1:
+                raise ValueError(f'min_events={self.min_events}, max_windows={self.max_windows}: at least 1 each')
+            self.N = None
+            self.max_imgs = max(int(qa.pop('max_imgs', 10)), 1)
+        else:
+            self.N = int(qa['N'])
+            max_imgs = round(max_n / self.N)                             # event2img.py:70
+            max_max_imgs = qa.pop('max_imgs', 10)                        # event2img.py:71
+            self.max_imgs = max(min(max_imgs, max_max_imgs), 1)          # event2img.py:72
         self.grayscale = qa.get('grayscale', True)
         self.thresh = float(qa.get('thresh', 10.))
         self.count_non_zero = bool(qa.get('count_non_zero', False))
@@ -126,11 +147,55 @@ class Event2ImagePipeline:
         ri = torch.from_numpy(row_idx)
         return fr, ri, ri >= 0
 
-    def frames(self, events, frame_range, hflip=False, tflip=False, total_events=0):
+    def plan_time_windows(self, events, n_events, tflip=False, starts=None):
+        """split_method='time_window': ``plan`` for windows of fixed duration.  The windows are found on the device
+        (vis.time_windows_device) and the plan is built from the bounds copied back: one small synchronisation.
+        A sample's views are its windows with at least ``min_events`` rows, in window order; more than T of them are
+        thinned by the draw chunks get.  tflip: the windows are counted back from the last event (``from_last``), which are
+        the windows of the time-reversed stream as stored rows.
+        Returns (frame_range, row_idx, valid_mask, window_index int32 [B, T]): the k of every view, -1 for a padded one."""
+        T, B = self.max_imgs, len(n_events)
+        n = np.asarray(n_events, dtype=np.int64)
+        if (n <= 0).any():
+            raise IndexError('sample with no events (the reference resamples these upstream, caltech.py:181-182)')
+        o0 = np.asarray(starts if starts is not None else np.concatenate([[0], np.cumsum(n)[:-1]]), dtype=np.int64)
+        sr = torch.tensor(np.stack([o0, o0 + n], 1), dtype=torch.int64)
+        bounds, stats = vis.time_windows_device(events, sr, self.window, self.stride, self.max_windows, from_last=tflip)
+        unsorted = np.flatnonzero(stats['unsorted'] > 0)
+        if len(unsorted):
+            raise ValueError(f'time_window: the timestamps of samples {unsorted.tolist()} are not sorted '
+                             f"({stats['unsorted'][unsorted].tolist()} rows earlier than the row before them)")
+        over = np.flatnonzero(stats['windows'] > self.max_windows)
+        if len(over):
+            raise ValueError(f"time_window: samples {over.tolist()} span {stats['windows'][over].tolist()} windows of stride "
+                             f'{self.stride} s, more than max_windows={self.max_windows}')
+        bounds = bounds.cpu().numpy()
+        ranges, empty = [], []
+        row_idx, window_index = np.full((B, T), -1, dtype=np.int32), np.full((B, T), -1, dtype=np.int32)
+        for b in range(B):
+            rows = bounds[b, :int(stats['windows'][b])]
+            sel = np.flatnonzero(rows[:, 1] - rows[:, 0] >= self.min_events).tolist()
+            if not sel:
+                empty.append(b)
+                continue
+            if len(sel) > T:                                             # event2img.py:83-86
+                sel = [sel[i] for i in torch.randperm(len(sel), generator=self.generator)[:T].tolist()]
+            for t, k in enumerate(sel):
+                row_idx[b, t], window_index[b, t] = len(ranges), k
+                ranges.append((int(rows[k, 0]), int(rows[k, 1])))
+        if empty:
+            raise ValueError(f'time_window: no window of samples {empty} holds min_events={self.min_events} events')
+        fr = torch.tensor(ranges, dtype=torch.int64).reshape(-1, 2)
+        ri = torch.from_numpy(row_idx)
+        return fr, ri, ri >= 0, torch.from_numpy(window_index)
+
+    def frames(self, events, frame_range, hflip=False, tflip=False, total_events=0, max_frame_events=None):
         """uint8 [Fv, H, W, 3] for the planned views (vis.events2frames, batched).  The time flip of a time surface or
-        a voxel grid (utils.py:26-35: t' = t_last - t, p' = -p) is reverse_t with negate_p on the stored rows."""
+        a voxel grid (utils.py:26-35: t' = t_last - t, p' = -p) is reverse_t with negate_p on the stored rows.
+        max_frame_events: the longest planned view (N when the views are chunks of N events)."""
         common = dict(grayscale=self.grayscale, background_mask=self.background_mask, return_stats=self.strict,
-                      max_frame_events=self.N, flip_x=hflip, negate_p=tflip, total_events=total_events)
+                      max_frame_events=self.N if max_frame_events is None else int(max_frame_events), flip_x=hflip,
+                      negate_p=tflip, total_events=total_events)
         if self.event_rep == 'time_surface':
             out = vis.time_surface_device(events, frame_range, self.resolution, decay=self.decay, tau=self.tau,
                                           reverse_t=tflip, **common)
@@ -205,11 +270,18 @@ class Event2ImagePipeline:
             vis.center_events_device(events, sr, self.resolution)
         if self.denoise is not None and not filtered:
             events, n_events, starts = self.filter(events, n_events, starts)
-        fr, ri, vm = self.plan(n_events, tflip=tflip, starts=starts)
+        wi = longest = None
+        if self.split_method == 'time_window':
+            fr, ri, vm, wi = self.plan_time_windows(events, n_events, tflip=tflip, starts=starts)
+            longest = int((fr[:, 1] - fr[:, 0]).max())
+        else:
+            fr, ri, vm = self.plan(n_events, tflip=tflip, starts=starts)
         fr_d = fr.to(dev)
         frames = self.frames(events, fr_d, hflip=hflip, tflip=tflip,
-                             total_events=int((fr[:, 1] - fr[:, 0]).sum()))
+                             total_events=int((fr[:, 1] - fr[:, 0]).sum()), max_frame_events=longest)
         out = dict(valid_mask=vm.to(dev), row_idx=ri.to(dev))
+        if wi is not None:
+            out['window_index'] = wi.to(dev)
         if self.denoise is not None:
             out['n_events'] = [int(n) for n in n_events]
         if self.augment:

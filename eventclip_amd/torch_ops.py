@@ -10,6 +10,7 @@ mirrors of the reference's interface (vis / preprocess / clip / adapter / clip_c
     torch.ops.eventclip_hip.events_to_time_surface   ec_events_to_time_surface[_packed]   (no counterpart: eventclip_time_surface.h)
     torch.ops.eventclip_hip.events_to_voxel_grid     ec_events_to_voxel_grid[_packed]     (no counterpart: eventclip_voxel_grid.h)
     torch.ops.eventclip_hip.events_denoise           ec_denoise_events[_packed]           (no counterpart: eventclip_denoise.h)
+    torch.ops.eventclip_hip.events_time_windows      ec_time_windows[_packed]             (no counterpart: eventclip_time_windows.h)
     torch.ops.eventclip_hip.preprocess         ec_preprocess                   datasets/event2img.py:119-122
     torch.ops.eventclip_hip.vit_encode         ec_vit_encode                   models/clip_cls.py:101
     torch.ops.eventclip_hip.text_encode        ec_text_encode                  models/clip_cls.py:84
@@ -161,6 +162,29 @@ def events_denoise(events: torch.Tensor, sample_range: torch.Tensor, H: int, W: 
 @events_denoise.register_fake
 def _(events, sample_range, H, W, dt_us, radius):
     return torch.empty_like(events), events.new_empty((sample_range.shape[0],), dtype=torch.int64)
+
+
+@custom_op(f'{NAMESPACE}::events_time_windows', mutates_args=(), device_types='cuda')
+def events_time_windows(events: torch.Tensor, sample_range: torch.Tensor, dt_us: int, stride_us: int, max_windows: int,
+                        from_last: bool, total_events: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """events float32 [n, 4] or packed int64 [n]; sample_range int64 [B, 2] -> (bounds int64 [B, max_windows, 2], stats int32
+    [B, 4]): the fixed-duration windows of include/eventclip_time_windows.h.  bounds[b, k] are the (begin, end) event rows of
+    window k of sample b, -1 in the rows the kernel does not write; stats[b] are the four words of ec_time_windows_stats
+    (t_first, t_last, unsorted, windows).  Nothing is read back: total_events (0 = unknown) only sizes the grid."""
+    from . import vis
+    B = int(sample_range.shape[0])
+    prm = vis.time_windows_params(dt_us, stride_us, max_windows, from_last, total_events)
+    bounds = torch.full((B, max_windows, 2), -1, dtype=torch.int64, device=events.device)
+    stats = torch.zeros((B, 4), dtype=torch.int32, device=events.device)
+    _lib.launch('ec_time_windows_packed' if vis.is_packed(events) else 'ec_time_windows', events, sample_range.contiguous(), B,
+                prm, bounds, stats)
+    return bounds, stats
+
+
+@events_time_windows.register_fake
+def _(events, sample_range, dt_us, stride_us, max_windows, from_last, total_events):
+    B = sample_range.shape[0]
+    return events.new_empty((B, max_windows, 2), dtype=torch.int64), events.new_empty((B, 4), dtype=torch.int32)
 
 
 # ------------------------------------------------------------------------------------------
@@ -719,5 +743,5 @@ def _vit_image_backward(ctx, d_feats, d_tape):
 vit_image_fwd.register_autograd(_vit_image_backward, setup_context=_vit_image_setup)
 
 
-OPS = ('events_to_frames', 'events_to_time_surface', 'events_to_voxel_grid', 'events_denoise', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode',
+OPS = ('events_to_frames', 'events_to_time_surface', 'events_to_voxel_grid', 'events_denoise', 'events_time_windows', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode',
        'classify_bwd', 'adapter_train_fwd', 'adapter_train_bwd', 'vit_train_fwd', 'vit_train_bwd', 'vit_image_fwd', 'vit_image_bwd')

@@ -12,6 +12,8 @@ plus the batched device entries ``events_to_frames_device`` (polarity histogram)
 include/eventclip_time_surface.h) and ``voxel_grid_device`` (temporal-bin frames, ``convert_method='voxel_grid'``:
 not in the reference either, defined in include/eventclip_voxel_grid.h) used by the pipeline, and in front of all three
 ``denoise_events_device`` / ``denoise_events`` (the background-activity filter of include/eventclip_denoise.h).
+``split_method='time_window'`` (not in the reference either) cuts a stream into windows of fixed duration instead of
+fixed event count: ``time_windows_device`` / ``split_time_window`` (include/eventclip_time_windows.h).
 There is no CPU fallback.
 """
 import collections
@@ -508,6 +510,104 @@ def denoise_events(events, resolution, dt, radius=1):
     return out[:int(counts[0])].cpu().numpy().view(arr.dtype)
 
 
+# ---- fixed-duration windows (include/eventclip_time_windows.h: the definition, steps 1 - 7) ----
+TIME_WINDOWS_HEADER = os.path.join(os.path.dirname(_lib.HEADER), 'eventclip_time_windows.h')
+_windows_constants, _windows_structs, TIME_WINDOWS_SIGNATURES = _lib.bind_header(os.path.basename(TIME_WINDOWS_HEADER))
+EcTimeWindowsParams, EcTimeWindowsStats = _windows_structs['EcTimeWindowsParams'], _windows_structs['EcTimeWindowsStats']
+TIME_WINDOWS_MAX_US = _windows_constants['EC_TIME_WINDOWS_MAX_US']
+# rows of one workgroup's slice and loads in flight per thread: the sizes at which the kernel's loops turn over
+TIME_WINDOWS_SLICE_ROWS = _windows_constants['EC_TIME_WINDOWS_SLICE_ROWS']
+TIME_WINDOWS_UNROLL = _windows_constants['EC_TIME_WINDOWS_UNROLL']
+TIME_WINDOWS_STATS_DTYPE = np.dtype([('t_first', '<u4'), ('t_last', '<u4'), ('unsorted', '<u4'), ('windows', '<i4')])
+SPLIT_METHODS = ('event_count', 'time_window')
+
+
+def time_window_us(seconds, what='window'):
+    """A window or a stride: seconds -> the integer microseconds of ``ec_time_windows_params`` (as ``denoise_dt_us``)."""
+    us = int(round(float(seconds) * 1e6))
+    if not 1 <= us <= TIME_WINDOWS_MAX_US:
+        raise ValueError(f'{what}={seconds} s: 1 .. {TIME_WINDOWS_MAX_US} microseconds')
+    return us
+
+
+def time_windows_params(dt_us, stride_us, max_windows, from_last=False, total_events=0):
+    """EcTimeWindowsParams: what the custom op fills."""
+    for what, us in (('dt_us', dt_us), ('stride_us', stride_us)):
+        if not 1 <= int(us) <= TIME_WINDOWS_MAX_US:
+            raise ValueError(f'{what}={us}: 1 .. {TIME_WINDOWS_MAX_US}')
+    if int(max_windows) <= 0:
+        raise ValueError(f'max_windows={max_windows}: at least 1')
+    p = EcTimeWindowsParams()
+    p.dt_us, p.stride_us, p.max_windows = int(dt_us), int(stride_us), int(max_windows)
+    p.from_last, p.total_events = int(bool(from_last)), int(total_events)
+    return p
+
+
+def time_windows_device(events, sample_range, window, stride=None, max_windows=64, from_last=False):
+    """Batched device entry of the fixed-duration windows (include/eventclip_time_windows.h).
+
+    events:       float32 CUDA tensor [n_total, 4] or packed events, int64 CUDA tensor [n_total]; not modified.
+    sample_range: int64 tensor [B, 2] of (begin, end) rows per sample, on the host or the device.
+    window, stride: SECONDS; ``stride=None`` means ``window`` (windows back to back).  Window k of a sample covers the
+                  ticks [t_first + k stride, t_first + k stride + window); with ``from_last`` the windows are counted back
+                  from the sample's last event (the time flip of test-time augmentation, as stored rows).
+    Returns (bounds, stats): bounds int64 CUDA [B, max_windows, 2], the (begin, end) event rows of every window, -1 in the
+    rows the call does not write (behind a sample's windows; of an empty sample); stats a numpy structured array
+    (t_first, t_last, unsorted, windows) -- windows is the full count even above max_windows, and -1 for a sample whose
+    ticks are not sorted, whose bounds mean nothing.  Reading stats waits for the kernel.
+    """
+    import torch
+    from . import torch_ops  # noqa: F401  (registers the namespace)
+    dev, _ = _check_device_events(events, sample_range, on_device=False)
+    dt_us = time_window_us(window)
+    stride_us = dt_us if stride is None else time_window_us(stride, 'stride')
+    # (sizes the grid and states the bytes; no sample is longer than the array)
+    total = int((sample_range[:, 1] - sample_range[:, 0]).clamp(min=0).sum()) if not sample_range.is_cuda else int(events.shape[0])
+    bounds, stats = torch.ops.eventclip_hip.events_time_windows(
+        events, sample_range.to(dev).contiguous(), dt_us, stride_us, int(max_windows), bool(from_last), total)
+    return bounds, stats.cpu().numpy().view(TIME_WINDOWS_STATS_DTYPE).reshape(int(sample_range.shape[0]))
+
+
+def _all_time_windows(ev_d, window, stride, from_last=False):
+    """Every window of ONE sample (all rows of ``ev_d``) -> (bounds numpy int64 [windows, 2], its stats record); a second
+    launch when there are more than the first one's 64.  Unsorted timestamps raise."""
+    import torch
+    rng = torch.tensor([[0, int(ev_d.shape[0])]], dtype=torch.int64)
+    bounds, stats = time_windows_device(ev_d, rng, window, stride, 64, from_last)
+    if stats['unsorted'][0] > 0:
+        raise ValueError(f"time_window: the timestamps are not sorted ({int(stats['unsorted'][0])} rows earlier than the row "
+                         'before them); nothing is sorted for the caller')
+    if stats['windows'][0] > 64:
+        bounds, stats = time_windows_device(ev_d, rng, window, stride, int(stats['windows'][0]), from_last)
+    return bounds[0, :int(stats['windows'][0])].cpu().numpy(), stats[0]
+
+
+def split_time_window(events_or_t, window, stride=None):
+    """The windows of one sample, numpy in: ``events_or_t`` is [n, 4] rows (or the dict form), packed uint64 / int64 [n],
+    or a 1-D float array of timestamps in seconds.  ``window`` and ``stride`` (default: ``window``) in seconds.
+    Returns (idx0, idx1, t0, t1) like ``split_event_count``: window k is rows [idx0[k], idx1[k]) -- every window, the empty
+    ones (idx0[k] == idx1[k]) too -- and t0[k], t1[k] are its edges in seconds, [t0, t1), on the kernel's microsecond ticks.
+    Computed by the kernel behind ``ec_time_windows``."""
+    import torch
+    dev = _lib.require_gpu()
+    arr = events_or_t if isinstance(events_or_t, dict) else np.asarray(events_or_t)
+    if not isinstance(arr, dict) and is_packed(arr):
+        ev = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).to(dev)
+    elif not isinstance(arr, dict) and arr.ndim == 1:
+        rows = np.zeros((arr.shape[0], 4), dtype=np.float32)
+        rows[:, 2] = arr
+        ev = torch.from_numpy(rows).to(dev)
+    else:
+        ev = torch.from_numpy(parse_events(arr)).to(dev)
+    if ev.shape[0] == 0:
+        raise IndexError('split_time_window: empty event array')
+    bounds, stats = _all_time_windows(ev, window, stride)
+    dt_us = time_window_us(window)
+    stride_us = dt_us if stride is None else time_window_us(stride, 'stride')
+    lo = int(stats['t_first']) + np.arange(len(bounds), dtype=np.int64) * stride_us
+    return bounds[:, 0].tolist(), bounds[:, 1].tolist(), lo / 1e6, (lo + dt_us) / 1e6
+
+
 def events2frames(events, split_method, convert_method, shape=(180, 240), **kwargs):
     """Drop-in for the reference's events2frames (vis.py:75-117): numpy in, numpy out.
 
@@ -516,22 +616,32 @@ def events2frames(events, split_method, convert_method, shape=(180, 240), **kwar
     convert_method='voxel_grid' (not in the reference) takes ``bins`` (3: the image form has three channels) and ignores
     those three and ``grayscale``: channel k is temporal bin k.
     ``denoise=dict(dt=seconds, radius=1)`` (not in the reference) runs the background-activity filter of
-    include/eventclip_denoise.h first: the chunks are cut from the survivors."""
+    include/eventclip_denoise.h first: the chunks are cut from the survivors.
+    split_method='time_window' (not in the reference) takes ``window`` and ``stride`` (seconds; stride defaults to window)
+    and ``min_events`` (1) instead of ``N``: one frame per window of include/eventclip_time_windows.h that holds at least
+    ``min_events`` events, in window order."""
     import torch
     grayscale = kwargs.pop('grayscale', True)
     denoise = kwargs.pop('denoise', None)
     ev = parse_events(events)
-    assert split_method == 'event_count'                 # vis.py:90
+    assert split_method in SPLIT_METHODS                 # vis.py:90, + 'time_window'
     if convert_method not in CONVERT_METHODS:            # vis.py:113
         raise NotImplementedError(f'{convert_method} not implemented!')
     if denoise is not None:
         ev = denoise_events(ev, shape, denoise['dt'], denoise.get('radius', 1))
-    N = int(kwargs['N'])
+    N = int(kwargs['N']) if split_method == 'event_count' else None      # 'time_window' neither needs nor reads it
     if ev.shape[0] == 0:
         raise IndexError('events2frames: empty event array')
-    idx0, idx1 = chunk_bounds(ev.shape[0], N)
     dev = _lib.require_gpu()
     ev_d = torch.from_numpy(ev).to(dev)
+    if split_method == 'time_window':
+        bounds, _ = _all_time_windows(ev_d, kwargs['window'], kwargs.get('stride'))
+        bounds = bounds[bounds[:, 1] - bounds[:, 0] >= max(1, int(kwargs.get('min_events', 1)))]
+        if len(bounds) == 0:
+            raise ValueError(f"events2frames: no window of {kwargs['window']} s holds min_events={kwargs.get('min_events', 1)} events")
+        idx0, idx1 = bounds[:, 0].tolist(), bounds[:, 1].tolist()
+    else:
+        idx0, idx1 = chunk_bounds(ev.shape[0], N)
     rng = torch.tensor(np.stack([idx0, idx1], 1), dtype=torch.int64, device=dev)
     common = dict(grayscale=grayscale, background_mask=kwargs.get('background_mask', True), return_stats=True,
                   max_frame_events=max(b - a for a, b in zip(idx0, idx1)),
