@@ -1007,7 +1007,9 @@ EC_API int ec_unpatchify(const float *rows, long ld, int seq, int row_off, int n
 
 /* fp32 [rows, cols] -> any of: hi = round16(w) [rows, cols]; lo = round16(w - hi); hi_t = hi transposed
  * [cols, rows] (NULL outputs are skipped), for a list of same-shape matrices in one launch (`items`: DEVICE array):
- * what the optimiser moved is repacked once per step. */
+ * what the optimiser moved is repacked once per step.
+ * round16 is IEEE round to nearest even, subnormals kept, and the remainder is the fp32 difference w - (float)hi: a
+ * finite w beyond the 16-bit range has hi = +-inf and therefore lo = -+inf (w - inf), an infinite w has lo = NaN. */
 typedef struct {
     const float *w;
     void *hi, *lo, *hi_t;

@@ -160,7 +160,14 @@ def test_embedding_stage(run):
 @pytest.mark.parametrize('case,spec,dtype', [('tiny_n5', 'qkvo-4', 'float16'), ('wide_odd_n9', 'qkvo-16', 'float16'),
                                              ('wide_odd_n9', 'qkvo-24', 'float16'), ('tiny_n5', 'qkvo-64', 'float16'),
                                              ('wide_odd_n9', 'qkvo-64', 'bfloat16'), ('l14_n32', 'qkvo-16', 'float16'),
-                                             ('b16_n32', 'qkvo-64', 'float16'), ('l14_336_n2', 'qkvo-24', 'float16')])
+                                             ('b16_n32', 'qkvo-64', 'float16'), ('l14_336_n2', 'qkvo-24', 'float16'),
+                                             # every rank next to a 16-row factor tile (RT = 1 .. 4) and the two- and
+                                             # three-set sharing bodies, on the two smallest towers (M = 25, M = 90)
+                                             ('tiny_n5', 'qv-1', 'float16'), ('tiny_n5', 'qkv-15', 'float16'),
+                                             ('wide_odd_n9', 'qv-16', 'float16'), ('wide_odd_n9', 'qv-17', 'float16'),
+                                             ('tiny_n5', 'qkvo-32', 'float16'), ('wide_odd_n9', 'qkvo-33', 'float16'),
+                                             ('tiny_n5', 'qkv-40', 'float16'), ('wide_odd_n9', 'qkvo-48', 'float16'),
+                                             ('tiny_n5', 'qkvo-49', 'float16'), ('tiny_n5', 'qkv-40', 'bfloat16')])
 def test_lora_factor_gradients(hip, case, spec, dtype):
     """d up = dy^T (x down^T), d down = (dy up)^T x of block 0 (q, k, v: x = ln_1 output, dy = dq | dk | dv;
     out_proj: x = the attention output, dy = the 16-bit gradient of xm).  With only LoRA factors training, the pass
