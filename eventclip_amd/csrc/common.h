@@ -35,7 +35,7 @@ enum ProfClass {
     PROF_GEMM_RESID32, PROF_GEMM_STORE32, PROF_LAYERNORM, PROF_ATTENTION, PROF_EMBED, PROF_CLASSIFY,
     PROF_ADAPTER, PROF_GEMM_DW, PROF_ATTENTION_BWD, PROF_LN_BWD, PROF_TRANSPOSE, PROF_REDUCE, PROF_SGEMM,
     PROF_OPTIMIZER, PROF_PACK, PROF_CONV3X3, PROF_CONV1X1, PROF_STEM, PROF_AVGPOOL, PROF_ATTNPOOL, PROF_UNPATCHIFY,
-    PROF_TIME_SURFACE, PROF_VOXEL_GRID, PROF_DENOISE, PROF_NCLASS
+    PROF_TIME_SURFACE, PROF_VOXEL_GRID, PROF_DENOISE, PROF_REFRACTORY, PROF_NCLASS
 };
 struct ProfScope {
     ProfScope(int cls, hipStream_t s, double flops, double bytes);

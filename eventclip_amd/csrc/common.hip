@@ -72,7 +72,7 @@ const char *const kProfNames[PROF_NCLASS] = {
     "transpose_kernel", "colsum_kernel + reduce_kernel", "sgemm_kernel", "adam_kernel + unscale_check_kernel",
     "pack_weight_kernel", "conv_igemm_kernel<3x3>", "conv_igemm_kernel<1x1>", "stem_rows_kernel",
     "avgpool2_kernel", "attnpool_tokens_kernel + attnpool_attend_kernel", "unpatchify_kernel",
-    "time_surface_kernel", "voxel_grid_kernel", "denoise_kernel"};
+    "time_surface_kernel", "voxel_grid_kernel", "denoise_kernel", "refractory_kernel"};
 
 hipEvent_t take_event()
 {

@@ -32,6 +32,7 @@
 #include "eventclip_time_surface.h"
 #include "eventclip_voxel_grid.h"
 #include "eventclip_denoise.h"
+#include "eventclip_refractory.h"
 #include "eventclip_time_windows.h"
 
 // numpy evaluates every ufunc with one rounding per operation: no FMA contraction anywhere in
@@ -2554,6 +2555,278 @@ int launch_denoise(const void *events, const int64_t *sample_range, int B, const
 }
 
 // ---------------------------------------------------------------------------------------------
+// refractory-period filtering (include/eventclip_refractory.h states the definition, steps 1 - 4).
+//
+// Whether an event survives depends on which earlier events of its class survived: a sequential chain, but one per CLASS
+// (pixel, or pixel and polarity), and the classes are independent.  A per-pixel last-kept-tick map solves the chain only
+// for events taken in time order -- wrong on unsorted rows, and a race among the threads of one pixel.  Here the events are
+// SORTED BY CLASS instead (denoise_kernel's counting sort, on classes rather than halo pixels), and every class's chain is
+// solved by selection inside its own list: exact, and independent of the row order but for the tie rule.
+// One 1024-thread workgroup owns a whole sample (samples blockIdx.x, + gridDim.x, ...) and walks its row bands itself; a
+// class lies in exactly one band, so there is no halo.  Per band:
+//   count    one LDS word per class of the band, LDS atomic adds over the band's counted events;
+//   scan     block_exclusive_scan turns the counts into list offsets (word q + 1 holds the start of class q);
+//   scatter  every counted event of the band takes a place with an LDS atomic add on its class's word (the cursor: word q
+//            ends as the start of class q and word q + 1 as its end) and stores the key (tick << 32) | row-in-sample there,
+//            in the workgroup's own slot of the workspace: plain stores, read back by the same workgroup behind a barrier
+//            (one compute unit, one L1: the scoping denoise_kernel and voxel_grid_kernel use);
+//   chain    the 64-bit key order is the (tick, row) order of step 3.  The first kept key of a list is its minimum; the
+//            next kept key is the smallest one >= (last kept tick + period) << 32 (a sum below 2^31).  One pass over the
+//            list finds it and, on its way, writes the keep byte 0 of every key strictly between the last kept key and
+//            that bound -- the events this dead time removes -- so every counted row's byte is written exactly once, 1 when
+//            it is selected or 0 in the pass behind the kept event that blinds it; kept + 1 passes in all.
+//            Thread t takes the classes t, t + 1024, ...: a list of one key writes its 1 and is done, a list shorter than
+//            EC_REFRACTORY_LONG_LIST is walked by its lane alone, and the longer ones of a wave's 64 classes are then
+//            walked one after the other by the whole wave (lane-strided passes, a wave minimum of the candidates): a hot
+//            pixel of 4096 events costs (kept + 1) x 64 loads per lane rather than (kept + 1) x 4096 in one.
+// Then denoise_kernel's in-order compaction.  Here a thread reads keep bytes other threads wrote: the band loop's closing
+// barrier stands between.  Rows that are not counted never read a byte.
+// No global atomics, no waiting on another workgroup; every loop is bounded by the range or by a count read from LDS (the
+// passes of a list by its length + 1), list ends are clamped to the slot's capacity, and a key's row is checked against the
+// sample's length before its byte is written.
+// Traffic: the events are read 2 bands + 1 times (L2 / MALL after the first), the keys written once and read kept + 1 times.
+// ---------------------------------------------------------------------------------------------
+constexpr int RF_CLASS_WORDS = 32 * 1024;              // LDS words of the offsets: the classes of a band + 1
+constexpr int RF_LDS_BYTES = RF_CLASS_WORDS * 4 + EV_REDUCE_BYTES;
+constexpr unsigned long long RF_NONE = ~0ull;          // no key: above every (tick << 32) | row with tick < 2^31
+
+struct RfArgs {
+    const void *events;      // float4 (x, y, t, p) or packed 8-byte events
+    const long long *range;  // [B,2]
+    int H, W, B, cpp;        // cpp: classes per pixel, 1 or 2 (per_polarity)
+    unsigned period;
+    void *out;               // the survivors, same type as events
+    long long *counts;       // [B]
+    uint8_t *keep;           // optional [n_events_total]
+    ec_refractory_stats *stats; // optional [B]
+    unsigned char *ws;       // slot g of workgroup g: cap keys (u64), then cap keep bytes
+    long long slot_bytes;
+    int cap;                 // max_sample_events
+    int rows_per_band, bands;
+};
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_xor(v, o, 64);
+        v = t < v ? t : v;
+    }
+    return v;
+}
+
+// One pass of the chain over keys[k0 .. k1) in steps of `step`: the keys strictly between `last` and `bound` lie in the dead
+// time of `last` and get their keep byte 0; -> the smallest key >= bound of this thread's share, or RF_NONE.
+__device__ __forceinline__ unsigned long long chain_pass(const unsigned long long *keys, unsigned k0, unsigned k1, unsigned step,
+                                                         unsigned long long last, unsigned long long bound, uint8_t *flags,
+                                                         unsigned n)
+{
+    unsigned long long m = RF_NONE;
+    for (unsigned k = k0; k < k1; k += step) {
+        const unsigned long long key = keys[k];
+        if (key >= bound) {
+            m = key < m ? key : m;
+        } else if (key > last && (unsigned)key < n) {
+            flags[(unsigned)key] = 0;
+        }
+    }
+    return m;
+}
+
+// the bound behind a kept key: (its tick + period) << 32
+__device__ __forceinline__ unsigned long long chain_bound(unsigned long long kept, unsigned period)
+{
+    return (unsigned long long)((unsigned)(kept >> 32) + period) << 32;
+}
+
+template <typename EV>
+__global__ __launch_bounds__(EV_THREADS) void refractory_kernel(const RfArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned *offs = reinterpret_cast<unsigned *>(smem);       // word 0 stays 0; word q + 1 belongs to class q
+    unsigned long long *scratch = reinterpret_cast<unsigned long long *>(smem + RF_CLASS_WORDS * 4);
+    int *wave_cnt = reinterpret_cast<int *>(scratch);          // [2][EV_WAVES] of the compaction
+    const int H = a.H, W = a.W, cpp = a.cpp;
+    const unsigned period = a.period;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(a.ws + (long long)blockIdx.x * a.slot_bytes);
+    uint8_t *flags = reinterpret_cast<uint8_t *>(keys + a.cap);
+
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const long long e0 = a.range[2 * b], n = a.range[2 * b + 1] - e0;
+        if (n < 0 || n > (long long)a.cap) {                   // longer than the slot: not filtered (the header says so)
+            if (threadIdx.x == 0) {
+                a.counts[b] = -1;
+                if (a.stats) a.stats[b] = ec_refractory_stats{0, 0, 0};
+            }
+            continue;
+        }
+        const EV *ev = reinterpret_cast<const EV *>(a.events) + e0;
+        const unsigned un = (unsigned)n;
+        for (int band = 0; band < a.bands && n > 0; band++) {
+            const int y0 = band * a.rows_per_band, y1 = min(H, y0 + a.rows_per_band);
+            const int ncls = (y1 - y0) * W * cpp;              // < RF_CLASS_WORDS by the plan
+            for (int i = threadIdx.x; i <= ncls; i += EV_THREADS) offs[i] = 0;
+            __syncthreads();
+            for_events(ev, n, [&](const EV e, long long) {
+                int x, y, p;
+                if (counted_event(e, H, W, 0, 0, x, y, p) && y >= y0 && y < y1)
+                    atomicAdd(&offs[1 + ((y - y0) * W + x) * cpp + (cpp == 2 && p < 0)], 1u);
+            });
+            __syncthreads();
+            block_exclusive_scan(offs + 1, ncls, scratch);
+            for_events(ev, n, [&](const EV e, long long j) {
+                int x, y, p;
+                if (counted_event(e, H, W, 0, 0, x, y, p) && y >= y0 && y < y1) {
+                    const unsigned pos = atomicAdd(&offs[1 + ((y - y0) * W + x) * cpp + (cpp == 2 && p < 0)], 1u);
+                    if (pos < (unsigned)a.cap)                 // (always: pos < the band's events <= n <= cap)
+                        keys[pos] = ((unsigned long long)tick_of(e) << 32) | (unsigned long long)(unsigned)j;
+                }
+            });
+            __syncthreads();                                   // the keys are stored: this workgroup may read them
+            for (int q0 = wave * 64; q0 < ncls; q0 += EV_THREADS) {
+                const int q = q0 + lane;
+                unsigned s = 0, e = 0;
+                if (q < ncls) e = min(offs[q + 1], (unsigned)a.cap), s = min(offs[q], e);
+                const unsigned len = e - s;
+                if (len == 1) {
+                    const unsigned row = (unsigned)keys[s];
+                    if (row < un) flags[row] = 1;
+                } else if (len > 1 && len < (unsigned)EC_REFRACTORY_LONG_LIST) {
+                    unsigned long long last = 0, bound = 0;
+                    for (unsigned pass = 0; pass <= len; pass++) {
+                        const unsigned long long m = chain_pass(keys, s, e, 1u, last, bound, flags, un);
+                        if (m == RF_NONE) break;
+                        if ((unsigned)m < un) flags[(unsigned)m] = 1;
+                        last = m, bound = chain_bound(m, period);
+                    }
+                }
+                // the long lists of these 64 classes, one after the other, by the whole wave
+                unsigned long long todo = __ballot(len >= (unsigned)EC_REFRACTORY_LONG_LIST);
+                while (todo) {
+                    const int src = __builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    const unsigned ws = (unsigned)__shfl((int)s, src, 64), we = (unsigned)__shfl((int)e, src, 64);
+                    unsigned long long last = 0, bound = 0;
+                    for (unsigned pass = 0; pass <= we - ws; pass++) {
+                        const unsigned long long m = wave_min_u64(chain_pass(keys, ws + lane, we, 64u, last, bound, flags, un));
+                        if (m == RF_NONE) break;
+                        if (lane == 0 && (unsigned)m < un) flags[(unsigned)m] = 1;
+                        last = m, bound = chain_bound(m, period);
+                    }
+                }
+            }
+            __syncthreads();                                   // the offsets are read, the keep bytes stored
+        }
+        // step 4: the survivors in stored order.  flags[i] was written by whichever thread walked row i's class: behind
+        // the band loop's last barrier
+        EV *dst = reinterpret_cast<EV *>(a.out) + e0;
+        long long done = 0;
+        unsigned kept = 0, removed = 0, passed = 0;
+        int buf = 0;
+        for (long long t0 = 0; t0 < n; t0 += EV_THREADS, buf ^= 1) {
+            const long long i = t0 + threadIdx.x;
+            bool ok = false;
+            EV e = {};
+            if (i < n) {
+                e = ev[i];
+                int x, y, p;
+                const bool cnt = counted_event(e, H, W, 0, 0, x, y, p);
+                ok = !cnt || flags[i] != 0;
+                kept += cnt && ok, removed += cnt && !ok, passed += !cnt;
+                if (a.keep) a.keep[e0 + i] = ok ? 1 : 0;
+            }
+            const unsigned long long mask = __ballot(ok);
+            const int before = __popcll(mask & ((1ull << lane) - 1ull));
+            if (lane == 0) wave_cnt[buf * EV_WAVES + wave] = __popcll(mask);
+            __syncthreads();
+            int base = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < EV_WAVES; w++) {
+                const int c = wave_cnt[buf * EV_WAVES + w];
+                base += w < wave ? c : 0;
+                total += c;
+            }
+            if (ok) dst[done + base + before] = e;
+            done += total;
+        }
+        if (a.stats) {
+            const unsigned long long kr = block_sum_u64((unsigned long long)kept | ((unsigned long long)removed << 32), scratch);
+            const unsigned long long ps = block_sum_u64(passed, scratch);
+            if (threadIdx.x == 0) a.stats[b] = ec_refractory_stats{(unsigned)kr, (unsigned)(kr >> 32), (unsigned)ps};
+        }
+        if (threadIdx.x == 0) a.counts[b] = done;
+        __syncthreads();                                       // scratch is read: the next sample may write it
+    }
+}
+
+// Row bands: as many rows as RF_CLASS_WORDS - 1 classes hold (W, per polarity 2 W, classes a row), evened out over the bands.
+// No halo: a class never leaves its band.  bands == 0: the entry points refuse this sensor.
+struct RfPlan {
+    int rows_per_band, bands;
+};
+inline RfPlan refractory_plan(int H, int W, int per_polarity)
+{
+    RfPlan p = {};
+    if (H <= 0 || W <= 0 || W > 65536 || (per_polarity != 0 && per_polarity != 1)) return p;
+    const int rows = (RF_CLASS_WORDS - 1) / (W * (per_polarity + 1));
+    if (rows < 1) return p;
+    p.bands = ec::ceil_div(H, std::min(H, rows));
+    p.rows_per_band = ec::ceil_div(H, p.bands);
+    return p;
+}
+
+inline size_t refractory_slot_bytes(int cap) { return (size_t)cap * 8 + ((size_t)cap + 15) / 16 * 16; }
+
+inline size_t refractory_workspace_bytes(const ec_refractory_params *prm, int B)
+{
+    if (!prm || B <= 0 || prm->max_sample_events <= 0 || refractory_plan(prm->H, prm->W, prm->per_polarity).bands == 0) return 0;
+    return refractory_slot_bytes(prm->max_sample_events) * (size_t)std::min<int>(B, EC_REFRACTORY_MAX_GROUPS);
+}
+
+template <typename EV>
+int launch_refractory(const void *events, const int64_t *sample_range, int B, const ec_refractory_params *prm, void *events_out,
+                      int64_t *counts, uint8_t *keep, ec_refractory_stats *stats, void *workspace, size_t workspace_bytes,
+                      ec_stream_t stream)
+{
+    int rc;
+    if (launch_is_over("ec_refractory_events", prm, 'B', B, events && sample_range && events_out && counts && workspace, rc)) return rc;
+    EC_REQUIRE(events != events_out, "ec_refractory_events: in-place operation is not supported");
+    EC_REQUIRE(prm->H > 0 && prm->W > 0, "ec_refractory_events: bad shape (%d,%d)", prm->H, prm->W);
+    EC_REQUIRE(prm->period_us >= 1u && prm->period_us <= (uint32_t)EC_REFRACTORY_MAX_PERIOD_US,
+               "ec_refractory_events: period_us=%u outside 1 .. %d", prm->period_us, (int)EC_REFRACTORY_MAX_PERIOD_US);
+    EC_REQUIRE(prm->per_polarity == 0 || prm->per_polarity == 1, "ec_refractory_events: per_polarity=%d is neither 0 nor 1",
+               prm->per_polarity);
+    EC_REQUIRE(prm->max_sample_events > 0, "ec_refractory_events: max_sample_events=%d (a bound: it sizes the workspace)",
+               prm->max_sample_events);
+    EC_REQUIRE((((uintptr_t)events | (uintptr_t)events_out) & (sizeof(EV) - 1)) == 0,
+               "ec_refractory_events: events and events_out must be %d-byte aligned", (int)sizeof(EV));
+    EC_REQUIRE(((uintptr_t)counts & 7) == 0 && ((uintptr_t)stats & 3) == 0 && ((uintptr_t)workspace & 15) == 0,
+               "ec_refractory_events: counts must be 8-byte, stats 4-byte and workspace 16-byte aligned");
+    const RfPlan plan = refractory_plan(prm->H, prm->W, prm->per_polarity);
+    EC_REQUIRE(plan.bands > 0, "ec_refractory_events: W=%d too wide for an LDS band of one row (%d classes a pixel)", prm->W,
+               prm->per_polarity + 1);
+    const size_t need = refractory_workspace_bytes(prm, B);
+    if (workspace_bytes < need)
+        return ec::fail(EC_ERR_WORKSPACE, "ec_refractory_events: workspace %zu < %zu bytes (ec_refractory_workspace_bytes)", workspace_bytes, need);
+
+    RfArgs a = {};
+    a.events = events;
+    a.range = reinterpret_cast<const long long *>(sample_range);
+    a.H = prm->H, a.W = prm->W, a.B = B, a.cpp = prm->per_polarity + 1;
+    a.period = prm->period_us;
+    a.out = events_out, a.counts = reinterpret_cast<long long *>(counts), a.keep = keep, a.stats = stats;
+    a.ws = static_cast<unsigned char *>(workspace);
+    a.slot_bytes = (long long)refractory_slot_bytes(prm->max_sample_events);
+    a.cap = prm->max_sample_events;
+    a.rows_per_band = plan.rows_per_band, a.bands = plan.bands;
+
+    // algorithmic bytes: every event read once and at most written once
+    return launch_form(refractory_kernel<EV>, std::min<int>(B, EC_REFRACTORY_MAX_GROUPS), RF_LDS_BYTES, ec::PROF_REFRACTORY,
+                       2.0 * event_bytes<EV>(0, 0, 0, prm->total_events), stream, a);
+}
+
+// ---------------------------------------------------------------------------------------------
 // fixed-duration event windows (include/eventclip_time_windows.h states the definition, steps 1 - 7).
 //
 // bounds[b, k] are counts of ticks below an edge, i.e. the first row at or above it.  In a sorted sample that row is the one
@@ -2810,6 +3083,25 @@ extern "C" EC_API int ec_denoise_events_packed(const uint64_t *events, const int
 extern "C" EC_API size_t ec_denoise_workspace_bytes(const ec_denoise_params *prm, int B) { return denoise_workspace_bytes(prm, B); }
 
 extern "C" EC_API int ec_denoise_bands(int H, int W, int radius) { return denoise_plan(H, W, radius).bands; }
+
+extern "C" EC_API int ec_refractory_events(const float *events, const int64_t *sample_range, int B, const ec_refractory_params *prm,
+                                           float *events_out, int64_t *counts, uint8_t *keep, ec_refractory_stats *stats,
+                                           void *workspace, size_t workspace_bytes, ec_stream_t stream)
+{
+    return launch_refractory<float4>(events, sample_range, B, prm, events_out, counts, keep, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" EC_API int ec_refractory_events_packed(const uint64_t *events, const int64_t *sample_range, int B,
+                                                  const ec_refractory_params *prm, uint64_t *events_out, int64_t *counts,
+                                                  uint8_t *keep, ec_refractory_stats *stats, void *workspace,
+                                                  size_t workspace_bytes, ec_stream_t stream)
+{
+    return launch_refractory<packed_t>(events, sample_range, B, prm, events_out, counts, keep, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" EC_API size_t ec_refractory_workspace_bytes(const ec_refractory_params *prm, int B) { return refractory_workspace_bytes(prm, B); }
+
+extern "C" EC_API int ec_refractory_bands(int H, int W, int per_polarity) { return refractory_plan(H, W, per_polarity).bands; }
 
 extern "C" EC_API int ec_time_windows(const float *events, const int64_t *sample_range, int B, const ec_time_windows_params *prm,
                                       int64_t *bounds, ec_time_windows_stats *stats, ec_stream_t stream)

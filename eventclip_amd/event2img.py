@@ -35,6 +35,9 @@ class Event2ImagePipeline:
         ``denoise`` (not in the reference; absent or ``None`` = off): ``dict(dt=seconds, radius=1)`` puts the
         background-activity filter of include/eventclip_denoise.h in front of whichever form is chosen: an event stays
         only if a neighbouring pixel fired in the ``dt`` before it, and the chunks are cut from the survivors.
+        ``refractory`` (not in the reference; absent or ``None`` = off): ``dict(period=seconds, per_polarity=False)`` puts
+        the refractory-period filter of include/eventclip_refractory.h first of all, in front of ``denoise`` when both are
+        given: after a kept event its pixel (with ``per_polarity``: its pixel and polarity) is blind for ``period``.
         ``split_method`` is ``'event_count'`` (views of ``N`` events) or ``'time_window'`` (not in the reference: the
         fixed-duration windows of include/eventclip_time_windows.h), which reads ``window`` (seconds, required), ``stride``
         (seconds, default ``window``), ``min_events`` (1: a window with fewer rows is no view), ``max_windows`` (64: a
@@ -97,6 +100,19 @@ class Event2ImagePipeline:
                 raise ValueError(f"denoise {self.denoise!r}: dict(dt=seconds, radius=1)")
             self.denoise = dict(dt=float(self.denoise['dt']), radius=int(self.denoise.get('radius', 1)))
             vis.denoise_params(self.resolution, vis.denoise_dt_us(self.denoise['dt']), self.denoise['radius'], 1)
+        # the refractory-period filter, in front of the background-activity one (None = off: nothing below changes)
+        self.refractory = qa.get('refractory')
+        if self.refractory is not None:
+            if (not isinstance(self.refractory, dict) or 'period' not in self.refractory
+                    or set(self.refractory) - {'period', 'per_polarity'}
+                    or not isinstance(self.refractory.get('per_polarity', False), (bool, np.bool_))):
+                raise ValueError(f"refractory {self.refractory!r}: dict(period=seconds, per_polarity=False)")
+            self.refractory = dict(period=float(self.refractory['period']),
+                                   per_polarity=bool(self.refractory.get('per_polarity', False)))
+            prm = vis.refractory_params(self.resolution, vis.refractory_period_us(self.refractory['period']),
+                                        self.refractory['per_polarity'], 1)
+            if vis.refractory_workspace_bytes(prm, 1) == 0:
+                raise ValueError(f'refractory: a sensor of {self.resolution} does not fit the filter\'s row band')
         self.n_px, self.patch, self.kpad, self.dtype = int(n_px), patch, kpad, dtype
         self.frames_u8 = bool(frames_u8)
         assert not (self.frames_u8 and self.patch), 'frames_u8 and patch rows are two different outputs'
@@ -110,6 +126,11 @@ class Event2ImagePipeline:
             self.augmentation = RandAugment(
                 num_ops=2, interpolation='bicubic',
                 fill=[255, 255, 255] if self.background_mask else [0, 0, 0])
+
+    @property
+    def filters(self):
+        """does an event filter (refractory, denoise) stand in front of the views?"""
+        return self.refractory is not None or self.denoise is not None
 
     # ---- host bookkeeping: which event rows make which view ----
     def plan(self, n_events, tflip=False, starts=None):
@@ -227,14 +248,22 @@ class Event2ImagePipeline:
         return torch.from_numpy(cat).to(dev), n_events
 
     def filter(self, events, n_events, starts=None):
-        """quantize_args['denoise']: the survivors of every sample, compacted at the sample's unchanged first row.
-        -> (events_out, filtered counts, starts).  The window looks into the stored past; flips are view transforms and
-        come after."""
+        """quantize_args['refractory'], then quantize_args['denoise']: the survivors of every sample, compacted at the
+        sample's unchanged first row.  -> (events_out, filtered counts, starts).  Both filters look at the stored ticks;
+        flips are view transforms and come after."""
         n = np.asarray(n_events, dtype=np.int64)
         o0 = np.asarray(starts if starts is not None else np.concatenate([[0], np.cumsum(n)[:-1]]), dtype=np.int64)
         too_long = np.flatnonzero(n > self.max_n)
         if len(too_long):
             raise ValueError(f'denoise: samples {too_long.tolist()} hold more than max_n={self.max_n} events')
+        if self.refractory is not None:
+            # (cannot empty a sample that has a counted event: the first event of every class is kept)
+            sr = torch.tensor(np.stack([o0, o0 + n], 1), dtype=torch.int64)
+            events, counts = vis.refractory_events_device(events, sr, self.resolution, self.refractory['period'],
+                                                          self.refractory['per_polarity'])
+            n = counts.cpu().numpy().astype(np.int64)
+            if self.denoise is None:
+                return events, [int(c) for c in n], o0
         sr = torch.tensor(np.stack([o0, o0 + n], 1), dtype=torch.int64)
         out, counts = vis.denoise_events_device(events, sr, self.resolution, self.denoise['dt'], self.denoise['radius'])
         counts = counts.cpu().numpy()
@@ -251,9 +280,9 @@ class Event2ImagePipeline:
         hflip / tflip: the test-time-augmentation views of event2img.py:94-112;
         center: apply center_events (utils.py:38-57, in place) first, as the N-Caltech /
         N-ImageNet readers do (caltech.py:176).
-        With ``quantize_args['denoise']`` the events are filtered after centring and before chunking (``filtered``: they
-        are the filter's survivors already, as ``tta`` passes them), and the result gains ``n_events``, the filtered
-        counts.
+        With ``quantize_args['refractory']`` or ``quantize_args['denoise']`` the events are filtered after centring and
+        before chunking, the refractory filter first (``filtered``: they are the filters' survivors already, as ``tta``
+        passes them), and the result gains ``n_events``, the filtered counts.
 
         Returns a dict with ``valid_mask`` [B, T] (CUDA bool), ``row_idx`` [B, T] (CUDA
         int32) and either ``patches`` [Fv, G, kpad] (fused path), ``frames_u8`` [Fv, R, R, 3] or ``img``
@@ -268,7 +297,7 @@ class Event2ImagePipeline:
             offs = np.stack([o0, o0 + np.asarray(n_events)], 1)
             sr = torch.tensor(offs, dtype=torch.int64, device=dev)
             vis.center_events_device(events, sr, self.resolution)
-        if self.denoise is not None and not filtered:
+        if self.filters and not filtered:
             events, n_events, starts = self.filter(events, n_events, starts)
         wi = longest = None
         if self.split_method == 'time_window':
@@ -282,7 +311,7 @@ class Event2ImagePipeline:
         out = dict(valid_mask=vm.to(dev), row_idx=ri.to(dev))
         if wi is not None:
             out['window_index'] = wi.to(dev)
-        if self.denoise is not None:
+        if self.filters:
             out['n_events'] = [int(n) for n in n_events]
         if self.augment:
             frames = self._augment_frames(frames, ri)
@@ -319,7 +348,7 @@ class Event2ImagePipeline:
         if isinstance(events, (list, tuple)):
             events, n_events = self._concat(events, _lib.require_gpu())
         starts = None
-        if self.denoise is not None:      # once, on the stored rows: the four views are views of the same survivors
+        if self.filters:                  # once, on the stored rows: the four views are views of the same survivors
             events, n_events, starts = self.filter(events, n_events)
         return [self(events, n_events, hflip=h, tflip=t, starts=starts, filtered=True)
                 for h, t in ((False, False), (True, False), (False, True), (True, True))]

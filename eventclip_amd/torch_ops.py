@@ -10,6 +10,7 @@ mirrors of the reference's interface (vis / preprocess / clip / adapter / clip_c
     torch.ops.eventclip_hip.events_to_time_surface   ec_events_to_time_surface[_packed]   (no counterpart: eventclip_time_surface.h)
     torch.ops.eventclip_hip.events_to_voxel_grid     ec_events_to_voxel_grid[_packed]     (no counterpart: eventclip_voxel_grid.h)
     torch.ops.eventclip_hip.events_denoise           ec_denoise_events[_packed]           (no counterpart: eventclip_denoise.h)
+    torch.ops.eventclip_hip.events_refractory        ec_refractory_events[_packed]        (no counterpart: eventclip_refractory.h)
     torch.ops.eventclip_hip.events_time_windows      ec_time_windows[_packed]             (no counterpart: eventclip_time_windows.h)
     torch.ops.eventclip_hip.preprocess         ec_preprocess                   datasets/event2img.py:119-122
     torch.ops.eventclip_hip.vit_encode         ec_vit_encode                   models/clip_cls.py:101
@@ -161,6 +162,29 @@ def events_denoise(events: torch.Tensor, sample_range: torch.Tensor, H: int, W: 
 
 @events_denoise.register_fake
 def _(events, sample_range, H, W, dt_us, radius):
+    return torch.empty_like(events), events.new_empty((sample_range.shape[0],), dtype=torch.int64)
+
+
+@custom_op(f'{NAMESPACE}::events_refractory', mutates_args=(), device_types='cuda')
+def events_refractory(events: torch.Tensor, sample_range: torch.Tensor, H: int, W: int, period_us: int,
+                      per_polarity: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """events float32 [n, 4] or packed int64 [n]; sample_range int64 [B, 2] -> (events_out like events, counts int64 [B]):
+    the refractory-period filter of include/eventclip_refractory.h.  The survivors of sample b are
+    events_out[begin_b : begin_b + counts[b]]; the rows behind them, and rows outside every sample, are zero.  The
+    longest sample sizes the workspace, so the ranges are read back once."""
+    from . import vis
+    B = int(sample_range.shape[0])
+    host = sample_range.cpu()
+    lengths = host[:, 1] - host[:, 0]
+    prm = vis.refractory_params((H, W), period_us, per_polarity, int(lengths.max()) if B else 1, int(lengths.sum()) if B else 0)
+    events_out = torch.zeros_like(events)
+    counts = torch.zeros((B,), dtype=torch.int64, device=events.device)
+    vis.refractory_launch(events, sample_range.contiguous(), prm, events_out, counts)
+    return events_out, counts
+
+
+@events_refractory.register_fake
+def _(events, sample_range, H, W, period_us, per_polarity):
     return torch.empty_like(events), events.new_empty((sample_range.shape[0],), dtype=torch.int64)
 
 
@@ -743,5 +767,5 @@ def _vit_image_backward(ctx, d_feats, d_tape):
 vit_image_fwd.register_autograd(_vit_image_backward, setup_context=_vit_image_setup)
 
 
-OPS = ('events_to_frames', 'events_to_time_surface', 'events_to_voxel_grid', 'events_denoise', 'events_time_windows', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode',
+OPS = ('events_to_frames', 'events_to_time_surface', 'events_to_voxel_grid', 'events_denoise', 'events_refractory', 'events_time_windows', 'preprocess', 'vit_encode', 'text_encode', 'adapter_fwd', 'classify', 'resnet_encode',
        'classify_bwd', 'adapter_train_fwd', 'adapter_train_bwd', 'vit_train_fwd', 'vit_train_bwd', 'vit_image_fwd', 'vit_image_bwd')

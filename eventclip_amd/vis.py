@@ -11,7 +11,8 @@ plus the batched device entries ``events_to_frames_device`` (polarity histogram)
 (latest-timestamp frames, ``convert_method='time_surface'``: not in the reference, defined in
 include/eventclip_time_surface.h) and ``voxel_grid_device`` (temporal-bin frames, ``convert_method='voxel_grid'``:
 not in the reference either, defined in include/eventclip_voxel_grid.h) used by the pipeline, and in front of all three
-``denoise_events_device`` / ``denoise_events`` (the background-activity filter of include/eventclip_denoise.h).
+``denoise_events_device`` / ``denoise_events`` (the background-activity filter of include/eventclip_denoise.h) and
+``refractory_events_device`` / ``refractory_events`` (the refractory-period filter of include/eventclip_refractory.h).
 ``split_method='time_window'`` (not in the reference either) cuts a stream into windows of fixed duration instead of
 fixed event count: ``time_windows_device`` / ``split_time_window`` (include/eventclip_time_windows.h).
 There is no CPU fallback.
@@ -510,6 +511,115 @@ def denoise_events(events, resolution, dt, radius=1):
     return out[:int(counts[0])].cpu().numpy().view(arr.dtype)
 
 
+# ---- refractory-period filtering (include/eventclip_refractory.h: the definition, steps 1 - 4) ----
+REFRACTORY_HEADER = os.path.join(os.path.dirname(_lib.HEADER), 'eventclip_refractory.h')
+_refractory_constants, _refractory_structs, REFRACTORY_SIGNATURES = _lib.bind_header(os.path.basename(REFRACTORY_HEADER))
+EcRefractoryParams, EcRefractoryStats = _refractory_structs['EcRefractoryParams'], _refractory_structs['EcRefractoryStats']
+REFRACTORY_MAX_PERIOD_US = _refractory_constants['EC_REFRACTORY_MAX_PERIOD_US']
+# the class-list length from which a whole wave walks the list: the size at which the kernel's chain takes its other path
+REFRACTORY_LONG_LIST = _refractory_constants['EC_REFRACTORY_LONG_LIST']
+REFRACTORY_STATS_DTYPE = np.dtype([('kept', '<u4'), ('removed', '<u4'), ('passed', '<u4')])
+
+_refractory_scratch = collections.defaultdict(_lib.Scratch)   # device index -> the filter's workspace, reused by every call
+
+
+def refractory_period_us(seconds):
+    """The dead time: seconds -> the integer microseconds of ``ec_refractory_params.period_us``."""
+    us = int(round(float(seconds) * 1e6))
+    if not 1 <= us <= REFRACTORY_MAX_PERIOD_US:
+        raise ValueError(f'period={seconds} s: the refractory period is 1 .. {REFRACTORY_MAX_PERIOD_US} microseconds')
+    return us
+
+
+def refractory_bands(shape, per_polarity=False):
+    """Row bands the kernel cuts a sensor into (``ec_refractory_bands``; host only, 0 = refused)."""
+    return int(_lib.lib().ec_refractory_bands(int(shape[0]), int(shape[1]), int(bool(per_polarity))))
+
+
+def refractory_params(shape, period_us, per_polarity, max_sample_events, total_events=0):
+    """EcRefractoryParams: what ``refractory_events_device`` and the custom op both fill."""
+    if not 1 <= int(period_us) <= REFRACTORY_MAX_PERIOD_US:
+        raise ValueError(f'period_us={period_us}: 1 .. {REFRACTORY_MAX_PERIOD_US}')
+    p = EcRefractoryParams()
+    p.H, p.W, p.period_us, p.per_polarity = int(shape[0]), int(shape[1]), int(period_us), int(bool(per_polarity))
+    p.max_sample_events = max(1, int(max_sample_events))
+    p.total_events = int(total_events)
+    return p
+
+
+def refractory_workspace_bytes(prm, B):
+    """``ec_refractory_workspace_bytes``: host only, 0 for parameters the entry points refuse."""
+    return int(_lib.lib().ec_refractory_workspace_bytes(ctypes.byref(prm), int(B)))
+
+
+def refractory_launch(events, sample_range, prm, events_out, counts, keep=None, stats=None):
+    """The C ABI call with the workspace this module keeps per device (the custom op and the debug form share it)."""
+    import torch
+    B = int(sample_range.shape[0])
+    need = refractory_workspace_bytes(prm, B)
+    key = events.device.index if events.device.index is not None else torch.cuda.current_device()
+    ws = _refractory_scratch[key].get(max(need, 256), torch.device('cuda', key))
+    _lib.launch('ec_refractory_events_packed' if is_packed(events) else 'ec_refractory_events', events, sample_range, B, prm,
+                events_out, counts, keep, stats, ws, ws.numel())
+
+
+def refractory_events_device(events, sample_range, shape, period, per_polarity=False, return_mask=False, return_stats=False):
+    """Batched device entry of the refractory-period filter (include/eventclip_refractory.h).
+
+    events:       float32 CUDA tensor [n_total, 4] or packed events, int64 CUDA tensor [n_total]; not modified.
+    sample_range: int64 tensor [B, 2] of (begin, end) rows per sample (disjoint), on the host or the device.
+    period:       the dead time in SECONDS (no default: it is the sensor's and the scene's); per_polarity: ON and OFF
+                  events of a pixel have separate dead times.
+    After a kept event its pixel is blind for ``period``: a later event of the pixel stays only if it comes at least
+    ``period`` after the last KEPT one (a removed event does not extend the dead time).  The rows need not be sorted by
+    time; rows the frame kernels would not count (p == 0, outside the sensor) pass through.
+    Returns (events_out, counts): the survivors of sample b are events_out[begin_b : begin_b + counts[b]], in stored
+    order, the rows behind them unspecified; counts int64 CUDA [B].  + keep uint8 CUDA [n_total] (1 = written; rows outside
+    every sample 0) with ``return_mask``, + a stats structured array (kept, removed, passed) with ``return_stats``.
+    """
+    import torch
+    dev, _ = _check_device_events(events, sample_range, on_device=False)
+    B = int(sample_range.shape[0])
+    period_us = refractory_period_us(period)
+    if not return_mask and not return_stats:
+        # the production form: the registered custom op (eventclip_hip::events_refractory)
+        from . import torch_ops  # noqa: F401  (registers the namespace)
+        return torch.ops.eventclip_hip.events_refractory(events, sample_range.to(dev).contiguous(), int(shape[0]), int(shape[1]),
+                                                         period_us, bool(per_polarity))
+    host = sample_range.cpu()
+    lengths = host[:, 1] - host[:, 0]
+    prm = refractory_params(shape, period_us, per_polarity, int(lengths.max()) if B else 1, int(lengths.sum()) if B else 0)
+    events_out = torch.empty_like(events)
+    counts = torch.zeros((B,), dtype=torch.int64, device=dev)
+    keep = torch.zeros((int(events.shape[0]),), dtype=torch.uint8, device=dev) if return_mask else None
+    stats = torch.zeros((B, ctypes.sizeof(EcRefractoryStats)), dtype=torch.uint8, device=dev) if return_stats else None
+    refractory_launch(events, sample_range.to(dev).contiguous(), prm, events_out, counts, keep, stats)
+    res = [events_out, counts]
+    if return_mask:
+        res.append(keep)
+    if return_stats:
+        res.append(stats.cpu().numpy().view(REFRACTORY_STATS_DTYPE).reshape(B))
+    return _first_or_tuple(res)
+
+
+def refractory_events(events, resolution, period, per_polarity=False):
+    """The filter for one sample, numpy in, numpy out: [n, 4] rows (or the dict form, or packed uint64 [n]) -> the
+    surviving rows in stored order."""
+    import torch
+    dev = _lib.require_gpu()
+    if not isinstance(events, dict) and is_packed(np.asarray(events)):
+        arr = np.ascontiguousarray(events)
+        ev = torch.from_numpy(arr.view(np.int64)).to(dev)
+    else:
+        arr = parse_events(events)
+        ev = torch.from_numpy(arr).to(dev)
+    rng = torch.tensor([[0, ev.shape[0]]], dtype=torch.int64)
+    if ev.shape[0] == 0:
+        return arr.copy()
+    out, counts = refractory_events_device(ev, rng, resolution, period, per_polarity)
+    return out[:int(counts[0])].cpu().numpy().view(arr.dtype)
+
+
 # ---- fixed-duration windows (include/eventclip_time_windows.h: the definition, steps 1 - 7) ----
 TIME_WINDOWS_HEADER = os.path.join(os.path.dirname(_lib.HEADER), 'eventclip_time_windows.h')
 _windows_constants, _windows_structs, TIME_WINDOWS_SIGNATURES = _lib.bind_header(os.path.basename(TIME_WINDOWS_HEADER))
@@ -617,16 +727,21 @@ def events2frames(events, split_method, convert_method, shape=(180, 240), **kwar
     those three and ``grayscale``: channel k is temporal bin k.
     ``denoise=dict(dt=seconds, radius=1)`` (not in the reference) runs the background-activity filter of
     include/eventclip_denoise.h first: the chunks are cut from the survivors.
+    ``refractory=dict(period=seconds, per_polarity=False)`` (not in the reference) runs the refractory-period filter of
+    include/eventclip_refractory.h first of all, before ``denoise`` when both are given.
     split_method='time_window' (not in the reference) takes ``window`` and ``stride`` (seconds; stride defaults to window)
     and ``min_events`` (1) instead of ``N``: one frame per window of include/eventclip_time_windows.h that holds at least
     ``min_events`` events, in window order."""
     import torch
     grayscale = kwargs.pop('grayscale', True)
     denoise = kwargs.pop('denoise', None)
+    refractory = kwargs.pop('refractory', None)
     ev = parse_events(events)
     assert split_method in SPLIT_METHODS                 # vis.py:90, + 'time_window'
     if convert_method not in CONVERT_METHODS:            # vis.py:113
         raise NotImplementedError(f'{convert_method} not implemented!')
+    if refractory is not None:
+        ev = refractory_events(ev, shape, refractory['period'], refractory.get('per_polarity', False))
     if denoise is not None:
         ev = denoise_events(ev, shape, denoise['dt'], denoise.get('radius', 1))
     N = int(kwargs['N']) if split_method == 'event_count' else None      # 'time_window' neither needs nor reads it

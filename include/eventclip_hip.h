@@ -69,13 +69,14 @@ EC_API const char *ec_last_error(void);
  *   610  + ec_events_to_voxel_grid / _packed and ec_voxel_grid_bands, declared in eventclip_voxel_grid.h (additive, as 609)
  *   611  + ec_denoise_events / _packed, ec_denoise_workspace_bytes and ec_denoise_bands, declared in eventclip_denoise.h (additive, as 609)
  *   612  + ec_time_windows / _packed, declared in eventclip_time_windows.h (additive, as 609)
+ *   613  + ec_refractory_events / _packed, ec_refractory_workspace_bytes and ec_refractory_bands, declared in eventclip_refractory.h (additive, as 609)
  * Structs are passed by pointer and only ever grow AT THE END; a library reads every field of ITS OWN struct
  * definition, so a caller built against an older (shorter) struct would have the tail read from past its object.
  * ec_abi_check(EC_ABI_VERSION, sizeof ...) -- EC_ABI_CHECK() below -- compares the caller's header version and struct
  * sizes with the library's and returns EC_ERR_INVALID (message in ec_last_error()) on any difference: call it once
  * after loading the library, before any other entry point.  (eventclip_amd/_lib.py does; its ctypes bindings are
  * derived from this header when it is imported, so THIS file is the only statement of the ABI.) */
-#define EC_ABI_VERSION 612
+#define EC_ABI_VERSION 613
 EC_API int ec_version(void);
 EC_API int ec_abi_check(int header_version, size_t gemm_args_bytes, size_t block_weights_bytes, size_t vit_weights_bytes,
                         size_t text_weights_bytes, size_t events_params_bytes, size_t adapter_weights_bytes);
